@@ -11,9 +11,17 @@
 
 One step = forward -> enRainfallLoss -> backward -> (bucketed gradient all-reduce over RCCL, overlapped with backward) ->
 clip_grad_norm_ -> AdamW.step -> zero_grad on a synthetic radar batch already resident in HBM (train.py:133-146 of the
-reference).  Protocol: W >= 10 warm-up steps, then 5 windows of exactly K steps, each bracketed by
-barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `value` / `ms_per_step` come from the
-MEDIAN window, every window is listed in `windows_ms_per_step`.  Rank 0 prints ONE JSON line.
+reference).  Protocol: W >= 10 warm-up steps, then exactly K timed steps split into up to 5 windows of near-equal
+length, each bracketed by barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `value` /
+`ms_per_step` come from the MEDIAN window's time per step, every window is listed in `windows_ms_per_step`.  Rank 0 prints ONE
+JSON line.
+
+A plain run does only that: set up, warm up, time the K steps, write --dump-outputs if asked, print the line (`roofline` and
+`cpu_baseline` are null there).  --full adds everything else below, after the timed steps: the instrumented steps behind
+`roofline` / `families_top` / --dump-prof, the PMC traffic join, `cpu_baseline` and the side file of full tables (--dump-json).
+
+--dump-outputs DIR: what the timed path computed in its last step, as .npy files (write_outputs()).  Inputs and parameters come
+from fixed recipes, so two builds run with the same arguments can be compared output for output.
 
 `roofline`: per-kernel HIP-event timing recorded by libadnm_hip around each of its launches (adnm_prof_enable/collect), on the
 stream the kernels run on, during extra eagerly-launched steps after the timed region.  The reported kernel is the one with
@@ -29,6 +37,7 @@ import hashlib
 import json
 import os
 import socket
+import statistics
 import subprocess
 import sys
 import time
@@ -38,6 +47,7 @@ sys.path.insert(0, os.path.join(ROOT, "adnm-unet_amd"))
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s is the measured copy ceiling
 N_WINDOWS = 5
+OUT_SAMPLE = 1 << 23   # parameter elements --dump-outputs writes at most (32 MB of float32); a fixed, seeded sample above that
 
 # profiler scope (csrc/*.hip ADNM_PROF names) -> north-star kernel family
 FAMILIES = [
@@ -64,26 +74,32 @@ FAMILIES = [
 ]
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps in all (split into up to 5 windows)")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the instrumented per-kernel steps "
+                         "(roofline, families, --dump-prof), the PMC traffic join, the CPU baseline and the --dump-json side file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (loss, grad_norm, params)")
     ap.add_argument("--batch", type=int, default=4, help="per-GPU batch (BASELINE config 2: 4)")
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--in-frames", type=int, default=5)
     ap.add_argument("--out-frames", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-steps", type=int, default=8, help="timed oracle steps of the CPU baseline (~1.5 s each on 16 threads: ~12-15 s in all)")
-    ap.add_argument("--prof-steps", type=int, default=3)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-steps", type=int, default=8, help="timed oracle steps of the CPU baseline of --full (~1.5 s each on 16 threads: ~12-15 s in all)")
+    ap.add_argument("--prof-steps", type=int, default=3, help="instrumented steps of --full")
     ap.add_argument("--overlap", type=int, default=-1,
                     help="gradient all-reduce overlapped with backward in bucket order (N>1): 1 on, 0 one blocking all-reduce after "
                          "backward, -1 (default) = on whenever N>1")
     ap.add_argument("--stages", type=int, default=0, help="stage cuts of the overlapped backward: 0 = every stage the model offers (5), 2 = encoder | rest")
     ap.add_argument("--reduce-dtype", default="f32", choices=["f32", "bf16"], help="wire dtype of the gradient all-reduce (N>1)")
-    ap.add_argument("--dump-json", default=os.path.join(ROOT, "bench_tables.json"),
-                    help="side file for the full record (the stdout line + the complete per-family / per-kernel tables)")
-    ap.add_argument("--dump-prof", default="", help="write the per-(kernel, shape) HIP-event table of the instrumented steps to this file")
+    ap.add_argument("--dump-json", default=None,
+                    help="--full: side file for the full record (the stdout line + the complete per-family / per-kernel tables); "
+                         "default bench_tables.json in the repository root")
+    ap.add_argument("--dump-prof", default="", help="--full: write the per-(kernel, shape) HIP-event table of the instrumented steps to this file")
     ap.add_argument("--side-stream", type=int, default=-1,
                     help="weight-gradient leaves (grouped weight-gradient GEMMs / stencils, their folds, the parameter-prep backward nodes) on a second "
                          "stream beside the input-gradient chain = parallel branches of the captured graph: 1 on, 0 off, -1 the trainer's default")
@@ -94,9 +110,16 @@ def parse():
                          "vs the fp32 HIP path, tests/test_model_gpu.py::test_visionmamba_bf16_mfma_vs_reference); f32 = exact fp32 MFMA (the "
                          "bit-level parity path, tolerance 1e-4 / 1e-3); fp8 = BASELINE config 5: per-tensor scaled OCP e4m3 / e5m2 operands into the "
                          "fp8 MFMA for the forward and input-gradient GEMMs / dense convs (delayed scaling, re-calibrated every 16 steps on the "
-                         "device), bf16 operands for the weight gradients (parity: rel-L2 <= 1.5e-1, 50-step loss curve within 5 %, "
+                         "device), bf16 operands for the weight gradients (parity: rel-L2 <= 1.5e-1, 50-step loss curve within 5 %%, "
                          "tests/test_model_gpu.py::test_visionmamba_fp8_vs_reference)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and (args.dump_json or args.dump_prof):
+        ap.error("--dump-json and --dump-prof come from the measurements of --full: add --full")
+    if args.full and args.dump_json is None:
+        args.dump_json = os.path.join(ROOT, "bench_tables.json")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ multi-GPU entry
@@ -348,6 +371,34 @@ def stdout_line(res, families, tables_path):
     return s
 
 
+def window_sizes(steps):
+    """The `steps` timed steps as up to N_WINDOWS windows of near-equal length (the longer ones first); they add up to `steps`."""
+    n = min(N_WINDOWS, steps)
+    return [steps // n + (i < steps % n) for i in range(n)]
+
+
+def write_outputs(path, loss, grad_norm, params):
+    """--dump-outputs: what the timed path hands its caller after its last step, as .npy files under `path`:
+      loss.npy       float64 [1]  the step's enRainfallLoss
+      grad_norm.npy  float64 [1]  the total gradient norm before clipping (FlatTrainer.grad_norm())
+      params.npy     float32 [n]  the parameters after the step's AdamW update: every tensor of `params` in logical shape, flattened
+                                  and concatenated in order; above OUT_SAMPLE elements, the elements at OUT_SAMPLE sorted distinct
+                                  indices drawn by a generator seeded with 0 (the same for every run of the same model)
+    Returns {name: shape}."""
+    import numpy as np
+    import torch
+    flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+    if flat.numel() > OUT_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), OUT_SAMPLE, replace=False, shuffle=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    arrays = {"loss": np.array([float(loss)], dtype=np.float64), "grad_norm": np.array([float(grad_norm)], dtype=np.float64),
+              "params": flat.cpu().numpy().astype(np.float32)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 # ------------------------------------------------------------------------------------------------ one rank
 def main():
     args = parse()
@@ -414,11 +465,12 @@ def main():
     sync()
     if rank == 0:
         print("[bench] warm-up done, timing ...", file=sys.stderr, flush=True)
-    windows = []
-    for w in range(N_WINDOWS):
+    sizes = window_sizes(args.steps)
+    windows = []   # ms per step of each window
+    for w, k in enumerate(sizes):
         sync()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(k):
             loss = trainer.step(x, tgt)
         sync()
         dt = time.perf_counter() - t0
@@ -426,22 +478,25 @@ def main():
             tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax)
-        windows.append(dt)
+        windows.append(1e3 * dt / k)
         if rank == 0:
-            print(f"[bench] window {w}: {1e3 * dt / args.steps:.3f} ms/step", file=sys.stderr, flush=True)
-    dt = sorted(windows)[N_WINDOWS // 2]
+            print(f"[bench] window {w}: {windows[-1]:.3f} ms/step over {k} steps", file=sys.stderr, flush=True)
+    step_s = 1e-3 * statistics.median(windows)
     loss_val = float(loss.detach())
+    if rank == 0 and args.dump_outputs:
+        shapes = write_outputs(args.dump_outputs, loss_val, trainer.grad_norm(), list(model.parameters()))
+        print(f"[bench] outputs of the last timed step written to {args.dump_outputs}: {shapes}", file=sys.stderr, flush=True)
 
     def eager_step():  # same work, launched eagerly: per-launch HIP events cannot be recorded inside a graph replay
         return trainer.step(x, tgt, eager=True)
 
-    # ---- instrumented steps (outside the timed region): per-kernel HIP-event timing inside libadnm_hip
+    # ---- --full: instrumented steps (outside the timed region): per-kernel HIP-event timing inside libadnm_hip
     prof = {}
-    if rank != 0 and args.prof_steps > 0:
+    if args.full and rank != 0 and args.prof_steps > 0:
         for _ in range(args.prof_steps):
             eager_step()  # every rank takes part: the step contains the gradient all-reduce
         torch.cuda.synchronize()
-    if rank == 0 and args.prof_steps > 0:
+    if args.full and rank == 0 and args.prof_steps > 0:
         lib.query("adnm_prof_enable", 1)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -464,12 +519,14 @@ def main():
                 for key, r in sorted(prof.items(), key=lambda kv: -kv[1]["ms"]):
                     f.write(f"{key}\t{r['launches'] / ps:.1f}\t{1e3 * r['ms'] / r['launches']:.2f}\t{r['ms'] / ps:.4f}\t"
                             f"{r['bytes'] / max(r['ms'], 1e-9) / 1e6:.1f}\n")
-        pmc, pmc_src = pmc_table()
-        kernels, families, roofline = summarise(prof, ps, pmc, pmc_src, dt / args.steps, prof_step_ms if prof else 0.0)
+        kernels, families, roofline = {}, {}, None
+        if args.full:
+            pmc, pmc_src = pmc_table()
+            kernels, families, roofline = summarise(prof, ps, pmc, pmc_src, step_s, prof_step_ms if prof else 0.0)
         res = {
-            "metric": f"sequences/sec training ADNM-UNet {args.in_frames}->{args.out_frames}x{args.size}x{args.size}", "value": round(world * args.batch * args.steps / dt, 3),
-            "unit": "sequences/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "metric": f"sequences/sec training ADNM-UNet {args.in_frames}->{args.out_frames}x{args.size}x{args.size}", "value": round(world * args.batch / step_s, 3),
+            "unit": "sequences/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
+            "ms_per_step": round(1e3 * step_s, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": args.dtype,
             "dtype_detail": {"f32": "exact fp32 MFMA (v_mfma_f32_16x16x4_f32) everywhere: the bit-level parity path",
                              "bf16": "bf16 x bf16 -> fp32 on v_mfma_f32_16x16x32_bf16 in every GEMM-shaped kernel; fp32 accumulation, master "
@@ -485,24 +542,27 @@ def main():
                            f", {len(trainer.buckets)} gradient buckets all-reduced ({args.reduce_dtype}) beside backward" if world > 1 and overlap
                            else (", one all-reduce after backward" if world > 1 else "")),
                        "dist_backend": (backend + ("=RCCL" if backend == "nccl" else "")) if world > 1 else None,
-                       "protocol": f"{args.warmup} warm-up steps, median of {N_WINDOWS} windows of {args.steps} steps, barrier+sync at window edges, max over ranks",
+                       "protocol": f"{args.warmup} warm-up steps, {args.steps} timed steps in {len(sizes)} windows of {'/'.join(map(str, sizes))}, "
+                                   "median window, barrier+sync at window edges, max over ranks",
                        "loss": round(loss_val, 6)},
-            "windows_ms_per_step": [round(1e3 * w / args.steps, 3) for w in windows],
+            "windows_ms_per_step": [round(w, 3) for w in windows],
             "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args, args.cpu_steps)
         else:
             res["cpu_baseline"] = None
-        tables = {"families": families, "kernels": kernels}
-        tables_path = args.dump_json
-        try:
-            with open(tables_path, "w") as f:
-                json.dump(dict(res, **tables), f, indent=1)
-        except OSError as e:   # a read-only checkout must not cost the measurement
-            print(f"[bench] could not write {tables_path}: {e}", file=sys.stderr)
-            tables_path = None
-        print("[bench] tables " + json.dumps(tables), file=sys.stderr, flush=True)
+        tables_path = None
+        if args.full:
+            tables = {"families": families, "kernels": kernels}
+            tables_path = args.dump_json
+            try:
+                with open(tables_path, "w") as f:
+                    json.dump(dict(res, **tables), f, indent=1)
+            except OSError as e:   # a read-only checkout must not cost the measurement
+                print(f"[bench] could not write {tables_path}: {e}", file=sys.stderr)
+                tables_path = None
+            print("[bench] tables " + json.dumps(tables), file=sys.stderr, flush=True)
         print(stdout_line(res, families, tables_path and os.path.basename(tables_path)), flush=True)
     if world > 1:
         dist.barrier()

@@ -162,6 +162,41 @@ def test_bench_stdout_line_is_small_and_parses():
         bench.stdout_line(dict(res, dtype_detail="d" * 5000), families, "t.json")
 
 
+def test_bench_times_exactly_the_steps_asked_for():
+    """--steps K is the number of timed steps in all: the windows add up to K, at most 5 of them, lengths within one step.  The
+    side files of --full's measurements are refused without it."""
+    import bench
+    for k in range(1, 60):
+        sizes = bench.window_sizes(k)
+        assert sum(sizes) == k and len(sizes) == min(5, k) and max(sizes) - min(sizes) <= 1
+    assert bench.parse(["--steps", "7"]).dump_json is None
+    assert bench.parse(["--full"]).dump_json == os.path.join(ROOT, "bench_tables.json")
+    assert bench.parse(["--full", "--dump-prof", "p.tsv"]).dump_prof == "p.tsv"
+    for bad in (["--steps", "0"], ["--dump-prof", "p.tsv"], ["--dump-json", "t.json"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_bench_dump_outputs_is_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: loss and gradient norm as float64, the parameters as float32 in named order — all of them while they fit,
+    else the same sorted sample of distinct elements on every run — and never more than 64 MB in all."""
+    import numpy as np
+    import bench
+    assert 4 * bench.OUT_SAMPLE + 16 <= 64 << 20
+    params = [torch.arange(300.0).view(3, 100), torch.arange(300.0, 305.0)]
+    shapes = bench.write_outputs(str(tmp_path / "all"), torch.tensor(0.25), torch.tensor(3.0), params)
+    assert shapes == {"loss": [1], "grad_norm": [1], "params": [305]}
+    p = np.load(tmp_path / "all" / "params.npy")
+    assert p.dtype == np.float32 and (p == np.arange(305)).all()
+    assert np.load(tmp_path / "all" / "loss.npy").dtype == np.float64 and float(np.load(tmp_path / "all" / "grad_norm.npy")[0]) == 3.0
+    monkeypatch.setattr(bench, "OUT_SAMPLE", 50)
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.write_outputs(a, 0.25, 3.0, params)
+    bench.write_outputs(b, 0.25, 3.0, params)
+    sa, sb = np.load(os.path.join(a, "params.npy")), np.load(os.path.join(b, "params.npy"))
+    assert sa.shape == (50,) and (sa == sb).all() and (np.diff(sa) > 0).all() and sa.max() < 305
+
+
 def test_flat_trainer_refuses_unclaimed_and_doubly_claimed_parameters():
     """a parameter that receives a gradient but is named by no stage (it would never be trained, only decayed), or by two
     stages, is an error, not a silent layout decision."""

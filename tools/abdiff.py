@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of two bench.py --dump-json records: step time and the kernels whose time moved (HIP-event ms per step)."""
+"""A/B of two bench.py --full --dump-json records: step time and the kernels whose time moved (HIP-event ms per step)."""
 import json
 import sys
 a, b = (json.load(open(f)) for f in sys.argv[1:3])
