@@ -16,7 +16,9 @@ def strip_prefix(state_dict):
 def load_reference_checkpoint(model, source, map_location="cpu"):
     """Load a reference `*_best.pth` (path or already-loaded state_dict, with or without the DataParallel prefix) into `model`
     after checking that the two key sets and every shape agree.  Works on a model whose parameters FlatTrainer has already re-homed
-    into its flat buffer (load_state_dict copies in place, so the flat buffer receives the values).  Returns the number of tensors."""
+    into its flat buffer: load_state_dict copies in place, so the flat buffer receives the values, and the copies move the parameters'
+    version counters, so the trainer's narrow bf16 / fp8 weight shadow is rewritten (fp8: weight scales re-derived) before the next eager
+    forward, GraphedForward replay or training step reads it (ops.ShadowSet).  Returns the number of tensors."""
     sd = torch.load(source, map_location=map_location) if isinstance(source, (str, bytes)) or hasattr(source, "read") else source
     sd = strip_prefix(sd)
     own = model.state_dict()

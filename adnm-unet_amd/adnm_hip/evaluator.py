@@ -20,7 +20,10 @@ from . import lib, ops
 
 
 class GraphedForward:
-    """model.eval() forward under no_grad, captured once per input shape and replayed (validate.py:101-104)."""
+    """model.eval() forward under no_grad, captured once per input shape and replayed (validate.py:101-104).  The graph of a model whose
+    parameters a FlatTrainer holds reads the trainer's narrow weight shadow (ops.ShadowSet) through baked-in pointers: every call first
+    rewrites the shadows it captured against if a parameter was written since (a checkpoint load, an in-place op), and the graph keeps
+    them alive, so it may outlive the trainer.  close() (or __del__) gives the graphs back."""
 
     def __init__(self, model):
         self.model = model
@@ -31,6 +34,10 @@ class GraphedForward:
         key = (tuple(x.shape), x.dtype, x.device)
         ent = self._graphs.get(key)
         if ent is None:
+            ptrs = [p.data_ptr() for p in self.model.parameters()]
+            shadows = [s for s in ops.SHADOWS.sets(x.device) if any(s.lo <= q < s.hi for q in ptrs)]
+            for s in shadows:   # (the capture cannot rewrite a stale one)
+                s.ensure_current()
             was_training = self.model.training
             self.model.eval()
             sx = x.clone()
@@ -44,17 +51,45 @@ class GraphedForward:
             # the graph's split GEMM launches get their own uncached workspace (kept with the graph: a training graph replayed on
             # another stream beside this one must not share it); fp8: the quantisation table's rows stay put while the graph lives
             scope = ops.SPLITWS.open_scope(x.device)
-            if ops.mfma_precision() == "fp8":
+            pinned = ops.mfma_precision() == "fp8"
+            if pinned:
                 ops.QUANT.pin(x.device)
-            with ops.SPLITWS.capturing(scope):
-                with torch.cuda.graph(g):
-                    out = self.model(sx)
-            self.model.train(was_training)
-            ent = self._graphs[key] = (g, sx, out, scope)
-        g, sx, out, _ = ent
-        sx.copy_(x, non_blocking=True)
-        g.replay()
-        return out
+            try:
+                with ops.SPLITWS.capturing(scope):
+                    with torch.cuda.graph(g):
+                        out = self.model(sx)
+            except BaseException:
+                if pinned:
+                    ops.QUANT.unpin(x.device)
+                raise
+            finally:
+                self.model.train(was_training)
+            ent = self._graphs[key] = {"graph": g, "sx": sx, "out": out, "scope": scope, "shadows": shadows, "pinned": pinned}
+        for s in ent["shadows"]:
+            s.ensure_current()
+        ent["sx"].copy_(x, non_blocking=True)
+        ent["graph"].replay()
+        return ent["out"]
+
+    def close(self):
+        """Give the captured graphs back now: the graphs first, then what their launches point into (static tensors, split-K
+        workspaces, the weight shadows), then the pins on the fp8 quantisation table.  Idempotent; __del__ calls it."""
+        graphs, self._graphs = self._graphs, {}
+        unpin = [key[2] for key, ent in graphs.items() if ent["pinned"]]
+        for ent in graphs.values():
+            ent["graph"] = None
+        graphs = None
+        for dev in unpin:
+            try:
+                ops.QUANT.unpin(dev)
+            except Exception:
+                pass
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class GpuEvaluator:

@@ -5,7 +5,9 @@ torch's caching allocator only, so a whole training step is hipGraph-capturable.
 Layout convention: token tensors are (B, L, C) / (M, C) channels-last; a "row view" is a 2-D
 tensor with stride (ld, 1) — kernels take the row stride, so column slices of wide buffers are
 passed without copies."""
+import bisect
 import math
+import operator
 import os
 import threading
 
@@ -119,6 +121,10 @@ class QuantTable:
 
     def table_ptr(self, device):
         return self._ent(device)["tab"].data_ptr()
+
+    def table(self, device):
+        """this device's (CAP, 8) fp32 record table: [scale_a, scale_b, amax_a, amax_b, fmax_a, fmax_b, record, -]"""
+        return self._ent(device)["tab"]
 
     def scale_b_view(self, device, row):
         """1-element view of a record's scale_b (what the fp8 shadow of a weight was / will be multiplied by)"""
@@ -745,31 +751,119 @@ class _ScopeActive:
         return False
 
 
+_VERSION = operator.attrgetter("_version")
+
+
+def _capturing():
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+class ShadowSet:
+    """One FlatTrainer's narrow SHADOW (ShadowRegistry below) and what keeping it current takes.  The optimiser pass rewrites the shadow
+    together with the parameters; any other write to the parameters leaves it STALE, and a stale shadow must never be read.  torch bumps
+    a version counter on every write it performs — load_state_dict's param.copy_ (FlatTrainer re-homes a parameter with `p.data = view`,
+    which keeps the parameter's own counter), an in-place op on a parameter or on a view of it, a write through flat_p — while the
+    optimiser's raw HIP writes move none.  So write() records the counters and stale() compares them (one attribute read per parameter:
+    ~0.1 ms of host time for the ~700 parameters of ADNM-UNet, run ahead of the device).  Writes torch cannot see — through p.data, a
+    raw device pointer, a DLPack alias — need an explicit FlatTrainer.refresh_shadows()."""
+
+    def __init__(self, flat_p, shadow, mode, offs, rows, params):
+        self.flat_p, self.shadow, self.mode = flat_p, shadow, mode
+        self.dev = flat_p.device
+        self.lo, self.hi = flat_p.data_ptr(), flat_p.data_ptr() + 4 * flat_p.numel()
+        self.starts, self.rows, self.params = list(offs), list(rows), list(params)
+        ends = [o // 4 for o in self.starts[1:]] + [flat_p.numel() // 4]
+        self.seg_end = torch.tensor(ends, dtype=torch.int32, device=self.dev)
+        self.seg_rec = torch.tensor(self.rows, dtype=torch.int32, device=self.dev)
+        wrows = [r for r in self.rows if r >= 0]
+        self._wrows = torch.tensor(wrows, dtype=torch.long, device=self.dev) if wrows else None
+        self.valid = False
+        self._vers = None   # version counters of params[...] and flat_p (last) when the shadow was last written
+        self.writes = 0
+
+    def _versions(self):
+        v = list(map(_VERSION, self.params))
+        v.append(self.flat_p._version)
+        return v
+
+    def stale(self):
+        return not self.valid or self._versions() != self._vers
+
+    def mark_current(self):
+        """the shadow was restored together with the parameters (FlatTrainer.prepare's tail warm-up): take the counters as they are now"""
+        self._vers = self._versions()
+
+    def write(self, collect_only=False):
+        """the shadow from the parameters as they are, fp8 with the weight records' scales as they are.  collect_only (fp8): only gather
+        max |w| into the weight records whose flag is set, no shadow written.  Outside a capture."""
+        tab = QUANT.table_ptr(self.dev) if self.mode == 2 else None
+        lib.call("adnm_shadow_refresh", self.flat_p.data_ptr(), self.flat_p.numel(), None if collect_only else self.shadow.data_ptr(), self.mode,
+                 self.seg_end.data_ptr(), self.seg_rec.data_ptr(), self.seg_end.numel(), tab, int(collect_only or self.mode == 2), _stream())
+        if not collect_only:
+            self._vers = self._versions()
+            self.valid = True
+            self.writes += 1
+
+    def rescale(self):
+        """fp8: the scale_b of every WEIGHT record from max |w| of its weight as it is now, by adnm_quant_update's formula
+        scale_b = fmax_b / (amax_b * headroom) in fp32 (an all-zero weight keeps its scale), amax cleared afterwards and the record
+        flags put back.  Weight records only: the activation / gradient records stay on their delayed-scaling schedule."""
+        if self.mode != 2 or self._wrows is None:
+            return
+        r = self._wrows
+        tab = QUANT.table(self.dev)
+        flags = tab[r, 6].clone()
+        tab[r, 3] = 0.0
+        tab[r, 6] = 1.0
+        self.write(collect_only=True)
+        amax, fmax, old = tab[r, 3].cpu(), tab[r, 5].cpu(), tab[r, 1].cpu()   # (IEEE fp32 division on the host: a few hundred records)
+        scale = torch.where((amax > 0) & (fmax > 0), fmax / (amax * torch.tensor(QUANT.headroom, dtype=torch.float32)), old)
+        tab[r, 1] = scale.to(self.dev)
+        tab[r, 3] = 0.0
+        tab[r, 6] = flags
+
+    def refresh(self):
+        if _capturing():
+            raise RuntimeError("adnm_hip: the narrow shadow cannot be rewritten inside a hipGraph capture")
+        self.rescale()
+        self.write()
+
+    def ensure_current(self):
+        """rewrite the shadow if it is stale.  -> False only inside a capture with a stale shadow (it cannot be rewritten there)"""
+        if not self.stale():
+            return True
+        if _capturing():
+            return False
+        self.refresh()
+        return True
+
+
 class ShadowRegistry:
     """Narrow SHADOW copies of the GEMM weights (include/adnm_hip.h: adnm_adamw_step `shadow`, adnm_skgemm `b_dtype`).  A FlatTrainer keeps,
     beside its flat fp32 parameter buffer, one buffer of the same element layout in bf16 (bf16 configuration) or per-tensor scaled OCP
     e4m3 (fp8 configuration), rewritten by the optimiser pass that updates the parameters.  The weight-streaming GEMMs (k_linear /
     k_linear_dx on the short-GEMM kernels) look their weight up here and read the shadow instead of the fp32 values: half / a quarter of
     the bytes of the two passes that stream the 72 M parameters every step, bit for bit the result of rounding the fp32 operand the
-    same way.  Outside a trainer (plain autograd use) nothing is registered and the kernels convert the fp32 weight on the fly."""
+    same way.  Outside a trainer (plain autograd use) nothing is registered and the kernels convert the fp32 weight on the fly.
+    Coherence (ShadowSet): lookup() never hands out a stale shadow — a parameter written through torch since the shadow was last written
+    (load_state_dict, an in-place op) makes it rewrite the shadow first (inside a capture, where it cannot, it returns None: the fp32
+    weight, rounded on the fly).  Captured graphs do no lookups: FlatTrainer.step and GraphedForward check before they replay, and a
+    GraphedForward keeps the ShadowSets it captured against (sets()) alive as long as its graphs."""
 
     def __init__(self):
         self._lock = threading.Lock()
-        self._own = {}   # owner id -> entry
+        self._own = {}   # owner id -> ShadowSet
 
-    def register(self, owner, flat_p, shadow, b_dtype, seg_start, seg_row):
-        """seg_start: sorted element offsets of the tensors inside flat_p; seg_row[k]: QUANT row of tensor k's weight record (fp8) or -1"""
+    def register(self, owner, sset):
         with self._lock:
-            self._own[owner] = {"lo": flat_p.data_ptr(), "hi": flat_p.data_ptr() + 4 * flat_p.numel(), "shadow": shadow, "dt": b_dtype,
-                                "starts": list(seg_start), "rows": list(seg_row), "dev": flat_p.device, "valid": False}
-
-    def set_valid(self, owner, ok=True):
-        with self._lock:
-            if owner in self._own:
-                self._own[owner]["valid"] = ok
+            self._own[owner] = sset
 
     def drop(self, owner):
         self._own.pop(owner, None)   # (atomic: callable from a finaliser)
+
+    def sets(self, device=None):
+        """the live ShadowSets (of `device`)"""
+        return [s for s in list(self._own.values()) if device is None or s.dev == torch.device(device)]
 
     def lookup(self, w, prec):
         """-> (shadow pointer of w, b_dtype, scale tensor or None) when the weight tensor `w` lies in a registered flat buffer whose shadow
@@ -777,19 +871,21 @@ class ShadowRegistry:
         if not self._own or prec == 0 or QUANT.calibrating:
             return None
         ptr = w.data_ptr()
-        for ent in list(self._own.values()):
-            if ent["lo"] <= ptr < ent["hi"] and ent["valid"]:
-                if (ent["dt"] == 1) != (prec == 1):
+        for s in list(self._own.values()):
+            if s.lo <= ptr < s.hi and s.valid:
+                if (s.mode == 1) != (prec == 1):
                     return None
-                off = (ptr - ent["lo"]) // 4
-                if ent["dt"] == 1:
-                    return ent["shadow"].data_ptr() + 2 * off, 1, None
-                import bisect
-                k = bisect.bisect_right(ent["starts"], off) - 1
-                row = ent["rows"][k]
+                off = (ptr - s.lo) // 4
+                k = bisect.bisect_right(s.starts, off) - 1
+                vers = s._vers
+                if (s.params[k]._version != vers[k] or s.flat_p._version != vers[-1]) and not s.ensure_current():
+                    return None
+                if s.mode == 1:
+                    return s.shadow.data_ptr() + 2 * off, 1, None
+                row = s.rows[k]
                 if row < 0:
                     return None
-                return ent["shadow"].data_ptr() + off, 2, QUANT.scale_b_view(ent["dev"], row)
+                return s.shadow.data_ptr() + off, 2, QUANT.scale_b_view(s.dev, row)
         return None
 
 

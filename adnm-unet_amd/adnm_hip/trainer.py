@@ -97,6 +97,7 @@ class FlatTrainer:
         self.flat_g = None
         self.buckets = []
         self._steps = 0
+        self._shadow = None   # ops.ShadowSet of the narrow shadow (bf16 / fp8 configurations)
 
     # ------------------------------------------------------------------ one-time setup
     def _fwd_bwd(self, x, tgt):
@@ -203,10 +204,10 @@ class FlatTrainer:
         return [(j, lo, hi, (hi - lo) * eb) for j, (lo, hi) in enumerate(self.buckets)]
 
     def _setup_shadows(self, mode):
-        """The narrow SHADOW of the flat parameter buffer (ops.ShadowRegistry; include/adnm_hip.h: adnm_adamw_step): mode 1 = bf16, 2 = per-tensor
-        scaled e4m3 (weight records in ops.QUANT's table, one per matrix-shaped parameter), rewritten by every optimiser pass.  The
-        weight-streaming GEMMs read it instead of the fp32 values.  mode 0 (exact fp32, CPU, ADNM_NARROW_WEIGHTS=0): none."""
-        self.shadow, self.shadow_mode = None, 0
+        """The narrow SHADOW of the flat parameter buffer (ops.ShadowRegistry / ops.ShadowSet; include/adnm_hip.h: adnm_adamw_step): mode 1 =
+        bf16, 2 = per-tensor scaled e4m3 (weight records in ops.QUANT's table, one per matrix-shaped parameter), rewritten by every
+        optimiser pass.  The weight-streaming GEMMs read it instead of the fp32 values.  mode 0 (exact fp32, CPU, ADNM_NARROW_WEIGHTS=0): none."""
+        self.shadow, self.shadow_mode, self._shadow = None, 0, None
         import os
         if mode == 0 or not self.fused or not self.flat_p.is_cuda or os.environ.get("ADNM_NARROW_WEIGHTS", "1") == "0":
             return
@@ -216,23 +217,24 @@ class FlatTrainer:
         rows = []
         for p in self.used:   # fp8: a record per GEMM-shaped weight (every other tensor: no scale, its shadow bytes are never read)
             rows.append(ops.QUANT.weight_row(dev, p.data_ptr()) if (mode == 2 and p.dim() >= 2 and p.numel() >= 1024) else -1)
-        ends = [o // 4 for o in self.offs[1:]] + [self.n // 4]
-        self.seg_end = torch.tensor(ends, dtype=torch.int32, device=dev)
-        self.seg_rec = torch.tensor(rows, dtype=torch.int32, device=dev)
-        ops.SHADOWS.register(id(self), self.flat_p, self.shadow, mode, self.offs, rows)
+        self._shadow = ops.ShadowSet(self.flat_p, self.shadow, mode, self.offs, rows, self.used)
+        self.seg_end, self.seg_rec = self._shadow.seg_end, self._shadow.seg_rec
+        ops.SHADOWS.register(id(self), self._shadow)
 
     def refresh_shadows(self, collect_only=False):
-        """rewrite the shadow from the parameters as they are (after they moved into the flat buffer; after a checkpoint was loaded into a
-        prepared trainer).  collect_only (fp8): only gather max |w| per weight record — the first calibration."""
-        if not getattr(self, "shadow_mode", 0):
+        """Rewrite the narrow shadow from the parameters as they are.  step(), the eager GEMMs' shadow lookups and GraphedForward do this
+        by themselves after every write torch can see (load_state_dict / checkpoint.load_reference_checkpoint, an in-place op on a
+        parameter or a view of it, a write through flat_p: ops.ShadowSet); call it after a write torch cannot see — through p.data, a raw
+        device pointer, a DLPack alias — before the next forward or step.  fp8: first re-derives the scale_b of every WEIGHT record from
+        max |w| as it is now (adnm_quant_update's formula), so that new weights are not quantised with the old weights' scales (and
+        saturate at 448); the activation / gradient records stay on their delayed-scaling schedule.  Not inside a hipGraph capture.
+        collect_only (fp8, prepare's first calibration): only gather max |w| per weight record."""
+        if self._shadow is None:
             return
-        dev = self.flat_p.device
-        tab = ops.QUANT.table_ptr(dev) if self.shadow_mode == 2 else None
-        lib.call("adnm_shadow_refresh", self.flat_p.data_ptr(), self.n, None if collect_only else self.shadow.data_ptr(), self.shadow_mode,
-                 self.seg_end.data_ptr(), self.seg_rec.data_ptr(), self.seg_end.numel(), tab, int(collect_only or self.shadow_mode == 2),
-                 torch.cuda.current_stream().cuda_stream)
-        if not collect_only:
-            ops.SHADOWS.set_valid(id(self), True)
+        if collect_only:
+            self._shadow.write(collect_only=True)
+        else:
+            self._shadow.refresh()
 
     def close(self):
         """Give back everything this trainer owns on the device, in a fixed order, NOW (not whenever the cyclic collector gets to
@@ -393,7 +395,7 @@ class FlatTrainer:
                 self._run_eager(x, tgt)                       # bf16 operands, fp32 weights: every call site's activation / gradient maxima
                 ops.QUANT.calibrating = False
                 ops.QUANT.update(x.device)                    # -> the first scales, weights included
-                self.refresh_shadows()                        # the e4m3 shadow, written with them
+                self._shadow.write()                          # the e4m3 shadow, written with them
                 for p in self.used:
                     p.grad = None
             else:
@@ -468,6 +470,8 @@ class FlatTrainer:
                         dst.copy_(src)
                 if qsave is not None:
                     ops.QUANT.restore(x.device, qsave)
+                if self._shadow is not None:   # (parameters and shadow restored together: the copy moved flat_p's version counter)
+                    self._shadow.mark_current()
 
     def _wire_cast(self, j):
         """fp32 -> bf16 copy of bucket j into the wire buffer (captured at the end of stage graph j)"""
@@ -541,6 +545,8 @@ class FlatTrainer:
         per-launch HIP events cannot be recorded inside a graph replay)."""
         if self.used is None:
             self.prepare(x, tgt)
+        elif self._shadow is not None and self._shadow.stale():   # a write outside the optimiser (a checkpoint load, an in-place op)
+            self._shadow.refresh()
         pending = []
         nb = len(self.buckets)
         graphed = False

@@ -226,3 +226,62 @@ def test_flat_trainer_refuses_unclaimed_and_doubly_claimed_parameters():
     tr = FlatTrainer(M((lambda m: [m.a, m.b], lambda m: [m.b])), loss, use_graph=False, fused=False, overlap=True)
     with pytest.raises(RuntimeError, match="more than one stage"):
         tr.prepare(x, t)
+
+
+def test_shadow_staleness_rule_on_cpu_tensors(monkeypatch):
+    """ops.ShadowSet / ShadowRegistry on CPU tensors (pointer arithmetic and version counters; the device rewrite is replaced by a
+    recorder): after a write torch performs on a re-homed parameter — an in-place op, load_state_dict, a write through the flat buffer —
+    lookup() rewrites the shadow before it hands it out, and only then.  A write through p.data is invisible (refresh_shadows())."""
+    from adnm_hip import ops
+    m = nn.Sequential(nn.Linear(8, 16), nn.Linear(16, 4))
+    params = list(m.parameters())
+    offs, n = [], 0
+    for p in params:
+        offs.append(n)
+        n += (p.numel() + 3) // 4 * 4
+    flat = torch.zeros(n)
+    for p, o in zip(params, offs):   # re-homed as FlatTrainer._flatten does
+        view = flat[o:o + p.numel()].view_as(p)
+        view.copy_(p.data)
+        p.data = view
+    shadow = torch.zeros(n, dtype=torch.bfloat16)
+    s = ops.ShadowSet(flat, shadow, 1, offs, [-1] * len(params), params)
+    writes = []
+
+    def write(collect_only=False):
+        writes.append(collect_only)
+        shadow.copy_(flat.to(torch.bfloat16))
+        s.mark_current()
+        s.valid = True
+    monkeypatch.setattr(s, "write", write)
+    reg = ops.ShadowRegistry()
+    reg.register("trainer", s)
+    w = params[2]   # the second Linear's weight
+    off = offs[2]
+    assert reg.lookup(w, 1) is None and not writes   # never written: not handed out
+    s.refresh()
+    assert writes == [False] and not s.stale()
+    assert reg.lookup(w, 1) == (shadow.data_ptr() + 2 * off, 1, None) and len(writes) == 1
+    assert reg.lookup(w, 2) is None and reg.lookup(w, 0) is None   # the bf16 shadow serves bf16 operands only
+    assert reg.lookup(torch.zeros(4), 1) is None   # outside the flat buffer
+
+    with torch.no_grad():
+        w.mul_(2.0)   # in-place op
+    assert s.stale()
+    assert reg.lookup(w, 1) is not None and len(writes) == 2 and torch.equal(shadow, flat.to(torch.bfloat16))
+    with torch.no_grad():
+        w[:2].zero_()   # through a view of the parameter
+    assert reg.lookup(w, 1) is not None and len(writes) == 3
+
+    m.load_state_dict({k: torch.full_like(v, 0.25) for k, v in m.state_dict().items()})
+    assert s.stale()
+    assert reg.lookup(w, 1) is not None and len(writes) == 4 and float(shadow[off]) == 0.25
+
+    flat.add_(1.0)   # through the flat buffer
+    assert reg.lookup(params[0], 1) is not None and len(writes) == 5
+
+    params[0].data.copy_(torch.ones_like(params[0]))   # p.data: a new alias with its own counter — not visible
+    assert not s.stale() and reg.lookup(params[0], 1) is not None and len(writes) == 5
+
+    reg.drop("trainer")
+    assert reg.lookup(w, 1) is None and reg.sets() == []

@@ -8,7 +8,7 @@ import torch.nn.functional as F
 
 import adnm_oracle as O
 from adnm_hip import ops, lib, recipe
-from util import load_case, load_npz, assert_close
+from util import load_case, load_npz, assert_close, _e4m3_bytes
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -1164,11 +1164,6 @@ def test_tsgemm_bf16_token_storage(M, K, N, bf16_mfma):
     assert_close(dw, cb.double().t() @ xb.double(), 1e-5, "dw from bf16 rows")
     dw2, _ = ops.k_linear_dw(cot.to(DEV), xb, False)                      # mixed: fp32 gradient rows, bf16 activations
     assert_close(dw2, cot.double().to(DEV).t() @ xb.double(), 1e-5, "dw from fp32 x bf16 rows")
-
-
-def _e4m3_bytes(t):
-    """e4m3 bytes of an fp32 tensor (saturating), as the kernels write them"""
-    return t.clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
 
 
 @pytest.mark.parametrize("M,K,N", [(64, 1024, 512), (1024, 256, 1216), (64, 4096, 1024), (256, 1024, 4672), (1024, 512, 2368), (16, 2048, 512)])

@@ -109,6 +109,48 @@ def test_benchmarked_workload_step_vs_reference_fixture():
     check_update_deltas(z, names, [p.detach().double() - b for p, b in zip(model.parameters(), before)])
 
 
+def test_benchmarked_workload_bf16_with_shadow():
+    """bench.py's configuration as it is timed: B=4, 128x128, recipe batch "bench", bf16 matrix-core operands, the bf16 weight shadow,
+    hipGraph replay.  First step against the reference's fp32 fixture (visionmamba_128_b4) within bf16 bars; 20 steps train (finite
+    parameters, the loss goes down) and leave the shadow bit for bit bf16(p)."""
+    from models.ADNMUNet import create_ADNMUNet
+    from models.loss import enRainfallLoss
+    from adnm_hip import ops
+    from util import load_npz
+    z = load_npz("visionmamba_128_b4")
+    frames = recipe.radar_batch(4, 25, 128, name="bench").to(DEV)
+    x, tgt = frames[:, :5].contiguous(), frames[:, 5:].contiguous()
+    ops.set_mfma_precision("bf16")
+    try:
+        model = create_ADNMUNet(5, 20, 6, img_size=128)
+        recipe.fill_parameters(model)
+        model = model.to(DEV).train()
+        tr = FlatTrainer(model, enRainfallLoss(0.57, 0.25, gamma=0.0), lr=1e-3, betas=(0.9, 0.999), eps=1e-9, weight_decay=1e-2, max_norm=0.025,
+                         use_graph=True)
+        try:
+            losses = [float(tr.step(x, tgt))]
+            norm = float(tr.grad_norm())
+            for _ in range(19):
+                losses.append(float(tr.step(x, tgt)))
+            torch.cuda.synchronize()
+            assert tr.shadow_mode == 1 and tr.graph is not None
+            dl = abs(losses[0] - float(z["loss"])) / abs(float(z["loss"]))
+            dn = abs(norm - float(z["clip_pre_norm"])) / float(z["clip_pre_norm"])
+            print(f"bf16 bench workload: first-step loss {losses[0]:.6f} ({dl:.2e} from the fp32 reference), pre-clip norm {norm:.6f} ({dn:.2e}); "
+                  f"loss after 20 steps {losses[-1]:.6f}")
+            assert dl <= 0.02, f"first-step loss {losses[0]} vs reference {float(z['loss'])}"
+            assert dn <= 0.05, f"first-step pre-clip norm {norm} vs reference {float(z['clip_pre_norm'])}"
+            bad = [k for k, p in model.named_parameters() if not bool(torch.isfinite(p).all())]
+            assert not bad, f"non-finite parameters after 20 steps: {bad[:5]}"
+            assert losses[-1] < losses[0], losses
+            assert torch.equal(tr.shadow, tr.flat_p.to(torch.bfloat16)), "the shadow is bf16(p) after every step"
+        finally:
+            tr.close()
+    finally:
+        ops.set_mfma_precision("f32")
+        ops.QUANT.reset()
+
+
 def test_deferred_folds_are_neutral_and_deterministic():
     """Batching the second-stage fold launches of the parameter gradients and grouping the weight-gradient launches (ops.FOLDS /
     adnm_foldq_* / adnm_leafq_*) must not change the step beyond fp32 summation order — a queued weight gradient splits its reduction

@@ -61,3 +61,8 @@ def check_update_deltas(z, names, deltas, lr=1e-3):
         elif n > 1:
             assert abs(float(d.sum()) - float(z["delta_sum"][i])) <= 3 * lr * n ** 0.5 + 0.05 * lr * n, f"{k}: update sum"
     assert checked_scalars >= 30, checked_scalars
+
+
+def _e4m3_bytes(t):
+    """e4m3 bytes of an fp32 tensor (saturating), as the kernels write them"""
+    return t.clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
