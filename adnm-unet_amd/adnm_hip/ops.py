@@ -1122,6 +1122,36 @@ def k_instnorm_bwd(dy, x, scale, shift, mu, rstd, B, HW, C, act, want_affine=Tru
     return dx, dsc, dsh
 
 
+def k_groupnorm_fwd(x, groups, weight, bias, scale, shift, B, HW, C, eps, act):
+    _need_gpu(x)
+    assert x.is_contiguous()
+    dev = x.device
+    y = torch.empty_like(x)
+    mu = torch.empty((B, groups), dtype=torch.float32, device=dev)
+    rstd = torch.empty((B, groups), dtype=torch.float32, device=dev)
+    nb = lib.query("adnm_groupnorm_ws_bytes", B, HW, C, groups)
+    ws = _ws(nb, dev)
+    lib.call("adnm_groupnorm_fwd", x.data_ptr(), _p(_f32(weight)), _p(_f32(bias)), _p(scale), _p(shift), y.data_ptr(), mu.data_ptr(),
+             rstd.data_ptr(), ws.data_ptr(), nb, B, HW, C, groups, float(eps), act, _dt(x), _stream())
+    return y, mu, rstd
+
+
+def k_groupnorm_bwd(dy, x, groups, weight, bias, scale, shift, mu, rstd, B, HW, C, act, want_affine=True):
+    dev = x.device
+    assert dy.is_contiguous() and x.is_contiguous()
+    dx = torch.empty_like(x)
+    dw = grad_dst(weight.data_ptr(), (C,), dev) if weight is not None else None
+    db = grad_dst(bias.data_ptr(), (C,), dev) if bias is not None else None
+    dsc = grad_dst(scale.data_ptr() if scale is not None else 0, (), dev) if want_affine else None
+    dsh = grad_dst(shift.data_ptr() if shift is not None else 0, (), dev) if want_affine else None
+    nb = lib.query("adnm_groupnorm_ws_bytes", B, HW, C, groups)
+    ws = _ws(nb, dev)
+    with FOLDS.defer(dev, ws):   # d gamma / d beta / d scale / d shift: parameter gradients (partials + the shared fold)
+        lib.call("adnm_groupnorm_bwd", dy.data_ptr(), x.data_ptr(), _p(weight), _p(bias), _p(scale), _p(shift), mu.data_ptr(), rstd.data_ptr(),
+                 dx.data_ptr(), _p(dw), _p(db), _p(dsc), _p(dsh), ws.data_ptr(), nb, B, HW, C, groups, act, _dt(x), _stream())
+    return dx, dw, db, dsc, dsh
+
+
 def k_gate_fwd(h, F):
     _need_gpu(h)
     M = h.shape[0]
@@ -1357,6 +1387,35 @@ class InstNormFn(torch.autograd.Function):
 
 def instnorm(x, scale=None, shift=None, eps=1e-5, act=lib.ACT_NONE):
     return InstNormFn.apply(x, scale, shift, eps, act)
+
+
+class GroupNormFn(torch.autograd.Function):
+    """act(scale * GroupNorm(groups, C)(x) + shift) on (B, H*W, C) tokens; weight / bias: the GroupNorm's per-channel affine (or None)."""
+
+    @staticmethod
+    def forward(ctx, x, groups, weight, bias, scale, shift, eps, act):
+        B, L, C = x.shape
+        x = x.contiguous()
+        y, mu, rstd = k_groupnorm_fwd(x, groups, weight, bias, scale, shift, B, L, C, eps, act)
+        ctx.save_for_backward(x, weight, bias, scale, shift, mu, rstd)
+        ctx.groups, ctx.act = groups, act
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, bias, scale, shift, mu, rstd = ctx.saved_tensors
+        B, L, C = x.shape
+        dx, dw, db, dsc, dsh = k_groupnorm_bwd(dy.contiguous(), x, ctx.groups, weight, bias, scale, shift, mu, rstd, B, L, C, ctx.act)
+        return dx, None, dw, db, dsc if scale is not None else None, dsh if shift is not None else None, None, None
+
+
+def groupnorm_supported(groups, C):
+    """the shapes the HIP GroupNorm takes: whole channel quads per group"""
+    return C % 4 == 0 and groups > 0 and C % groups == 0 and (C // groups) % 4 == 0
+
+
+def groupnorm(x, groups, weight=None, bias=None, scale=None, shift=None, eps=1e-5, act=lib.ACT_NONE):
+    return GroupNormFn.apply(x, groups, weight, bias, scale, shift, eps, act)
 
 
 class GateFn(torch.autograd.Function):
@@ -2270,12 +2329,15 @@ def colsum(t, out=None, defer=False):
     return out
 
 
-def k_linear_dw(dy2, x2, want_bias, w_ptr=0, b_ptr=0, dw_out=None):
+def k_linear_dw(dy2, x2, want_bias, w_ptr=0, b_ptr=0, dw_out=None, now=False):
     """dW = dY^T X (N,K), dbias = column sums of dY.  w_ptr / b_ptr: data_ptr of the parameters (gradient-destination lookup);
-    dw_out: an explicit contiguous (N,K) destination instead."""
+    dw_out: an explicit contiguous (N,K) destination instead.  now: the caller reads dW / dbias right away (they are not parameter
+    gradients), so neither the GEMM nor its fold may wait in a queue."""
     M, N = dy2.shape
     K = x2.shape[1]
     dev = x2.device
+    if now:
+        FOLDS.hold(dev)
     dw = dw_out if dw_out is not None else grad_dst(w_ptr, (N, K), dev)
     db = grad_dst(b_ptr, (N,), dev) if want_bias else None
     if ts_ok_tn(M, N, K, x2):
@@ -2307,6 +2369,7 @@ class LinearFn(torch.autograd.Function):
         ctx.save_for_backward(x2, w)
         ctx.has_bias = bias is not None
         ctx.ptrs = (w.data_ptr(), bias.data_ptr() if bias is not None else 0)
+        ctx.temp_w = qkey is not None   # linear()'s zero-padded copy: autograd slices its gradient as soon as backward returns
         ctx.shp = shp
         return y.view(*shp[:-1], w.shape[0])
 
@@ -2317,7 +2380,7 @@ class LinearFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, N)
         dy2 = dy2 if dy2.stride(-1) == 1 else dy2.contiguous()
         dx = k_linear_dx(dy2, w, qkey=ctx.qkey).view(ctx.shp) if ctx.needs_input_grad[0] else None
-        dw, db = k_linear_dw(dy2, x2, ctx.has_bias, *ctx.ptrs)
+        dw, db = k_linear_dw(dy2, x2, ctx.has_bias, *ctx.ptrs, now=ctx.temp_w)
         return dx, dw, db, None
 
 

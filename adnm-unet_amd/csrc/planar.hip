@@ -2,6 +2,7 @@
 //   * Haar (db1) analysis / synthesis butterflies of WTConv2d (WTConv2d.py:31-51, 111-141)        [K3]
 //   * InstanceNorm2d(affine=False) with the external scalar scale/shift and optional GELU fused
 //     (model_untils.py:90,113 around nn.InstanceNorm2d at :284,371,741,814)                        [K8]
+//   * nn.GroupNorm(G, C) at the same four sites (the long-interval recipe), same fusion, plus its per-channel gamma / beta
 // All are HBM-bound element streams: lane = 4 adjacent channels (16 B), consecutive lanes = consecutive
 // channel quads of a pixel, so every access is a coalesced row segment.
 #include "adnm_common.h"
@@ -300,10 +301,10 @@ __device__ __forceinline__ void merge_partials(const float* __restrict__ part, i
   s2 = *reinterpret_cast<const float4*>(&mout[1][cgl][0]);
 }
 
-// pass 1 of forward: shifted sums.  part[(b,chunk), {S1,S2}, c] with shift K = x[b,0,c]
+// pass 1 of forward: shifted sums.  part[(b,chunk), {S1,S2}, c] with shift K = x[b,0,c] (cpg == 0: InstanceNorm) or, for GroupNorm,
+// K = x[b,0,first channel of c's group]: one shift per group, so the S1 / S2 of a group's channels may simply be added.
 template <typename T>
-__global__ __launch_bounds__(kBlock) void instnorm_stats_kernel(const T* __restrict__ x, float* __restrict__ part, int64_t HW, int C,
-                                                                int cgb, int ppc) {
+__device__ __forceinline__ void shifted_sums(const T* __restrict__ x, float* __restrict__ part, int64_t HW, int C, int cpg, int cgb, int ppc) {
   __shared__ __attribute__((aligned(16))) float smem[3 * 2 * 64 * 4];
   const int C4 = C >> 2;
   const int cgl = threadIdx.x & (cgb - 1), slot = threadIdx.x / cgb, slots = kBlock / cgb;
@@ -312,7 +313,9 @@ __global__ __launch_bounds__(kBlock) void instnorm_stats_kernel(const T* __restr
   const int c = cv ? cg * 4 : 0;
   const int b = blockIdx.z;
   const T* xb = x + (int64_t)b * HW * C + c;
-  const float4 K = Io<T>::ld4(xb);
+  float4 K;
+  if (cpg) K.x = K.y = K.z = K.w = Io<T>::ld(xb - c % cpg);
+  else K = Io<T>::ld4(xb);
   float4 acc[2] = {f4zero(), f4zero()};
   const int64_t p0 = (int64_t)blockIdx.y * ppc;
   const int64_t p1 = p0 + ppc < HW ? p0 + ppc : HW;
@@ -330,6 +333,16 @@ __global__ __launch_bounds__(kBlock) void instnorm_stats_kernel(const T* __restr
     *reinterpret_cast<float4*>(dst + c) = acc[0];
     *reinterpret_cast<float4*>(dst + C + c) = acc[1];
   }
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void instnorm_stats_kernel(const T* __restrict__ x, float* __restrict__ part, int64_t HW, int C,
+                                                                int cgb, int ppc) {
+  shifted_sums<T>(x, part, HW, C, 0, cgb, ppc);
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void groupnorm_stats_kernel(const T* __restrict__ x, float* __restrict__ part, int64_t HW, int C,
+                                                                 int cpg, int cgb, int ppc) {
+  shifted_sums<T>(x, part, HW, C, cpg, cgb, ppc);
 }
 
 __device__ __forceinline__ float4 act4(float4 v, int act) {
@@ -478,6 +491,187 @@ __global__ __launch_bounds__(kBlock) void instnorm_bwd_apply_kernel(const T* __r
   }
 }
 
+
+// ---------------------------------------------------------------------------------------------- GroupNorm
+// nn.GroupNorm(G, C) with its per-channel gamma / beta, the layer's scalar scale / shift and the activation, on InstanceNorm's grid and
+// partial layout; cpg = C / G channels per group, a multiple of 4 (a lane's channel quad lies inside one group).
+
+__device__ __forceinline__ float hsum4(float4 v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float dot4(float4 a, float4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
+__device__ __forceinline__ float4 ld4_or(const float* p, int c, float dflt) {
+  return p ? *reinterpret_cast<const float4*>(p + c) : make_float4(dflt, dflt, dflt, dflt);
+}
+
+// (h1, h2): this lane's channel quad of the merged chunk partials, reduced to one value each (w-weighted when the caller weights).
+// -> (g1, g2): their sums over the quads of the lane's group.  A group that lies inside the workgroup's channel range is added up
+// from LDS; one that does not (cpg > 256, or cpg not a divisor of 256 with C > 256) is re-derived from the partials in global
+// memory, by every workgroup it touches in the same order, so all of them see the same bits.  All threads of the block must call it.
+__device__ __forceinline__ void group_sums(float h1, float h2, const float* __restrict__ part, const float* __restrict__ w, int b,
+                                           int nchunk, int C, int c, bool cv, int cgb, int cpg, float& g1, float& g2) {
+  __shared__ float gsm[2][64];
+  if (threadIdx.x < cgb) gsm[0][threadIdx.x] = h1, gsm[1][threadIdx.x] = h2;
+  __syncthreads();
+  g1 = g2 = 0.f;
+  if (!cv) return;
+  const int qpg = cpg >> 2, q0 = c / cpg * qpg, base = blockIdx.x * cgb;
+  if (q0 >= base && q0 + qpg <= base + cgb) {
+    for (int q = q0 - base; q < q0 - base + qpg; ++q) g1 += gsm[0][q], g2 += gsm[1][q];
+  } else {
+    for (int q = q0; q < q0 + qpg; ++q) {
+      float4 a = f4zero(), s = f4zero();
+      for (int k = 0; k < nchunk; ++k) {
+        const float* src = part + ((int64_t)b * nchunk + k) * 2 * C + q * 4;
+        const float4 ak = *reinterpret_cast<const float4*>(src), sk = *reinterpret_cast<const float4*>(src + C);
+        a.x += ak.x; a.y += ak.y; a.z += ak.z; a.w += ak.w;
+        s.x += sk.x; s.y += sk.y; s.z += sk.z; s.w += sk.w;
+      }
+      const float4 wq = ld4_or(w, q * 4, 1.f);
+      g1 += dot4(wq, a), g2 += dot4(wq, s);
+    }
+  }
+}
+
+// pass 2 of forward: merge chunk partials and the group's channels -> mu, rstd (saved once per (b, group)), normalise.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void groupnorm_apply_kernel(const T* __restrict__ x, const float* __restrict__ part,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                 T* __restrict__ y, float* __restrict__ mu_out, float* __restrict__ rstd_out,
+                                                                 int64_t HW, int C, int cpg, int cgb, int ppc, int nchunk, float eps, int act) {
+  const int C4 = C >> 2;
+  const int cgl = threadIdx.x & (cgb - 1), slot = threadIdx.x / cgb, slots = kBlock / cgb;
+  const int cg = blockIdx.x * cgb + cgl;
+  const bool cv = cg < C4;
+  const int c = cv ? cg * 4 : 0;
+  const int b = blockIdx.z;
+  float4 s1, s2;
+  merge_partials(part, b, nchunk, C, c, cv, cgb, s1, s2);
+  float g1, g2;
+  group_sums(hsum4(s1), hsum4(s2), part, nullptr, b, nchunk, C, c, cv, cgb, cpg, g1, g2);
+  if (!cv) return;
+  const T* xb = x + (int64_t)b * HW * C + c;
+  T* yb = y + (int64_t)b * HW * C + c;
+  const float K = Io<T>::ld(xb - c % cpg);
+  const float inv = 1.0f / ((float)HW * (float)cpg);
+  const float m = g1 * inv;  // mean of (x-K)
+  const float rstd = rsqrtf(fmaxf(g2 * inv - m * m, 0.f) + eps);
+  if (blockIdx.y == 0 && slot == 0 && c % cpg == 0) {
+    const int64_t at = (int64_t)b * (C / cpg) + c / cpg;
+    mu_out[at] = K + m;
+    rstd_out[at] = rstd;
+  }
+  const float sc = scale ? *scale : 1.f, sh = shift ? *shift : 0.f;
+  const float4 ga = ld4_or(gamma, c, 1.f), be = ld4_or(beta, c, 0.f);
+  const float4 a = make_float4(sc * ga.x * rstd, sc * ga.y * rstd, sc * ga.z * rstd, sc * ga.w * rstd);
+  const float4 o0 = make_float4(fmaf(sc, be.x, sh), fmaf(sc, be.y, sh), fmaf(sc, be.z, sh), fmaf(sc, be.w, sh));
+  const int64_t p0 = (int64_t)blockIdx.y * ppc;
+  const int64_t p1 = p0 + ppc < HW ? p0 + ppc : HW;
+  for (int64_t p = p0 + slot; p < p1; p += slots) {
+    const float4 v = Io<T>::ld4(xb + p * C);
+    // (x - K) - m, not x - (K + m): the rounding of the mean to fp32 stays out of the result when |mean| >> spread
+    float4 o = make_float4(fmaf((v.x - K) - m, a.x, o0.x), fmaf((v.y - K) - m, a.y, o0.y), fmaf((v.z - K) - m, a.z, o0.z),
+                           fmaf((v.w - K) - m, a.w, o0.w));
+    Io<T>::st4(yb + p * C, act4(o, act));
+  }
+}
+
+// backward pass 1: per (b,chunk,c) sums of scale*dpre and scale*dpre*xhat, dpre = dy * act'(scale*(gamma*xhat+beta)+shift): summed over
+// (b,chunk) they are d beta and d gamma; per workgroup, sum dpre and sum dpre*(gamma*xhat+beta) for d shift and d scale.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void groupnorm_bwd_stats_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                     const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                     const float* __restrict__ mu_in, const float* __restrict__ rstd_in,
+                                                                     float* __restrict__ part, float* __restrict__ spart, int64_t HW, int C,
+                                                                     int cpg, int cgb, int ppc, int act) {
+  __shared__ __attribute__((aligned(16))) float smem[3 * 2 * 64 * 4];
+  const int C4 = C >> 2;
+  const int cgl = threadIdx.x & (cgb - 1), slot = threadIdx.x / cgb, slots = kBlock / cgb;
+  const int cg = blockIdx.x * cgb + cgl;
+  const bool cv = cg < C4;
+  const int c = cv ? cg * 4 : 0;
+  const int b = blockIdx.z;
+  const T* xb = x + (int64_t)b * HW * C + c;
+  const T* db = dy + (int64_t)b * HW * C + c;
+  const float mu = mu_in[(int64_t)b * (C / cpg) + c / cpg], rs = rstd_in[(int64_t)b * (C / cpg) + c / cpg];
+  const float sc = scale ? *scale : 1.f, sh = shift ? *shift : 0.f;
+  const float4 ga = ld4_or(gamma, c, 1.f), be = ld4_or(beta, c, 0.f);
+  float4 acc[2] = {f4zero(), f4zero()};
+  const int64_t p0 = (int64_t)blockIdx.y * ppc;
+  const int64_t p1 = p0 + ppc < HW ? p0 + ppc : HW;
+  if (cv)
+    for (int64_t p = p0 + slot; p < p1; p += slots) {
+      const float4 v = Io<T>::ld4(xb + p * C), g = Io<T>::ld4(db + p * C);
+      const float4 xh = make_float4((v.x - mu) * rs, (v.y - mu) * rs, (v.z - mu) * rs, (v.w - mu) * rs);
+      const float4 ag = actg4(make_float4(fmaf(sc, fmaf(ga.x, xh.x, be.x), sh), fmaf(sc, fmaf(ga.y, xh.y, be.y), sh),
+                                          fmaf(sc, fmaf(ga.z, xh.z, be.z), sh), fmaf(sc, fmaf(ga.w, xh.w, be.w), sh)), act);
+      const float4 dp = make_float4(g.x * ag.x, g.y * ag.y, g.z * ag.z, g.w * ag.w);
+      acc[0].x += dp.x; acc[0].y += dp.y; acc[0].z += dp.z; acc[0].w += dp.w;
+      acc[1].x = fmaf(dp.x, xh.x, acc[1].x); acc[1].y = fmaf(dp.y, xh.y, acc[1].y);
+      acc[1].z = fmaf(dp.z, xh.z, acc[1].z); acc[1].w = fmaf(dp.w, xh.w, acc[1].w);
+    }
+  fold_slots<2>(acc, cgb, smem);
+  if ((threadIdx.x >> 6) == 0) {
+    const bool mine = (threadIdx.x & 63) < cgb && cv;
+    if (mine) {
+      float* dst = part + ((int64_t)b * gridDim.y + blockIdx.y) * 2 * C;
+      *reinterpret_cast<float4*>(dst + c) = make_float4(sc * acc[0].x, sc * acc[0].y, sc * acc[0].z, sc * acc[0].w);
+      *reinterpret_cast<float4*>(dst + C + c) = make_float4(sc * acc[1].x, sc * acc[1].y, sc * acc[1].z, sc * acc[1].w);
+    }
+    if (spart) {   // one partial row per workgroup for the shared (deferrable) fold, as instnorm_bwd_stats_kernel
+      float a = mine ? hsum4(acc[0]) : 0.f, q = mine ? dot4(ga, acc[1]) + dot4(be, acc[0]) : 0.f;
+      a = wave_sum(a), q = wave_sum(q);
+      if (threadIdx.x == 0) {
+        float* sp = spart + (((int64_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2;
+        sp[0] = a, sp[1] = q;
+      }
+    }
+  }
+}
+
+// backward pass 2: dx = rstd*(scale*gamma*dpre - mean_g(scale*gamma*dpre) - xhat*mean_g(scale*gamma*dpre*xhat))
+template <typename T>
+__global__ __launch_bounds__(kBlock) void groupnorm_bwd_apply_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                                     const float* __restrict__ part, const float* __restrict__ gamma,
+                                                                     const float* __restrict__ beta, const float* __restrict__ scale,
+                                                                     const float* __restrict__ shift, const float* __restrict__ mu_in,
+                                                                     const float* __restrict__ rstd_in, T* __restrict__ dx, int64_t HW,
+                                                                     int C, int cpg, int cgb, int ppc, int nchunk, int act) {
+  const int C4 = C >> 2;
+  const int cgl = threadIdx.x & (cgb - 1), slot = threadIdx.x / cgb, slots = kBlock / cgb;
+  const int cg = blockIdx.x * cgb + cgl;
+  const bool cv = cg < C4;
+  const int c = cv ? cg * 4 : 0;
+  const int b = blockIdx.z;
+  float4 s1, s2;
+  merge_partials(part, b, nchunk, C, c, cv, cgb, s1, s2);
+  const float4 ga = ld4_or(gamma, c, 1.f), be = ld4_or(beta, c, 0.f);
+  float m1, m2;
+  group_sums(dot4(ga, s1), dot4(ga, s2), part, gamma, b, nchunk, C, c, cv, cgb, cpg, m1, m2);
+  if (!cv) return;
+  const T* xb = x + (int64_t)b * HW * C + c;
+  const T* db = dy + (int64_t)b * HW * C + c;
+  T* ob = dx + (int64_t)b * HW * C + c;
+  const float mu = mu_in[(int64_t)b * (C / cpg) + c / cpg], rs = rstd_in[(int64_t)b * (C / cpg) + c / cpg];
+  const float sc = scale ? *scale : 1.f, sh = shift ? *shift : 0.f;
+  const float inv = 1.0f / ((float)HW * (float)cpg);
+  m1 *= inv, m2 *= inv;
+  const float4 sg = make_float4(sc * ga.x, sc * ga.y, sc * ga.z, sc * ga.w);
+  const int64_t p0 = (int64_t)blockIdx.y * ppc;
+  const int64_t p1 = p0 + ppc < HW ? p0 + ppc : HW;
+  for (int64_t p = p0 + slot; p < p1; p += slots) {
+    const float4 v = Io<T>::ld4(xb + p * C), g = Io<T>::ld4(db + p * C);
+    const float4 xh = make_float4((v.x - mu) * rs, (v.y - mu) * rs, (v.z - mu) * rs, (v.w - mu) * rs);
+    const float4 ag = actg4(make_float4(fmaf(sc, fmaf(ga.x, xh.x, be.x), sh), fmaf(sc, fmaf(ga.y, xh.y, be.y), sh),
+                                        fmaf(sc, fmaf(ga.z, xh.z, be.z), sh), fmaf(sc, fmaf(ga.w, xh.w, be.w), sh)), act);
+    float4 o;
+    o.x = rs * (sg.x * g.x * ag.x - m1 - xh.x * m2);
+    o.y = rs * (sg.y * g.y * ag.y - m1 - xh.y * m2);
+    o.z = rs * (sg.z * g.z * ag.z - m1 - xh.z * m2);
+    o.w = rs * (sg.w * g.w * ag.w - m1 - xh.w * m2);
+    Io<T>::st4(ob + p * C, o);
+  }
+}
 
 }  // namespace
 
@@ -642,5 +836,82 @@ extern "C" int adnm_instnorm_bwd(const void* dy, const void* x, const float* sca
   // d shift / d scale: parameter gradients through the shared fold (deferrable: the caller may have bound a fold queue)
   if (spart) adnm_launch_fold("instnorm_bwd_scalar", spart, (int)(B * g.nchunk * g.gx), 2, {dshift, 1}, {dscale, 1}, {nullptr, 0}, {nullptr, 0}, st);
   ADNM_CHECK_LAUNCH("instnorm_bwd");
+  return ADNM_OK;
+}
+
+extern "C" int64_t adnm_groupnorm_ws_bytes(int64_t B, int64_t HW, int64_t C, int64_t G) {
+  if (G <= 0 || C % G) return 0;
+  return adnm_instnorm_ws_bytes(B, HW, C);   // same grid: channel partials + per-workgroup scalar partials
+}
+
+static int groupnorm_check(const char* who, int64_t B, int64_t HW, int64_t C, int64_t G, int act, int dtype, void* ws, int64_t ws_bytes) {
+  ADNM_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && B <= 65535 && C <= (1 << 24), "%s: bad shape B=%lld HW=%lld C=%lld", who, (long long)B,
+               (long long)HW, (long long)C);
+  ADNM_REQUIRE(G > 0 && C % G == 0, "%s: %lld groups do not divide %lld channels", who, (long long)G, (long long)C);
+  ADNM_REQUIRE((C / G) % 4 == 0, "%s: %lld channels per group (C=%lld, G=%lld): must be a multiple of 4 channels per group (a lane's channel quad lies inside one group)",
+               who, (long long)(C / G), (long long)C, (long long)G);
+  ADNM_REQUIRE(act == ADNM_ACT_NONE || act == ADNM_ACT_GELU || act == ADNM_ACT_SILU, "%s: bad activation %d", who, act);
+  ADNM_REQUIRE(dtype == ADNM_F32 || dtype == ADNM_BF16, "%s: bad dtype %d", who, dtype);
+  if (!ws || ws_bytes < adnm_groupnorm_ws_bytes(B, HW, C, G)) {
+    adnm_set_error("%s: workspace %lld < %lld bytes", who, (long long)ws_bytes, (long long)adnm_groupnorm_ws_bytes(B, HW, C, G));
+    return ADNM_EWORKSPACE;
+  }
+  return ADNM_OK;
+}
+
+extern "C" int adnm_groupnorm_fwd(const void* x, const float* gamma, const float* beta, const float* scale, const float* shift, void* y,
+                                  float* mu, float* rstd, void* ws, int64_t ws_bytes, int64_t B, int64_t HW, int64_t C, int64_t G, float eps,
+                                  int act, int dtype, adnm_stream_t stream) {
+  ADNM_REQUIRE(x && y && mu && rstd, "groupnorm_fwd: null pointer");
+  if (int rc = groupnorm_check("groupnorm_fwd", B, HW, C, G, act, dtype, ws, ws_bytes)) return rc;
+  const IGeo g = igeo(HW, C);
+  const dim3 grid(g.gx, g.nchunk, (unsigned)B);
+  hipStream_t st = (hipStream_t)stream;
+  float* part = (float*)ws;
+  const int cpg = (int)(C / G);
+  const double es = dtype == ADNM_F32 ? 4.0 : 2.0;
+  if (dtype == ADNM_F32) {
+    { ADNM_PROF("groupnorm_stats", st, es * B * HW * C); groupnorm_stats_kernel<float><<<grid, kBlock, 0, st>>>((const float*)x, part, HW, (int)C, cpg, g.cgb, g.pix_per_chunk); }
+    { ADNM_PROF("groupnorm_apply", st, es * B * HW * C * 2); groupnorm_apply_kernel<float><<<grid, kBlock, 0, st>>>((const float*)x, part, gamma, beta, scale, shift, (float*)y, mu, rstd, HW,
+                                                            (int)C, cpg, g.cgb, g.pix_per_chunk, g.nchunk, eps, act); }
+  } else {
+    { ADNM_PROF("groupnorm_stats", st, es * B * HW * C); groupnorm_stats_kernel<uint16_t><<<grid, kBlock, 0, st>>>((const uint16_t*)x, part, HW, (int)C, cpg, g.cgb, g.pix_per_chunk); }
+    { ADNM_PROF("groupnorm_apply", st, es * B * HW * C * 2); groupnorm_apply_kernel<uint16_t><<<grid, kBlock, 0, st>>>((const uint16_t*)x, part, gamma, beta, scale, shift, (uint16_t*)y, mu, rstd,
+                                                               HW, (int)C, cpg, g.cgb, g.pix_per_chunk, g.nchunk, eps, act); }
+  }
+  ADNM_CHECK_LAUNCH("groupnorm_fwd");
+  return ADNM_OK;
+}
+
+extern "C" int adnm_groupnorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const float* scale, const float* shift,
+                                  const float* mu, const float* rstd, void* dx, float* dgamma, float* dbeta, float* dscale, float* dshift,
+                                  void* ws, int64_t ws_bytes, int64_t B, int64_t HW, int64_t C, int64_t G, int act, int dtype,
+                                  adnm_stream_t stream) {
+  ADNM_REQUIRE(dy && x && mu && rstd && dx, "groupnorm_bwd: null pointer");
+  if (int rc = groupnorm_check("groupnorm_bwd", B, HW, C, G, act, dtype, ws, ws_bytes)) return rc;
+  const IGeo g = igeo(HW, C);
+  const dim3 grid(g.gx, g.nchunk, (unsigned)B);
+  hipStream_t st = (hipStream_t)stream;
+  float* part = (float*)ws;
+  float* spart = (dscale || dshift) ? part + B * g.nchunk * 2 * C : nullptr;
+  const int cpg = (int)(C / G);
+  const double es = dtype == ADNM_F32 ? 4.0 : 2.0;
+  if (dtype == ADNM_F32) {
+    { ADNM_PROF("groupnorm_bwd_stats", st, es * B * HW * C * 2); groupnorm_bwd_stats_kernel<float><<<grid, kBlock, 0, st>>>((const float*)dy, (const float*)x, gamma, beta, scale, shift, mu, rstd, part,
+                                                                spart, HW, (int)C, cpg, g.cgb, g.pix_per_chunk, act); }
+    { ADNM_PROF("groupnorm_bwd_apply", st, es * B * HW * C * 3); groupnorm_bwd_apply_kernel<float><<<grid, kBlock, 0, st>>>((const float*)dy, (const float*)x, part, gamma, beta, scale, shift, mu, rstd,
+                                                                (float*)dx, HW, (int)C, cpg, g.cgb, g.pix_per_chunk, g.nchunk, act); }
+  } else {
+    { ADNM_PROF("groupnorm_bwd_stats", st, es * B * HW * C * 2); groupnorm_bwd_stats_kernel<uint16_t><<<grid, kBlock, 0, st>>>((const uint16_t*)dy, (const uint16_t*)x, gamma, beta, scale, shift, mu, rstd,
+                                                                   part, spart, HW, (int)C, cpg, g.cgb, g.pix_per_chunk, act); }
+    { ADNM_PROF("groupnorm_bwd_apply", st, es * B * HW * C * 3); groupnorm_bwd_apply_kernel<uint16_t><<<grid, kBlock, 0, st>>>((const uint16_t*)dy, (const uint16_t*)x, part, gamma, beta, scale, shift, mu,
+                                                                   rstd, (uint16_t*)dx, HW, (int)C, cpg, g.cgb, g.pix_per_chunk, g.nchunk, act); }
+  }
+  ADNM_CHECK_LAUNCH("groupnorm_bwd");
+  // parameter gradients through the shared fold (deferrable): the (b,chunk) rows of the channel partials are [d beta | d gamma], the
+  // per-workgroup rows [d shift | d scale]
+  if (dgamma || dbeta) adnm_launch_fold("groupnorm_bwd_affine", part, (int)(B * g.nchunk), (int)(2 * C), {dbeta, (int)C}, {dgamma, (int)C}, {nullptr, 0}, {nullptr, 0}, st);
+  if (spart) adnm_launch_fold("groupnorm_bwd_scalar", spart, (int)(B * g.nchunk * g.gx), 2, {dshift, 1}, {dscale, 1}, {nullptr, 0}, {nullptr, 0}, st);
+  ADNM_CHECK_LAUNCH("groupnorm_bwd");
   return ADNM_OK;
 }

@@ -154,6 +154,11 @@ def _act_code(act):
     return None
 
 
+def _hip_groupnorm(norm, channels):
+    """is `norm` a GroupNorm the HIP kernel takes on `channels` channels?"""
+    return isinstance(norm, nn.GroupNorm) and norm.num_channels == channels and ops.groupnorm_supported(norm.num_groups, channels)
+
+
 class Conv2dLayer(nn.Module):
     """conv -> [scale*norm+shift] -> [act] (model_untils.py:73-93 of the reference)."""
 
@@ -214,11 +219,14 @@ class Conv2dLayer(nn.Module):
 
     def _norm_tokens(self, x, h, w, code):
         n = self.norm
+        fuse = code in (lib.ACT_NONE, lib.ACT_GELU)
         if isinstance(n, nn.InstanceNorm2d) and not n.affine and not n.track_running_stats and x.shape[-1] % 4 == 0:
-            fuse = code in (lib.ACT_NONE, lib.ACT_GELU)
             return ops.instnorm(x, self.scale, self.shift, n.eps, code if fuse else lib.ACT_NONE), fuse
+        if _hip_groupnorm(n, x.shape[-1]):
+            return ops.groupnorm(x, n.num_groups, n.weight, n.bias, self.scale, self.shift, n.eps, code if fuse else lib.ACT_NONE), fuse
         raise RuntimeError(f"Conv2dLayer: no HIP kernel for the norm {n} on {x.shape[-1]} channels (affine-less InstanceNorm2d on a multiple "
-                           "of 4 channels is implemented; the HIP path has no PyTorch fallback)")
+                           "of 4 channels and GroupNorm with a multiple of 4 channels per group are implemented; the HIP path has no "
+                           "PyTorch fallback)")
 
     def _keeps_shape(self):
         c = self.conv
@@ -268,9 +276,13 @@ class WTConvLayer(nn.Module):
             if isinstance(n, nn.InstanceNorm2d) and not n.affine and x.shape[-1] % 4 == 0 and code in (lib.ACT_NONE, lib.ACT_GELU):
                 x = ops.instnorm(x, self.scale, self.shift, n.eps, code)  # IN + scalar affine + GELU in one pass
                 fused = True
+            elif _hip_groupnorm(n, x.shape[-1]) and code in (lib.ACT_NONE, lib.ACT_GELU):
+                x = ops.groupnorm(x, n.num_groups, n.weight, n.bias, self.scale, self.shift, n.eps, code)
+                fused = True
             else:
                 raise RuntimeError(f"WTConvLayer: no HIP kernel for the norm {n} with activation {self.act} on {x.shape[-1]} channels "
-                                   "(affine-less InstanceNorm2d [+ GELU] on a multiple of 4 channels is implemented; no PyTorch fallback)")
+                                   "(affine-less InstanceNorm2d or GroupNorm with a multiple of 4 channels per group [+ GELU] on a "
+                                   "multiple of 4 channels is implemented; no PyTorch fallback)")
         if self.act and not fused:
             x = _apply_act(self.act, x)
         return (x, alias) if tap else x
@@ -548,11 +560,16 @@ class EncoderToDecoder(nn.Module):
         """x: (B, L, d) skip; res: the bridge gate, (B, 1, d) or (B, L, d)."""
         b, l, d = x.shape
         h, w = _hw(l)
-        if not (isinstance(self.norm, nn.InstanceNorm2d) and d % 4 == 0):
-            raise RuntimeError(f"EncoderToDecoder: the HIP kernels take InstanceNorm2d and a multiple of 4 channels, got {self.norm}, dim {d} "
-                               "(the HIP path has no PyTorch fallback)")
+        n = self.norm
+        group = _hip_groupnorm(n, d)
+        if not (group or isinstance(n, nn.InstanceNorm2d) and d % 4 == 0):
+            raise RuntimeError(f"EncoderToDecoder: the HIP kernels take InstanceNorm2d, or GroupNorm with a multiple of 4 channels per group, "
+                               f"and a multiple of 4 channels, got {n}, dim {d} (the HIP path has no PyTorch fallback)")
         x = ops.igate_res(x, res, self.gama, self.act.enhance, self.act.threshold)   # act(x + gama * res), one pass each way
-        x = ops.instnorm(x, self.scale, self.shift, self.norm.eps, lib.ACT_NONE)
+        if group:
+            x = ops.groupnorm(x, n.num_groups, n.weight, n.bias, self.scale, self.shift, n.eps, lib.ACT_NONE)
+        else:
+            x = ops.instnorm(x, self.scale, self.shift, n.eps, lib.ACT_NONE)
         # pools + grouped convs + gates + mix: 2 launches forward, 5-6 backward (csrc/skipgate.hip).  The reference applies
         # ffd13 / act_func13 to both the 1x3 and the 3x1 branch (:770-777); ffd31 / act_func31 / conv33 are never used.
         f13, f33 = self.ffd13.conv, self.ffd33.conv

@@ -248,6 +248,24 @@ int adnm_instnorm_bwd(const void* dy, const void* x, const float* scale, const f
                       const float* rstd, void* dx, float* dscale, float* dshift, void* ws, int64_t ws_bytes,
                       int64_t B, int64_t HW, int64_t C, int act, int dtype, adnm_stream_t stream);
 
+/* ---------------------------------------------------------------- GroupNorm, NHWC
+ * y = act( scale * (gamma_c * (x - mean_{b,g}) * rsqrt(var_{b,g} + eps) + beta_c) + shift ): nn.GroupNorm(G, C), the norm the
+ * reference builds instead of nn.InstanceNorm2d when InstanceNorm=False (model_untils.py:284,371,741,814; the long-interval recipe of
+ * ADNMUNet.py:906-940), with the same external scalar scale/shift (model_untils.py:90,113,155) and activation fused.  Group g = channels
+ * [g*C/G, (g+1)*C/G); mean and (biased) variance over HW x C/G elements.  gamma, beta: (C) fp32 = GroupNorm.weight / .bias, NULL = 1 / 0;
+ * scale, shift: NULL = 1 / 0.  x,y:(B,HW,C) contiguous; mu,rstd:(B,G) fp32 saved for backward.  act in {NONE, GELU}.
+ * Supported: C % 4 == 0, C % G == 0 and (C/G) % 4 == 0 (a lane's 16-byte channel quad lies inside one group); anything else is EINVAL.
+ * bwd: dx, and the parameter gradients dgamma, dbeta (C each), dscale, dshift (NULL = not wanted) through per-workgroup fp32 partials
+ * and the shared deterministic fold (deferred while a fold queue is bound: ws must then stay untouched until adnm_foldq_flush). */
+int64_t adnm_groupnorm_ws_bytes(int64_t B, int64_t HW, int64_t C, int64_t G);
+int adnm_groupnorm_fwd(const void* x, const float* gamma, const float* beta, const float* scale, const float* shift, void* y,
+                       float* mu, float* rstd, void* ws, int64_t ws_bytes, int64_t B, int64_t HW, int64_t C, int64_t G, float eps,
+                       int act, int dtype, adnm_stream_t stream);
+int adnm_groupnorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const float* scale, const float* shift,
+                       const float* mu, const float* rstd, void* dx, float* dgamma, float* dbeta, float* dscale, float* dshift,
+                       void* ws, int64_t ws_bytes, int64_t B, int64_t HW, int64_t C, int64_t G, int act, int dtype,
+                       adnm_stream_t stream);
+
 /* ---------------------------------------------------------------- gated FFN activation (part of K6's epilogue)
  * FeedForward.forward (model_untils.py:194-195): h:(M,2F) -> y[m,f] = gelu(h[m,f]) * sigmoid(h[m,F+f]).
  * bwd: dh:(M,2F) from dy:(M,F).  F % 4 == 0; row strides in elements. */

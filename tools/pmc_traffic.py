@@ -29,7 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # every scope whose launch is the shared fold_rows_kernel: one PMC row for the group ("a|b|c" keys = the kernel symbol serves all of them)
 FOLDS = "|".join(["fold_batch", "skgemm_fold", "ssd_head_fold", "lincomb_bwd_fold", "mixnorm_bwd_fold", "igate_bwd_fold", "rainloss_fold", "grad_sumsq_fold",
                   "dwconv_wgrad_fold", "rownorm_bwd_fold", "tsgemm_tn_fold", "conv3_wgrad_fold", "catmix_bwd_fold", "colsum", "adn_prep_bwd_fold",
-                  "skip_vec_fold", "skip_scal_fold", "skip_wgrad_fold", "bridge_heads_fold", "bridge_pool_fold", "instnorm_bwd_scalar", "swish_bwd_fold"])
+                  "skip_vec_fold", "skip_scal_fold", "skip_wgrad_fold", "bridge_heads_fold", "bridge_pool_fold", "instnorm_bwd_scalar", "groupnorm_bwd_scalar", "groupnorm_bwd_affine",
+                  "swish_bwd_fold"])
 # (regex on the demangled kernel symbol, profiler scope); first match wins
 SCOPES = [
     (r"^skgemm_kernel<true, true", "skgemm_nt"), (r"^skgemm_kernel<true, false", "skgemm_nn"), (r"^skgemm_kernel<false, false|^skgemm_tn_multi_kernel", "skgemm_tn"),
