@@ -41,30 +41,21 @@ class GraphedForward:
             was_training = self.model.training
             self.model.eval()
             sx = x.clone()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self.model(sx)
-            torch.cuda.current_stream().wait_stream(side)
+            ops.warm_up(lambda: self.model(sx), 2)
             g = torch.cuda.CUDAGraph()
             # the graph's split GEMM launches get their own uncached workspace (kept with the graph: a training graph replayed on
             # another stream beside this one must not share it); fp8: the quantisation table's rows stay put while the graph lives
             scope = ops.SPLITWS.open_scope(x.device)
-            pinned = ops.mfma_precision() == "fp8"
-            if pinned:
-                ops.QUANT.pin(x.device)
+            pin = ops.QUANT.pinned(x.device) if ops.mfma_precision() == "fp8" else None
             try:
-                with ops.SPLITWS.capturing(scope):
-                    with torch.cuda.graph(g):
-                        out = self.model(sx)
+                out = ops.capture(g, lambda: self.model(sx), scope)
             except BaseException:
-                if pinned:
-                    ops.QUANT.unpin(x.device)
+                if pin is not None:
+                    pin.release()
                 raise
             finally:
                 self.model.train(was_training)
-            ent = self._graphs[key] = {"graph": g, "sx": sx, "out": out, "scope": scope, "shadows": shadows, "pinned": pinned}
+            ent = self._graphs[key] = {"graph": g, "sx": sx, "out": out, "scope": scope, "shadows": shadows, "pin": pin}
         for s in ent["shadows"]:
             s.ensure_current()
         ent["sx"].copy_(x, non_blocking=True)
@@ -75,15 +66,12 @@ class GraphedForward:
         """Give the captured graphs back now: the graphs first, then what their launches point into (static tensors, split-K
         workspaces, the weight shadows), then the pins on the fp8 quantisation table.  Idempotent; __del__ calls it."""
         graphs, self._graphs = self._graphs, {}
-        unpin = [key[2] for key, ent in graphs.items() if ent["pinned"]]
+        pins = [ent["pin"] for ent in graphs.values() if ent["pin"] is not None]
         for ent in graphs.values():
             ent["graph"] = None
         graphs = None
-        for dev in unpin:
-            try:
-                ops.QUANT.unpin(dev)
-            except Exception:
-                pass
+        for pin in pins:
+            pin.release()
 
     def __del__(self):
         try:

@@ -154,8 +154,8 @@ class QuantTable:
 
     def reset(self, device=None):
         """Start a new calibration.  The table's memory is NEVER given back (captured hipGraphs have `tab.data_ptr() + 32 * row` baked
-        into their kernel arguments).  While a capture that may hold record pointers is alive on the device (pin() / unpin(), taken by
-        FlatTrainer and GraphedForward around the lifetime of their graphs) the key -> row map is kept as well and only the VALUES go
+        into their kernel arguments).  While a capture that may hold record pointers is alive on the device (pinned(): one handle per
+        FlatTrainer / GraphedForward graph, held as long as the graphs live) the key -> row map is kept as well and only the VALUES go
         back to their defaults (scale 1, recording on), so a replayed graph keeps reading the record of ITS call site — freshly
         calibrated by whoever asked for the reset.  With nothing pinned the keys are forgotten too (tests building model after model)."""
         with self._lock:
@@ -192,12 +192,32 @@ class QuantTable:
             if ent is not None and ent.get("pins", 0) > 0:
                 ent["pins"] -= 1
 
+    def pins(self, device):
+        return self._dev.get(self._idx(device), {}).get("pins", 0)
+
+    def pinned(self, device):
+        """pin() for an owner of captured graphs: -> the handle whose release() is the matching unpin()"""
+        self.pin(device)
+        return _QuantPin(self, device)
+
     def dump(self, device):
         ent = self._dev.get(self._idx(device))
         if ent is None:
             return {}
         tab = ent["tab"].cpu()
         return {k: tab[r].tolist() for k, r in ent["keys"].items()}
+
+
+class _QuantPin:
+    """one owner's pin (QuantTable.pinned); release() is idempotent: every path that ends the owner's life may call it"""
+
+    def __init__(self, table, device):
+        self._table, self._device = table, device
+
+    def release(self):
+        table, self._table = self._table, None
+        if table is not None:
+            table.unpin(self._device)
 
 
 QUANT = QuantTable()
@@ -749,6 +769,24 @@ class _ScopeActive:
             with self.reg._lock:
                 self.reg._scope.pop(self.scope["device"], None)
         return False
+
+
+def warm_up(body, n):
+    """body() n times on a fresh stream forked from and joined to the current one: what has to run before body() is captured"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(n):
+            body()
+    torch.cuda.current_stream().wait_stream(side)
+
+
+def capture(graph, body, scope, **how):
+    """body() captured into `graph`, its split launches on `scope`'s region (SplitWorkspaces.open_scope); `how`: torch.cuda.graph's
+    pool / capture_error_mode.  -> what body() returned.  An exception ends the capture (torch.cuda.graph's __exit__) and passes."""
+    with SPLITWS.capturing(scope):
+        with torch.cuda.graph(graph, **how):
+            return body()
 
 
 _VERSION = operator.attrgetter("_version")

@@ -90,14 +90,24 @@ class FlatTrainer:
         # ROCm 7.2 the forked branches of the replayed hipGraph buy nothing and every fork costs (11.4 ms/step off, 12.1 with a fork per
         # 16 weight gradients, 13.1 with one per weight gradient); bitwise neutral either way (tests/test_trainer_gpu.py)
         self.side_stream = side_stream
+        self._steps = 0
+        # the flat layout (_flatten)
         self.used = None
-        self.graph = self.graph2 = None
+        self.flat_p = self.flat_g = self.exp_avg = self.exp_avg_sq = self.state = self.comm = self.ws = None
+        self.groups, self.late, self.early, self.g_views, self.offs, self.gathered = [], [], [], [], [], []
+        self.buckets, self.group_ranges = [], []
+        self.n = self.n_late = 0
+        # the narrow shadow (_setup_shadows; bf16 / fp8 configurations)
+        self.fp8 = False
+        self.shadow, self.shadow_mode, self._shadow = None, 0, None   # _shadow: its ops.ShadowSet
+        self.seg_end = self.seg_rec = None
+        # what the captures own (_prepare); _release_captures() is the one place that gives it back
+        self.graph = self.graph2 = self.tail = None
         self.graphs = []
         self.static_loss = self._carry = self._cuts = self.sx = self.st = None
-        self.flat_g = None
-        self.buckets = []
-        self._steps = 0
-        self._shadow = None   # ops.ShadowSet of the narrow shadow (bf16 / fp8 configurations)
+        self.hyper = self._hyper_host = None   # [lr, max_norm] as the tail graph reads them, and the host's copy
+        self._splitws = None                   # the split-K capture scope of all graphs (ops.SPLITWS)
+        self._pin = None                       # the pin on the fp8 table (ops.QUANT.pinned)
 
     # ------------------------------------------------------------------ one-time setup
     def _fwd_bwd(self, x, tgt):
@@ -236,14 +246,11 @@ class FlatTrainer:
         else:
             self._shadow.refresh()
 
-    def close(self):
-        """Give back everything this trainer owns on the device, in a fixed order, NOW (not whenever the cyclic collector gets to
-        it): the captured graphs first (they reference graph-pool memory), then the tensors that live in that pool (the static loss
-        with its autograd graph, the stage hand-over, the static inputs), then the gradient-destination registration.  Idempotent;
-        __del__ calls it.  A round-2 run aborted (rc 134) because dead trainers of failed tests — kept alive by their tracebacks —
-        were finalised by the cyclic GC in the middle of a NEW trainer's warm-up / stream capture: destroying a hipGraph (and
-        freeing its private pool) while another capture is in flight on the device is not allowed by the runtime.  prepare()
-        therefore also collects BEFORE it starts and keeps the collector off until both captures have ended."""
+    def _release_captures(self):
+        """What the captures own, given back in a fixed order: the graphs first, the tail before the stage graphs before the first (they
+        reference graph-pool memory), then the tensors that live in that pool (the static loss with its autograd graph, the stage
+        hand-over, the static inputs, the tail's hyper-parameters), then the split-K scope the graphs' launches point into, then the
+        pin on the fp8 table.  The only such list: close() and a failed prepare() both end here."""
         self.tail = None
         self.graphs = []
         self.graph2 = None
@@ -251,13 +258,20 @@ class FlatTrainer:
         self.static_loss = None
         self._carry = self._cuts = None
         self.sx = self.st = None
-        self._splitws = None   # (after the graphs: their launches point into it)
-        if getattr(self, "_quant_pinned", False):
-            self._quant_pinned = False
-            try:
-                ops.QUANT.unpin(self.flat_g.device)
-            except Exception:
-                pass
+        self.hyper = self._hyper_host = None
+        self._splitws = None
+        pin, self._pin = self._pin, None
+        if pin is not None:
+            pin.release()
+
+    def close(self):
+        """Give back everything this trainer owns on the device, in a fixed order, NOW (not whenever the cyclic collector gets to
+        it): what the captures own (_release_captures), then the shadow and gradient-destination registrations.  Idempotent;
+        __del__ calls it.  A round-2 run aborted (rc 134) because dead trainers of failed tests — kept alive by their tracebacks —
+        were finalised by the cyclic GC in the middle of a NEW trainer's warm-up / stream capture: destroying a hipGraph (and
+        freeing its private pool) while another capture is in flight on the device is not allowed by the runtime.  prepare()
+        therefore also collects BEFORE it starts and keeps the collector off until the last capture has ended."""
+        self._release_captures()
         try:
             ops.SHADOWS.drop(id(self))
         except Exception:
@@ -354,24 +368,19 @@ class FlatTrainer:
     def _abort_prepare(self):
         """After an exception in prepare(): torch.cuda.graph's __exit__ has already ended a capture in flight; what is left is
         OUR state — the thread's fold-queue binding (a kernel wrapper may have died between bind and unbind), the deferral /
-        side-stream switches of this device, and the graph objects, which must not survive half-captured."""
+        side-stream switches of this device, and what the captures own (_release_captures), which must not survive half-captured."""
         try:
             lib.load().adnm_foldq_bind(None)
         except Exception:
             pass
-        dev = self.flat_g.device if getattr(self, "flat_g", None) is not None else None
+        dev = self.flat_g.device if self.flat_g is not None else None
         if dev is not None and dev.type == "cuda":
             for reg in (ops.FOLDS, ops.SIDE):
                 try:
                     reg.abort(dev)
                 except Exception:
                     pass
-        self.graphs = []
-        self.graph2 = None
-        self.graph = None
-        self.static_loss = None
-        self._carry = self._cuts = None
-        self._splitws = None
+        self._release_captures()
 
     def _prepare(self, x, tgt):
         self.model.zero_grad(set_to_none=True)
@@ -408,14 +417,12 @@ class FlatTrainer:
         if not self.use_graph:
             return
         self.sx, self.st = x.clone(), tgt.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                for p in self.used:
-                    p.grad = None
-                self._run_eager(self.sx, self.st)
-        torch.cuda.current_stream().wait_stream(side)
+
+        def eager():
+            for p in self.used:
+                p.grad = None
+            self._run_eager(self.sx, self.st)
+        ops.warm_up(eager, 2)
         torch.cuda.synchronize()
         for p in self.used:
             p.grad = None
@@ -424,54 +431,51 @@ class FlatTrainer:
         # scope for all of this trainer's graphs: they replay one after the other on one stream) and, in the fp8 configuration, pointers
         # into the device's quantisation table (pinned: a later calibration re-uses the rows instead of re-assigning them)
         self._splitws = ops.SPLITWS.open_scope(x.device)
-        if self.fp8 and not getattr(self, "_quant_pinned", False):
-            ops.QUANT.pin(x.device)
-            self._quant_pinned = True
-        # thread_local: RCCL's watchdog thread may query events while we capture; only this thread's calls are checked
-        with ops.SPLITWS.capturing(self._splitws):
-            if not self.staged:
-                with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                    self.static_loss = self._fwd_bwd(self.sx, self.st)
-                    self._gather()
-            else:
-                # each stage graph ends with the wire cast of ITS bucket (bf16 wire): a step at N > 1 is then K graph replays + K collective
-                # calls + the tail graph below, nothing else is launched from the host
-                with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                    self.static_loss = self._stage_part0(self.sx, self.st)
-                    self._wire_cast(0)
-                self.graphs = []   # same memory pool: every part reads what the parts before saved for it
-                for j in range(1, len(self.stage_defs)):
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, pool=self.graph.pool(), capture_error_mode="thread_local"):
-                        self._stage_part(j)
-                        self._wire_cast(j)
-                    self.graphs.append(g)
-                self.graph2 = self.graphs[0] if self.graphs else None
-            # the tail of a step: (bf16 wire: averages back to fp32) -> fp8 scale update -> clip + AdamW (+ shadow), with the learning rate and
-            # the clip threshold in device memory (self.hyper) so that the captured launches follow the host's schedules
-            self.tail = None
-            if self.fused and self.staged:
-                self.hyper = torch.tensor([self.lr, self.max_norm], dtype=torch.float32, device=x.device)
-                self._hyper_host = (float(self.lr), float(self.max_norm))
-                keep = (self.flat_p.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), self.state.clone(), self.flat_g.clone(),
-                        self.shadow.clone() if getattr(self, "shadow", None) is not None else None)
-                qsave = ops.QUANT.snapshot(x.device) if self.fp8 else None
-                side2 = torch.cuda.Stream()
-                side2.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side2):
-                    self._tail_body()   # warm-up outside capture
-                torch.cuda.current_stream().wait_stream(side2)
-                self.tail = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.tail, pool=self.graph.pool(), capture_error_mode="thread_local"):
-                    self._tail_body()
-                # the warm-up advanced the optimiser once: put everything back
-                for dst, src in zip((self.flat_p, self.exp_avg, self.exp_avg_sq, self.state, self.flat_g, getattr(self, "shadow", None)), keep):
-                    if src is not None:
-                        dst.copy_(src)
-                if qsave is not None:
-                    ops.QUANT.restore(x.device, qsave)
-                if self._shadow is not None:   # (parameters and shadow restored together: the copy moved flat_p's version counter)
-                    self._shadow.mark_current()
+        if self.fp8 and self._pin is None:
+            self._pin = ops.QUANT.pinned(x.device)
+
+        def grab(g, body, *args, pool=None):
+            # thread_local: RCCL's watchdog thread may query events while we capture; only this thread's calls are checked
+            return ops.capture(g, lambda: body(*args), self._splitws, pool=pool, capture_error_mode="thread_local")
+
+        def part(j):
+            # each stage graph ends with the wire cast of ITS bucket (bf16 wire): a step at N > 1 is then K graph replays + K collective
+            # calls + the tail graph below, nothing else is launched from the host
+            loss = self._stage_part0(self.sx, self.st) if j == 0 else self._stage_part(j)
+            self._wire_cast(j)
+            return loss
+        self.graphs, self.graph2, self.tail = [], None, None
+        if not self.staged:
+            self.static_loss = grab(self.graph, self._run_eager, self.sx, self.st)   # forward, backward, gather
+            return
+        self.static_loss = grab(self.graph, part, 0)
+        for j in range(1, len(self.stage_defs)):   # same memory pool: every part reads what the parts before saved for it
+            g = torch.cuda.CUDAGraph()
+            grab(g, part, j, pool=self.graph.pool())
+            self.graphs.append(g)
+        self.graph2 = self.graphs[0] if self.graphs else None
+        if not self.fused:
+            return
+        # the tail of a step: (bf16 wire: averages back to fp32) -> fp8 scale update -> clip + AdamW (+ shadow), with the learning rate and
+        # the clip threshold in device memory (self.hyper) so that the captured launches follow the host's schedules
+        self.hyper = torch.tensor([self.lr, self.max_norm], dtype=torch.float32, device=x.device)
+        self._hyper_host = (float(self.lr), float(self.max_norm))
+        live = [t for t in (self.flat_p, self.exp_avg, self.exp_avg_sq, self.state, self.flat_g, self.shadow) if t is not None]
+        keep = [t.clone() for t in live]
+        qsave = ops.QUANT.snapshot(x.device) if self.fp8 else None
+        try:
+            ops.warm_up(self._tail_body, 1)
+            self.tail = torch.cuda.CUDAGraph()
+            grab(self.tail, self._tail_body, pool=self.graph.pool())
+        finally:
+            # the warm-up advanced the optimiser once: put everything back, also when the warm-up or the capture raised (should the
+            # restore itself fail, its exception carries the first one as __context__)
+            for dst, src in zip(live, keep):
+                dst.copy_(src)
+            if qsave is not None:
+                ops.QUANT.restore(x.device, qsave)
+            if self._shadow is not None:   # (parameters and shadow restored together: the copy moved flat_p's version counter)
+                self._shadow.mark_current()
 
     def _wire_cast(self, j):
         """fp32 -> bf16 copy of bucket j into the wire buffer (captured at the end of stage graph j)"""
@@ -485,7 +489,7 @@ class FlatTrainer:
             for lo, hi in self.buckets:
                 if hi > lo:
                     self._cast(self.comm[lo:hi], self.flat_g[lo:hi], 1.0 / self.world)
-        if getattr(self, "fp8", False):
+        if self.fp8:
             ops.QUANT.update(self.flat_g.device)
         self._optimizer_step(hyper=True)
 
@@ -574,7 +578,7 @@ class FlatTrainer:
                 self._reduce_begin(*self.buckets[0], pending)
             for p in self.used:
                 p.grad = None
-        tail = graphed and getattr(self, "tail", None) is not None and (self.world == 1 or self.reduce_dtype == "bf16" or dist.get_backend(self.group) == "nccl")
+        tail = graphed and self.tail is not None and (self.world == 1 or self.reduce_dtype == "bf16" or dist.get_backend(self.group) == "nccl")
         self._reduce_end(pending, tail=tail)
         if tail:
             if (float(self.lr), float(self.max_norm)) != self._hyper_host:   # a schedule moved them: two floats to the device
@@ -582,7 +586,7 @@ class FlatTrainer:
                 self.hyper.copy_(torch.tensor(self._hyper_host, dtype=torch.float32), non_blocking=True)
             self.tail.replay()
         else:
-            if getattr(self, "fp8", False):
+            if self.fp8:
                 # one launch: amax -> scales on calibration steps, the next step's record flags.  BEFORE the optimiser pass: that pass writes
                 # the e4m3 shadow of the updated weights with the scales the next step's GEMMs will read
                 ops.QUANT.update(self.flat_g.device)
@@ -592,7 +596,7 @@ class FlatTrainer:
 
     def _optimizer_step(self, hyper=False):
         if self.fused:
-            mode = getattr(self, "shadow_mode", 0)
+            mode = self.shadow_mode
             sh = (self.shadow.data_ptr(), mode, self.seg_end.data_ptr(), self.seg_rec.data_ptr(), self.seg_end.numel(),
                   ops.QUANT.table_ptr(self.flat_p.device) if mode == 2 else None) if mode else (None, 0, None, None, 0, None)
             lib.call("adnm_adamw_step", self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(),

@@ -49,6 +49,7 @@ def test_prepare_exception_path_restores_state():
     with pytest.raises(ValueError):
         tr2.prepare(x, t)       # raises inside prepare's dry run
     assert gc.isenabled() and tr2.graph is None and tr2.graph2 is None and tr2.static_loss is None
+    assert tr2.tail is None and tr2.sx is None and tr2.st is None
     calls[0] = 10
     tr2.prepare(x, t)           # and the same object can be prepared again
     tr2.step(x, t)

@@ -291,3 +291,120 @@ def test_tail_graph_follows_host_schedules():
         tr.close()
         del tr
     assert torch.equal(flats[0][1], flats[1][1]) and torch.equal(flats[0][0], flats[1][0])
+
+
+@pytest.mark.parametrize("prec", ["bf16", "fp8"])
+def test_failed_tail_capture_leaves_the_trainer_as_before_prepare(prec, monkeypatch):
+    """prepare() of the staged trainer warms its tail up with a real optimiser pass and puts parameters, moments and step counter back
+    afterwards.  An ordinary Python exception inside the tail capture (here: _tail_body raises at the end of its second call) must not
+    skip that: the trainer holds what a twin built from the same seed holds after a successful prepare() — which is what it held before:
+    the filled parameters, zero moments, a zero step counter —, no graph, no pin on the fp8 table, and after close() the model trains
+    under a fresh trainer."""
+    from models.ADNMUNet import create_ADNMUNet
+    from models.loss import enRainfallLoss
+    from adnm_hip import ops
+    frames = recipe.radar_batch(1, 25, 64, name="tailfail").to(DEV)
+    x, tgt = frames[:, :5].contiguous(), frames[:, 5:].contiguous()
+    names = ("flat_p", "exp_avg", "exp_avg_sq", "state", "flat_g", "shadow")
+
+    def build():
+        model = create_ADNMUNet(5, 20, 6, img_size=64)
+        recipe.fill_parameters(model)
+        model = model.to(DEV).train()
+        return model, FlatTrainer(model, enRainfallLoss(0.57, 0.25, gamma=0.0), lr=1e-3, max_norm=0.025, use_graph=True, overlap=True)
+
+    ops.set_mfma_precision(prec)
+    try:
+        model, twin = build()
+        filled = [p.detach().clone() for p in model.parameters()]
+        twin.prepare(x, tgt)
+        torch.cuda.synchronize()
+        assert twin.tail is not None and (twin.shadow_mode == 2) == (prec == "fp8")
+        assert all(torch.equal(p, q) for p, q in zip(model.parameters(), filled)), "prepare() moved the parameters"
+        assert not twin.exp_avg.any() and not twin.exp_avg_sq.any() and not twin.state.any(), "prepare() moved the optimiser state"
+        want = {k: getattr(twin, k).clone() for k in names}
+        want_q = ops.QUANT.snapshot(x.device)   # (record table, calibration state): clones
+        twin.close()
+        del twin, model
+
+        model, tr = build()
+        pins0 = ops.QUANT.pins(x.device)
+        real, calls = tr._tail_body, [0]
+
+        def tail_body():
+            calls[0] += 1
+            real()
+            if calls[0] == 2:   # the call inside the capture
+                raise ValueError("boom")
+        monkeypatch.setattr(tr, "_tail_body", tail_body)
+        with pytest.raises(ValueError):
+            tr.prepare(x, tgt)
+        torch.cuda.synchronize()
+        assert calls[0] == 2
+        assert tr.tail is None and tr.graph is None and tr.graphs == [] and tr.sx is None and tr.st is None
+        assert ops.QUANT.pins(x.device) == pins0
+        for k in names:
+            assert torch.equal(getattr(tr, k), want[k]), f"{k} differs from its value before prepare()"
+        assert all(torch.equal(a, b) for a, b in zip(ops.QUANT.snapshot(x.device), want_q)), "the fp8 table differs from its value before prepare()"
+        tr.close()
+        assert ops.QUANT.pins(x.device) == pins0
+
+        tr2 = FlatTrainer(model, enRainfallLoss(0.57, 0.25, gamma=0.0), lr=1e-3, max_norm=0.025, use_graph=True, overlap=True)
+        tr2.prepare(x, tgt)
+        loss = tr2.step(x, tgt)
+        torch.cuda.synchronize()
+        assert tr2.tail is not None and bool(torch.isfinite(loss))
+        assert tr2.exp_avg.any() and not torch.equal(tr2.flat_p, want["flat_p"]), "the step ran no optimiser pass"
+        tr2.close()
+    finally:
+        ops.set_mfma_precision("f32")
+        ops.QUANT.reset()
+
+
+def test_graphed_forward_failed_capture_gives_the_pin_back():
+    """A model forward that raises inside GraphedForward's capture (fp8: the pin on the quantisation table is already taken) leaves the
+    pin count where it was and the model in its mode; close() is idempotent, and the same object captures once the forward works."""
+    from models.ADNMUNet import create_ADNMUNet
+    from adnm_hip import ops
+    from adnm_hip.evaluator import GraphedForward
+
+    class FailsOnThird(torch.nn.Module):
+        def __init__(self, inner):
+            super().__init__()
+            self.inner, self.calls = inner, 0
+
+        def forward(self, x):
+            self.calls += 1
+            out = self.inner(x)
+            if self.calls == 3:   # two warm-up calls, then the one inside the capture
+                raise ValueError("boom")
+            return out
+
+    inner = create_ADNMUNet(5, 20, 6, img_size=64)
+    recipe.fill_parameters(inner)
+    model = FailsOnThird(inner.to(DEV)).train()
+    x = recipe.radar_batch(1, 25, 64, name="evalfail").to(DEV)[:, :5].contiguous()
+    try:
+        with torch.no_grad():
+            model.eval()
+            ops.fp8_calibrate(x.device, lambda: inner(x))   # every call site's record; leaves the precision at fp8
+            model.train()
+        pins0 = ops.QUANT.pins(x.device)
+        fwd = GraphedForward(model)
+        with pytest.raises(ValueError):
+            fwd(x)
+        torch.cuda.synchronize()
+        assert model.calls == 3 and model.training
+        assert ops.QUANT.pins(x.device) == pins0
+        fwd.close()
+        fwd.close()
+        assert ops.QUANT.pins(x.device) == pins0
+        out = fwd(x)
+        torch.cuda.synchronize()
+        assert torch.isfinite(out).all() and ops.QUANT.pins(x.device) == pins0 + 1
+        fwd.close()
+        fwd.close()
+        assert ops.QUANT.pins(x.device) == pins0
+    finally:
+        ops.set_mfma_precision("f32")
+        ops.QUANT.reset()
