@@ -51,11 +51,13 @@ class _Both:
 class FlatTrainer:
     def __init__(self, model, loss_fn, lr=1e-3, betas=(0.9, 0.999), eps=1e-9, weight_decay=1e-2, max_norm=0.0,
                  process_group=None, use_graph=True, fused=True, overlap="auto", reduce_dtype="f32", stages=None, defer_folds=True, side_stream=False,
-                 nstages=None):
+                 nstages=None, accum_steps=1):
         """overlap: cut the backward at the model's stage boundaries and all-reduce every stage's gradients while the backward of the
         stages before it runs.  "auto" = whenever there is more than one rank.  `stages` is the older name of the same switch
         (True / False).  nstages: None = every stage the model offers (forward_stages(): 5 for ADNM-UNet); 2 = the two-stage cut
-        (encoder | decoder + refiner)."""
+        (encoder | decoder + refiner).
+        accum_steps: k calls of step() make ONE optimiser step on the mean gradient of their k micro-batches (train.py:136-145 with
+        loss.backward() repeated before optimizer.step()); see step()."""
         self.model, self.loss_fn = model, loss_fn
         self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_norm
         self.group = process_group
@@ -91,6 +93,10 @@ class FlatTrainer:
         # 16 weight gradients, 13.1 with one per weight gradient); bitwise neutral either way (tests/test_trainer_gpu.py)
         self.side_stream = side_stream
         self._steps = 0
+        # gradient accumulation: micro-steps per optimiser step, micro-steps done in the running cycle, the fp32 sum (only when k > 1)
+        self._accum_steps = self._check_accum(accum_steps)
+        self._micro = 0
+        self.acc = None
         # the flat layout (_flatten)
         self.used = None
         self.flat_p = self.flat_g = self.exp_avg = self.exp_avg_sq = self.state = self.comm = self.ws = None
@@ -108,6 +114,75 @@ class FlatTrainer:
         self.hyper = self._hyper_host = None   # [lr, max_norm] as the tail graph reads them, and the host's copy
         self._splitws = None                   # the split-K capture scope of all graphs (ops.SPLITWS)
         self._pin = None                       # the pin on the fp8 table (ops.QUANT.pinned)
+
+    # ------------------------------------------------------------------ gradient accumulation
+    @staticmethod
+    def _check_accum(k):
+        if isinstance(k, bool) or int(k) != k or int(k) < 1:
+            raise ValueError(f"FlatTrainer: accum_steps={k!r} must be an integer >= 1")
+        return int(k)
+
+    @property
+    def accum_steps(self):
+        return self._accum_steps
+
+    @accum_steps.setter
+    def accum_steps(self, k):
+        k = self._check_accum(k)
+        if self._micro != 0:
+            raise RuntimeError(f"FlatTrainer: accum_steps assigned in mid-cycle (micro-step {self._micro} of {self._accum_steps}): the "
+                               "accumulator holds a partial sum; finish the cycle first")
+        self._accum_steps = k
+        if k == 1:
+            self.acc = None
+
+    @property
+    def micro_step(self):
+        """micro-steps done in the running cycle: 0 (between cycles) .. accum_steps - 1 (the next step() is the optimiser step)"""
+        return self._micro
+
+    def _accumulator(self):
+        """the fp32 sum of the cycle's micro-gradients, laid out like flat_g; exists only while accum_steps > 1.  Never zeroed: the first
+        micro-step of a cycle overwrites it"""
+        if self.acc is None:
+            self.acc = torch.empty_like(self.flat_g)
+        return self.acc
+
+    @torch.no_grad()
+    def _accumulate(self, lo, hi, final):
+        """micro-steps 1 .. k-1: acc[lo:hi] (+)= flat_g[lo:hi]; micro-step k: flat_g[lo:hi] = (acc + flat_g) / k and, on the bf16 wire,
+        its image in comm[lo:hi] (over the micro-gradient's image the stage graph left there).  HIP pass on the GPU; torch on the CPU
+        test path, same statement order"""
+        g, acc = self.flat_g[lo:hi], self._accumulator()[lo:hi]
+        wire = self.comm[lo:hi] if (final and self.comm is not None) else None
+        scale = 1.0 / self._accum_steps
+        if self.fused and g.is_cuda:
+            st = torch.cuda.current_stream().cuda_stream
+            if final:
+                lib.call("adnm_grad_accum_final", acc.data_ptr(), g.data_ptr(), None if wire is None else wire.data_ptr(), hi - lo, scale, st)
+            else:
+                lib.call("adnm_grad_accum", acc.data_ptr(), g.data_ptr(), hi - lo, int(self._micro == 0), st)
+        elif final:
+            g.copy_((acc + g) * scale)
+            if wire is not None:
+                wire.copy_(g.to(torch.bfloat16))
+        elif self._micro == 0:
+            acc.copy_(g)
+        else:
+            acc.add_(g)
+
+    def _bucket_ready(self, j, pending, cast_done=False):
+        """bucket j of this pass is complete.  accum_steps == 1: start its all-reduce.  k > 1: fold it into the accumulator first — right
+        here, so that on the last micro-step bucket j's averaged gradient goes on the wire while the earlier stages' backward still
+        runs — and start the all-reduce on the last micro-step only"""
+        lo, hi = self.buckets[j]
+        if self._accum_steps > 1 and hi > lo:
+            final = self._micro == self._accum_steps - 1
+            self._accumulate(lo, hi, final)
+            if not final:
+                return
+            cast_done = cast_done or self.comm is not None   # (the final pass wrote the wire image itself)
+        self._reduce_begin(lo, hi, pending, cast_done=cast_done)
 
     # ------------------------------------------------------------------ one-time setup
     def _fwd_bwd(self, x, tgt):
@@ -206,6 +281,8 @@ class FlatTrainer:
         ops.GRADS.register(id(self), {p.data_ptr(): gv for p, gv in zip(used, self.g_views)})
         if self.fused:
             self.ws = torch.empty(int(lib.query("adnm_adamw_ws_bytes")), dtype=torch.uint8, device=dev)
+        if self._accum_steps > 1:
+            self._accumulator()
 
     def bucket_report(self):
         """[(bucket index in all-reduce order, first element, last element + 1, bytes on the wire)]: what each stage's collective moves —
@@ -250,7 +327,8 @@ class FlatTrainer:
         """What the captures own, given back in a fixed order: the graphs first, the tail before the stage graphs before the first (they
         reference graph-pool memory), then the tensors that live in that pool (the static loss with its autograd graph, the stage
         hand-over, the static inputs, the tail's hyper-parameters), then the split-K scope the graphs' launches point into, then the
-        pin on the fp8 table.  The only such list: close() and a failed prepare() both end here."""
+        pin on the fp8 table; last the gradient accumulator (no graph points into it; a step after a failed prepare() makes a new one).
+        The only such list: close() and a failed prepare() both end here."""
         self.tail = None
         self.graphs = []
         self.graph2 = None
@@ -263,6 +341,8 @@ class FlatTrainer:
         pin, self._pin = self._pin, None
         if pin is not None:
             pin.release()
+        self.acc = None
+        self._micro = 0
 
     def close(self):
         """Give back everything this trainer owns on the device, in a fixed order, NOW (not whenever the cyclic collector gets to
@@ -546,7 +626,10 @@ class FlatTrainer:
     # ------------------------------------------------------------------ per step
     def step(self, x, tgt, eager=False):
         """One training step.  eager=True launches the same work without the captured graphs (bench.py's instrumented steps:
-        per-launch HIP events cannot be recorded inside a graph replay)."""
+        per-launch HIP events cannot be recorded inside a graph replay).
+        accum_steps = k > 1: one MICRO-step; returns this micro-batch's loss.  Calls 1 .. k-1 of a cycle run forward and backward and
+        add every bucket into the accumulator: no collective, no fp8 table update, no optimiser pass.  Call k adds its own gradient,
+        leaves the mean of the k gradients in flat_g and goes on exactly like a plain step (all-reduce, clip, AdamW, shadow)."""
         if self.used is None:
             self.prepare(x, tgt)
         elif self._shadow is not None and self._shadow.stale():   # a write outside the optimiser (a checkpoint load, an in-place op)
@@ -559,25 +642,29 @@ class FlatTrainer:
                 self.sx.copy_(x, non_blocking=True)
                 self.st.copy_(tgt, non_blocking=True)
             self.graph.replay()
-            self._reduce_begin(*self.buckets[0], pending, cast_done=self.staged)
+            self._bucket_ready(0, pending, cast_done=self.staged)
             if self.staged:
                 for j, g in enumerate(self.graphs, start=1):
                     g.replay()
                     if j < nb:
-                        self._reduce_begin(*self.buckets[j], pending, cast_done=True)
+                        self._bucket_ready(j, pending, cast_done=True)
             loss = self.static_loss
             graphed = True
         else:
             for p in self.used:
                 p.grad = None
             if self.staged:
-                loss = self._run_eager(x, tgt, between=lambda j: self._reduce_begin(*self.buckets[j], pending))
-                self._reduce_begin(*self.buckets[nb - 1], pending)
+                loss = self._run_eager(x, tgt, between=lambda j: self._bucket_ready(j, pending))
+                self._bucket_ready(nb - 1, pending)
             else:
                 loss = self._run_eager(x, tgt)
-                self._reduce_begin(*self.buckets[0], pending)
+                self._bucket_ready(0, pending)
             for p in self.used:
                 p.grad = None
+        if self._micro < self._accum_steps - 1:   # a micro-step inside a cycle ends here: parameters, moments, step counter, fp8 table untouched
+            self._micro += 1
+            return loss
+        self._micro = 0
         tail = graphed and self.tail is not None and (self.world == 1 or self.reduce_dtype == "bf16" or dist.get_backend(self.group) == "nccl")
         self._reduce_end(pending, tail=tail)
         if tail:

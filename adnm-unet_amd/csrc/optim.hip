@@ -229,7 +229,68 @@ __global__ __launch_bounds__(kBlock) void cast_bf16_f32_kernel(const uint16_t* _
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 7)) dst[(n8 << 3) + threadIdx.x] = scale * bf16_to_f32(src[(n8 << 3) + threadIdx.x]);
 }
+
+// gradient accumulation over micro-batches (FlatTrainer(accum_steps=k)): one float4 per lane and stream, grid-stride.  n % 4 == 0 (every
+// tensor and every bucket of the flat layout is 16-byte aligned), so there is no scalar tail.
+// FIRST: acc = g without reading acc (the first micro-step of a cycle restarts the accumulator: no memset, 8 B/element instead of 12).
+// acc is read and written once per micro-step and not looked at in between: non-temporal; g was just written by the backward kernels.
+template <bool FIRST>
+__global__ __launch_bounds__(kBlock) void grad_accum_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n4) {
+#pragma clang fp contract(off)
+  using f4 = __attribute__((ext_vector_type(4))) float;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kBlock) {
+    f4 v = reinterpret_cast<const f4*>(g)[i];
+    if (!FIRST) v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(acc) + i) + v;
+    __builtin_nontemporal_store(v, reinterpret_cast<f4*>(acc) + i);
+  }
+}
+// the last micro-step: g = (acc + g) * scale — add, THEN multiply, each rounded on its own (what torch's (acc + g) * scale gives) — and,
+// WIRE, the bf16 image of that value for the collective in the same pass.  g keeps plain stores: the norm pass reads it next.
+template <bool WIRE>
+__global__ __launch_bounds__(kBlock) void grad_accum_final_kernel(const float* __restrict__ acc, float* __restrict__ g, uint16_t* __restrict__ wire,
+                                                                  int64_t n4, float scale) {
+#pragma clang fp contract(off)
+  using f4 = __attribute__((ext_vector_type(4))) float;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kBlock) {
+    f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(acc) + i) + reinterpret_cast<const f4*>(g)[i];
+    v = v * scale;
+    reinterpret_cast<f4*>(g)[i] = v;
+    if (WIRE) Io<uint16_t>::st4(wire + 4 * i, make_float4(v[0], v[1], v[2], v[3]));
+  }
+}
 }  // namespace
+
+// <= 2048 workgroups of 256 lanes (8 per CU on 256 CUs: every wave slot of the chip), the rest by grid stride
+static int64_t accum_blocks(int64_t n4) {
+  int64_t blocks = adnm_cdiv(n4, kBlock);
+  if (blocks > 2048) blocks = 2048;
+  return blocks < 1 ? 1 : blocks;
+}
+extern "C" int adnm_grad_accum(float* acc, const float* g, int64_t n, int first, adnm_stream_t stream) {
+  ADNM_REQUIRE(acc && g && n > 0, "grad_accum: null pointer or n <= 0");
+  ADNM_REQUIRE(((uintptr_t)acc | (uintptr_t)g) % 16 == 0, "grad_accum: buffers must be 16-byte aligned");
+  ADNM_REQUIRE(n % 4 == 0, "grad_accum: n=%lld must be a multiple of 4 (the flat layout pads every tensor)", (long long)n);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n4 = n / 4, blocks = accum_blocks(n4);
+  ADNM_PROF(first ? "grad_accum_first" : "grad_accum", st, (first ? 8.0 : 12.0) * n);
+  if (first) grad_accum_kernel<true><<<(unsigned)blocks, kBlock, 0, st>>>(acc, g, n4);
+  else grad_accum_kernel<false><<<(unsigned)blocks, kBlock, 0, st>>>(acc, g, n4);
+  ADNM_CHECK_LAUNCH("grad_accum");
+  return ADNM_OK;
+}
+extern "C" int adnm_grad_accum_final(const float* acc, float* g, void* wire_bf16, int64_t n, float scale, adnm_stream_t stream) {
+  ADNM_REQUIRE(acc && g && n > 0, "grad_accum_final: null pointer or n <= 0");
+  ADNM_REQUIRE(((uintptr_t)acc | (uintptr_t)g) % 16 == 0 && (uintptr_t)wire_bf16 % 8 == 0,
+               "grad_accum_final: acc and g must be 16-byte aligned, the bf16 wire range 8-byte aligned");
+  ADNM_REQUIRE(n % 4 == 0, "grad_accum_final: n=%lld must be a multiple of 4 (the flat layout pads every tensor)", (long long)n);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n4 = n / 4, blocks = accum_blocks(n4);
+  ADNM_PROF("grad_accum_final", st, (wire_bf16 ? 14.0 : 12.0) * n);
+  if (wire_bf16) grad_accum_final_kernel<true><<<(unsigned)blocks, kBlock, 0, st>>>(acc, g, (uint16_t*)wire_bf16, n4, scale);
+  else grad_accum_final_kernel<false><<<(unsigned)blocks, kBlock, 0, st>>>(acc, g, nullptr, n4, scale);
+  ADNM_CHECK_LAUNCH("grad_accum_final");
+  return ADNM_OK;
+}
 
 static int cast_launch(const void* src, void* dst, int64_t n, float scale, adnm_stream_t stream, bool to_bf16) {
   ADNM_REQUIRE(src && dst && n > 0, "cast: null pointer or n <= 0");

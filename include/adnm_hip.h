@@ -566,6 +566,18 @@ int adnm_swish_bwd(const float* dy, const float* x, const float* beta, float* dx
 int adnm_cast_f32_bf16(const void* src, void* dst, int64_t n, float scale, adnm_stream_t stream);
 int adnm_cast_bf16_f32(const void* src, void* dst, int64_t n, float scale, adnm_stream_t stream);
 
+/* Gradient accumulation over micro-batches: train.py:136-145 with loss.backward() repeated k times before optimizer.step() — there
+ * autograd adds into p.grad; here the backward kernels OVERWRITE their flat_g slices every pass, so the sum lives in a second flat
+ * fp32 buffer.  Streaming passes over a flat range: acc, g 16-byte aligned, n > 0, n % 4 == 0.
+ *   adnm_grad_accum, micro-steps 1 .. k-1:   first != 0: acc[i] = g[i]   (acc is NOT read: no memset is ever needed; 8 B/element)
+ *                                            first == 0: acc[i] = acc[i] + g[i]                                  (12 B/element)
+ *   adnm_grad_accum_final, micro-step k:     g[i] = (acc[i] + g[i]) * scale   (add, then multiply, each rounded once; scale = 1/k)
+ *       wire_bf16 != NULL (8-byte aligned): also wire_bf16[i] = bf16_rne(g[i]), the range's image for the bf16 collective
+ *       (adnm_cast_f32_bf16 of the result, without the second pass).  12 (14) B/element.
+ * After the final pass g holds the averaged accumulated gradient; adnm_adamw_step runs on it unchanged. */
+int adnm_grad_accum(float* acc, const float* g, int64_t n, int first, adnm_stream_t stream);
+int adnm_grad_accum_final(const float* acc, float* g, void* wire_bf16, int64_t n, float scale, adnm_stream_t stream);
+
 /* ---------------------------------------------------------------- tall-skinny fp32 GEMMs on MFMA (K6)
  * The Linear / 1x1 projections of the full-resolution stages (ADNssd.py:309,461; model_untils.py:64,67,193,196,831;
  * ADNMUNet.py:634): M = B*H*W tokens, K,N <= 256.  v_mfma_f32_16x16x4_f32: exact fp32 (an fmaf chain).
