@@ -105,7 +105,11 @@ class QuantTable:
 
     def weight_row(self, device, key):
         """-> row of the record of WEIGHT `key` (a parameter's data_ptr) in this device's table: the b-slots hold the scale its fp8 shadow is
-        written with (adnm_adamw_step) and the max |w| the optimiser pass collects for the next one; the a-slots are unused."""
+        written with (adnm_adamw_step) and the max |w| the optimiser pass collects for the next one; the a-slots are unused.
+        INVARIANT: fmax_a == 0 marks a weight record, fmax_a > 0 (record(), set()) a GEMM call site.  adnm_quant_update_guarded tells
+        them apart by it: a skipped step's discard zeroes the maxima of the call sites only and keeps a weight record's amax_b (gathered
+        by the optimiser pass of the step before).  A weight record given an fmax_a > 0 would have that maximum wiped; a call site given
+        fmax_a == 0 would carry a skipped step's maxima into its scales."""
         with self._lock:
             ent = self._ent(device)
             row = ent["keys"].get((key, "w"))
@@ -145,10 +149,15 @@ class QuantTable:
             ent["tab"][row] = torch.tensor([scale_a, scale_b, 0.0, 0.0, 57344.0 if role[0] == "g" else 448.0, 448.0, 1.0 if record else 0.0, 0.0])
             return ent["tab"][row]
 
-    def update(self, device):
-        """once per training step, after it: amax -> scales on calibration steps, set the record flags of the next step"""
+    def update(self, device, guard=None):
+        """once per training step, after it: amax -> scales on calibration steps, set the record flags of the next step.
+        guard: the statistics block of a monitored trainer (adnm_step_guard ran before): a skipped step only discards its maxima"""
         ent = self._dev.get(self._idx(device))
         if ent is None:
+            return
+        if guard is not None:
+            lib.call("adnm_quant_update_guarded", ent["tab"].data_ptr(), len(ent["keys"]), ent["state"].data_ptr(), float(self.headroom),
+                     guard.data_ptr(), _stream())
             return
         lib.call("adnm_quant_update", ent["tab"].data_ptr(), len(ent["keys"]), ent["state"].data_ptr(), float(self.headroom), _stream())
 

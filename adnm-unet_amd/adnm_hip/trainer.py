@@ -51,13 +51,17 @@ class _Both:
 class FlatTrainer:
     def __init__(self, model, loss_fn, lr=1e-3, betas=(0.9, 0.999), eps=1e-9, weight_decay=1e-2, max_norm=0.0,
                  process_group=None, use_graph=True, fused=True, overlap="auto", reduce_dtype="f32", stages=None, defer_folds=True, side_stream=False,
-                 nstages=None, accum_steps=1):
+                 nstages=None, accum_steps=1, monitor=False):
         """overlap: cut the backward at the model's stage boundaries and all-reduce every stage's gradients while the backward of the
         stages before it runs.  "auto" = whenever there is more than one rank.  `stages` is the older name of the same switch
         (True / False).  nstages: None = every stage the model offers (forward_stages(): 5 for ADNM-UNet); 2 = the two-stage cut
         (encoder | decoder + refiner).
         accum_steps: k calls of step() make ONE optimiser step on the mean gradient of their k micro-batches (train.py:136-145 with
-        loss.backward() repeated before optimizer.step()); see step()."""
+        loss.backward() repeated before optimizer.step()); see step().
+        monitor: keep the epoch's statistics (train.py:140-153: gradient norms, clip count, summed loss) in device memory — stats()
+        reads them with ONE synchronising copy per epoch instead of two .item() per step — and SKIP every optimiser step whose
+        gradient is not finite (parameters, moments, step counter, shadow and fp8 table stay as they were).  False: nothing of this
+        exists, the step is launch for launch what it was."""
         self.model, self.loss_fn = model, loss_fn
         self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_norm
         self.group = process_group
@@ -114,6 +118,12 @@ class FlatTrainer:
         self.hyper = self._hyper_host = None   # [lr, max_norm] as the tail graph reads them, and the host's copy
         self._splitws = None                   # the split-K capture scope of all graphs (ops.SPLITWS)
         self._pin = None                       # the pin on the fp8 table (ops.QUANT.pinned)
+        # monitor=True: the statistics block (include/adnm_hip.h: adnm_step_guard), allocated with the flat buffers; the tail graph holds
+        # its address.  fused=False keeps the same nine doubles and takes the decision on the host (_skip_host)
+        self.monitor = bool(monitor)
+        self._stats = None
+        self._skip_host = False
+        self._norm_host = None
 
     # ------------------------------------------------------------------ gradient accumulation
     @staticmethod
@@ -283,6 +293,8 @@ class FlatTrainer:
             self.ws = torch.empty(int(lib.query("adnm_adamw_ws_bytes")), dtype=torch.uint8, device=dev)
         if self._accum_steps > 1:
             self._accumulator()
+        if self.monitor:
+            self._stats_block()
 
     def bucket_report(self):
         """[(bucket index in all-reduce order, first element, last element + 1, bytes on the wire)]: what each stage's collective moves —
@@ -327,7 +339,8 @@ class FlatTrainer:
         """What the captures own, given back in a fixed order: the graphs first, the tail before the stage graphs before the first (they
         reference graph-pool memory), then the tensors that live in that pool (the static loss with its autograd graph, the stage
         hand-over, the static inputs, the tail's hyper-parameters), then the split-K scope the graphs' launches point into, then the
-        pin on the fp8 table; last the gradient accumulator (no graph points into it; a step after a failed prepare() makes a new one).
+        pin on the fp8 table; last the gradient accumulator (no graph points into it; a step after a failed prepare() makes a new one)
+        and the statistics block of a monitored run (the tail graph, gone by then, held its address; its counts end with the captures).
         The only such list: close() and a failed prepare() both end here."""
         self.tail = None
         self.graphs = []
@@ -343,6 +356,7 @@ class FlatTrainer:
             pin.release()
         self.acc = None
         self._micro = 0
+        self._stats = None
 
     def close(self):
         """Give back everything this trainer owns on the device, in a fixed order, NOW (not whenever the cyclic collector gets to
@@ -540,7 +554,8 @@ class FlatTrainer:
         # the clip threshold in device memory (self.hyper) so that the captured launches follow the host's schedules
         self.hyper = torch.tensor([self.lr, self.max_norm], dtype=torch.float32, device=x.device)
         self._hyper_host = (float(self.lr), float(self.max_norm))
-        live = [t for t in (self.flat_p, self.exp_avg, self.exp_avg_sq, self.state, self.flat_g, self.shadow) if t is not None]
+        # (the statistics block of a monitored run among them: the warm-up's guard counted one step, prepare() leaves the block zero)
+        live = [t for t in (self.flat_p, self.exp_avg, self.exp_avg_sq, self.state, self.flat_g, self.shadow, self._stats) if t is not None]
         keep = [t.clone() for t in live]
         qsave = ops.QUANT.snapshot(x.device) if self.fp8 else None
         try:
@@ -569,9 +584,24 @@ class FlatTrainer:
             for lo, hi in self.buckets:
                 if hi > lo:
                     self._cast(self.comm[lo:hi], self.flat_g[lo:hi], 1.0 / self.world)
+        self._update(hyper=True)
+
+    def _update(self, hyper=False):
+        """the end of a step, on gradients that are final: (monitor: guard + statistics ->) fp8 table update -> clip + AdamW (+ shadow).
+        Eagerly and as the body of the tail graph.
+        monitor, more than one rank: the guard runs AFTER the all-reduce, on a flat_g that holds the same bits on every rank (the
+        collective leaves one result everywhere — fp32 sums and, on the bf16 wire, the bf16 sums every rank casts back with the same
+        kernel), so every rank takes the same decision from the same state[1]: the ranks skip or apply together without exchanging
+        a flag (tests/test_step_guard_gloo.py)."""
+        guard = None
+        if self.monitor:
+            self._guard(hyper)
+            guard = self._stats
         if self.fp8:
-            ops.QUANT.update(self.flat_g.device)
-        self._optimizer_step(hyper=True)
+            # one launch: amax -> scales on calibration steps, the next step's record flags.  BEFORE the optimiser pass: that pass writes
+            # the e4m3 shadow of the updated weights with the scales the next step's GEMMs will read
+            ops.QUANT.update(self.flat_g.device, guard=guard)
+        self._optimizer_step(hyper=hyper)
 
     def _run_eager(self, x, tgt, between=None):
         """between(j): called after part j (its bucket is complete) while parts remain — the N > 1 flow starts the bucket's all-reduce there"""
@@ -629,7 +659,10 @@ class FlatTrainer:
         per-launch HIP events cannot be recorded inside a graph replay).
         accum_steps = k > 1: one MICRO-step; returns this micro-batch's loss.  Calls 1 .. k-1 of a cycle run forward and backward and
         add every bucket into the accumulator: no collective, no fp8 table update, no optimiser pass.  Call k adds its own gradient,
-        leaves the mean of the k gradients in flat_g and goes on exactly like a plain step (all-reduce, clip, AdamW, shadow)."""
+        leaves the mean of the k gradients in flat_g and goes on exactly like a plain step (all-reduce, clip, AdamW, shadow).
+        monitor=True: every call adds its loss to the statistics; the optimiser step (once per cycle, on the averaged gradient — a
+        non-finite micro-gradient reaches it through the accumulator) is skipped when that gradient is not finite.  A skipped cycle ends
+        like any other: micro_step is 0 again and the next cycle overwrites the accumulator."""
         if self.used is None:
             self.prepare(x, tgt)
         elif self._shadow is not None and self._shadow.stale():   # a write outside the optimiser (a checkpoint load, an in-place op)
@@ -661,6 +694,8 @@ class FlatTrainer:
                 self._bucket_ready(0, pending)
             for p in self.used:
                 p.grad = None
+        if self.monitor:
+            self._loss_stat(loss)
         if self._micro < self._accum_steps - 1:   # a micro-step inside a cycle ends here: parameters, moments, step counter, fp8 table untouched
             self._micro += 1
             return loss
@@ -673,33 +708,114 @@ class FlatTrainer:
                 self.hyper.copy_(torch.tensor(self._hyper_host, dtype=torch.float32), non_blocking=True)
             self.tail.replay()
         else:
-            if self.fp8:
-                # one launch: amax -> scales on calibration steps, the next step's record flags.  BEFORE the optimiser pass: that pass writes
-                # the e4m3 shadow of the updated weights with the scales the next step's GEMMs will read
-                ops.QUANT.update(self.flat_g.device)
-            self._optimizer_step()
-        self._steps += 1
+            self._update()
+        if not self._skip_host:   # (fused: always; the device's own counter, state[0], is the one a skipped step leaves alone)
+            self._steps += 1
         return loss
+
+    # ------------------------------------------------------------------ monitor=True: statistics and the skipped step
+    STAT_FIELDS = ("steps", "skipped", "norm_sum", "norm_max", "last_norm", "clip_count", "loss_sum", "loss_nonfinite")
+
+    def _stats_block(self):
+        """nine doubles laid out as adnm_step_guard documents them (eight statistics, then the skip flag as an int); zero at birth"""
+        if self._stats is None:
+            self._stats = torch.zeros(9, dtype=torch.float64, device=self.flat_g.device)
+        return self._stats
+
+    def _require_monitor(self, what):
+        if not self.monitor:
+            raise RuntimeError(f"FlatTrainer.{what}: this trainer was built with monitor=False and keeps no statistics; build it with monitor=True")
+
+    def stats(self, reset=False):
+        """The statistics since the last reset, as a dict: steps (optimiser steps applied), skipped (steps whose gradient was not
+        finite), loss_sum / loss_nonfinite (over every step() call, micro-steps included; this rank's batches), norm_sum / norm_mean /
+        norm_max (pre-clip gradient norms of the applied steps — norm_mean is train.py:148's avg_grad_norm), last_norm (of the last step,
+        applied or skipped), clip_count / clip_rate (applied steps with max_norm > 0 and norm > max_norm, train.py:142).
+        SYNCHRONISES: one device -> host copy that waits for every step enqueued so far.  Meant to be called once per epoch.
+        reset=True: reset_stats() afterwards."""
+        self._require_monitor("stats")
+        vals = self._stats[:8].tolist() if self._stats is not None else [0.0] * 8   # (no step yet / closed: nothing counted)
+        d = dict(zip(self.STAT_FIELDS, vals))
+        for k in ("steps", "skipped", "clip_count", "loss_nonfinite"):
+            d[k] = int(d[k])
+        d["norm_mean"] = d["norm_sum"] / d["steps"] if d["steps"] else 0.0
+        d["clip_rate"] = d["clip_count"] / d["steps"] if d["steps"] else 0.0
+        if reset:
+            self.reset_stats()
+        return d
+
+    def reset_stats(self):
+        """zero the statistics (one memset on the compute stream, behind the steps enqueued so far; no synchronisation)"""
+        self._require_monitor("reset_stats")
+        if self._stats is not None:
+            self._stats.zero_()
+
+    @torch.no_grad()
+    def _loss_stat(self, loss):
+        """loss_sum += loss (finite) or loss_nonfinite += 1: one eager one-lane launch behind the forward / backward, outside the
+        stage graphs; torch on the CPU test path"""
+        s = self._stats_block()
+        if self.fused and s.is_cuda:
+            l = loss.detach()
+            if l.dtype != torch.float32 or l.numel() != 1 or not l.is_cuda:
+                raise RuntimeError(f"FlatTrainer(monitor=True): the loss must be one fp32 value on the GPU, got {l.dtype} {tuple(l.shape)} on {l.device}")
+            lib.call("adnm_loss_stat", l.data_ptr(), s.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            return
+        v = float(loss)
+        if v == v and abs(v) != float("inf"):
+            s[6] += v
+        else:
+            s[7] += 1
+
+    @torch.no_grad()
+    def _guard(self, hyper=False):
+        """sum of squares of the final gradient -> state[1], the decision skip = not finite, the counters (adnm_step_guard); the same
+        statements in torch on the CPU test path, where the decision is a host bool"""
+        s = self._stats_block()
+        if self.fused:
+            lib.call("adnm_step_guard", self.flat_g.data_ptr(), self.n, self.state.data_ptr(), float(self.max_norm),
+                     self.hyper.data_ptr() if hyper else None, self.ws.data_ptr(), self.ws.numel(), s.data_ptr(),
+                     torch.cuda.current_stream().cuda_stream)
+            return
+        self._norm_host = self.flat_g.norm()
+        norm = float(self._norm_host)
+        s[4] = norm
+        self._skip_host = not (norm == norm and norm != float("inf"))
+        if self._skip_host:
+            s[1] += 1
+            return
+        s[0] += 1
+        s[2] += norm
+        s[3] = max(float(s[3]), norm)
+        max_norm = float(torch.tensor(self.max_norm, dtype=torch.float32))   # (the kernel compares in fp32)
+        if max_norm > 0 and norm > max_norm:
+            s[5] += 1
 
     def _optimizer_step(self, hyper=False):
         if self.fused:
             mode = self.shadow_mode
             sh = (self.shadow.data_ptr(), mode, self.seg_end.data_ptr(), self.seg_rec.data_ptr(), self.seg_end.numel(),
                   ops.QUANT.table_ptr(self.flat_p.device) if mode == 2 else None) if mode else (None, 0, None, None, 0, None)
+            if self.monitor:   # the norm is the guard's; every kernel returns at entry when the guard set the skip flag
+                lib.call("adnm_adamw_step_guarded", self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(),
+                         self.exp_avg_sq.data_ptr(), self.n, self.state.data_ptr(), float(self.lr), float(self.betas[0]), float(self.betas[1]),
+                         float(self.eps), float(self.wd), float(self.max_norm), *sh, self.hyper.data_ptr() if hyper else None,
+                         self._stats.data_ptr(), torch.cuda.current_stream().cuda_stream)
+                return
             lib.call("adnm_adamw_step", self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(),
                      self.exp_avg_sq.data_ptr(), self.n, self.state.data_ptr(), float(self.lr), float(self.betas[0]), float(self.betas[1]),
                      float(self.eps), float(self.wd), float(self.max_norm), self.ws.data_ptr(), self.ws.numel(), *sh,
                      self.hyper.data_ptr() if hyper else None, torch.cuda.current_stream().cuda_stream)
-        else:
-            self._torch_adamw_for_tests()
+        elif not self._skip_host:   # (monitor, CPU test path: a skipped step touches nothing, _steps included)
+            self._torch_adamw_for_tests(self._norm_host if self.monitor else None)
 
     @torch.no_grad()
-    def _torch_adamw_for_tests(self):
+    def _torch_adamw_for_tests(self, norm=None):
         """Same arithmetic in torch ops — exists only so the CPU (gloo) tests can exercise the N>1 logic and the
         GPU test has an independent statement of the fused kernel's update rule.  bench.py never takes it."""
         g = self.flat_g
         if self.max_norm > 0:
-            g = g * torch.clamp(self.max_norm / (g.norm() + 1e-6), max=1.0)
+            g = g * torch.clamp(self.max_norm / ((g.norm() if norm is None else norm) + 1e-6), max=1.0)   # (norm: the guard's, formed once)
         step = self._steps + 1
         b1, b2 = self.betas
         self.flat_p.mul_(1 - self.lr * self.wd)
@@ -709,5 +825,6 @@ class FlatTrainer:
         self.flat_p.addcdiv_(self.exp_avg, denom, value=-self.lr / (1 - b1 ** step))
 
     def grad_norm(self):
-        """Pre-clip total gradient norm of the last step (device scalar; train.py:141 reads it with .item())."""
+        """Pre-clip total gradient norm of the last step (device scalar; train.py:141 reads it with .item()).  monitor=True: of the last
+        APPLIED step (a skipped step leaves state alone; stats()["last_norm"] shows its inf / nan)."""
         return self.state[1].sqrt() if self.fused else self.flat_g.norm()

@@ -179,6 +179,18 @@ struct AdnmQuant {
   float scale_a, scale_b, amax_a, amax_b, fmax_a, fmax_b, record, pad;
 };
 
+// Statistics block of a monitored training run (device memory, 9 doubles = 72 B; layout documented in include/adnm_hip.h:
+// adnm_step_guard).  Counts are doubles too: one dtype for the host's single read.  `skip` is the flag of the step in flight: written by
+// the guard's one-wave kernel, read (one uniform load) by the guarded table update, tick and AdamW kernels behind it on the stream.
+// `sumsq`: where the guard's fold leaves the sum of squares; it moves on to state[1] only when it is finite.
+struct AdnmStepStats {
+  double applied, skipped, norm_sum, norm_max, last_norm, clip_count, loss_sum, loss_nonfinite;
+  int skip;
+  float sumsq;
+};
+// finiteness on the bit pattern (exponent all ones = Inf or NaN): no math flag of the build can fold this test away
+__device__ __forceinline__ bool adnm_nonfinite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
 __device__ __forceinline__ adnm_bf16x8 adnm_pack_bf16x8(const float (&v)[8]) {
   using f8 = __attribute__((ext_vector_type(8))) float;
   const f8 t = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};

@@ -492,7 +492,19 @@ extern "C" int adnm_colsum(const float* x, float* out, int64_t rows, int64_t n, 
 // ---- delayed per-tensor scaling of the fp8 configuration (include/adnm_hip.h: adnm_quant_update).  One workgroup: a model has a
 // few hundred GEMM call sites, and a single workgroup can advance the step counter behind its own barrier.
 namespace {
-__global__ __launch_bounds__(256) void quant_update_kernel(AdnmQuant* __restrict__ tab, int n, float* __restrict__ state, float headroom) {
+// GUARD (the monitored run): a step whose guard set stats->skip discards what it collected — a maximum taken over non-finite values must
+// not become a scale — and leaves the scales, the record flags and the counter alone: a skipped calibration step is simply repeated.
+// What the step collected: the maxima of the GEMM call sites' records (fmax_a > 0).  A WEIGHT record (fmax_a == 0: its a-slots are unused)
+// holds max |w| gathered by the optimiser pass of the step BEFORE, over finite weights the skipped step did not move: it is kept, and the
+// repeated calibration makes the scale from it that the skipped one would have made.
+template <bool GUARD>
+__global__ __launch_bounds__(256) void quant_update_kernel(AdnmQuant* __restrict__ tab, int n, float* __restrict__ state, float headroom,
+                                                           const AdnmStepStats* __restrict__ stats) {
+  if (GUARD && stats->skip) {
+    for (int i = threadIdx.x; i < n; i += 256)
+      if (tab[i].fmax_a > 0.f) tab[i].amax_a = 0.f, tab[i].amax_b = 0.f;
+    return;
+  }
   const float c = state[0], period = state[1] < 1.f ? 1.f : state[1];
   const bool was_recording = fmodf(c, period) == 0.f;        // the step that just ended collected amax
   const bool will_record = fmodf(c + 1.f, period) == 0.f;
@@ -516,8 +528,22 @@ extern "C" int adnm_quant_update(float* table, int64_t n, float* state, float he
   ADNM_REQUIRE(headroom >= 1.f, "quant_update: headroom %f must be >= 1", headroom);
   hipStream_t st = (hipStream_t)stream;
   ADNM_PROF("quant_update", st, 64.0 * (double)n);
-  quant_update_kernel<<<1, 256, 0, st>>>(reinterpret_cast<AdnmQuant*>(table), (int)n, state, headroom);
+  quant_update_kernel<false><<<1, 256, 0, st>>>(reinterpret_cast<AdnmQuant*>(table), (int)n, state, headroom, nullptr);
   ADNM_CHECK_LAUNCH("quant_update");
+  return ADNM_OK;
+}
+
+// adnm_quant_update behind adnm_step_guard (the monitored run; train.py:136-153 has no fp8 path: this keeps a skipped step of that loop
+// from leaving a trace in the table).  Flag set: amax_a = amax_b = 0 in every call-site record, nothing else written.  Flag clear: bit-identical to
+// adnm_quant_update.
+extern "C" int adnm_quant_update_guarded(float* table, int64_t n, float* state, float headroom, const void* stats, adnm_stream_t stream) {
+  ADNM_REQUIRE(table && state && stats && n >= 0 && n < (1 << 20), "quant_update_guarded: bad arguments");
+  ADNM_REQUIRE(headroom >= 1.f, "quant_update_guarded: headroom %f must be >= 1", headroom);
+  ADNM_REQUIRE((uintptr_t)stats % 8 == 0, "quant_update_guarded: the statistics block must be 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  ADNM_PROF("quant_update_guarded", st, 64.0 * (double)n);
+  quant_update_kernel<true><<<1, 256, 0, st>>>(reinterpret_cast<AdnmQuant*>(table), (int)n, state, headroom, reinterpret_cast<const AdnmStepStats*>(stats));
+  ADNM_CHECK_LAUNCH("quant_update_guarded");
   return ADNM_OK;
 }
 

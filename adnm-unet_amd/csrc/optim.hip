@@ -28,7 +28,11 @@ __global__ __launch_bounds__(kBlock) void sumsq_partial_kernel(const float* __re
 }
 
 // state: [0] step, [1] sum of squares of the gradient, [2] 1 - beta1^step, [3] sqrt(1 - beta2^step)
-__global__ void optim_tick_kernel(float* __restrict__ state, float beta1, float beta2) {
+// GUARD (the monitored run, adnm_adamw_step_guarded): a step whose guard (step_guard_kernel) set stats->skip leaves the counter and the bias
+// corrections alone
+template <bool GUARD>
+__global__ void optim_tick_kernel(float* __restrict__ state, float beta1, float beta2, const AdnmStepStats* __restrict__ stats) {
+  if (GUARD && stats->skip) return;
   const float step = state[0] + 1.0f;
   state[0] = step;
   state[2] = 1.0f - powf(beta1, step);
@@ -52,11 +56,13 @@ __device__ __forceinline__ void adamw_elem(float& P, float g, float& M, float& V
 // SH16: also write the bf16 SHADOW of the updated parameters (element i of sh16 = bf16(p[i])): the narrow copy the weight-streaming GEMMs
 // read in the bf16 configuration (adnm_skgemm b_dtype ADNM_B_BF16) — half the bytes of the pass that re-reads 72 M parameters twice a step,
 // for 2 more bytes per parameter here (the values are in registers anyway)
-template <bool NT, int U, bool SH16>
+// GUARD: one uniform load and branch at entry: a skipped step returns before touching p, m, v or the shadow
+template <bool NT, int U, bool SH16, bool GUARD>
 __global__ __launch_bounds__(kBlock) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                        float* __restrict__ v, int64_t n, const float* __restrict__ state, float lr,
                                                        float beta1, float beta2, float eps, float wd, float max_norm, uint16_t* __restrict__ sh16,
-                                                       const float* __restrict__ hyper) {
+                                                       const float* __restrict__ hyper, const AdnmStepStats* __restrict__ stats) {
+  if (GUARD && stats->skip) return;
   if (hyper) lr = hyper[0], max_norm = hyper[1];   // device-resident learning rate / clip threshold: a captured launch follows the host's schedule
   float coef = 1.0f;
   if (max_norm > 0.f) {  // torch.nn.utils.clip_grad_norm_: coef = clamp(max_norm / (norm + 1e-6), max=1)
@@ -112,12 +118,15 @@ __global__ __launch_bounds__(kBlock) void adamw_kernel(float* __restrict__ p, co
 // Tensors are the segments of the flat buffer: seg_end[s] = end of segment s in float4 units (tensors are 16-byte aligned in the flat
 // layout), seg_rec[s] = row of its record in the table, or < 0 (not a GEMM weight: no scale, the shadow bytes are never read).
 // A workgroup owns a CONTIGUOUS range, so a wave stays inside one tensor for many trips and commits one atomic max per tensor it crosses.
-template <bool UPD, int SH>
+// GUARD: as in adamw_kernel; a skipped step also commits no amax_b
+template <bool UPD, int SH, bool GUARD>
 __global__ __launch_bounds__(kBlock) void adamw_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, int64_t n4, int64_t per_block, const float* __restrict__ state,
                                                            float lr, float beta1, float beta2, float eps, float wd, float max_norm,
                                                            void* __restrict__ shadow, const int* __restrict__ seg_end, const int* __restrict__ seg_rec,
-                                                           int nseg, AdnmQuant* __restrict__ tab, int collect, const float* __restrict__ hyper) {
+                                                           int nseg, AdnmQuant* __restrict__ tab, int collect, const float* __restrict__ hyper,
+                                                           const AdnmStepStats* __restrict__ stats) {
+  if (GUARD && stats->skip) return;
   if (UPD && hyper) lr = hyper[0], max_norm = hyper[1];
   float coef = 1.0f, bc1 = 1.f, bc2s = 1.f;
   if (UPD) {
@@ -317,7 +326,7 @@ extern "C" int64_t adnm_adamw_ws_bytes(void) { return kNormBlocks * (int64_t)siz
 namespace {
 int seg_launch(bool upd, float* p, const float* g, float* m, float* v, int64_t n, float* state, float lr, float beta1, float beta2, float eps,
                float wd, float max_norm, void* shadow, int shadow_dtype, const int* seg_end, const int* seg_rec, int64_t nseg, float* tab,
-               int collect, const float* hyper, hipStream_t st) {
+               int collect, const float* hyper, const AdnmStepStats* stats, hipStream_t st) {
   ADNM_REQUIRE(seg_end && seg_rec && nseg >= 1 && nseg < (1 << 24) && (tab || shadow_dtype != ADNM_B_FP8),
                "adamw / shadow pass: the fp8 shadow needs the segment tables and the record table");
   ADNM_REQUIRE(n / 4 < (1ll << 31), "adamw / shadow pass: more than 2^31 quads");
@@ -327,14 +336,50 @@ int seg_launch(bool upd, float* p, const float* g, float* m, float* v, int64_t n
   if (blocks < 1) blocks = 1;
   const int64_t per_block = adnm_cdiv(adnm_cdiv(n4, blocks), kBlock) * kBlock;
   AdnmQuant* t = reinterpret_cast<AdnmQuant*>(tab);
-#define SEG(UPDV, SHV) adamw_seg_kernel<UPDV, SHV><<<(unsigned)blocks, kBlock, 0, st>>>(p, g, m, v, n4, per_block, state, lr, beta1, beta2, eps, wd, \
-                                                                                       max_norm, shadow, seg_end, seg_rec, (int)nseg, t, collect, hyper)
-  if (upd) {
-    if (shadow_dtype == ADNM_B_BF16) SEG(true, 1); else SEG(true, 2);
+#define SEG(UPDV, SHV, GV) adamw_seg_kernel<UPDV, SHV, GV><<<(unsigned)blocks, kBlock, 0, st>>>(p, g, m, v, n4, per_block, state, lr, beta1, beta2, eps, \
+                                                                                               wd, max_norm, shadow, seg_end, seg_rec, (int)nseg, t, collect, hyper, stats)
+  if (upd && stats) {
+    if (shadow_dtype == ADNM_B_BF16) SEG(true, 1, true); else SEG(true, 2, true);
+  } else if (upd) {
+    if (shadow_dtype == ADNM_B_BF16) SEG(true, 1, false); else SEG(true, 2, false);
   } else {
-    if (shadow_dtype == ADNM_B_BF16) SEG(false, 1); else SEG(false, 2);
+    if (shadow_dtype == ADNM_B_BF16) SEG(false, 1, false); else SEG(false, 2, false);
   }
 #undef SEG
+  return ADNM_OK;
+}
+}  // namespace
+
+namespace {
+// the global sum of squares of g into *dst: one partial per workgroup, then the deterministic fold
+void sumsq_launch(const float* g, int64_t n, float* dst, void* ws, hipStream_t st) {
+  float* part = (float*)ws;
+  { ADNM_PROF("grad_sumsq", st, 4.0 * n); sumsq_partial_kernel<<<kNormBlocks, kBlock, 0, st>>>(g, n, part); }
+  adnm_launch_fold("grad_sumsq_fold", part, kNormBlocks, 1, {dst, 1}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}, st);
+}
+// tick + AdamW (+ shadow) behind a sum of squares that is already in state[1].  stats == NULL: adnm_adamw_step's launches; else the
+// same kernels with the entry check on stats->skip (adnm_adamw_step_guarded)
+int update_launch(float* p, const float* g, float* m, float* v, int64_t n, float* state, float lr, float beta1, float beta2, float eps,
+                  float weight_decay, float max_norm, void* shadow, int shadow_dtype, const int* seg_end, const int* seg_rec, int64_t nseg,
+                  float* wtab, const float* hyper, const AdnmStepStats* stats, hipStream_t st) {
+  if (stats) optim_tick_kernel<true><<<1, 1, 0, st>>>(state, beta1, beta2, stats);
+  else optim_tick_kernel<false><<<1, 1, 0, st>>>(state, beta1, beta2, nullptr);
+  int64_t blocks = adnm_cdiv(n / 4, kBlock);
+  if (blocks > 4096) blocks = 4096;
+  {   // measured in one session (two runs each): plain accesses 0.446 ms, non-temporal g / m / v 0.414, + two float4 per lane 0.400 / 0.47 without
+    ADNM_PROF("adamw_update", st, 4.0 * n * 7 + (shadow ? (shadow_dtype == ADNM_B_BF16 ? 2.0 : 1.0) * n : 0.0));
+    // with the segment tables at hand the contiguous-range kernel takes the bf16 shadow too (measured in one trace: 0.36 ms against 0.41 ms
+    // for the interleaved kernel with the extra 2-byte stream)
+    if (shadow && (shadow_dtype == ADNM_B_FP8 || (seg_end && seg_rec && nseg >= 1))) {
+      if (int rc = seg_launch(true, p, g, m, v, n, state, lr, beta1, beta2, eps, weight_decay, max_norm, shadow, shadow_dtype, seg_end, seg_rec, nseg, wtab, 1, hyper, stats, st)) return rc;
+    } else if (shadow) {
+      if (stats) adamw_kernel<true, 1, true, true><<<(unsigned)blocks, kBlock, 0, st>>>(p, g, m, v, n, state, lr, beta1, beta2, eps, weight_decay, max_norm, (uint16_t*)shadow, hyper, stats);
+      else adamw_kernel<true, 1, true, false><<<(unsigned)blocks, kBlock, 0, st>>>(p, g, m, v, n, state, lr, beta1, beta2, eps, weight_decay, max_norm, (uint16_t*)shadow, hyper, nullptr);
+    } else {
+      if (stats) adamw_kernel<true, 1, false, true><<<(unsigned)blocks, kBlock, 0, st>>>(p, g, m, v, n, state, lr, beta1, beta2, eps, weight_decay, max_norm, nullptr, hyper, stats);
+      else adamw_kernel<true, 1, false, false><<<(unsigned)blocks, kBlock, 0, st>>>(p, g, m, v, n, state, lr, beta1, beta2, eps, weight_decay, max_norm, nullptr, hyper, nullptr);
+    }
+  }
   return ADNM_OK;
 }
 }  // namespace
@@ -350,25 +395,92 @@ extern "C" int adnm_adamw_step(float* p, const float* g, float* m, float* v, int
     return ADNM_EWORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)ws;
-  { ADNM_PROF("grad_sumsq", st, 4.0 * n); sumsq_partial_kernel<<<kNormBlocks, kBlock, 0, st>>>(g, n, part); }
-  adnm_launch_fold("grad_sumsq_fold", part, kNormBlocks, 1, {state + 1, 1}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}, st);
-  optim_tick_kernel<<<1, 1, 0, st>>>(state, beta1, beta2);
-  int64_t blocks = adnm_cdiv(n / 4, kBlock);
-  if (blocks > 4096) blocks = 4096;
-  {   // measured in one session (two runs each): plain accesses 0.446 ms, non-temporal g / m / v 0.414, + two float4 per lane 0.400 / 0.47 without
-    ADNM_PROF("adamw_update", st, 4.0 * n * 7 + (shadow ? (shadow_dtype == ADNM_B_BF16 ? 2.0 : 1.0) * n : 0.0));
-    // with the segment tables at hand the contiguous-range kernel takes the bf16 shadow too (measured in one trace: 0.36 ms against 0.41 ms
-    // for the interleaved kernel with the extra 2-byte stream)
-    if (shadow && (shadow_dtype == ADNM_B_FP8 || (seg_end && seg_rec && nseg >= 1))) {
-      if (int rc = seg_launch(true, p, g, m, v, n, state, lr, beta1, beta2, eps, weight_decay, max_norm, shadow, shadow_dtype, seg_end, seg_rec, nseg, wtab, 1, hyper, st)) return rc;
-    } else if (shadow) {
-      adamw_kernel<true, 1, true><<<(unsigned)blocks, kBlock, 0, st>>>(p, g, m, v, n, state, lr, beta1, beta2, eps, weight_decay, max_norm, (uint16_t*)shadow, hyper);
-    } else {
-      adamw_kernel<true, 1, false><<<(unsigned)blocks, kBlock, 0, st>>>(p, g, m, v, n, state, lr, beta1, beta2, eps, weight_decay, max_norm, nullptr, hyper);
-    }
-  }
+  sumsq_launch(g, n, state + 1, ws, st);
+  if (int rc = update_launch(p, g, m, v, n, state, lr, beta1, beta2, eps, weight_decay, max_norm, shadow, shadow_dtype, seg_end, seg_rec, nseg, wtab,
+                             hyper, nullptr, st))
+    return rc;
   ADNM_CHECK_LAUNCH("adamw_step");
+  return ADNM_OK;
+}
+
+// ---- the monitored step (FlatTrainer(monitor=True); train.py:136-153: the loop that reads original_norm.item() and loss.item() after
+// every step to feed the adaptive clip threshold of train.py:122-130 and the epoch's printout) — the same quantities kept on the device,
+// and the step every mixed-precision trainer skips: one whose gradient is not finite.
+namespace {
+// one wave, lane 0 works: decide, count.  Sums are doubles, written with ordinary stores.
+__global__ __launch_bounds__(64) void step_guard_kernel(float* __restrict__ state, float max_norm, const float* __restrict__ hyper,
+                                                        AdnmStepStats* __restrict__ stats) {
+  if (threadIdx.x != 0) return;
+  if (hyper) max_norm = hyper[1];   // as the AdamW kernels read it
+  const float sumsq = stats->sumsq;   // where the fold left it
+  const float norm = sqrtf(sumsq);   // the value grad_norm() reports and the clip coefficient is made from
+  stats->last_norm = (double)norm;   // of every step, applied or not: a skipped step shows as inf / nan here
+  if (adnm_nonfinite_bits(sumsq)) {
+    stats->skipped += 1.0;
+    stats->skip = 1;
+  } else {
+    state[1] = sumsq;   // an applied step: where the AdamW kernels and grad_norm() read it.  A skipped one leaves all of state alone
+    stats->applied += 1.0;
+    stats->norm_sum += (double)norm;
+    if ((double)norm > stats->norm_max) stats->norm_max = (double)norm;
+    if (max_norm > 0.f && norm > max_norm) stats->clip_count += 1.0;   // train.py:142: original_norm > current_norm, strictly
+    stats->skip = 0;
+  }
+}
+__global__ void loss_stat_kernel(const float* __restrict__ loss, AdnmStepStats* __restrict__ stats) {
+  const float l = *loss;
+  if (adnm_nonfinite_bits(l)) stats->loss_nonfinite += 1.0;
+  else stats->loss_sum += (double)l;
+}
+}  // namespace
+
+// Guard + statistics of one optimiser step (train.py:140-143), after the gradient is final and before the fp8 table update: sum g^2 by the
+// launches of adnm_adamw_step (the norm is bit-identical), then the decision skip = !finite(sum), state[1] = sum unless skipped, and the
+// counters.  A FINITE gradient whose fp32 sum of squares overflows counts as non-finite too: its norm cannot be formed, its clip
+// coefficient would be 0.
+extern "C" int adnm_step_guard(const float* g, int64_t n, float* state, float max_norm, const float* hyper, void* ws, int64_t ws_bytes,
+                               void* stats, adnm_stream_t stream) {
+  ADNM_REQUIRE(g && state && stats, "step_guard: null pointer");
+  ADNM_REQUIRE(n > 0 && n % 4 == 0, "step_guard: n=%lld must be a positive multiple of 4 (pad the flat buffers)", (long long)n);
+  ADNM_REQUIRE((uintptr_t)stats % 8 == 0, "step_guard: the statistics block must be 8-byte aligned");
+  if (!ws || ws_bytes < adnm_adamw_ws_bytes()) {
+    adnm_set_error("step_guard: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)adnm_adamw_ws_bytes());
+    return ADNM_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  sumsq_launch(g, n, &((AdnmStepStats*)stats)->sumsq, ws, st);
+  { ADNM_PROF("step_guard", st, 8.0 + sizeof(AdnmStepStats) * 2.0); step_guard_kernel<<<1, 64, 0, st>>>(state, max_norm, hyper, (AdnmStepStats*)stats); }
+  ADNM_CHECK_LAUNCH("step_guard");
+  return ADNM_OK;
+}
+
+// optimizer.step() of train.py:144 behind adnm_step_guard: adnm_adamw_step's tick + AdamW (+ shadow) launches WITHOUT a second norm pass
+// (state[1] is the guard's), each kernel returning at entry when the guard set the skip flag.  Flag clear: every value written is
+// bit-identical to adnm_adamw_step (same kernels, same adamw_elem, same order).
+extern "C" int adnm_adamw_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, float* state, float lr, float beta1, float beta2,
+                                       float eps, float weight_decay, float max_norm, void* shadow, int shadow_dtype, const int* seg_end,
+                                       const int* seg_rec, int64_t nseg, float* wtab, const float* hyper, const void* stats,
+                                       adnm_stream_t stream) {
+  ADNM_REQUIRE(p && g && m && v && state && stats, "adamw_step_guarded: null pointer");
+  ADNM_REQUIRE(n > 0 && n % 4 == 0, "adamw_step_guarded: n=%lld must be a positive multiple of 4 (pad the flat buffers)", (long long)n);
+  ADNM_REQUIRE(!shadow || shadow_dtype == ADNM_B_BF16 || shadow_dtype == ADNM_B_FP8, "adamw_step_guarded: the shadow is bf16 (1) or scaled e4m3 (2)");
+  ADNM_REQUIRE((uintptr_t)stats % 8 == 0, "adamw_step_guarded: the statistics block must be 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = update_launch(p, g, m, v, n, state, lr, beta1, beta2, eps, weight_decay, max_norm, shadow, shadow_dtype, seg_end, seg_rec, nseg, wtab,
+                             hyper, (const AdnmStepStats*)stats, st))
+    return rc;
+  ADNM_CHECK_LAUNCH("adamw_step_guarded");
+  return ADNM_OK;
+}
+
+// test_loss += loss.item() of train.py:145, without the .item(): one lane adds the device scalar into the block (or counts it as
+// non-finite).  Launched eagerly behind every forward / backward, micro-steps included; never part of a stage graph.
+extern "C" int adnm_loss_stat(const float* loss, void* stats, adnm_stream_t stream) {
+  ADNM_REQUIRE(loss && stats, "loss_stat: null pointer");
+  ADNM_REQUIRE((uintptr_t)loss % 4 == 0 && (uintptr_t)stats % 8 == 0, "loss_stat: misaligned pointer");
+  hipStream_t st = (hipStream_t)stream;
+  { ADNM_PROF("loss_stat", st, 4.0 + 16.0); loss_stat_kernel<<<1, 1, 0, st>>>(loss, (AdnmStepStats*)stats); }
+  ADNM_CHECK_LAUNCH("loss_stat");
   return ADNM_OK;
 }
 
@@ -385,7 +497,7 @@ extern "C" int adnm_shadow_refresh(const float* p, int64_t n, void* shadow, int 
     return adnm_cast_f32_bf16(p, shadow, n, 1.0f, stream);
   }
   if (int rc = seg_launch(false, const_cast<float*>(p), nullptr, nullptr, nullptr, n, nullptr, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, shadow, shadow_dtype, seg_end,
-                          seg_rec, nseg, wtab, collect, nullptr, st))
+                          seg_rec, nseg, wtab, collect, nullptr, nullptr, st))
     return rc;
   ADNM_CHECK_LAUNCH("shadow_refresh");
   return ADNM_OK;

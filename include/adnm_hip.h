@@ -62,6 +62,12 @@ enum { ADNM_B_F32 = 0, ADNM_B_BF16 = 1, ADNM_B_FP8 = 2 };
  * fmax_a / fmax_b are set by the caller when a record is created (448 for e4m3 operands, 57344 for e5m2).  headroom >= 1 leaves room
  * for the tensor to grow between calibrations (2 = one binade). */
 int adnm_quant_update(float* table, int64_t n, float* state, float headroom, adnm_stream_t stream);
+/* The same pass behind adnm_step_guard (below: the monitored training step), reading the skip flag of the statistics block `stats` from
+ * device memory.  Flag set: amax_a = amax_b = 0 in every record of a GEMM call site (fmax_a > 0): what the skipped step collected is
+ * discarded; a weight record (fmax_a == 0) keeps its amax_b, which the optimiser pass of the step BEFORE gathered over finite weights.
+ * NOTHING else is written: scales, record flags and the step counter stay, so a skipped calibration step is repeated by the next one
+ * and ends in the scales the skipped one would have made.  Flag clear: bit-identical to adnm_quant_update. */
+int adnm_quant_update_guarded(float* table, int64_t n, float* state, float headroom, const void* stats, adnm_stream_t stream);
 
 const char* adnm_last_error(void);
 int adnm_abi_version(void);
@@ -493,6 +499,32 @@ int adnm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, flo
                     const int* seg_end, const int* seg_rec, int64_t nseg, float* wtab, const float* hyper, adnm_stream_t stream);
 int adnm_shadow_refresh(const float* p, int64_t n, void* shadow, int shadow_dtype, const int* seg_end, const int* seg_rec, int64_t nseg,
                         float* wtab, int collect, adnm_stream_t stream);
+
+/* The monitored step: train.py:136-153 reads original_norm.item() and loss.item() after every step (for the adaptive clip threshold of
+ * train.py:122-130, the clip rate and the summed loss it prints); here those sums stay on the device and the host reads them once per
+ * epoch.  The same block carries the decision every mixed-precision trainer makes: a step whose gradient is not finite is SKIPPED.
+ * stats: 72 bytes of device memory, 8-byte aligned, zero-initialised by the caller:
+ *   double [0] applied steps   [1] skipped steps   [2] sum of the pre-clip norms of the applied steps   [3] their maximum
+ *          [4] norm of the last step, applied or skipped (inf / nan after a skipped one)
+ *          [5] applied steps with max_norm > 0 && norm > max_norm (train.py:142's strict comparison, not the + 1e-6 of the coefficient)
+ *          [6] sum of the finite losses   [7] number of non-finite losses
+ *   int    [16] skip flag of the step in flight (byte offset 64);  float [17] the guard's sum of squares (byte offset 68).
+ * adnm_step_guard, after the gradient is final (bf16 wire cast back, adnm_grad_accum_final) and before the fp8 table update:
+ *   sum g^2 by adnm_adamw_step's own two launches (bit-identical norm), left in the block; skip = exponent bits of the sum all ones, i.e.
+ *   a gradient with an Inf or a NaN — or a FINITE gradient whose fp32 sum of squares overflows, which counts as non-finite as well (its
+ *   norm cannot be formed; the clip coefficient would be 0).  An applied step moves the sum to state[1]; a skipped one leaves all four
+ *   floats of state as they were (state[1] then still holds the last applied step's sum).  Then the counters above, norm = sqrtf(sum).  max_norm comes
+ *   from hyper[1] when hyper != NULL, exactly as the AdamW kernels read it.  ws: adnm_adamw_ws_bytes().
+ * adnm_adamw_step_guarded: adnm_adamw_step WITHOUT its norm pass (state[1] is the guard's), every kernel checking the flag with one
+ *   uniform load at entry.  Flag set: state[0], state[2], state[3], p, m, v, the shadow and every amax_b stay untouched.  Flag clear:
+ *   bit-identical to adnm_adamw_step.
+ * adnm_loss_stat (train.py:145): stats[6] += *loss when finite, else stats[7] += 1; one lane. */
+int adnm_step_guard(const float* g, int64_t n, float* state, float max_norm, const float* hyper, void* ws, int64_t ws_bytes, void* stats,
+                    adnm_stream_t stream);
+int adnm_adamw_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, float* state, float lr, float beta1, float beta2,
+                            float eps, float weight_decay, float max_norm, void* shadow, int shadow_dtype, const int* seg_end,
+                            const int* seg_rec, int64_t nseg, float* wtab, const float* hyper, const void* stats, adnm_stream_t stream);
+int adnm_loss_stat(const float* loss, void* stats, adnm_stream_t stream);
 
 /* ---------------------------------------------------------------- dense 3x3 'same' convolution, NHWC, on MFMA (K5)
  * nn.Conv2d(k=3, s=1, p=1) [+ bias] [+ GELU] of the U-Net conv stack: PatchEmbed.conv2 (model_untils.py:259-273), WTLayer.conv
