@@ -124,6 +124,9 @@ class FlatTrainer:
         self._stats = None
         self._skip_host = False
         self._norm_host = None
+        # a state loaded before the flat buffers exist (load_state_dict): applied as the last act of _flatten; its fp8 part after the
+        # calibration of prepare() has made the table's rows
+        self._pending = self._pending_quant = None
 
     # ------------------------------------------------------------------ gradient accumulation
     @staticmethod
@@ -295,6 +298,9 @@ class FlatTrainer:
             self._accumulator()
         if self.monitor:
             self._stats_block()
+        if self._pending is not None:   # a state loaded before the first backward: now there is a layout to write it into
+            sd, self._pending = self._pending, None
+            self._apply_state(sd, quant=False)
 
     def bucket_report(self):
         """[(bucket index in all-reduce order, first element, last element + 1, bytes on the wire)]: what each stage's collective moves —
@@ -508,6 +514,12 @@ class FlatTrainer:
             ops.QUANT.calibrating = False
             if self.fp8:
                 ops.set_mfma_precision("fp8")
+        if self._pending_quant is not None:   # (the calibration above made the rows; the captures below read the loaded scales)
+            q, self._pending_quant = self._pending_quant, None
+            if self.fp8:
+                self._load_quant(q)
+                self._shadow.write()
+                self._shadow.mark_current()
         if not self.use_graph:
             return
         self.sx, self.st = x.clone(), tgt.clone()
@@ -828,3 +840,276 @@ class FlatTrainer:
         """Pre-clip total gradient norm of the last step (device scalar; train.py:141 reads it with .item()).  monitor=True: of the last
         APPLIED step (a skipped step leaves state alone; stats()["last_norm"] shows its inf / nan)."""
         return self.state[1].sqrt() if self.fused else self.flat_g.norm()
+
+    # ------------------------------------------------------------------ save and resume (DESIGN.md §4c)
+    STATE_VERSION = 1
+
+    def _precision(self):
+        return "fp8" if self.fp8 else ops.mfma_precision()
+
+    def _used_names(self):
+        name_of = {id(p): n for n, p in self.model.named_parameters()}
+        return [name_of[id(p)] for p in self.used]
+
+    def _logical(self, host, i):
+        """used[i]'s slice of a HOST copy of one flat buffer, seen through the parameter's own layout: logical shape, the strides its
+        view into flat_p has (channels-last for the dense-conv weights), no padding"""
+        p = self.used[i]
+        return host.as_strided(p.shape, p.stride(), self.offs[i])
+
+    def _quant_rows(self):
+        """fp8: [(name, row)] of the records of this device's table that belong to this trainer.  A record's key is a weight's data_ptr:
+        the name is the parameter whose storage contains it, the offset inside it (when not 0) and the role.  A key inside another
+        live trainer's flat buffer is that trainer's; any other key that no parameter of this model contains cannot be named, and
+        naming it by guesswork would restore some other call site's scales: NotImplementedError."""
+        dev = self.flat_p.device
+        keys = ops.QUANT._ent(dev)["keys"]
+        lo, params = self.flat_p.data_ptr(), []
+        names = self._used_names()
+        mine = {id(q) for q in self.used}
+        for n, p in self.model.named_parameters():
+            if p.device == dev and id(p) not in mine:
+                params.append((p.data_ptr(), p.data_ptr() + p.numel() * p.element_size(), n, p.element_size()))
+        others = [s for s in ops.SHADOWS.sets(dev) if s is not self._shadow]
+        import bisect
+        out = []
+        for (key, role), row in sorted(keys.items(), key=lambda kv: kv[1]):
+            if lo <= key < lo + 4 * self.n:
+                off = (key - lo) // 4
+                i = bisect.bisect_right(self.offs, off) - 1
+                name, inner = names[i], off - self.offs[i]
+                if inner >= self.used[i].numel():
+                    raise NotImplementedError(f"FlatTrainer.state_dict (fp8): record key of role {role!r} points into the padding behind {name}")
+            else:
+                hit = [(n, (key - a) // es) for a, b, n, es in params if a <= key < b]
+                if not hit:
+                    if any(s.lo <= key < s.hi for s in others):
+                        continue
+                    raise NotImplementedError(f"FlatTrainer.state_dict (fp8): a quantisation record of role {role!r} is keyed by an address "
+                                              "that lies in no parameter of this trainer's model; its call site cannot be named")
+                name, inner = hit[0]
+            out.append((f"{name}|{role}" if inner == 0 else f"{name}+{inner}|{role}", row))
+        seen = set()
+        for n, _ in out:
+            if n in seen:
+                raise NotImplementedError(f"FlatTrainer.state_dict (fp8): two quantisation records would both be named {n!r}")
+            seen.add(n)
+        return out
+
+    def _scalars(self):
+        return {"version": self.STATE_VERSION, "precision": self._precision(), "steps": int(self._steps), "lr": float(self.lr),
+                "max_norm": float(self.max_norm), "betas": (float(self.betas[0]), float(self.betas[1])), "eps": float(self.eps),
+                "weight_decay": float(self.wd), "accum_steps": self._accum_steps, "micro_step": self._micro}
+
+    def _live_buffers(self, params=False):
+        """the device buffers a saved state is made of (None: this trainer has no such buffer)"""
+        open_cycle = self._micro > 0 and self.acc is not None
+        bufs = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "state": self.state, "acc": self.acc if open_cycle else None,
+                "stats": self._stats if self.monitor else None, "qtab": None, "qstate": None}
+        if params:
+            bufs["flat_p"] = self.flat_p
+        if self.fp8:
+            ent = ops.QUANT._ent(self.flat_p.device)
+            bufs["qtab"], bufs["qstate"] = ent["tab"], ent["state"]
+        return bufs
+
+    def _pack_state(self, host, scalars, qrows):
+        """host: CPU copies of _live_buffers(); -> the layout-independent dict (every tensor owns its memory)"""
+        names = self._used_names()
+        sd = dict(scalars)
+        sd["state_bits"] = host["state"].view(torch.int32).clone()
+        per = {}
+        for i, name in enumerate(names):
+            ent = {k: self._logical(host[k], i).clone(memory_format=torch.contiguous_format) for k in ("exp_avg", "exp_avg_sq")}
+            if host["acc"] is not None:
+                ent["acc"] = self._logical(host["acc"], i).clone(memory_format=torch.contiguous_format)
+            per[name] = ent
+        sd["params"] = per
+        sd["monitor"] = host["stats"].clone() if host["stats"] is not None else None
+        sd["fp8"] = None
+        if qrows is not None:
+            sd["fp8"] = {"state": host["qstate"].clone(), "rows": {n: host["qtab"][r].clone() for n, r in qrows}}
+        if host.get("flat_p") is not None:
+            sd["parameters"] = {name: self._logical(host["flat_p"], i).clone(memory_format=torch.contiguous_format) for i, name in enumerate(names)}
+        return sd
+
+    def _require_state(self, what):
+        if self.used is None:
+            raise RuntimeError(f"FlatTrainer.{what}: the flat buffers do not exist yet (they are laid out by prepare() or the first step())")
+        if self.flat_p.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"FlatTrainer.{what}: not inside a hipGraph capture")
+
+    @torch.no_grad()
+    def state_dict(self):
+        """Everything an interrupted run needs beside model.state_dict(), independent of the flat layout: a plain dict of CPU tensors and
+        Python scalars.  "params": {parameter name: {"exp_avg", "exp_avg_sq" (, "acc" while an accumulation cycle is open)}} in the
+        parameter's logical shape, contiguous (NCHW for the conv weights the flat buffers hold channels-last), without padding, for the
+        parameters that receive gradients; "state_bits": the four floats of `state` as int32; "steps", "lr", "max_norm", "betas", "eps",
+        "weight_decay", "accum_steps", "micro_step", "precision", "version"; "monitor": the nine doubles of a monitored trainer or None;
+        "fp8": {"state", "rows": {"<parameter name>|<role>": the record's 8 floats}} or None.  SYNCHRONISES: one device -> host copy per
+        flat buffer (snapshot() is the form that does not stall the step).  fp8: NotImplementedError when a record of the table cannot
+        be named by one of the model's parameters."""
+        self._require_state("state_dict")
+        qrows = self._quant_rows() if self.fp8 else None
+        host = {k: (None if v is None else v.detach().to("cpu", copy=True)) for k, v in self._live_buffers().items()}
+        return self._pack_state(host, self._scalars(), qrows)
+
+    def _check_state(self, sd, strict):
+        if not isinstance(sd, dict) or sd.get("version") != self.STATE_VERSION or "params" not in sd:
+            raise RuntimeError(f"FlatTrainer.load_state_dict: not a trainer state of format version {self.STATE_VERSION} "
+                               f"(version: {sd.get('version') if isinstance(sd, dict) else type(sd).__name__!r})")
+        if sd["precision"] != self._precision():
+            raise RuntimeError(f"FlatTrainer.load_state_dict: the state was saved at matrix-core precision {sd['precision']!r}, this trainer runs "
+                               f"at {self._precision()!r}")
+        if strict:
+            mine = {"betas": (float(self.betas[0]), float(self.betas[1])), "eps": float(self.eps), "weight_decay": float(self.wd)}
+            bad = [f"{k}: saved {tuple(sd[k]) if k == 'betas' else sd[k]!r}, trainer {v!r}" for k, v in mine.items()
+                   if (tuple(sd[k]) if k == "betas" else sd[k]) != v]
+            if bad:
+                raise RuntimeError("FlatTrainer.load_state_dict: hyper-parameters differ (" + "; ".join(bad) + "); strict=False loads anyway "
+                                   "and keeps the trainer's")
+        if sd["micro_step"] > 0 and sd["accum_steps"] != self._accum_steps:
+            raise RuntimeError(f"FlatTrainer.load_state_dict: the state was saved inside an accumulation cycle (micro-step {sd['micro_step']} of "
+                               f"accum_steps={sd['accum_steps']}), this trainer has accum_steps={self._accum_steps}")
+        shapes = {n: tuple(p.shape) for n, p in self.model.named_parameters()}
+        unknown = sorted(set(sd["params"]) - set(shapes))
+        if unknown:
+            raise RuntimeError(f"FlatTrainer.load_state_dict: {len(unknown)} names of the state are no parameters of the model, e.g. {unknown[:3]}")
+        self._check_shapes(sd, shapes)
+
+    @staticmethod
+    def _check_shapes(sd, shapes):
+        open_cycle = sd["micro_step"] > 0
+        for n, ent in sd["params"].items():
+            for k in ("exp_avg", "exp_avg_sq") + (("acc",) if open_cycle else ()):
+                if k not in ent:
+                    raise RuntimeError(f"FlatTrainer.load_state_dict: {n} has no {k!r} in the state")
+                if tuple(ent[k].shape) != shapes[n]:
+                    raise RuntimeError(f"FlatTrainer.load_state_dict: {k} of {n} has shape {tuple(ent[k].shape)}, the parameter {shapes[n]}")
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, strict=True):
+        """Take over a state_dict(): moments, `state`, step count, lr and max_norm (they reach the tail graph's device copy with the next
+        step), an open accumulation cycle, the monitor block, the fp8 table's rows.  IN PLACE, on the current stream: no buffer moves, so
+        the captured graphs of a prepared trainer stay valid.  Any flat layout loads any other: the parameter name is the only key.
+        Raises on another set of names or another shape, on other betas / eps / weight_decay (strict=False: the trainer keeps its own),
+        on another accum_steps while the saved cycle is open, on another precision, and in fp8 on a record that one side lacks.  The
+        parameters themselves are model.state_dict()'s business: load them FIRST (checkpoint.load_training_state does both).
+        Before the flat buffers exist (no prepare(), no step yet) the scalars are taken at once and the tensors are kept and written
+        when the layout is made; fp8 rows after prepare()'s calibration has created them."""
+        self._load(sd, strict)
+
+    def _load(self, sd, strict=True, quant=True):
+        if self.used is not None and self.flat_p.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FlatTrainer.load_state_dict: not inside a hipGraph capture")
+        self._check_state(sd, strict)
+        if self.used is None:
+            self._take_scalars(sd)
+            self._pending, self._pending_quant = sd, (sd.get("fp8") if quant else None)
+            return
+        self._apply_state(sd, quant=quant)
+
+    def _take_scalars(self, sd):
+        self._steps, self._micro = int(sd["steps"]), int(sd["micro_step"])
+        self.lr, self.max_norm = float(sd["lr"]), float(sd["max_norm"])
+
+    def _apply_state(self, sd, quant=True):
+        names = self._used_names()
+        missing, unexpected = sorted(set(names) - set(sd["params"])), sorted(set(sd["params"]) - set(names))
+        if missing or unexpected:
+            raise RuntimeError(f"FlatTrainer.load_state_dict: the state does not match the parameters this trainer updates: {len(missing)} "
+                               f"missing (e.g. {missing[:3]}), {len(unexpected)} unexpected (e.g. {unexpected[:3]})")
+        self._check_shapes(sd, {n: tuple(p.shape) for n, p in zip(names, self.used)})
+        if quant and self.fp8:
+            rows = self._match_quant(sd.get("fp8"))   # (raises before anything is written)
+        open_cycle = sd["micro_step"] > 0
+
+        def put(buf, key):
+            # one host image of the whole flat buffer (padding zero, as the buffers are born), then ONE copy into the buffer where it is
+            host = torch.zeros(self.n, dtype=buf.dtype)
+            for i, name in enumerate(names):
+                self._logical(host, i).copy_(sd["params"][name][key])
+            buf.copy_(host)
+        put(self.exp_avg, "exp_avg")
+        put(self.exp_avg_sq, "exp_avg_sq")
+        if open_cycle:
+            put(self._accumulator(), "acc")
+        self.state.copy_(sd["state_bits"].view(torch.float32))
+        if self.monitor and sd.get("monitor") is not None:
+            self._stats_block().copy_(sd["monitor"])
+        self._take_scalars(sd)
+        if quant and self.fp8:
+            self._write_quant(sd["fp8"], rows)
+        if self._shadow is not None:
+            # the shadow of the parameters as they are now, fp8 with the RESTORED scale_b (refresh() would re-derive the weight scales
+            # from max |w|: other bits than the interrupted run's)
+            self._shadow.write()
+            self._shadow.mark_current()
+
+    def _match_quant(self, q):
+        if q is None:
+            raise RuntimeError("FlatTrainer.load_state_dict: this trainer runs in fp8, the state holds no quantisation table")
+        rows = dict(self._quant_rows())
+        missing, unexpected = sorted(set(rows) - set(q["rows"])), sorted(set(q["rows"]) - set(rows))
+        if missing or unexpected:
+            raise RuntimeError(f"FlatTrainer.load_state_dict (fp8): quantisation records differ: {len(missing)} of this trainer are not in the "
+                               f"state (e.g. {missing[:3]}), {len(unexpected)} of the state do not exist here (e.g. {unexpected[:3]}); "
+                               "prepare() creates the records: call it before the load")
+        return rows
+
+    def _write_quant(self, q, rows):
+        ent = ops.QUANT._ent(self.flat_p.device)
+        host = ent["tab"].cpu()
+        for n, r in rows.items():
+            host[r] = q["rows"][n]
+        ent["tab"].copy_(host)
+        ent["state"].copy_(q["state"])
+
+    def _load_quant(self, q):
+        self._write_quant(q, self._match_quant(q))
+
+    @torch.no_grad()
+    def snapshot(self):
+        """A consistent copy of the training state WITHOUT stalling the step: device-to-device copies of flat_p, exp_avg, exp_avg_sq,
+        state (and acc, the monitor block, the fp8 table where they exist) into buffers the snapshot owns, enqueued on the current stream
+        behind the steps issued so far, then an event; returns at once.  Call it between steps, outside any capture; read it later with
+        TrainerSnapshot.state_dict().  Costs one more copy of the optimiser-sized buffers in device memory while the snapshot lives
+        (3 x 4 bytes per parameter: ~0.9 GB for the 72 M parameters of ADNM-UNet); nothing is allocated before the first call."""
+        self._require_state("snapshot")
+        return TrainerSnapshot(self)
+
+
+class TrainerSnapshot:
+    """FlatTrainer.snapshot(): the state as it was between two steps, in device buffers of its own."""
+
+    def __init__(self, tr):
+        self._tr = tr
+        self._scalars = tr._scalars()
+        self._qrows = tr._quant_rows() if tr.fp8 else None
+        self._bufs = {}
+        for k, v in tr._live_buffers(params=True).items():
+            self._bufs[k] = None if v is None else torch.empty_like(v).copy_(v)
+        self._event = None
+        if tr.flat_p.is_cuda:
+            self._event = torch.cuda.Event()
+            self._event.record()
+        self._sd = None
+
+    @torch.no_grad()
+    def state_dict(self):
+        """FlatTrainer.state_dict() of the moment the snapshot was taken, plus "parameters": {name: the parameter in logical shape}.
+        Waits for the snapshot's event on a side stream, copies to pinned host memory there and synchronises only that stream: the
+        training stream is never waited for.  The device buffers are given back after the first call."""
+        if self._sd is None:
+            if self._event is None:
+                host = {k: (None if v is None else v.clone()) for k, v in self._bufs.items()}
+            else:
+                side = torch.cuda.Stream(self._tr.flat_p.device)
+                side.wait_event(self._event)
+                with torch.cuda.stream(side):
+                    host = {k: (None if v is None else torch.empty(v.shape, dtype=v.dtype, pin_memory=True).copy_(v, non_blocking=True))
+                            for k, v in self._bufs.items()}
+                side.synchronize()
+            self._sd = self._tr._pack_state(host, self._scalars, self._qrows)
+            self._bufs = {}
+        return self._sd
