@@ -25,9 +25,21 @@ class GraphedForward:
     rewrites the shadows it captured against if a parameter was written since (a checkpoint load, an in-place op), and the graph keeps
     them alive, so it may outlive the trainer.  close() (or __del__) gives the graphs back."""
 
-    def __init__(self, model):
+    def __init__(self, model, head=None, tail=None):
+        """head(sx) / tail(sx, out): optional extra bodies captured into the same graph right before / after the forward (sx: the
+        graph's static input, out: its static output) — adnm_hip.validate.Validator's loss and metrics pass.  They run ONLY inside the
+        capture, never in the warm-up forwards: whatever they launch must have run once before.  Without them nothing changes."""
         self.model = model
+        self._head, self._tail = head, tail
         self._graphs = {}
+
+    def _body(self, sx):
+        if self._head is not None:
+            self._head(sx)
+        out = self.model(sx)
+        if self._tail is not None:
+            self._tail(sx, out)
+        return out
 
     @torch.no_grad()
     def __call__(self, x):
@@ -48,7 +60,7 @@ class GraphedForward:
             scope = ops.SPLITWS.open_scope(x.device)
             pin = ops.QUANT.pinned(x.device) if ops.mfma_precision() == "fp8" else None
             try:
-                out = ops.capture(g, lambda: self.model(sx), scope)
+                out = ops.capture(g, lambda: self._body(sx), scope)
             except BaseException:
                 if pin is not None:
                     pin.release()

@@ -15,6 +15,11 @@ and lr(e) is what the optimiser holds after e calls of lr_scheduler.step().
         for x, tgt in loader:
             trainer.step(x, tgt)
         prev = trainer.stats(reset=True)       # FlatTrainer(monitor=True): the one synchronising read of the epoch
+        for x, tgt in val_loader:
+            validator.step(x, tgt)             # adnm_hip.validate.Validator
+        d = selection.update(epoch, validator.done(reset=True)["loss_sum"])     # ReferenceSelection(sched)
+        if d["save"]: ...                      # the best checkpoint (train.py:169-178)
+        if d["stop"]: break                    # the early stop (train.py:205)
 """
 import math
 
@@ -75,3 +80,42 @@ class ReferenceSchedule:
         trainer.lr = lr
         trainer.max_norm = mn
         return lr, mn
+
+
+class ReferenceSelection:
+    """The decisions train.py takes on the validation loss of every epoch, in closed form, for the ADNM-UNet recipe (if_save_epoch and
+    if_early_stop both true): save the best checkpoint only after `save_epoch` epochs (train.py:169-178), count the epochs that did not
+    improve on it, stop at `early_stop` of them in a row (train.py:179-183, 205; train_untils.py:47-50: 3 for the short-interval recipe,
+    5 for the long one).  `val_loss_sum` is the SUM of the per-batch validation losses (train.py:163), Validator.done()["loss_sum"].
+
+    With e1 = epoch + 1 (train.py's counter; `epoch` is 0-based as everywhere in this module) and best = 10000 at the start:
+        e1 <= save_epoch:                      nothing changes (no save, no count, however good the loss)
+        e1 >  save_epoch and loss <  best:     save, best = loss, bad_epochs = 0
+        e1 >  save_epoch and not (loss < best): bad_epochs += 1        (an equal loss and a NaN loss are "not better")
+        stop = bad_epochs >= early_stop"""
+
+    def __init__(self, schedule):
+        self.save_epoch = int(schedule.save_epoch)
+        self.early_stop = 3 if schedule.short_interval else 5
+        self.best, self.bad_epochs = 10000.0, 0
+
+    def update(self, epoch, val_loss_sum):
+        if epoch < 0:
+            raise ValueError(f"ReferenceSelection.update: epoch {epoch} < 0")
+        loss, save = float(val_loss_sum), False
+        if epoch + 1 > self.save_epoch:
+            if loss < self.best:   # False for a NaN
+                save, self.best, self.bad_epochs = True, loss, 0
+            else:
+                self.bad_epochs += 1
+        return {"save": save, "stop": self.bad_epochs >= self.early_stop, "best": self.best, "bad_epochs": self.bad_epochs}
+
+    def state_dict(self):
+        """plain Python scalars: fits checkpoint.save_training_state's schedule_stats as it is"""
+        return {"best": float(self.best), "bad_epochs": int(self.bad_epochs), "save_epoch": int(self.save_epoch), "early_stop": int(self.early_stop)}
+
+    def load_state_dict(self, sd):
+        if int(sd["save_epoch"]) != self.save_epoch or int(sd["early_stop"]) != self.early_stop:
+            raise ValueError(f"ReferenceSelection.load_state_dict: saved for save_epoch {sd['save_epoch']} / early_stop {sd['early_stop']}, "
+                             f"this recipe has {self.save_epoch} / {self.early_stop}")
+        self.best, self.bad_epochs = float(sd["best"]), int(sd["bad_epochs"])

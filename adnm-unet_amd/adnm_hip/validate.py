@@ -1,0 +1,217 @@
+"""The validation half of an epoch on the device (train.py:156-206 of the reference: a forward-only pass over the validation set, the
+loss per batch, the metrics, then the best-checkpoint rule and the early stop).
+
+    val = Validator(model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None)
+    for x, tgt in val_loader:
+        val.step(x, tgt)          # one replay of a captured graph: no allocation, no host synchronisation
+    res = val.done(reset=True)    # the one synchronising read of the epoch
+    decision = selection.update(epoch, res["loss_sum"])      # ReferenceSelection (adnm_hip.schedule)
+
+A step is GraphedForward's captured graph with a second body behind the forward: csrc/dataio.hip::valid_accum (the enRainfallLoss
+value of the batch — no gradient tensor — and SimplifiedEvaluator's contingency counts and error sums, one pass over prediction and
+target) and valid_ssim_accum, both ADDING into one block of doubles that lives on the device for the epoch (layout:
+include/adnm_hip.h, adnm_valid_accum).  done() reads that block — summed over the ranks of `process_group` with one all-reduce —
+and aggregates it exactly as GpuEvaluator.done() does.
+
+The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
+not reproduced: the Validator validates the batches it is given."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import lib, ops
+from .evaluator import GraphedForward
+
+HEADER = 4   # doubles in front of the table: loss_sum, batches, samples, nonfinite_batches
+
+
+def reduce_block(block, process_group=None):
+    """The multi-rank step of Validator.done(): `block` (a float64 tensor on any device, gloo on the CPU included) becomes the
+    elementwise sum over the ranks of `process_group`, in place, with ONE all-reduce; every rank then holds the same block.  Counts are
+    integers in doubles and the loss sums are sums of fp32 values: the result does not depend on the ranks' order beyond the last bit
+    of the float columns.  process_group None: nothing to do."""
+    if process_group is not None:
+        import torch.distributed as dist
+        if block.dtype != torch.float64:
+            raise RuntimeError(f"reduce_block: the accumulator block is float64, got {block.dtype}")
+        dist.all_reduce(block, op=dist.ReduceOp.SUM, group=process_group)
+    return block
+
+
+def aggregate(block, thresholds, seq_len, hw, ssim_area):
+    """host: the block (a float64 array of HEADER + T * (4*nthr + 3) values) -> the dictionary of Validator.done().  The metrics are
+    SimplifiedEvaluator.done's (Shanghai_metrics.py:218-290) as GpuEvaluator.done() states them, from per-frame-index sums."""
+    nthr, T = len(thresholds), seq_len
+    blk = np.asarray(block, dtype=np.float64)
+    loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
+    tab = blk[HEADER:].reshape(T, 4 * nthr + 3)
+    metrics, all_far = {}, []
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for k, thr in enumerate(thresholds):
+            TP, FN, FP, TN = (tab[:, 4 * k + i].sum() for i in range(4))
+            csi, pod = TP / (TP + FP + FN), TP / (TP + FN)
+            hss = (2 * (TP * TN - FP * FN)) / (FP ** 2 + FN ** 2 + 2 * TP * TN + (FP + FN) * (TP + TN))
+            all_far.append(FP / (TP + FP))
+            key = int(thr) if float(thr).is_integer() else thr
+            metrics[key] = {"TP": TP, "TN": TN, "FP": FP, "FN": FN, "CSI": csi, "POD": pod, "HSS": hss}
+        mse_t = tab[:, 4 * nthr + 1] / (hw * samples)            # per frame index: the mean over the samples of the frame's MSE
+        rmse = float(np.mean(np.sqrt(mse_t)))
+        mae = float(tab[:, 4 * nthr].sum() / (hw * samples * T))
+        ssim = None if ssim_area is None else float(tab[:, 4 * nthr + 2].sum() / (ssim_area * samples * T))
+        finite = batches - nonfinite
+    return {"threshold_metrics": metrics, "FAR": float(np.mean(all_far)), "RMSE": rmse, "MAE": mae, "MSE": float(mse_t.mean()), "SSIM": ssim,
+            "LPIPS": None, "loss_sum": loss_sum, "loss_mean": loss_sum / finite if finite > 0 else float("nan"), "batches": int(batches),
+            "samples": int(samples), "nonfinite": int(nonfinite)}
+
+
+class Validator:
+    def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None):
+        from models.loss import enRainfallLoss
+        if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
+            raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
+                               f"there is no torch fallback), got {type(loss_fn).__name__}")
+        self.model, self.loss_fn, self.seq_len, self.value_scale = model, loss_fn, int(seq_len), float(value_scale)
+        self.thresholds = [float(t) for t in thresholds]
+        if not 1 <= len(self.thresholds) <= 8:
+            raise ValueError("1..8 thresholds")
+        if self.seq_len < 1:
+            raise ValueError("seq_len >= 1")
+        self.ssim, self.process_group = bool(ssim), process_group
+        self._thr = (ctypes.c_float * len(self.thresholds))(*self.thresholds)
+        self._fwd = GraphedForward(model, head=self._head, tail=self._tail)
+        self._block = self._last = None    # the epoch's accumulator block and the last batch's fp32 loss: they outlive the graphs
+        self._static, self._cur = {}, None
+        self._frame = None                  # (H, W) of the epoch
+
+    # ---- device state
+    def _block_for(self, device):
+        if self._block is None:
+            n = lib.query("adnm_valid_block_bytes", self.seq_len, len(self.thresholds))
+            self._block = torch.zeros(n // 8, dtype=torch.float64, device=device)
+            self._last = torch.zeros((), dtype=torch.float32, device=device)
+        elif self._block.device != device:
+            raise RuntimeError(f"Validator: one device per Validator (the block is on {self._block.device}, the batch on {device})")
+        return self._block
+
+    def _launch(self, st, pred, block, loss_out):
+        B, T, H, W = st["shape"]
+        nthr, stream = len(self.thresholds), torch.cuda.current_stream().cuda_stream
+        lib.call("adnm_valid_accum", pred.data_ptr(), st["tgt"].data_ptr(), block.data_ptr(), loss_out.data_ptr(), self._thr, nthr, self.value_scale,
+                 st["loss"][0], st["loss"][1], st["loss"][2], st["ws"].data_ptr(), st["ws"].numel(), B * T, T, H * W, stream)
+        if st["ws_ssim"] is not None:
+            lib.call("adnm_valid_ssim_accum", pred.data_ptr(), st["tgt"].data_ptr(), block.data_ptr(), nthr, self.value_scale, st["ws_ssim"].data_ptr(),
+                     st["ws_ssim"].numel(), B * T, T, H, W, stream)
+
+    def _make_static(self, x, shape):
+        """what the graph of one input shape points into: the static target, the two workspaces, in fp8 the table's save area; and one
+        eager run of the two entry points on a scratch block (a kernel's first launch must not happen inside a capture)"""
+        B, T, H, W = shape
+        dev, nthr = x.device, len(self.thresholds)
+        nb = lib.query("adnm_valid_accum_ws_bytes", B * T, T, H * W, nthr)
+        if nb < 0:
+            raise RuntimeError(f"Validator: a batch of {B * T} frames of {H} x {W} is outside adnm_valid_accum's limits (frames <= 65535, pixels per frame < 2^24)")
+        ws_ssim = None
+        if self.ssim and H > 10 and W > 10:   # 11 x 11 windows need a valid region; smaller frames: SSIM is None
+            ws_ssim = torch.empty(max(int(lib.query("adnm_valid_ssim_accum_ws_bytes", B * T, T, H, W, nthr)), 16), dtype=torch.uint8, device=dev)
+        fp8 = ops.mfma_precision() == "fp8"
+        st = {"shape": shape, "tgt": torch.zeros(shape, dtype=torch.float32, device=dev), "ws": torch.empty(max(int(nb), 16), dtype=torch.uint8, device=dev),
+              "ws_ssim": ws_ssim, "loss": (float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)),
+              "qsave": torch.empty_like(ops.QUANT.table(dev)) if fp8 else None}
+        scratch = torch.zeros_like(self._block_for(dev))
+        self._launch(st, st["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
+        return st
+
+    # ---- the bodies captured around the forward (GraphedForward calls them inside its capture only)
+    def _head(self, sx):
+        st = self._cur
+        if st["qsave"] is not None:
+            # fp8: while a record's flag is set the GEMMs of ANY forward collect max |activation| into the delayed-scaling table.  A
+            # validation forward must not move the training run's next scales: the table is put back as it was (tail).
+            st["qsave"].copy_(ops.QUANT.table(sx.device))
+
+    def _tail(self, sx, out):
+        st = self._cur
+        B, T, H, W = st["shape"]
+        if out.dtype != torch.float32 or out.numel() != B * T * H * W or tuple(out.shape[:2]) != (B, T):
+            raise RuntimeError(f"Validator: the model's output {tuple(out.shape)} {out.dtype} does not match the target's (B, T, H, W) = {st['shape']} fp32")
+        if st["qsave"] is not None:
+            ops.QUANT.table(sx.device).copy_(st["qsave"])
+        st["pred"] = out.contiguous()   # (the model emits it contiguous; a copy made here belongs to the graph's pool and is kept with it)
+        self._launch(st, st["pred"], self._block, self._last)
+
+    # ---- the public surface
+    def step(self, x, tgt):
+        """x: the model's input; tgt: (B, seq_len, H, W) or (B, seq_len, 1, H, W) fp32, both on the GPU.  Adds the batch to the epoch's
+        block.  -> the model's output (the graph's static tensor: valid until the next step of this shape)."""
+        if not (torch.is_tensor(x) and x.is_cuda and torch.is_tensor(tgt) and tgt.is_cuda):
+            raise RuntimeError("Validator runs on GPU tensors only (there is no CPU path here)")
+        if tgt.dtype != torch.float32 or tgt.dim() not in (4, 5) or (tgt.dim() == 5 and tgt.shape[2] != 1):
+            raise RuntimeError(f"Validator: the target must be fp32 (B, T, H, W) or (B, T, 1, H, W), got {tgt.dtype} {tuple(tgt.shape)}")
+        if tgt.shape[1] != self.seq_len:
+            raise RuntimeError(f"Validator: the target has {tgt.shape[1]} frames per sample, seq_len is {self.seq_len}")
+        if tgt.shape[0] != x.shape[0] or tgt.device != x.device:
+            raise RuntimeError(f"Validator: input {tuple(x.shape)} on {x.device} and target {tuple(tgt.shape)} on {tgt.device} do not belong together")
+        shape = (tgt.shape[0], tgt.shape[1], tgt.shape[-2], tgt.shape[-1])
+        if self._frame is None:
+            self._frame = shape[2:]
+        elif self._frame != shape[2:]:
+            raise RuntimeError(f"Validator: frames of {shape[2]} x {shape[3]} in an epoch of {self._frame[0]} x {self._frame[1]} frames (done(reset=True) first)")
+        self._block_for(x.device)
+        key = (tuple(x.shape), x.dtype, x.device)
+        st = self._static.get(key)
+        first = st is None
+        snap = None
+        if first:
+            st = self._make_static(x, shape)
+            if st["qsave"] is not None:   # the eager warm-up forwards of the capture collect too
+                snap = ops.QUANT.snapshot(x.device)
+        elif st["shape"] != shape:
+            raise RuntimeError(f"Validator: input {tuple(x.shape)} came with a target of {st['shape']} before, now {shape}")
+        st["tgt"].view(tgt.shape).copy_(tgt, non_blocking=True)
+        self._cur = st
+        try:
+            out = self._fwd(x)
+        finally:
+            self._cur = None
+            if snap is not None:
+                ops.QUANT.restore(x.device, snap)
+        if first:
+            self._static[key] = st
+        return out
+
+    @property
+    def last_loss(self):
+        """the fp32 loss of the last batch: a 0-dim device tensor (reading it synchronises; the epoch's sum is in done())"""
+        return self._last
+
+    def done(self, reset=False):
+        """-> what GpuEvaluator.done() returns (the same keys, the same aggregation; SSIM None when ssim=False or the frames are too small
+        for the window) plus "loss_sum" (what train.py:163 / :201 accumulate and compare against `best`), "loss_mean" (over the finite
+        batches), "batches", "samples", "nonfinite".  With a process_group the blocks of all ranks are summed first.  The one host read."""
+        if self._block is None or self._frame is None:
+            raise RuntimeError("Validator.done: no batch since the last reset")
+        blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
+        host = blk.cpu().numpy()   # the one device -> host read
+        H, W = self._frame
+        area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
+        res = aggregate(host, self.thresholds, self.seq_len, H * W, area)
+        if reset:
+            self.reset()
+        return res
+
+    def reset(self):
+        if self._block is not None:
+            self._block.zero_()
+        self._frame = None
+
+    def close(self):
+        """Give the captured graphs and what they point into back (GraphedForward.close); the block and its sums stay.  Idempotent."""
+        self._fwd.close()
+        self._static = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

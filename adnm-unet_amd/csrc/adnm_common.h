@@ -328,6 +328,26 @@ __device__ __forceinline__ float softplusf_(float x) {
   return __logf(1.0f + e);
 }
 
+// One element of enRainfallLoss (models/loss.py:30-57 of the reference), shared by the training pass (value and d/dpred: rainloss_kernel)
+// and the validation pass (value only: valid_accum_kernel), so the two cannot drift:
+//   e = w(pred>=t) * |pred-t| * (1 + [t>=0.7] alpha exp(t))  +  [t>=0.7 and pred<t] gamma (exp(alpha (t-pred)) - 1)
+// GRAD: *g receives d e / d pred; without it the gradient is not formed.
+template <bool GRAD>
+__device__ __forceinline__ float adnm_rainloss_term(float p, float t, float omega, float alpha, float gamma, float* g) {
+  const float diff = p - t;
+  const bool over = p >= t, heavy = t >= 0.7f;
+  const float w = over ? 1.0f - omega : omega;
+  const float wi = heavy ? alpha * __expf(t) : 0.f;
+  float e = w * fabsf(diff) * (1.0f + wi);
+  if (GRAD) *g = w * (1.0f + wi) * (diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f));
+  if (gamma != 0.f && heavy && !over) {
+    const float ex = __expf(alpha * (t - p));
+    e += gamma * (ex - 1.0f);
+    if (GRAD) *g -= gamma * alpha * ex;
+  }
+  return e;
+}
+
 template <int ACT>
 __device__ __forceinline__ float act_fwd(float x) {
   if (ACT == ADNM_ACT_SILU) return siluf_(x);

@@ -7,6 +7,8 @@
 //   eval_counts   — SimplifiedEvaluator.evaluate (datasets/Shanghai_metrics.py:49-152) without the round trip to numpy: per frame the
 //                   contingency counts TP / FN / FP / TN at every threshold on the uint16-truncated, value_scale'd, [0,1]-clipped fields
 //                   (:45-47,103-112) and the sums |d|, d^2 of the scaled float fields (:114-120) from which MAE / MSE / RMSE / PSNR follow.
+//   valid_accum   — the validation half of an epoch (train.py:156-206): the same counts and sums plus the enRainfallLoss value of the batch,
+//                   ADDED to a block of doubles the caller keeps on the device for the whole epoch (no gradient tensor, no host read).
 #include "adnm_common.h"
 #include <math.h>
 
@@ -38,18 +40,18 @@ struct Thr {
   int n;
 };
 
-// part[blk][frame][4*nthr + 2]; blocks along a frame: gridDim.x, frames: gridDim.y
-__global__ __launch_bounds__(kBlock) void eval_counts_kernel(const float* __restrict__ truth, const float* __restrict__ pred, float* __restrict__ part,
-                                                             int64_t hw, float value_scale, Thr thr) {
-  __shared__ float sm[kBlock / 64][4 * kMaxThr + 2];
-  const int64_t f = blockIdx.y;
-  const float* t = truth + f * hw;
-  const float* p = pred + f * hw;
-  float cnt[4 * kMaxThr], sa = 0.f, sq = 0.f;
+// One lane's share of a frame's contingency counts and error sums, and the workgroup's fold of it: the arithmetic of eval_counts, stated
+// ONCE for eval_counts_kernel and valid_accum_kernel (the validation epoch's accumulating pass) so that their counts cannot drift apart.
+struct EvalAcc {
+  float cnt[4 * kMaxThr], sa, sq;
+  __device__ __forceinline__ void clear() {
 #pragma unroll
-  for (int k = 0; k < 4 * kMaxThr; ++k) cnt[k] = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < hw; i += (int64_t)gridDim.x * kBlock) {
-    const float tc = fminf(fmaxf(t[i], 0.f), 1.f), pc = fminf(fmaxf(p[i], 0.f), 1.f);
+    for (int k = 0; k < 4 * kMaxThr; ++k) cnt[k] = 0.f;
+    sa = sq = 0.f;
+  }
+  // clip to [0,1], scale, truncate, compare (Shanghai_metrics.py:45-47,103-120)
+  __device__ __forceinline__ void add(float tv, float pv, float value_scale, const Thr& thr) {
+    const float tc = fminf(fmaxf(tv, 0.f), 1.f), pc = fminf(fmaxf(pv, 0.f), 1.f);
     const float ts = tc * value_scale, ps = pc * value_scale;
     const float d = ps - ts;
     sa += fabsf(d);
@@ -65,21 +67,114 @@ __global__ __launch_bounds__(kBlock) void eval_counts_kernel(const float* __rest
         cnt[4 * k + 3] += (!o && !s) ? 1.f : 0.f;   // TN
       }
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nout = 4 * thr.n + 2;
+  // wave sums -> sm[wave][0 .. 4*nthr + 2); EXTRA: a further per-lane sum of the caller's -> sm[wave][4*nthr + 2].  The caller
+  // synchronises and adds the four waves as (0 + 1) + (2 + 3).
+  template <bool EXTRA, int COLS>
+  __device__ __forceinline__ void to_lds(float (*sm)[COLS], int nthr, float extra) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
-  for (int k = 0; k < 4 * kMaxThr; ++k) {
-    const float v = wave_sum(cnt[k]);
-    if (lane == 0 && k < 4 * thr.n) sm[wave][k] = v;
+    for (int k = 0; k < 4 * kMaxThr; ++k) {
+      const float v = wave_sum(cnt[k]);
+      if (lane == 0 && k < 4 * nthr) sm[wave][k] = v;
+    }
+    sa = wave_sum(sa);
+    sq = wave_sum(sq);
+    if (EXTRA) extra = wave_sum(extra);
+    if (lane == 0) {
+      sm[wave][4 * nthr] = sa;
+      sm[wave][4 * nthr + 1] = sq;
+      if (EXTRA) sm[wave][4 * nthr + 2] = extra;
+    }
   }
-  sa = wave_sum(sa);
-  sq = wave_sum(sq);
-  if (lane == 0) {
-    sm[wave][4 * thr.n] = sa;
-    sm[wave][4 * thr.n + 1] = sq;
-  }
+};
+
+// part[blk][frame][4*nthr + 2]; blocks along a frame: gridDim.x, frames: gridDim.y
+__global__ __launch_bounds__(kBlock) void eval_counts_kernel(const float* __restrict__ truth, const float* __restrict__ pred, float* __restrict__ part,
+                                                             int64_t hw, float value_scale, Thr thr) {
+  __shared__ float sm[kBlock / 64][4 * kMaxThr + 2];
+  const int64_t f = blockIdx.y;
+  const float* t = truth + f * hw;
+  const float* p = pred + f * hw;
+  EvalAcc acc;
+  acc.clear();
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < hw; i += (int64_t)gridDim.x * kBlock) acc.add(t[i], p[i], value_scale, thr);
+  const int nout = 4 * thr.n + 2;
+  acc.to_lds<false>(sm, thr.n, 0.f);
   __syncthreads();
   if ((int)threadIdx.x < nout)
     part[((int64_t)blockIdx.x * gridDim.y + f) * nout + threadIdx.x] = (sm[0][threadIdx.x] + sm[1][threadIdx.x]) + (sm[2][threadIdx.x] + sm[3][threadIdx.x]);
+}
+
+// The validation epoch's pass (include/adnm_hip.h: adnm_valid_accum): eval_counts_kernel's grid and arithmetic, and beside it the
+// enRainfallLoss terms of the UNCLIPPED values (adnm_rainloss_term, no gradient).  part[blk][frame][4*nthr + 3]: the last column is
+// the workgroup's sum of e.  Longest chain of fp32 additions behind a loss partial: the lane's trips (hw / (blocks * 256) <= 16 while
+// hw <= 2^18: eval_blocks) + 6 (wave) + 2 (the four waves); the partials are then folded in double.
+__global__ __launch_bounds__(kBlock) void valid_accum_kernel(const float* __restrict__ pred, const float* __restrict__ tgt, float* __restrict__ part,
+                                                             int64_t hw, float value_scale, Thr thr, float omega, float alpha, float gamma) {
+  __shared__ float sm[kBlock / 64][4 * kMaxThr + 3];
+  const int64_t f = blockIdx.y;
+  const float* t = tgt + f * hw;
+  const float* p = pred + f * hw;
+  EvalAcc acc;
+  acc.clear();
+  float e = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < hw; i += (int64_t)gridDim.x * kBlock) {
+    const float tv = t[i], pv = p[i];
+    acc.add(tv, pv, value_scale, thr);
+    e += adnm_rainloss_term<false>(pv, tv, omega, alpha, gamma, nullptr);
+  }
+  const int nout = 4 * thr.n + 3;
+  acc.to_lds<true>(sm, thr.n, e);
+  __syncthreads();
+  if ((int)threadIdx.x < nout)
+    part[((int64_t)blockIdx.x * gridDim.y + f) * nout + threadIdx.x] = (sm[0][threadIdx.x] + sm[1][threadIdx.x]) + (sm[2][threadIdx.x] + sm[3][threadIdx.x]);
+}
+
+// The accumulator block of a validation epoch (include/adnm_hip.h: adnm_valid_accum): 4 header doubles, then the (T, 4*nthr + 3) table.
+constexpr int kValidHdr = 4;
+constexpr int kFoldBlock = 256;
+
+// One workgroup, fixed order, double arithmetic: row t of the table += sum over the samples b (ascending) of frame b*T + t's partials
+// (blocks ascending); the batch loss = sum of every loss partial (lane-strided, then an LDS tree) / n, rounded to fp32.
+__global__ __launch_bounds__(kFoldBlock) void valid_fold_kernel(const float* __restrict__ part, int nb, int frames, int T, int nthr, double inv_n,
+                                                                double* __restrict__ blk, float* __restrict__ loss_out) {
+  __shared__ double red[kFoldBlock];
+  const int nin = 4 * nthr + 3, ncol = 4 * nthr + 3, B = frames / T;
+  for (int i = threadIdx.x; i < T * (nin - 1); i += kFoldBlock) {
+    const int t = i / (nin - 1), c = i % (nin - 1);
+    double a = 0.0;
+    for (int b = 0; b < B; ++b)
+      for (int k = 0; k < nb; ++k) a += (double)part[((int64_t)k * frames + (b * T + t)) * nin + c];
+    blk[kValidHdr + t * ncol + c] += a;
+  }
+  double e = 0.0;
+  for (int64_t i = threadIdx.x; i < (int64_t)nb * frames; i += kFoldBlock) e += (double)part[i * nin + (nin - 1)];
+  red[threadIdx.x] = e;
+  __syncthreads();
+  for (int o = kFoldBlock / 2; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float loss = (float)(red[0] * inv_n);
+    if (adnm_nonfinite_bits(loss)) blk[3] += 1.0;
+    else blk[0] += (double)loss;
+    blk[1] += 1.0;
+    blk[2] += (double)B;
+    if (loss_out) *loss_out = loss;
+  }
+}
+
+// part[tile][frame] (eval_ssim_kernel) -> column 4*nthr + 2 of row t += sum over the samples (ascending) of frame b*T + t's tiles (ascending)
+__global__ __launch_bounds__(kFoldBlock) void valid_ssim_fold_kernel(const float* __restrict__ part, int tiles, int frames, int T, int nthr,
+                                                                     double* __restrict__ blk) {
+  const int ncol = 4 * nthr + 3, B = frames / T;
+  for (int t = threadIdx.x; t < T; t += kFoldBlock) {
+    double a = 0.0;
+    for (int b = 0; b < B; ++b)
+      for (int k = 0; k < tiles; ++k) a += (double)part[(int64_t)k * frames + (b * T + t)];
+    blk[kValidHdr + t * ncol + 4 * nthr + 2] += a;
+  }
 }
 
 // SSIM of SimplifiedEvaluator.cal_ssim (datasets/Shanghai_metrics.py:132-152): per frame, the mean over the VALID region of
@@ -145,6 +240,14 @@ inline int eval_blocks(int64_t hw) {
   int64_t b = adnm_cdiv(hw, kBlock * 16);
   return (int)(b < 1 ? 1 : (b > 64 ? 64 : b));
 }
+// the normalised sampled Gaussian cv2.getGaussianKernel(11, 1.5) documents
+inline GaussWin gauss_window() {
+  GaussWin g;
+  double sum = 0.0;
+  for (int j = 0; j <= 2 * kSsimR; ++j) sum += (g.k[j] = exp(-(double)((j - kSsimR) * (j - kSsimR)) / (2.0 * 1.5 * 1.5)));
+  for (int j = 0; j <= 2 * kSsimR; ++j) g.k[j] /= sum;
+  return g;
+}
 }  // namespace
 
 extern "C" int adnm_radar_ingest(const void* src_u8, float* dst, int64_t frames, int64_t H0, int64_t W0, int64_t S, float mul, adnm_stream_t stream) {
@@ -206,10 +309,7 @@ extern "C" int adnm_eval_ssim(const float* truth, const float* pred, float* out,
     adnm_set_error("eval_ssim: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)adnm_eval_ssim_ws_bytes(frames, H, W));
     return ADNM_EWORKSPACE;
   }
-  GaussWin g;
-  double sum = 0.0;
-  for (int j = 0; j <= 2 * kSsimR; ++j) sum += (g.k[j] = exp(-(double)((j - kSsimR) * (j - kSsimR)) / (2.0 * 1.5 * 1.5)));
-  for (int j = 0; j <= 2 * kSsimR; ++j) g.k[j] /= sum;
+  const GaussWin g = gauss_window();
   const int tx = (int)adnm_cdiv(W - 2 * kSsimR, kSsimT), ty = (int)adnm_cdiv(H - 2 * kSsimR, kSsimT);
   hipStream_t st = (hipStream_t)stream;
   {
@@ -219,5 +319,88 @@ extern "C" int adnm_eval_ssim(const float* truth, const float* pred, float* out,
   ADNM_CHECK_LAUNCH("eval_ssim");
   adnm_launch_fold("eval_ssim_fold", (const float*)ws, tx * ty, (int)frames, {out, (int)frames}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}, st);
   ADNM_CHECK_LAUNCH("eval_ssim_fold");
+  return ADNM_OK;
+}
+
+
+// ---- the validation epoch: accumulate on the device (include/adnm_hip.h) ----
+namespace {
+bool valid_shape_ok(int64_t frames, int64_t T, int64_t hw, int64_t nthr) {
+  return frames > 0 && frames <= 65535 && T >= 1 && frames % T == 0 && hw > 0 && hw < (1ll << 24) && nthr >= 1 && nthr <= kMaxThr;
+}
+}  // namespace
+
+extern "C" int64_t adnm_valid_block_bytes(int64_t T, int64_t nthr) {
+  if (T < 1 || T > 65535 || nthr < 1 || nthr > kMaxThr) return -1;
+  return (int64_t)sizeof(double) * (kValidHdr + T * (4 * nthr + 3));
+}
+
+extern "C" int64_t adnm_valid_accum_ws_bytes(int64_t frames, int64_t T, int64_t hw, int64_t nthr) {
+  if (!valid_shape_ok(frames, T, hw, nthr)) return -1;
+  return (int64_t)eval_blocks(hw) * frames * (4 * nthr + 3) * (int64_t)sizeof(float);
+}
+
+extern "C" int adnm_valid_accum(const float* pred, const float* target, void* block, float* loss_out, const float* thresholds_host, int64_t nthr,
+                                float value_scale, float omega_t, float alpha, float gamma, void* ws, int64_t ws_bytes, int64_t frames, int64_t T,
+                                int64_t hw, adnm_stream_t stream) {
+  ADNM_REQUIRE(pred && target && block && thresholds_host, "valid_accum: null pointer");
+  ADNM_REQUIRE((uintptr_t)block % 8 == 0, "valid_accum: the accumulator block must be 8-byte aligned");
+  ADNM_REQUIRE(valid_shape_ok(frames, T, hw, nthr),
+               "valid_accum: bad shape (frames <= 65535, T >= 1 dividing frames, pixels per frame < 2^24, 1..8 thresholds), got frames %lld T %lld hw %lld "
+               "nthr %lld", (long long)frames, (long long)T, (long long)hw, (long long)nthr);
+  if (!ws || ws_bytes < adnm_valid_accum_ws_bytes(frames, T, hw, nthr)) {
+    adnm_set_error("valid_accum: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)adnm_valid_accum_ws_bytes(frames, T, hw, nthr));
+    return ADNM_EWORKSPACE;
+  }
+  Thr thr;
+  thr.n = (int)nthr;
+  for (int k = 0; k < kMaxThr; ++k) thr.t[k] = k < nthr ? thresholds_host[k] : 0.f;
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = eval_blocks(hw);
+  {
+    ADNM_PROF("valid_accum", st, 8.0 * frames * hw);
+    valid_accum_kernel<<<dim3(nb, (unsigned)frames), kBlock, 0, st>>>(pred, target, (float*)ws, hw, value_scale, thr, omega_t, alpha, gamma);
+  }
+  ADNM_CHECK_LAUNCH("valid_accum");
+  {
+    ADNM_PROF("valid_accum_fold", st, 4.0 * nb * frames * (4 * nthr + 3));
+    valid_fold_kernel<<<1, kFoldBlock, 0, st>>>((const float*)ws, nb, (int)frames, (int)T, (int)nthr, 1.0 / ((double)frames * (double)hw), (double*)block,
+                                                loss_out);
+  }
+  ADNM_CHECK_LAUNCH("valid_accum_fold");
+  return ADNM_OK;
+}
+
+extern "C" int64_t adnm_valid_ssim_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr) {
+  if (H <= 2 * kSsimR || W <= 2 * kSsimR || H >= 32768 || W >= 32768 || !valid_shape_ok(frames, T, H * W, nthr)) return -1;
+  return adnm_eval_ssim_ws_bytes(frames, H, W);
+}
+
+extern "C" int adnm_valid_ssim_accum(const float* pred, const float* target, void* block, int64_t nthr, float value_scale, void* ws, int64_t ws_bytes,
+                                     int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream) {
+  ADNM_REQUIRE(pred && target && block, "valid_ssim_accum: null pointer");
+  ADNM_REQUIRE((uintptr_t)block % 8 == 0, "valid_ssim_accum: the accumulator block must be 8-byte aligned");
+  ADNM_REQUIRE(H > 2 * kSsimR && W > 2 * kSsimR && H < 32768 && W < 32768,
+               "valid_ssim_accum: needs frames of more than 10 x 10 pixels (11 x 11 window, valid region), got %lld x %lld", (long long)H, (long long)W);
+  ADNM_REQUIRE(valid_shape_ok(frames, T, H * W, nthr),
+               "valid_ssim_accum: bad shape (frames <= 65535, T >= 1 dividing frames, pixels per frame < 2^24, 1..8 thresholds), got frames %lld T %lld "
+               "%lld x %lld nthr %lld", (long long)frames, (long long)T, (long long)H, (long long)W, (long long)nthr);
+  if (!ws || ws_bytes < adnm_valid_ssim_accum_ws_bytes(frames, T, H, W, nthr)) {
+    adnm_set_error("valid_ssim_accum: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)adnm_valid_ssim_accum_ws_bytes(frames, T, H, W, nthr));
+    return ADNM_EWORKSPACE;
+  }
+  const GaussWin g = gauss_window();
+  const int tx = (int)adnm_cdiv(W - 2 * kSsimR, kSsimT), ty = (int)adnm_cdiv(H - 2 * kSsimR, kSsimT);
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ADNM_PROF("valid_ssim", st, 8.0 * frames * H * W);
+    eval_ssim_kernel<<<dim3((unsigned)(tx * ty), (unsigned)frames), kSsimT * kSsimT, 0, st>>>(target, pred, (float*)ws, (int)H, (int)W, tx, tx * ty, value_scale, g);
+  }
+  ADNM_CHECK_LAUNCH("valid_ssim_accum");
+  {
+    ADNM_PROF("valid_ssim_fold", st, 4.0 * tx * ty * frames);
+    valid_ssim_fold_kernel<<<1, kFoldBlock, 0, st>>>((const float*)ws, tx * ty, (int)frames, (int)T, (int)nthr, (double*)block);
+  }
+  ADNM_CHECK_LAUNCH("valid_ssim_fold");
   return ADNM_OK;
 }

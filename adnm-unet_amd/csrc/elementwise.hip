@@ -145,26 +145,16 @@ __global__ __launch_bounds__(kBlock) void catmix_bwd_kernel(const T* __restrict_
   if (threadIdx.x < 4) part[blockIdx.x * 4 + threadIdx.x] = (sm[threadIdx.x][0] + sm[threadIdx.x][1]) + (sm[threadIdx.x][2] + sm[threadIdx.x][3]);
 }
 
-// enRainfallLoss (models/loss.py:30-57 of the reference), value and d/dpred in one pass.
-//   e = w(pred>=t) * |pred-t| * (1 + [t>=0.7] alpha exp(t))  +  [t>=0.7 and pred<t] gamma (exp(alpha (t-pred)) - 1);  loss = sum e / n
+// enRainfallLoss (models/loss.py:30-57 of the reference), value and d/dpred in one pass: loss = sum e / n, e = adnm_rainloss_term
+// (adnm_common.h).
 __global__ __launch_bounds__(kBlock) void rainloss_kernel(const float* __restrict__ pred, const float* __restrict__ tgt, float* __restrict__ grad,
                                                           float* __restrict__ part, int64_t n, float omega, float alpha, float gamma) {
   __shared__ float sm[kBlock / 64];
   const float inv_n = 1.0f / (float)n;
   float acc = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    const float p = pred[i], t = tgt[i], diff = p - t;
-    const bool over = p >= t, heavy = t >= 0.7f;
-    const float w = over ? 1.0f - omega : omega;
-    const float wi = heavy ? alpha * __expf(t) : 0.f;
-    float e = w * fabsf(diff) * (1.0f + wi);
-    float g = w * (1.0f + wi) * (diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f));
-    if (gamma != 0.f && heavy && !over) {
-      const float ex = __expf(alpha * (t - p));
-      e += gamma * (ex - 1.0f);
-      g -= gamma * alpha * ex;
-    }
-    acc += e;
+    float g;
+    acc += adnm_rainloss_term<true>(pred[i], tgt[i], omega, alpha, gamma, &g);
     grad[i] = g * inv_n;
   }
   acc = wave_sum(acc);

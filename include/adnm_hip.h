@@ -580,6 +580,31 @@ int64_t adnm_eval_ssim_ws_bytes(int64_t frames, int64_t H, int64_t W);
 int adnm_eval_ssim(const float* truth, const float* pred, float* out, float value_scale, void* ws, int64_t ws_bytes, int64_t frames,
                    int64_t H, int64_t W, adnm_stream_t stream);
 
+/* The validation half of an epoch (train.py:156-206: a forward-only pass, the loss per batch, the metrics) accumulated ON THE DEVICE:
+ * a batch adds into a block the caller keeps for the whole epoch, and the host reads the block once.
+ * block: adnm_valid_block_bytes(T, nthr) bytes of device memory, 8-byte aligned, zero-initialised by the caller, all double:
+ *   double [0] sum of the finite batch losses (what train.py:163 accumulates)   [1] batches   [2] samples (frames / T per batch)
+ *          [3] batches whose loss was not finite (they add nothing to [0]: adnm_loss_stat's rule)
+ *   then a table (T, 4*nthr + 3), row t = frame index within a sample (frame f of a batch belongs to row f mod T):
+ *          [4*k .. 4*k + 3] TP, FN, FP, TN at threshold k, summed over every sample so far (integers held in doubles: exact over a dataset)
+ *          [4*nthr] sum |d|   [4*nthr + 1] sum d^2   of the value_scale'd [0,1]-clipped fields   [4*nthr + 2] sum of the SSIM maps' sums.
+ * adnm_valid_accum: ONE pass over contiguous fp32 pred / target of shape (frames, hw), frames = B*T; two launches.  The counts and the two
+ *   error sums are adnm_eval_counts' (the same device code: clip, scale, truncate, compare); the loss is enRainfallLoss on the UNCLIPPED
+ *   values with adnm_rainloss' per-element expression (the same device function), value only — no gradient is formed or written.  Per
+ *   workgroup fp32 partials go to ws; one workgroup folds them in double, in a fixed order (samples ascending), and updates the block:
+ *   loss = (float)(sum e / (frames*hw)); finite: [0] += loss, else [3] += 1; [1] += 1; [2] += B; loss_out (optional device float, NULL
+ *   skips) receives the fp32 batch loss.  Deterministic: the same calls on the same block give the same bits.  NaN / Inf data are inputs.
+ * adnm_valid_ssim_accum: adnm_eval_ssim's kernel, then column 4*nthr + 2 of row f mod T += the frame's map sum.  H > 10 && W > 10.
+ * Limits: frames <= 65535, hw < 2^24, 1 <= nthr <= 8 (adnm_eval_counts'), T >= 1, T | frames.  The *_bytes queries return -1 outside them. */
+int64_t adnm_valid_block_bytes(int64_t T, int64_t nthr);
+int64_t adnm_valid_accum_ws_bytes(int64_t frames, int64_t T, int64_t hw, int64_t nthr);
+int adnm_valid_accum(const float* pred, const float* target, void* block, float* loss_out, const float* thresholds_host, int64_t nthr,
+                     float value_scale, float omega_t, float alpha, float gamma, void* ws, int64_t ws_bytes, int64_t frames, int64_t T,
+                     int64_t hw, adnm_stream_t stream);
+int64_t adnm_valid_ssim_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr);
+int adnm_valid_ssim_accum(const float* pred, const float* target, void* block, int64_t nthr, float value_scale, void* ws, int64_t ws_bytes,
+                          int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
+
 /* ---------------------------------------------------------------- stand-alone activations
  * act_fwd / act_bwd: y = act(x), dpre = dy * act'(pre) over flat fp32 arrays (n % 4 == 0), act in {ADNM_ACT_SILU, ADNM_ACT_GELU}: nn.GELU
  *   between Mlp.fc1 and fc2 (model_untils.py:52-70) and the backward of the GELUs fused into GEMM / conv epilogues.
