@@ -530,6 +530,24 @@ def test_igate_res(B, L, C, per_token):
         assert_close(a.grad, b.grad, GRAD_TOL, n, atol=1e-5)
 
 
+def test_emul_column_slices():
+    """VSSD's gate form (Vssd.py:91): the operands are column slices of wider matrices, so their row strides differ from C (and from each
+    other).  One fp32 multiply per element each way: y, da and db must be the fp32 products bit for bit.  Odd M, C = 12, several workgroups."""
+    M, C = 301, 12
+    wa, wb, cot = T("em.a", (M, 28), 2.0), T("em.b", (M, 20), 0.5), T("em.c", (M, C))
+    wag, wbg = leaf(wa, DEV), leaf(wb, DEV)
+    a, b = wag[:, :C], wbg[:, 8:8 + C]
+    assert a.stride(0) == 28 and b.stride(0) == 20
+    y = ops.emul(a, b)
+    y.backward(cot.to(DEV))
+    ar, br = wa[:, :C], wb[:, 8:8 + C]
+    assert torch.equal(y.detach().cpu(), ar * br), "y"
+    da, db = torch.zeros_like(wa), torch.zeros_like(wb)
+    da[:, :C], db[:, 8:8 + C] = cot * br, cot * ar
+    assert torch.equal(wag.grad.cpu(), da), "da"
+    assert torch.equal(wbg.grad.cpu(), db), "db"
+
+
 # ------------------------------------------------------------------------------------------- EncoderToDecoder core (K12)
 @pytest.mark.parametrize("B,H,W,C", [(2, 4, 4, 256), (1, 8, 8, 512), (4, 2, 2, 1024), (2, 16, 16, 256), (1, 40, 40, 256),
                                      (1, 32, 32, 128), (2, 9, 7, 64), (1, 64, 64, 32), (3, 5, 5, 36)])
