@@ -25,18 +25,26 @@ class GraphedForward:
     rewrites the shadows it captured against if a parameter was written since (a checkpoint load, an in-place op), and the graph keeps
     them alive, so it may outlive the trainer.  close() (or __del__) gives the graphs back."""
 
-    def __init__(self, model, head=None, tail=None):
+    def __init__(self, model, head=None, tail=None, source=None, probe=None):
         """head(sx) / tail(sx, out): optional extra bodies captured into the same graph right before / after the forward (sx: the
         graph's static input, out: its static output) — adnm_hip.validate.Validator's loss and metrics pass.  They run ONLY inside the
-        capture, never in the warm-up forwards: whatever they launch must have run once before.  Without them nothing changes."""
+        capture, never in the warm-up forwards: whatever they launch must have run once before.  Without them nothing changes.
+        source(sx) -> the model's input, made from the static input into a tensor the caller owns (adnm_hip.forecast.Forecaster: raw
+        radar bytes through adnm_radar_ingest).  It runs in the warm-up forwards too and is captured between head and the forward;
+        None: the static input is the model's input.
+        probe(out): called once per input shape on a warm-up forward's output, BEFORE the capture begins: where the owner of a
+        tail checks the output (and may raise outside the capture) and allocates what the tail writes."""
         self.model = model
-        self._head, self._tail = head, tail
+        self._head, self._tail, self._source, self._probe = head, tail, source, probe
         self._graphs = {}
+
+    def _forward(self, sx):
+        return self.model(sx if self._source is None else self._source(sx))
 
     def _body(self, sx):
         if self._head is not None:
             self._head(sx)
-        out = self.model(sx)
+        out = self._forward(sx)
         if self._tail is not None:
             self._tail(sx, out)
         return out
@@ -53,7 +61,17 @@ class GraphedForward:
             was_training = self.model.training
             self.model.eval()
             sx = x.clone()
-            ops.warm_up(lambda: self.model(sx), 2)
+            if self._probe is None:
+                ops.warm_up(lambda: self._forward(sx), 2)
+            else:
+                try:
+                    ops.warm_up(lambda: self._forward(sx), 1)
+                    warm = []
+                    ops.warm_up(lambda: warm.append(self._forward(sx)), 1)
+                    self._probe(warm.pop())
+                except BaseException:
+                    self.model.train(was_training)
+                    raise
             g = torch.cuda.CUDAGraph()
             # the graph's split GEMM launches get their own uncached workspace (kept with the graph: a training graph replayed on
             # another stream beside this one must not share it); fp8: the quantisation table's rows stay put while the graph lives

@@ -1,0 +1,253 @@
+"""The output side of the hot path: the reference's third script, pic_results.py, loads the best checkpoint, forecasts the test set,
+copies every prediction to numpy as floats and colours it frame by frame with matplotlib (vis_res, pic_results.py:104-184).  Here
+
+    pal = Palette(BOUNDS, COLOR_MAP)                              # the caller's own table: the package ships none
+    fc = Forecaster(model, pal, pixel_scale=90.0, size=128, frame_start=1, frame_step=2)
+    res = fc(x)                 # ONE replay of a captured graph; x: fp32 (B, T_in, 1, S, S) or RAW uint8 (B, T_in, H0, W0) on the device
+    res.pred, res.fields, res.strip                               # fp32 forecast, a byte per pixel, the RGBA colour strip
+    fc.save(out_dir, res, "ADNMUnet", batch=cnt)                  # {batch}-{i+1}/ADNMUnet.png, as pic_results.py:263-271 lays them out
+    fc.save(out_dir, fc.render(targets), "gt", batch=cnt)         # the gt.png row: the same palette on any other (B, T, ...) tensor
+
+A call is GraphedForward's captured graph with csrc/dataio.hip::forecast_render as the body behind the forward (one launch: the
+quantised fields, the frame selection, the colour lookup, the gaps) and, for raw bytes, adnm_radar_ingest as the body in front of it.
+What leaves the device is 1 + 4 n / T bytes per pixel (n of T frames selected) instead of 4, and the host does no per-frame work.
+
+The value rule is stated in include/adnm_hip.h (adnm_forecast_render); inside the uint8 range it is pic_results.py's, byte for byte
+(tests/golden/forecast_render_*.npz are matplotlib's own output).  Figure layout beyond the strip and LPIPS are not reproduced."""
+import json
+import os
+import struct
+import zlib
+
+import numpy as np
+import torch
+
+from . import lib, ops
+from .evaluator import GraphedForward
+
+MAX_BINS = 32
+
+
+class Palette:
+    """BoundaryNorm(bounds, K) + ListedColormap(colours) as a table: K + 1 ascending edges, K RGBA rows.  colours: (K, 4) uint8, or
+    floats in [0, 1] converted with (c * 255).astype(uint8) as matplotlib does.  `edges` keeps the doubles as given; `bounds` is what
+    the kernel compares against: each edge rounded UP to the smallest float32 >= it (ops.edges_up_f32)."""
+
+    def __init__(self, bounds, colours):
+        self.edges = tuple(float(e) for e in bounds)
+        c = np.asarray(colours)
+        if c.ndim != 2 or c.shape[1] != 4:
+            raise ValueError(f"Palette: colours must be (K, 4) RGBA rows, got {c.shape}")
+        if c.dtype.kind == "f":
+            if not (np.isfinite(c).all() and c.min() >= 0.0 and c.max() <= 1.0):
+                raise ValueError("Palette: float colours must lie in [0, 1]")
+            c = (c * 255).astype(np.uint8)
+        elif c.dtype.kind in "iu":
+            if c.min() < 0 or c.max() > 255:
+                raise ValueError("Palette: integer colours must lie in 0..255")
+            c = c.astype(np.uint8)
+        else:
+            raise ValueError(f"Palette: colours must be uint8 or floats in [0, 1], got {c.dtype}")
+        K = c.shape[0]
+        if not 1 <= K <= MAX_BINS:
+            raise ValueError(f"Palette: 1..{MAX_BINS} colours, got {K}")
+        if len(self.edges) != K + 1:
+            raise ValueError(f"Palette: {K} colours need {K + 1} edges, got {len(self.edges)}")
+        self.colours = np.ascontiguousarray(c)
+        self.bounds = ops.edges_up_f32(self.edges)
+        if not (np.diff(self.bounds) > 0).all():
+            raise ValueError("Palette: the edges must be strictly ascending (as float32 too)")
+        self._c = ops.render_tables(self.edges, self.colours)   # the host tables as the entry point reads them, made once
+
+    @property
+    def nbins(self):
+        return self.colours.shape[0]
+
+    # the JSON form of tests/golden/forecast_palette_*.json: the edges and the 8-bit RGBA rows, nothing else
+    def to_json(self):
+        return json.dumps({"bounds": list(self.edges), "rgba": self.colours.tolist()})
+
+    @classmethod
+    def from_json(cls, text):
+        d = json.loads(text)
+        if set(d) != {"bounds", "rgba"}:
+            raise ValueError(f"Palette: expected the keys 'bounds' and 'rgba', got {sorted(d)}")
+        return cls(d["bounds"], np.asarray(d["rgba"], dtype=np.int64))
+
+    def save(self, path):
+        with open(path, "w") as f:
+            f.write(self.to_json() + "\n")
+
+    @classmethod
+    def load(cls, path):
+        with open(path) as f:
+            return cls.from_json(f.read())
+
+    def __eq__(self, other):
+        return isinstance(other, Palette) and self.edges == other.edges and np.array_equal(self.colours, other.colours)
+
+
+def save_png(path, rgba_u8):
+    """An (H, W, 4) uint8 array (numpy or a tensor on any device) -> an 8-bit RGBA PNG, with the standard library only (what plt.imsave
+    writes for pic_results.py, without matplotlib on the machine that forecasts)."""
+    a = rgba_u8.detach().cpu().numpy() if torch.is_tensor(rgba_u8) else np.asarray(rgba_u8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"save_png: needs a uint8 (H, W, 4) image, got {a.dtype} {a.shape}")
+    H, W = a.shape[:2]
+    rows = np.zeros((H, 1 + 4 * W), dtype=np.uint8)          # filter type 0 in front of every scanline
+    rows[:, 1:] = a.reshape(H, 4 * W)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+
+    png = (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 6, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6))
+           + chunk(b"IEND", b""))
+    with open(path, "wb") as f:
+        f.write(png)
+
+
+class Forecast:
+    """What a Forecaster call returns: .pred (fp32, the model's output in the model's own shape: (B, T, 1, H, W) from create_ADNMUNet's
+    models, (B, T, H, W) from a model that emits that; for render() the tensor it was given), .fields (uint8 (B, T, H, W)),
+    .strip (uint8 (B, H, Ws, 4))."""
+    __slots__ = ("pred", "fields", "strip")
+
+    def __init__(self, pred, fields, strip):
+        self.pred, self.fields, self.strip = pred, fields, strip
+
+
+class Forecaster:
+    def __init__(self, model, palette, pixel_scale=90.0, size=None, in_frames=5, frame_start=0, frame_step=1, gap=10):
+        """pixel_scale: pic_results.py's PIXEL_SCALE; None or 0 bins the float itself (the LAPS form).  size: the model's input edge,
+        needed for raw uint8 input only.  frame_start / frame_step: the frames of the strip (even_index_only=True is 1, 2)."""
+        if not isinstance(palette, Palette):
+            raise RuntimeError(f"Forecaster: palette must be a forecast.Palette, got {type(palette).__name__}")
+        self.model, self.palette = model, palette
+        self.pixel_scale = 0.0 if pixel_scale is None else float(pixel_scale)
+        self.size, self.in_frames = (None if size is None else int(size)), int(in_frames)
+        self.frame_start, self.frame_step, self.gap = int(frame_start), int(frame_step), int(gap)
+        if not (self.pixel_scale >= 0.0 and np.isfinite(self.pixel_scale)) or self.frame_start < 0 or self.frame_step < 1 or self.gap < 0:
+            raise ValueError("Forecaster: pixel_scale >= 0, frame_start >= 0, frame_step >= 1, gap >= 0")
+        self.out_frames = None              # T of the model's output, known after the first call
+        self._fwd = GraphedForward(model, head=self._head, tail=self._tail, source=self._source, probe=self._probe)
+        self._static, self._cur, self._warm = {}, None, set()
+
+    # ---- the bodies captured around the forward (GraphedForward)
+    def _head(self, sx):
+        st = self._cur
+        if st["qsave"] is not None:
+            # fp8: a forecast beside a training run must not move the delayed-scaling table (Validator._head)
+            st["qsave"].copy_(ops.QUANT.table(sx.device))
+
+    def _source(self, sx):
+        st = self._cur
+        if st["xin"] is None:
+            return sx
+        B, T, H0, W0 = sx.shape
+        lib.call("adnm_radar_ingest", sx.data_ptr(), st["xin"].data_ptr(), B * T, H0, W0, self.size, 1.0 / 255.0, torch.cuda.current_stream().cuda_stream)
+        return st["xin"]
+
+    def _probe(self, out):
+        """on a warm-up forward's output, before the capture: the checks that may raise, and the buffers the tail writes"""
+        st = self._cur
+        if out.dtype != torch.float32 or out.dim() not in (4, 5) or (out.dim() == 5 and out.shape[2] != 1):
+            raise RuntimeError(f"Forecaster: the model's output must be fp32 (B, T, H, W) or (B, T, 1, H, W), got {out.dtype} {tuple(out.shape)}")
+        B, T, H, W = out.shape[0], out.shape[1], out.shape[-2], out.shape[-1]
+        if self.frame_start >= T:
+            raise RuntimeError(f"Forecaster: frame_start {self.frame_start} outside the model's {T} output frames")
+        st["fields"] = torch.empty((B, T, H, W), dtype=torch.uint8, device=out.device)
+        st["strip"] = torch.empty((B, H, ops.strip_width(T, W, self.frame_start, self.frame_step, self.gap), 4), dtype=torch.uint8, device=out.device)
+
+    def _tail(self, sx, out):
+        st = self._cur
+        if st["qsave"] is not None:
+            ops.QUANT.table(sx.device).copy_(st["qsave"])
+        pred = (out.squeeze(2) if out.dim() == 5 else out).contiguous()   # (a copy made here belongs to the graph's pool and is kept with it)
+        ops.forecast_render_into(pred, st["fields"], st["strip"], self.palette._c, self.pixel_scale, self.frame_start, self.frame_step, self.gap)
+        st["keep"] = pred
+        st["res"] = Forecast(out, st["fields"], st["strip"])
+
+    def _warm_up(self, device):
+        """both variants of the render kernel run once before a capture launches them (a kernel's first launch must not be captured)"""
+        if device in self._warm:
+            return
+        for w in (4, 1):
+            ops.forecast_render_tables(torch.zeros((1, 1, 1, w), dtype=torch.float32, device=device), self.palette._c, self.pixel_scale, gap=0)
+        self._warm.add(device)
+
+    # ---- the public surface
+    @torch.no_grad()
+    def __call__(self, x):
+        """x: fp32 (B, in_frames, 1, S, S), or raw uint8 (B, in_frames, H0, W0) radar frames (then / 255 and the bilinear resize to
+        `size` run inside the same graph), on the GPU.  -> Forecast(pred, fields, strip): STATIC buffers of the graph of this input
+        shape, valid until the next call with that shape (copy what has to last)."""
+        if not (torch.is_tensor(x) and x.is_cuda):
+            raise RuntimeError("Forecaster runs on GPU tensors only (there is no CPU path here)")
+        raw = x.dtype == torch.uint8
+        if raw:
+            if x.dim() != 4:
+                raise RuntimeError(f"Forecaster: raw input must be uint8 (B, T_in, H0, W0), got {tuple(x.shape)}")
+            if self.size is None:
+                raise RuntimeError("Forecaster: raw uint8 input needs size= (the model's input edge)")
+        elif x.dtype != torch.float32 or x.dim() != 5 or x.shape[2] != 1:
+            raise RuntimeError(f"Forecaster: input must be fp32 (B, T_in, 1, S, S) or raw uint8 (B, T_in, H0, W0), got {x.dtype} {tuple(x.shape)}")
+        if x.shape[1] != self.in_frames:
+            raise RuntimeError(f"Forecaster: the input has {x.shape[1]} frames per sample, in_frames is {self.in_frames}")
+        key = (tuple(x.shape), x.dtype, x.device)
+        st = self._static.get(key)
+        first, snap = st is None, None
+        if first:
+            self._warm_up(x.device)
+            fp8 = ops.mfma_precision() == "fp8"
+            st = {"xin": torch.empty((x.shape[0], x.shape[1], 1, self.size, self.size), dtype=torch.float32, device=x.device) if raw else None,
+                  "qsave": torch.empty_like(ops.QUANT.table(x.device)) if fp8 else None, "res": None}
+            if fp8:   # the eager warm-up forwards of the capture collect too
+                snap = ops.QUANT.snapshot(x.device)
+        self._cur = st
+        try:
+            self._fwd(x.contiguous())
+        finally:
+            self._cur = None
+            if snap is not None:
+                ops.QUANT.restore(x.device, snap)
+        if first:
+            self._static[key] = st
+            self.out_frames = st["res"].fields.shape[1]
+        return st["res"]
+
+    def render(self, t, frame_start=None, frame_step=None):
+        """The same palette, pixel_scale and gap on any other (B, T, H, W) / (B, T, 1, H, W) fp32 GPU tensor -> a Forecast whose .pred is
+        `t` (freshly allocated outputs, one launch).  With the Forecaster's own frame selection (the default) `t` must have the
+        forecast's T — the gt.png row; give frame_start=0, frame_step=1 for the input.png row, which keeps every frame."""
+        own = frame_start is None and frame_step is None
+        fs = self.frame_start if frame_start is None else int(frame_start)
+        step = self.frame_step if frame_step is None else int(frame_step)
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise RuntimeError("Forecaster runs on GPU tensors only (there is no CPU path here)")
+        if own and self.out_frames is not None and t.dim() >= 2 and t.shape[1] != self.out_frames:
+            raise RuntimeError(f"Forecaster.render: {t.shape[1]} frames per sample, but the frame selection was built for the forecast's {self.out_frames} "
+                               "(pass frame_start / frame_step for another sequence)")
+        fields, strip = ops.forecast_render_tables(t, self.palette._c, self.pixel_scale, fs, step, self.gap)
+        return Forecast(t, fields, strip)
+
+    def save(self, directory, result, name, batch=1):
+        """result.strip -> {directory}/{batch}-{i+1}/{name}.png per sample i (pic_results.py:263-271).  One device -> host copy."""
+        strips = result.strip.cpu().numpy()
+        paths = []
+        for i in range(strips.shape[0]):
+            d = os.path.join(directory, f"{batch}-{i + 1}")
+            os.makedirs(d, exist_ok=True)
+            paths.append(os.path.join(d, f"{name}.png"))
+            save_png(paths[-1], strips[i])
+        return paths
+
+    def close(self):
+        """Give the captured graphs and their static buffers back (GraphedForward.close).  Idempotent; __del__ calls it."""
+        self._fwd.close()
+        self._static = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -6,11 +6,13 @@ Layout convention: token tensors are (B, L, C) / (M, C) channels-last; a "row vi
 tensor with stride (ld, 1) — kernels take the row stride, so column slices of wide buffers are
 passed without copies."""
 import bisect
+import ctypes
 import math
 import operator
 import os
 import threading
 
+import numpy as np
 import torch
 
 from . import lib
@@ -3107,3 +3109,67 @@ def attn4(qkv, heads, scale):
         _unsupported("attn4", f"is soft-max attention with 4-wide heads over <= 2048 tokens on fp32 (B, L, 12*heads) qkv, got {qkv.dtype} "
                               f"{tuple(qkv.shape)} for {heads} heads")
     return Attn4Fn.apply(qkv, heads, scale)
+
+
+# ======================================================================================= the output side (csrc/dataio.hip: forecast_render)
+def edges_up_f32(edges):
+    """double edges -> float32, each rounded UP to the smallest float >= it: the kernel compares an fp32 value with fp32 edges where
+    matplotlib compares it with the double ones, and only the rounded-up edge decides every float the same way (include/adnm_hip.h)."""
+    e = np.asarray(edges, dtype=np.float64).reshape(-1)
+    if not np.isfinite(e).all():
+        raise ValueError("forecast_render: the edges must be finite")
+    f = e.astype(np.float32)
+    low = f.astype(np.float64) < e
+    f[low] = np.nextafter(f[low], np.float32(np.inf))
+    return f
+
+
+def render_tables(bounds, palette):
+    """K + 1 ascending edges (doubles are rounded up, edges_up_f32) and (K, 4) uint8 RGBA rows -> (bounds_c, palette_c, K): the two
+    host tables in the form adnm_forecast_render reads them, checked ONCE (forecast.Palette keeps the result)."""
+    b32 = edges_up_f32(bounds)
+    pal = np.ascontiguousarray(np.asarray(palette))
+    if pal.dtype != np.uint8 or pal.ndim != 2 or pal.shape[1] != 4 or pal.shape[0] != b32.size - 1:
+        raise RuntimeError(f"forecast_render: the palette must be uint8 (K, 4) for K + 1 = {b32.size} edges, got {pal.dtype} {pal.shape}")
+    K = pal.shape[0]
+    return (ctypes.c_float * (K + 1))(*b32.tolist()), (ctypes.c_uint8 * (4 * K))(*pal.reshape(-1).tolist()), K
+
+
+def forecast_render_into(pred, fields, strip, tables, pixel_scale, frame_start, frame_step, gap):
+    """the launch alone, on tensors the caller owns (pred (B, T, H, W) fp32 contiguous; fields / strip may be None) and on
+    render_tables' result: what a captured graph's body calls"""
+    B, T, H, W = pred.shape
+    lib.call("adnm_forecast_render", pred.data_ptr(), _p(fields), _p(strip), tables[0], tables[1], tables[2], float(pixel_scale), B, T, H, W,
+             int(frame_start), int(frame_step), int(gap), _stream())
+
+
+def strip_width(T, W, frame_start, frame_step, gap):
+    n = -(-(T - frame_start) // frame_step)
+    return n * W + (n - 1) * gap
+
+
+def forecast_render_tables(pred, tables, pixel_scale, frame_start=0, frame_step=1, gap=10, fields=True, strip=True):
+    """forecast_render on tables that render_tables already made"""
+    if not torch.is_tensor(pred):
+        raise RuntimeError("forecast_render: needs a GPU tensor")
+    _need_gpu(pred)
+    if pred.dtype != torch.float32 or pred.dim() not in (4, 5) or (pred.dim() == 5 and pred.shape[2] != 1):
+        _unsupported("forecast_render", f"takes fp32 (B, T, H, W) or (B, T, 1, H, W), got {pred.dtype} {tuple(pred.shape)}")
+    if not (fields or strip):
+        raise RuntimeError("forecast_render: neither fields nor strip was asked for")
+    p = (pred.squeeze(2) if pred.dim() == 5 else pred).contiguous()
+    B, T, H, W = p.shape
+    if not 0 <= int(frame_start) < T or int(frame_step) < 1 or int(gap) < 0:
+        raise RuntimeError(f"forecast_render: frame_start {frame_start} / frame_step {frame_step} / gap {gap} do not fit {T} frames")
+    f = torch.empty((B, T, H, W), dtype=torch.uint8, device=p.device) if fields else None
+    s = torch.empty((B, H, strip_width(T, W, int(frame_start), int(frame_step), int(gap)), 4), dtype=torch.uint8, device=p.device) if strip else None
+    forecast_render_into(p, f, s, tables, pixel_scale, frame_start, frame_step, gap)
+    return f, s
+
+
+def forecast_render(pred, bounds, palette, pixel_scale, frame_start=0, frame_step=1, gap=10, fields=True, strip=True):
+    """pic_results.py:104-184 on the device, one launch: pred (B, T, H, W) or (B, T, 1, H, W) fp32 ->
+    (fields (B, T, H, W) uint8 or None, strip (B, H, n*W + (n-1)*gap, 4) uint8 RGBA or None) of the frames frame_start::frame_step.
+    bounds: K + 1 ascending edges (doubles are rounded up to fp32, edges_up_f32); palette: (K, 4) uint8 RGBA rows, K <= 32.
+    pixel_scale > 0: the byte (uint8)(pred * pixel_scale) is stored and binned; 0: the float itself is binned and fields holds the bin."""
+    return forecast_render_tables(pred, render_tables(bounds, palette), pixel_scale, frame_start, frame_step, gap, fields, strip)

@@ -9,6 +9,9 @@
 //                   (:45-47,103-112) and the sums |d|, d^2 of the scaled float fields (:114-120) from which MAE / MSE / RMSE / PSNR follow.
 //   valid_accum   — the validation half of an epoch (train.py:156-206): the same counts and sums plus the enRainfallLoss value of the batch,
 //                   ADDED to a block of doubles the caller keeps on the device for the whole epoch (no gradient tensor, no host read).
+//   forecast_render — the output side, pic_results.py:104-184: the forecast quantised to a byte per pixel ((seq * pixel_scale).astype(uint8)),
+//                   the frame selection seq[1::2], BoundaryNorm + ListedColormap as a table lookup and the frames laid side by side with a
+//                   gap of opaque white, as RGBA bytes: what a consumer stores, instead of a float copy and numpy / matplotlib per frame.
 #include "adnm_common.h"
 #include <math.h>
 
@@ -402,5 +405,130 @@ extern "C" int adnm_valid_ssim_accum(const float* pred, const float* target, voi
     valid_ssim_fold_kernel<<<1, kFoldBlock, 0, st>>>((const float*)ws, tx * ty, (int)frames, (int)T, (int)nthr, (double*)block);
   }
   ADNM_CHECK_LAUNCH("valid_ssim_fold");
+  return ADNM_OK;
+}
+
+
+// ---- the output side: forecast fields and colour strips (include/adnm_hip.h: adnm_forecast_render) ----
+namespace {
+constexpr int kMaxBins = 32;
+// edges and colours travel by value in the kernarg segment: every lane's edge loads are uniform, and nothing on the device has to outlive the call
+struct RenderTab {
+  float bounds[kMaxBins + 1];
+  uint32_t rgba[kMaxBins];   // R | G << 8 | B << 16 | A << 24: the dword whose bytes in memory are R, G, B, A
+  int n;
+};
+
+// the value rule of one pixel -> the byte for `fields`, the RGBA dword for `strip`
+__device__ __forceinline__ void render_pixel(float p, float pixel_scale, const RenderTab& tab, uint32_t& byte, uint32_t& colour) {
+  float v = p;
+  if (pixel_scale > 0.f) {
+    const float prod = __fmul_rn(p, pixel_scale);            // the fp32 product on its own, as numpy forms it (never contracted)
+    const float c = fminf(fmaxf(prod, 0.f), 255.f);          // fmaxf(NaN, 0) = 0
+    byte = (uint32_t)(int)c;                                 // truncation toward zero
+    v = (float)byte;
+  }
+  int cnt = 0;
+#pragma unroll
+  for (int k = 0; k <= kMaxBins; ++k) cnt += (k <= tab.n && tab.bounds[k] <= v) ? 1 : 0;   // NaN: no edge is <= it
+  int idx = cnt - 1;
+  idx = idx < 0 ? 0 : (idx > tab.n - 1 ? tab.n - 1 : idx);
+  colour = tab.rgba[idx];
+  if (!(pixel_scale > 0.f)) {
+    byte = (uint32_t)idx;
+    if (v != v) colour = 0u;                                 // matplotlib's "bad" colour
+  }
+}
+
+// A lane owns up to 4 consecutive pixels of one row of one frame: lane i -> group q = i % Q of row i / Q, Q = ceil(W / 4).
+// VEC (W % 4 == 0, pred 16-byte and fields 4-byte aligned): one 16-byte load, one packed dword store to fields.  The strip is written
+// pixel by pixel as dwords: a frame's origin in a strip row is 4 * j * (W + gap) bytes, which is 16-byte aligned only when
+// (W + gap) % 4 == 0 (W = 128, gap = 10: 552 * j).  The gap behind a selected frame (all but the last) is written by that frame's
+// lanes of the same row, lane q taking the gap pixels q, q + Q, ...
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void forecast_render_kernel(const float* __restrict__ pred, uint8_t* __restrict__ fields, uint32_t* __restrict__ strip,
+                                                                 RenderTab tab, float pixel_scale, int64_t lanes, int T, int H, int W, int Q, int frame_start,
+                                                                 int frame_step, int nsel, int gap, int64_t strip_w) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= lanes) return;
+  const int q = (int)(i % Q);
+  const int64_t row = i / Q;                     // (b * T + t) * H + y
+  const int y = (int)(row % H);
+  const int64_t ft = row / H;
+  const int t = (int)(ft % T);
+  const int64_t b = ft / T;
+  const int x0 = 4 * q, npx = W - x0 < 4 ? W - x0 : 4;
+  const int64_t src = row * W + x0;
+  float p[4] = {0.f, 0.f, 0.f, 0.f};
+  if (VEC) {
+    const float4 v = *reinterpret_cast<const float4*>(pred + src);
+    p[0] = v.x, p[1] = v.y, p[2] = v.z, p[3] = v.w;
+  } else {
+    for (int k = 0; k < npx; ++k) p[k] = pred[src + k];
+  }
+  uint32_t byte[4] = {0u, 0u, 0u, 0u}, colour[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < npx) render_pixel(p[k], pixel_scale, tab, byte[k], colour[k]);
+  if (fields) {
+    if (VEC) *reinterpret_cast<uint32_t*>(fields + src) = byte[0] | (byte[1] << 8) | (byte[2] << 16) | (byte[3] << 24);
+    else
+      for (int k = 0; k < npx; ++k) fields[src + k] = (uint8_t)byte[k];
+  }
+  if (strip && t >= frame_start && (t - frame_start) % frame_step == 0) {
+    const int j = (t - frame_start) / frame_step;
+    uint32_t* dst = strip + ((b * H + y) * strip_w + (int64_t)j * (W + gap));
+    for (int k = 0; k < npx; ++k) dst[x0 + k] = colour[k];
+    if (j < nsel - 1)
+      for (int g = q; g < gap; g += Q) dst[W + g] = 0xffffffffu;
+  }
+}
+}  // namespace
+
+extern "C" int adnm_forecast_render(const float* pred, uint8_t* fields, uint8_t* strip, const float* bounds_host, const uint8_t* palette_host, int64_t nbins,
+                                    float pixel_scale, int64_t B, int64_t T, int64_t H, int64_t W, int64_t frame_start, int64_t frame_step, int64_t gap,
+                                    adnm_stream_t stream) {
+  ADNM_REQUIRE(pred && bounds_host && palette_host, "forecast_render: null pointer");
+  ADNM_REQUIRE(fields || strip, "forecast_render: no output (fields and strip are both NULL)");
+  ADNM_REQUIRE(nbins >= 1 && nbins <= kMaxBins, "forecast_render: 1..32 bins, got %lld", (long long)nbins);
+  for (int64_t k = 0; k <= nbins; ++k)
+    ADNM_REQUIRE(isfinite(bounds_host[k]) && (k == 0 || bounds_host[k] > bounds_host[k - 1]), "forecast_render: the %lld edges must be finite and ascending (edge %lld)",
+                 (long long)(nbins + 1), (long long)k);
+  ADNM_REQUIRE(pixel_scale >= 0.f && isfinite(pixel_scale), "forecast_render: pixel_scale must be finite and >= 0 (0: bin the float value itself)");
+  ADNM_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && B < (1ll << 31) && T < (1ll << 31) && H < (1ll << 31) && W < (1ll << 31) &&
+                   (double)B * (double)T * (double)H * (double)W < 2147483648.0,
+               "forecast_render: bad shape (B, T, H, W >= 1, B*T*H*W < 2^31), got %lld %lld %lld %lld", (long long)B, (long long)T, (long long)H, (long long)W);
+  ADNM_REQUIRE(frame_start >= 0 && frame_start < T, "forecast_render: frame_start %lld outside the %lld frames", (long long)frame_start, (long long)T);
+  ADNM_REQUIRE(frame_step >= 1 && frame_step < (1ll << 31), "forecast_render: frame_step must be >= 1, got %lld", (long long)frame_step);
+  ADNM_REQUIRE(gap >= 0 && gap < (1ll << 24), "forecast_render: gap must be in [0, 2^24), got %lld", (long long)gap);
+  const int64_t nsel = adnm_cdiv(T - frame_start, frame_step);
+  const int64_t strip_w = nsel * W + (nsel - 1) * gap;
+  ADNM_REQUIRE((uintptr_t)pred % 4 == 0, "forecast_render: pred must be 4-byte aligned");
+  if (strip) {   // a fields-only call is not held to the strip's limits
+    ADNM_REQUIRE(strip_w < (1ll << 24), "forecast_render: the strip would be %lld pixels wide (limit 2^24)", (long long)strip_w);
+    ADNM_REQUIRE((uintptr_t)strip % 4 == 0, "forecast_render: strip must be 4-byte aligned");
+  }
+  RenderTab tab;
+  tab.n = (int)nbins;
+  for (int k = 0; k <= kMaxBins; ++k) tab.bounds[k] = k <= nbins ? bounds_host[k] : 0.f;
+  for (int k = 0; k < kMaxBins; ++k) {
+    const uint8_t* c = palette_host + 4 * (k < nbins ? k : 0);
+    tab.rgba[k] = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24);
+  }
+  const int Q = (int)adnm_cdiv(W, 4);
+  const int64_t lanes = B * T * H * Q;
+  const bool vec = W % 4 == 0 && (uintptr_t)pred % 16 == 0 && (uintptr_t)fields % 4 == 0;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ADNM_PROF("forecast_render", st, (double)B * T * H * W * (4.0 + (fields ? 1.0 : 0.0)) + (strip ? 4.0 * B * H * strip_w : 0.0));
+    const unsigned blocks = (unsigned)adnm_cdiv(lanes, kBlock);
+    if (vec)
+      forecast_render_kernel<true><<<blocks, kBlock, 0, st>>>(pred, fields, (uint32_t*)strip, tab, pixel_scale, lanes, (int)T, (int)H, (int)W, Q, (int)frame_start,
+                                                              (int)frame_step, (int)nsel, (int)gap, strip_w);
+    else
+      forecast_render_kernel<false><<<blocks, kBlock, 0, st>>>(pred, fields, (uint32_t*)strip, tab, pixel_scale, lanes, (int)T, (int)H, (int)W, Q, (int)frame_start,
+                                                               (int)frame_step, (int)nsel, (int)gap, strip_w);
+  }
+  ADNM_CHECK_LAUNCH("forecast_render");
   return ADNM_OK;
 }

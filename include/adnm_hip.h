@@ -605,6 +605,30 @@ int64_t adnm_valid_ssim_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int
 int adnm_valid_ssim_accum(const float* pred, const float* target, void* block, int64_t nthr, float value_scale, void* ws, int64_t ws_bytes,
                           int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
 
+/* The output side (pic_results.py:104-184 of the reference): a forecast as the bytes a consumer keeps, in ONE launch.
+ * adnm_forecast_render: pred contiguous fp32 (B, T, H, W), 4-byte aligned.  fields: (B, T, H, W) uint8 or NULL.  strip: (B, H, Ws, 4) uint8
+ *   (RGBA, 4-byte aligned) or NULL, Ws = n*W + (n-1)*gap, holding the n = ceil((T - frame_start) / frame_step) frames frame_start,
+ *   frame_start + frame_step, ... side by side along the width with `gap` pixels 255,255,255,255 between neighbours and none at the ends.
+ *   At least one of fields / strip.  bounds_host: nbins + 1 finite, strictly ascending floats; palette_host: nbins x 4 bytes (R, G, B, A);
+ *   both in HOST memory, read at call time and passed by value as kernel arguments (nothing to keep alive; the call can be captured).
+ * Value rule, per pixel p:
+ *   pixel_scale > 0:  b = (uint8) trunc(clamp(p * pixel_scale, 0, 255)), the product formed in fp32 on its own (not contracted into
+ *       anything else); NaN gives 0.  fields receives b; the binned value is v = (float) b.  Inside [0, 256) this is numpy's
+ *       (seq * pixel_scale).astype(np.uint8); numpy's cast of a float outside the range is undefined, so the clamp is THIS project's
+ *       definition there (negative, -Inf, NaN -> 0; above 255, +Inf -> 255).
+ *   pixel_scale == 0: the binned value is v = p itself; fields receives the bin index; a NaN pixel renders 0,0,0,0 (matplotlib's "bad"
+ *       colour) and its fields byte is 0.
+ *   bin index = clamp(#{k : bounds[k] <= v} - 1, 0, nbins - 1) (BoundaryNorm + ListedColormap: below the first edge the first colour, at
+ *       or above the last edge the last); strip receives palette[index].  The comparison is made in fp32 AGAINST THE EDGES AS GIVEN:
+ *       matplotlib compares the fp32 value with double edges, so a caller holding double edges passes each one rounded UP to the
+ *       smallest float >= it (an edge rounded down would admit the value equal to that float, which the double edge rejects).
+ * Limits: 1 <= nbins <= 32, B*T*H*W < 2^31, 0 <= frame_start < T, frame_step >= 1, 0 <= gap < 2^24, pixel_scale finite >= 0; with a strip
+ *   (not for a fields-only call) Ws < 2^24 and strip 4-byte aligned.
+ *   Anything else is refused before any launch. */
+int adnm_forecast_render(const float* pred, uint8_t* fields, uint8_t* strip, const float* bounds_host, const uint8_t* palette_host,
+                         int64_t nbins, float pixel_scale, int64_t B, int64_t T, int64_t H, int64_t W, int64_t frame_start,
+                         int64_t frame_step, int64_t gap, adnm_stream_t stream);
+
 /* ---------------------------------------------------------------- stand-alone activations
  * act_fwd / act_bwd: y = act(x), dpre = dy * act'(pre) over flat fp32 arrays (n % 4 == 0), act in {ADNM_ACT_SILU, ADNM_ACT_GELU}: nn.GELU
  *   between Mlp.fc1 and fc2 (model_untils.py:52-70) and the backward of the GELUs fused into GEMM / conv epilogues.
