@@ -19,82 +19,116 @@ import torch
 from . import lib, ops
 
 
+class ForwardClient:
+    """What a GraphedForward hands its per-shape entry `ent` (a dict) to.  Every method here is a no-op or the identity; a client keeps
+    whatever belongs to one input shape IN `ent`, which lives and dies with that shape's graph."""
+
+    def open(self, ent, x):
+        """Once per input shape, outside any capture: allocate what this shape's graph will point into, into `ent`, and launch eagerly
+        once every kernel after() will launch (a kernel's first launch must not be captured)."""
+
+    def model_input(self, ent, sx):
+        """-> the model's input, made from the static input `sx`.  Runs in both warm-up forwards and inside the capture."""
+        return sx
+
+    def check(self, ent, out):
+        """Once per input shape, on the second warm-up forward's output, BEFORE the capture begins: may raise, may allocate into `ent`."""
+
+    def after(self, ent, sx, out):
+        """Inside the capture only, behind the forward (out: the graph's static output)."""
+
+
 class GraphedForward:
     """model.eval() forward under no_grad, captured once per input shape and replayed (validate.py:101-104).  The graph of a model whose
     parameters a FlatTrainer holds reads the trainer's narrow weight shadow (ops.ShadowSet) through baked-in pointers: every call first
     rewrites the shadows it captured against if a parameter was written since (a checkpoint load, an in-place op), and the graph keeps
-    them alive, so it may outlive the trainer.  close() (or __del__) gives the graphs back."""
+    them alive, so it may outlive the trainer.  close() (or __del__) gives the graphs back.
 
-    def __init__(self, model, head=None, tail=None, source=None, probe=None):
-        """head(sx) / tail(sx, out): optional extra bodies captured into the same graph right before / after the forward (sx: the
-        graph's static input, out: its static output) — adnm_hip.validate.Validator's loss and metrics pass.  They run ONLY inside the
-        capture, never in the warm-up forwards: whatever they launch must have run once before.  Without them nothing changes.
-        source(sx) -> the model's input, made from the static input into a tensor the caller owns (adnm_hip.forecast.Forecaster: raw
-        radar bytes through adnm_radar_ingest).  It runs in the warm-up forwards too and is captured between head and the forward;
-        None: the static input is the model's input.
-        probe(out): called once per input shape on a warm-up forward's output, BEFORE the capture begins: where the owner of a
-        tail checks the output (and may raise outside the capture) and allocates what the tail writes."""
-        self.model = model
-        self._head, self._tail, self._source, self._probe = head, tail, source, probe
+    Per (shape, dtype, device) there is ONE entry: the graph, its static input "sx" and output "out", its split-K scope, shadows and
+    fp8 pin, and whatever the client (ForwardClient) put there.  fwd(x) is fwd.replay(fwd.entry(x), x)["out"]; a client that fills static
+    buffers of its own does so between the two.  An entry whose open, warm-up, check or capture raised is not kept.
+    keep_quant: in fp8, while a record's flag is set the GEMMs of ANY forward collect max |activation| into the delayed-scaling table.
+    An evaluation forward must not move the training run's next scales: the graph saves the table in front of the forward and puts it
+    back behind it, and the first call of a shape (its eager warm-up forwards collect too) runs between a snapshot and its restore."""
+
+    def __init__(self, model, client=None, keep_quant=False):
+        self.model, self.client, self.keep_quant = model, ForwardClient() if client is None else client, keep_quant
         self._graphs = {}
 
-    def _forward(self, sx):
-        return self.model(sx if self._source is None else self._source(sx))
-
-    def _body(self, sx):
-        if self._head is not None:
-            self._head(sx)
-        out = self._forward(sx)
-        if self._tail is not None:
-            self._tail(sx, out)
-        return out
-
-    @torch.no_grad()
-    def __call__(self, x):
+    def entry(self, x):
+        """-> the entry of x's (shape, dtype, device), made on first sight (the static input, the client's open()); not captured yet"""
         key = (tuple(x.shape), x.dtype, x.device)
         ent = self._graphs.get(key)
         if ent is None:
+            fp8 = self.keep_quant and ops.mfma_precision() == "fp8"
+            ent = {"key": key, "graph": None, "sx": x.detach().clone(), "pin": None, "qsave": torch.empty_like(ops.QUANT.table(x.device)) if fp8 else None}
+            self.client.open(ent, x)
+            self._graphs[key] = ent
+        return ent
+
+    def _body(self, ent):
+        sx, qsave = ent["sx"], ent["qsave"]
+        if qsave is not None:
+            qsave.copy_(ops.QUANT.table(sx.device))
+        out = self.model(self.client.model_input(ent, sx))
+        if qsave is not None:
+            ops.QUANT.table(sx.device).copy_(qsave)
+        self.client.after(ent, sx, out)
+        return out
+
+    def _capture(self, ent):
+        sx, was_training = ent["sx"], self.model.training
+        try:
             ptrs = [p.data_ptr() for p in self.model.parameters()]
-            shadows = [s for s in ops.SHADOWS.sets(x.device) if any(s.lo <= q < s.hi for q in ptrs)]
-            for s in shadows:   # (the capture cannot rewrite a stale one)
+            ent["shadows"] = [s for s in ops.SHADOWS.sets(sx.device) if any(s.lo <= q < s.hi for q in ptrs)]
+            for s in ent["shadows"]:   # (the capture cannot rewrite a stale one)
                 s.ensure_current()
-            was_training = self.model.training
             self.model.eval()
-            sx = x.clone()
-            if self._probe is None:
-                ops.warm_up(lambda: self._forward(sx), 2)
-            else:
-                try:
-                    ops.warm_up(lambda: self._forward(sx), 1)
-                    warm = []
-                    ops.warm_up(lambda: warm.append(self._forward(sx)), 1)
-                    self._probe(warm.pop())
-                except BaseException:
-                    self.model.train(was_training)
-                    raise
+            warm = [None]
+
+            def forward():
+                warm[0] = self.model(self.client.model_input(ent, sx))
+            ops.warm_up(forward, 2)
+            self.client.check(ent, warm.pop())
             g = torch.cuda.CUDAGraph()
             # the graph's split GEMM launches get their own uncached workspace (kept with the graph: a training graph replayed on
             # another stream beside this one must not share it); fp8: the quantisation table's rows stay put while the graph lives
-            scope = ops.SPLITWS.open_scope(x.device)
-            pin = ops.QUANT.pinned(x.device) if ops.mfma_precision() == "fp8" else None
+            ent["scope"] = ops.SPLITWS.open_scope(sx.device)
+            ent["pin"] = ops.QUANT.pinned(sx.device) if ops.mfma_precision() == "fp8" else None
+            ent["out"] = ops.capture(g, lambda: self._body(ent), ent["scope"])
+        except BaseException:
+            self._graphs.pop(ent["key"], None)
+            if ent["pin"] is not None:
+                ent["pin"].release()
+            raise
+        finally:
+            self.model.train(was_training)
+        ent["graph"] = g
+
+    @torch.no_grad()
+    def replay(self, ent, x):
+        """x into the entry's static input and one replay of its graph, captured first if there is none yet.  -> ent"""
+        if ent["graph"] is None:
+            snap = ops.QUANT.snapshot(x.device) if ent["qsave"] is not None else None
             try:
-                out = ops.capture(g, lambda: self._body(sx), scope)
-            except BaseException:
-                if pin is not None:
-                    pin.release()
-                raise
+                self._capture(ent)
+                return self.replay(ent, x)
             finally:
-                self.model.train(was_training)
-            ent = self._graphs[key] = {"graph": g, "sx": sx, "out": out, "scope": scope, "shadows": shadows, "pin": pin}
+                if snap is not None:
+                    ops.QUANT.restore(x.device, snap)
         for s in ent["shadows"]:
             s.ensure_current()
         ent["sx"].copy_(x, non_blocking=True)
         ent["graph"].replay()
-        return ent["out"]
+        return ent
+
+    def __call__(self, x):
+        return self.replay(self.entry(x), x)["out"]
 
     def close(self):
-        """Give the captured graphs back now: the graphs first, then what their launches point into (static tensors, split-K
-        workspaces, the weight shadows), then the pins on the fp8 quantisation table.  Idempotent; __del__ calls it."""
+        """Give the captured graphs back now: the graphs first, then what their launches point into (the entries: static tensors, the
+        client's buffers, split-K workspaces, the weight shadows), then the pins on the fp8 quantisation table.  Idempotent; __del__
+        calls it."""
         graphs, self._graphs = self._graphs, {}
         pins = [ent["pin"] for ent in graphs.values() if ent["pin"] is not None]
         for ent in graphs.values():
@@ -108,6 +142,21 @@ class GraphedForward:
             self.close()
         except Exception:
             pass
+
+
+def contingency_metrics(sums, thresholds):
+    """sums: the TP, FN, FP, TN counts per threshold, summed over everything evaluated (4 * nthr integers in doubles) -> (the
+    threshold_metrics dictionary, the FAR of every threshold), as SimplifiedEvaluator.done states them (Shanghai_metrics.py:218-290)."""
+    metrics, all_far = {}, []
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for k, thr in enumerate(thresholds):
+            TP, FN, FP, TN = sums[4 * k:4 * k + 4]
+            csi, pod = TP / (TP + FP + FN), TP / (TP + FN)
+            hss = (2 * (TP * TN - FP * FN)) / (FP ** 2 + FN ** 2 + 2 * TP * TN + (FP + FN) * (TP + TN))
+            all_far.append(FP / (TP + FP))
+            key = int(thr) if float(thr).is_integer() else thr
+            metrics[key] = {"TP": TP, "TN": TN, "FP": FP, "FN": FN, "CSI": csi, "POD": pod, "HSS": hss}
+    return metrics, all_far
 
 
 class GpuEvaluator:
@@ -156,16 +205,8 @@ class GpuEvaluator:
         counts = np.concatenate([t[..., :4 * nthr] for t, _ in tabs], axis=0)   # (samples, T, 4*nthr)
         mse = np.concatenate([t[..., 4 * nthr + 1] / hw for t, hw in tabs], axis=0)   # (samples, T)
         mae = np.concatenate([t[..., 4 * nthr] / hw for t, hw in tabs], axis=0)
-        metrics, all_far = {}, []
-        with np.errstate(divide="ignore", invalid="ignore"):
-            for k, thr in enumerate(self.thresholds):
-                TP, FN, FP, TN = (counts[..., 4 * k + i].sum() for i in range(4))
-                csi, pod = TP / (TP + FP + FN), TP / (TP + FN)
-                hss = (2 * (TP * TN - FP * FN)) / (FP ** 2 + FN ** 2 + 2 * TP * TN + (FP + FN) * (TP + TN))
-                all_far.append(FP / (TP + FP))
-                key = int(thr) if float(thr).is_integer() else thr
-                metrics[key] = {"TP": TP, "TN": TN, "FP": FP, "FN": FN, "CSI": csi, "POD": pod, "HSS": hss}
-            rmse = float(np.mean(np.sqrt(np.mean(mse, axis=0))))
+        metrics, all_far = contingency_metrics(counts.sum(axis=(0, 1)), self.thresholds)
+        rmse = float(np.mean(np.sqrt(np.mean(mse, axis=0))))
         return {"threshold_metrics": metrics, "FAR": float(np.mean(all_far)), "RMSE": rmse, "MAE": float(mae.mean()), "MSE": float(mse.mean()),
                 "SSIM": (float(np.mean(np.concatenate([s.double().cpu().numpy() / area for s, area in self._ssim], axis=0)))
                          if self._ssim and all(s is not None for s, _ in self._ssim) else None),

@@ -8,8 +8,8 @@ copies every prediction to numpy as floats and colours it frame by frame with ma
     fc.save(out_dir, res, "ADNMUnet", batch=cnt)                  # {batch}-{i+1}/ADNMUnet.png, as pic_results.py:263-271 lays them out
     fc.save(out_dir, fc.render(targets), "gt", batch=cnt)         # the gt.png row: the same palette on any other (B, T, ...) tensor
 
-A call is GraphedForward's captured graph with csrc/dataio.hip::forecast_render as the body behind the forward (one launch: the
-quantised fields, the frame selection, the colour lookup, the gaps) and, for raw bytes, adnm_radar_ingest as the body in front of it.
+A call is GraphedForward's captured graph with csrc/dataio.hip::forecast_render behind the forward (ForwardClient.after; one launch: the
+quantised fields, the frame selection, the colour lookup, the gaps) and, for raw bytes, adnm_radar_ingest in front of it (model_input).
 What leaves the device is 1 + 4 n / T bytes per pixel (n of T frames selected) instead of 4, and the host does no per-frame work.
 
 The value rule is stated in include/adnm_hip.h (adnm_forecast_render); inside the uint8 range it is pic_results.py's, byte for byte
@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import lib, ops
-from .evaluator import GraphedForward
+from .evaluator import ForwardClient, GraphedForward
 
 MAX_BINS = 32
 
@@ -116,7 +116,7 @@ class Forecast:
         self.pred, self.fields, self.strip = pred, fields, strip
 
 
-class Forecaster:
+class Forecaster(ForwardClient):
     def __init__(self, model, palette, pixel_scale=90.0, size=None, in_frames=5, frame_start=0, frame_step=1, gap=10):
         """pixel_scale: pic_results.py's PIXEL_SCALE; None or 0 bins the float itself (the LAPS form).  size: the model's input edge,
         needed for raw uint8 input only.  frame_start / frame_step: the frames of the strip (even_index_only=True is 1, 2)."""
@@ -129,51 +129,42 @@ class Forecaster:
         if not (self.pixel_scale >= 0.0 and np.isfinite(self.pixel_scale)) or self.frame_start < 0 or self.frame_step < 1 or self.gap < 0:
             raise ValueError("Forecaster: pixel_scale >= 0, frame_start >= 0, frame_step >= 1, gap >= 0")
         self.out_frames = None              # T of the model's output, known after the first call
-        self._fwd = GraphedForward(model, head=self._head, tail=self._tail, source=self._source, probe=self._probe)
-        self._static, self._cur, self._warm = {}, None, set()
+        self._fwd = GraphedForward(model, client=self, keep_quant=True)
+        self._warm = set()                  # the devices the render kernel has run on
 
-    # ---- the bodies captured around the forward (GraphedForward)
-    def _head(self, sx):
-        st = self._cur
-        if st["qsave"] is not None:
-            # fp8: a forecast beside a training run must not move the delayed-scaling table (Validator._head)
-            st["qsave"].copy_(ops.QUANT.table(sx.device))
+    # ---- ForwardClient: what GraphedForward calls with the entry of one input shape
+    def open(self, ent, x):
+        """both variants of the render kernel run once before a capture launches them (a kernel's first launch must not be captured);
+        raw bytes: the fp32 tensor adnm_radar_ingest fills for the model"""
+        if x.device not in self._warm:
+            for w in (4, 1):
+                ops.forecast_render_tables(torch.zeros((1, 1, 1, w), dtype=torch.float32, device=x.device), self.palette._c, self.pixel_scale, gap=0)
+            self._warm.add(x.device)
+        raw = x.dtype == torch.uint8
+        ent["xin"] = torch.empty((x.shape[0], x.shape[1], 1, self.size, self.size), dtype=torch.float32, device=x.device) if raw else None
 
-    def _source(self, sx):
-        st = self._cur
-        if st["xin"] is None:
+    def model_input(self, ent, sx):
+        if ent["xin"] is None:
             return sx
         B, T, H0, W0 = sx.shape
-        lib.call("adnm_radar_ingest", sx.data_ptr(), st["xin"].data_ptr(), B * T, H0, W0, self.size, 1.0 / 255.0, torch.cuda.current_stream().cuda_stream)
-        return st["xin"]
+        lib.call("adnm_radar_ingest", sx.data_ptr(), ent["xin"].data_ptr(), B * T, H0, W0, self.size, 1.0 / 255.0, torch.cuda.current_stream().cuda_stream)
+        return ent["xin"]
 
-    def _probe(self, out):
-        """on a warm-up forward's output, before the capture: the checks that may raise, and the buffers the tail writes"""
-        st = self._cur
+    def check(self, ent, out):
+        """the checks that may raise, and the buffers after() writes"""
         if out.dtype != torch.float32 or out.dim() not in (4, 5) or (out.dim() == 5 and out.shape[2] != 1):
             raise RuntimeError(f"Forecaster: the model's output must be fp32 (B, T, H, W) or (B, T, 1, H, W), got {out.dtype} {tuple(out.shape)}")
         B, T, H, W = out.shape[0], out.shape[1], out.shape[-2], out.shape[-1]
         if self.frame_start >= T:
             raise RuntimeError(f"Forecaster: frame_start {self.frame_start} outside the model's {T} output frames")
-        st["fields"] = torch.empty((B, T, H, W), dtype=torch.uint8, device=out.device)
-        st["strip"] = torch.empty((B, H, ops.strip_width(T, W, self.frame_start, self.frame_step, self.gap), 4), dtype=torch.uint8, device=out.device)
+        ent["fields"] = torch.empty((B, T, H, W), dtype=torch.uint8, device=out.device)
+        ent["strip"] = torch.empty((B, H, ops.strip_width(T, W, self.frame_start, self.frame_step, self.gap), 4), dtype=torch.uint8, device=out.device)
 
-    def _tail(self, sx, out):
-        st = self._cur
-        if st["qsave"] is not None:
-            ops.QUANT.table(sx.device).copy_(st["qsave"])
-        pred = (out.squeeze(2) if out.dim() == 5 else out).contiguous()   # (a copy made here belongs to the graph's pool and is kept with it)
-        ops.forecast_render_into(pred, st["fields"], st["strip"], self.palette._c, self.pixel_scale, self.frame_start, self.frame_step, self.gap)
-        st["keep"] = pred
-        st["res"] = Forecast(out, st["fields"], st["strip"])
-
-    def _warm_up(self, device):
-        """both variants of the render kernel run once before a capture launches them (a kernel's first launch must not be captured)"""
-        if device in self._warm:
-            return
-        for w in (4, 1):
-            ops.forecast_render_tables(torch.zeros((1, 1, 1, w), dtype=torch.float32, device=device), self.palette._c, self.pixel_scale, gap=0)
-        self._warm.add(device)
+    def after(self, ent, sx, out):
+        ent["keep"] = pred = (out.squeeze(2) if out.dim() == 5 else out).contiguous()   # (a copy made here belongs to the graph's pool and is kept with it)
+        ops.forecast_render_into(pred, ent["fields"], ent["strip"], self.palette._c, self.pixel_scale, self.frame_start, self.frame_step, self.gap)
+        ent["res"] = Forecast(out, ent["fields"], ent["strip"])
+        self.out_frames = out.shape[1]
 
     # ---- the public surface
     @torch.no_grad()
@@ -183,8 +174,7 @@ class Forecaster:
         shape, valid until the next call with that shape (copy what has to last)."""
         if not (torch.is_tensor(x) and x.is_cuda):
             raise RuntimeError("Forecaster runs on GPU tensors only (there is no CPU path here)")
-        raw = x.dtype == torch.uint8
-        if raw:
+        if x.dtype == torch.uint8:
             if x.dim() != 4:
                 raise RuntimeError(f"Forecaster: raw input must be uint8 (B, T_in, H0, W0), got {tuple(x.shape)}")
             if self.size is None:
@@ -193,27 +183,8 @@ class Forecaster:
             raise RuntimeError(f"Forecaster: input must be fp32 (B, T_in, 1, S, S) or raw uint8 (B, T_in, H0, W0), got {x.dtype} {tuple(x.shape)}")
         if x.shape[1] != self.in_frames:
             raise RuntimeError(f"Forecaster: the input has {x.shape[1]} frames per sample, in_frames is {self.in_frames}")
-        key = (tuple(x.shape), x.dtype, x.device)
-        st = self._static.get(key)
-        first, snap = st is None, None
-        if first:
-            self._warm_up(x.device)
-            fp8 = ops.mfma_precision() == "fp8"
-            st = {"xin": torch.empty((x.shape[0], x.shape[1], 1, self.size, self.size), dtype=torch.float32, device=x.device) if raw else None,
-                  "qsave": torch.empty_like(ops.QUANT.table(x.device)) if fp8 else None, "res": None}
-            if fp8:   # the eager warm-up forwards of the capture collect too
-                snap = ops.QUANT.snapshot(x.device)
-        self._cur = st
-        try:
-            self._fwd(x.contiguous())
-        finally:
-            self._cur = None
-            if snap is not None:
-                ops.QUANT.restore(x.device, snap)
-        if first:
-            self._static[key] = st
-            self.out_frames = st["res"].fields.shape[1]
-        return st["res"]
+        x = x.contiguous()
+        return self._fwd.replay(self._fwd.entry(x), x)["res"]
 
     def render(self, t, frame_start=None, frame_step=None):
         """The same palette, pixel_scale and gap on any other (B, T, H, W) / (B, T, 1, H, W) fp32 GPU tensor -> a Forecast whose .pred is
@@ -244,7 +215,6 @@ class Forecaster:
     def close(self):
         """Give the captured graphs and their static buffers back (GraphedForward.close).  Idempotent; __del__ calls it."""
         self._fwd.close()
-        self._static = {}
 
     def __del__(self):
         try:

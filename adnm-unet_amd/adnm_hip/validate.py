@@ -7,7 +7,7 @@ loss per batch, the metrics, then the best-checkpoint rule and the early stop).
     res = val.done(reset=True)    # the one synchronising read of the epoch
     decision = selection.update(epoch, res["loss_sum"])      # ReferenceSelection (adnm_hip.schedule)
 
-A step is GraphedForward's captured graph with a second body behind the forward: csrc/dataio.hip::valid_accum (the enRainfallLoss
+A step is GraphedForward's captured graph with a second body behind the forward (ForwardClient.after): csrc/dataio.hip::valid_accum (the enRainfallLoss
 value of the batch — no gradient tensor — and SimplifiedEvaluator's contingency counts and error sums, one pass over prediction and
 target) and valid_ssim_accum, both ADDING into one block of doubles that lives on the device for the epoch (layout:
 include/adnm_hip.h, adnm_valid_accum).  done() reads that block — summed over the ranks of `process_group` with one all-reduce —
@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import lib, ops
-from .evaluator import GraphedForward
+from .evaluator import ForwardClient, GraphedForward, contingency_metrics
 
 HEADER = 4   # doubles in front of the table: loss_sum, batches, samples, nonfinite_batches
 
@@ -46,15 +46,8 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area):
     blk = np.asarray(block, dtype=np.float64)
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
     tab = blk[HEADER:].reshape(T, 4 * nthr + 3)
-    metrics, all_far = {}, []
+    metrics, all_far = contingency_metrics(tab[:, :4 * nthr].sum(axis=0), thresholds)
     with np.errstate(divide="ignore", invalid="ignore"):
-        for k, thr in enumerate(thresholds):
-            TP, FN, FP, TN = (tab[:, 4 * k + i].sum() for i in range(4))
-            csi, pod = TP / (TP + FP + FN), TP / (TP + FN)
-            hss = (2 * (TP * TN - FP * FN)) / (FP ** 2 + FN ** 2 + 2 * TP * TN + (FP + FN) * (TP + TN))
-            all_far.append(FP / (TP + FP))
-            key = int(thr) if float(thr).is_integer() else thr
-            metrics[key] = {"TP": TP, "TN": TN, "FP": FP, "FN": FN, "CSI": csi, "POD": pod, "HSS": hss}
         mse_t = tab[:, 4 * nthr + 1] / (hw * samples)            # per frame index: the mean over the samples of the frame's MSE
         rmse = float(np.mean(np.sqrt(mse_t)))
         mae = float(tab[:, 4 * nthr].sum() / (hw * samples * T))
@@ -65,7 +58,7 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area):
             "samples": int(samples), "nonfinite": int(nonfinite)}
 
 
-class Validator:
+class Validator(ForwardClient):
     def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
@@ -79,9 +72,8 @@ class Validator:
             raise ValueError("seq_len >= 1")
         self.ssim, self.process_group = bool(ssim), process_group
         self._thr = (ctypes.c_float * len(self.thresholds))(*self.thresholds)
-        self._fwd = GraphedForward(model, head=self._head, tail=self._tail)
+        self._fwd = GraphedForward(model, client=self, keep_quant=True)
         self._block = self._last = None    # the epoch's accumulator block and the last batch's fp32 loss: they outlive the graphs
-        self._static, self._cur = {}, None
         self._frame = None                  # (H, W) of the epoch
 
     # ---- device state
@@ -94,19 +86,20 @@ class Validator:
             raise RuntimeError(f"Validator: one device per Validator (the block is on {self._block.device}, the batch on {device})")
         return self._block
 
-    def _launch(self, st, pred, block, loss_out):
-        B, T, H, W = st["shape"]
+    def _launch(self, ent, pred, block, loss_out):
+        B, T, H, W = ent["shape"]
         nthr, stream = len(self.thresholds), torch.cuda.current_stream().cuda_stream
-        lib.call("adnm_valid_accum", pred.data_ptr(), st["tgt"].data_ptr(), block.data_ptr(), loss_out.data_ptr(), self._thr, nthr, self.value_scale,
-                 st["loss"][0], st["loss"][1], st["loss"][2], st["ws"].data_ptr(), st["ws"].numel(), B * T, T, H * W, stream)
-        if st["ws_ssim"] is not None:
-            lib.call("adnm_valid_ssim_accum", pred.data_ptr(), st["tgt"].data_ptr(), block.data_ptr(), nthr, self.value_scale, st["ws_ssim"].data_ptr(),
-                     st["ws_ssim"].numel(), B * T, T, H, W, stream)
+        lib.call("adnm_valid_accum", pred.data_ptr(), ent["tgt"].data_ptr(), block.data_ptr(), loss_out.data_ptr(), self._thr, nthr, self.value_scale,
+                 ent["loss"][0], ent["loss"][1], ent["loss"][2], ent["ws"].data_ptr(), ent["ws"].numel(), B * T, T, H * W, stream)
+        if ent["ws_ssim"] is not None:
+            lib.call("adnm_valid_ssim_accum", pred.data_ptr(), ent["tgt"].data_ptr(), block.data_ptr(), nthr, self.value_scale, ent["ws_ssim"].data_ptr(),
+                     ent["ws_ssim"].numel(), B * T, T, H, W, stream)
 
-    def _make_static(self, x, shape):
-        """what the graph of one input shape points into: the static target, the two workspaces, in fp8 the table's save area; and one
-        eager run of the two entry points on a scratch block (a kernel's first launch must not happen inside a capture)"""
-        B, T, H, W = shape
+    # ---- ForwardClient: what GraphedForward calls with the entry of one input shape
+    def open(self, ent, x):
+        """what the graph of one input shape points into: the static target and the two workspaces; and one eager run of the two entry
+        points on a scratch block (a kernel's first launch must not happen inside a capture)"""
+        B, T, H, W = shape = (x.shape[0], self.seq_len) + self._frame
         dev, nthr = x.device, len(self.thresholds)
         nb = lib.query("adnm_valid_accum_ws_bytes", B * T, T, H * W, nthr)
         if nb < 0:
@@ -114,31 +107,19 @@ class Validator:
         ws_ssim = None
         if self.ssim and H > 10 and W > 10:   # 11 x 11 windows need a valid region; smaller frames: SSIM is None
             ws_ssim = torch.empty(max(int(lib.query("adnm_valid_ssim_accum_ws_bytes", B * T, T, H, W, nthr)), 16), dtype=torch.uint8, device=dev)
-        fp8 = ops.mfma_precision() == "fp8"
-        st = {"shape": shape, "tgt": torch.zeros(shape, dtype=torch.float32, device=dev), "ws": torch.empty(max(int(nb), 16), dtype=torch.uint8, device=dev),
-              "ws_ssim": ws_ssim, "loss": (float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)),
-              "qsave": torch.empty_like(ops.QUANT.table(dev)) if fp8 else None}
+        ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=torch.empty(max(int(nb), 16), dtype=torch.uint8, device=dev),
+                   ws_ssim=ws_ssim, loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
-        self._launch(st, st["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
-        return st
+        self._launch(ent, ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
 
-    # ---- the bodies captured around the forward (GraphedForward calls them inside its capture only)
-    def _head(self, sx):
-        st = self._cur
-        if st["qsave"] is not None:
-            # fp8: while a record's flag is set the GEMMs of ANY forward collect max |activation| into the delayed-scaling table.  A
-            # validation forward must not move the training run's next scales: the table is put back as it was (tail).
-            st["qsave"].copy_(ops.QUANT.table(sx.device))
-
-    def _tail(self, sx, out):
-        st = self._cur
-        B, T, H, W = st["shape"]
+    def check(self, ent, out):
+        B, T, H, W = ent["shape"]
         if out.dtype != torch.float32 or out.numel() != B * T * H * W or tuple(out.shape[:2]) != (B, T):
-            raise RuntimeError(f"Validator: the model's output {tuple(out.shape)} {out.dtype} does not match the target's (B, T, H, W) = {st['shape']} fp32")
-        if st["qsave"] is not None:
-            ops.QUANT.table(sx.device).copy_(st["qsave"])
-        st["pred"] = out.contiguous()   # (the model emits it contiguous; a copy made here belongs to the graph's pool and is kept with it)
-        self._launch(st, st["pred"], self._block, self._last)
+            raise RuntimeError(f"Validator: the model's output {tuple(out.shape)} {out.dtype} does not match the target's (B, T, H, W) = {ent['shape']} fp32")
+
+    def after(self, ent, sx, out):
+        ent["pred"] = out.contiguous()   # (the model emits it contiguous; a copy made here belongs to the graph's pool and is kept with it)
+        self._launch(ent, ent["pred"], self._block, self._last)
 
     # ---- the public surface
     def step(self, x, tgt):
@@ -158,27 +139,11 @@ class Validator:
         elif self._frame != shape[2:]:
             raise RuntimeError(f"Validator: frames of {shape[2]} x {shape[3]} in an epoch of {self._frame[0]} x {self._frame[1]} frames (done(reset=True) first)")
         self._block_for(x.device)
-        key = (tuple(x.shape), x.dtype, x.device)
-        st = self._static.get(key)
-        first = st is None
-        snap = None
-        if first:
-            st = self._make_static(x, shape)
-            if st["qsave"] is not None:   # the eager warm-up forwards of the capture collect too
-                snap = ops.QUANT.snapshot(x.device)
-        elif st["shape"] != shape:
-            raise RuntimeError(f"Validator: input {tuple(x.shape)} came with a target of {st['shape']} before, now {shape}")
-        st["tgt"].view(tgt.shape).copy_(tgt, non_blocking=True)
-        self._cur = st
-        try:
-            out = self._fwd(x)
-        finally:
-            self._cur = None
-            if snap is not None:
-                ops.QUANT.restore(x.device, snap)
-        if first:
-            self._static[key] = st
-        return out
+        ent = self._fwd.entry(x)
+        if ent["shape"] != shape:
+            raise RuntimeError(f"Validator: input {tuple(x.shape)} came with a target of {ent['shape']} before, now {shape}")
+        ent["tgt"].view(tgt.shape).copy_(tgt, non_blocking=True)
+        return self._fwd.replay(ent, x)["out"]
 
     @property
     def last_loss(self):
@@ -208,7 +173,6 @@ class Validator:
     def close(self):
         """Give the captured graphs and what they point into back (GraphedForward.close); the block and its sums stay.  Idempotent."""
         self._fwd.close()
-        self._static = {}
 
     def __del__(self):
         try:

@@ -244,7 +244,7 @@ def test_forecaster_raw_bytes():
         a = fc(x)                                                             # the fp32-input graph
         pa, fa, sa = a.pred.clone(), a.fields.clone(), a.strip.clone()
         b = fc(raw)                                                           # the uint8-input graph: ingest in front of the forward
-        assert b.fields.data_ptr() != a.fields.data_ptr() and len(fc._static) == 2
+        assert b.fields.data_ptr() != a.fields.data_ptr() and len(fc._fwd._graphs) == 2
         assert torch.equal(b.pred, pa) and torch.equal(b.fields, fa) and torch.equal(b.strip, sa), "raw bytes and ingest() + fp32 differ"
         _expect(b, fc)
         raw2 = (raw // 2).contiguous()
@@ -406,4 +406,6 @@ def test_refusals():
     with pytest.raises(RuntimeError, match="frame_start 7"):
         late(x)
     assert not torch.cuda.is_current_stream_capturing()
+    late.frame_start = 1                                                          # the refused call left nothing behind
+    _expect(late(x), late)
     late.close()

@@ -384,3 +384,21 @@ def test_refusals():
     res = val.done()
     assert res["loss_sum"] == 0.0 and res["MSE"] == 0.0 and res["samples"] == 2 and abs(res["SSIM"] - 1.0) <= 1e-12
     val.close()
+
+    # a model whose output does not match the target: refused on the warm-up forward's output, before any capture
+    class FirstFrames(torch.nn.Module):
+        t = 19
+
+        def forward(self, x):
+            return x[:, :self.t]
+
+    short = FirstFrames()
+    val = Validator(short, RainfallLoss(), 20, 255.0)
+    with pytest.raises(RuntimeError, match="does not match the target"):
+        val.step(x.to(DEV), tgt.to(DEV))
+    assert not torch.cuda.is_current_stream_capturing()
+    assert float(val._block.abs().sum()) == 0.0
+    short.t = 20
+    val.step(x.to(DEV), tgt.to(DEV))
+    assert val.done()["batches"] == 1
+    val.close()

@@ -99,22 +99,36 @@ def test_selection_state_travels_in_a_training_state_file(tmp_path):
     assert back.state_dict() == sel.state_dict() == {"best": 5.0, "bad_epochs": 1, "save_epoch": 34, "early_stop": 3}
 
 
+_fixture = {}
+
+
+def _fixture_block():
+    """-> (the reference's fixture, thresholds, hw, SSIM area, the (T, 4 * nthr + 3) table of a block) built from the oracle's per-frame
+    counts of the reference's own fixture, once"""
+    if not _fixture:
+        import numpy as np
+        import adnm_oracle as O
+        from util import load_npz
+        z = load_npz("evaluator_b3_t5")
+        thr, scale = [20, 30, 35, 40], float(z["value_scale"])
+        counts, mae, mse = O.evaluator_counts(z["truth"], z["pred"], scale, thr)
+        ssim = O.evaluator_ssim(z["truth"], z["pred"], scale)
+        hw, area = 48 * 48, 38 * 38
+        tab = np.zeros((5, 4 * 4 + 3))
+        for k, t in enumerate(thr):
+            tab[:, 4 * k:4 * k + 4] = counts[t].double().sum(0).numpy()     # (B, T, [TP, FN, FP, TN]) summed over the samples
+        tab[:, 16], tab[:, 17], tab[:, 18] = (mae.double() * hw).sum(0).numpy(), (mse.double() * hw).sum(0).numpy(), (ssim.double() * area).sum(0).numpy()
+        tab.setflags(write=False)
+        _fixture["v"] = (z, thr, hw, area, tab)
+    return _fixture["v"]
+
+
 def test_aggregate_of_a_block_built_by_the_oracle_matches_the_reference_fixture():
     """Validator.done()'s host half: per-frame-index sums (what the device block holds) are enough for every score of
     SimplifiedEvaluator.done — the block is built here from the oracle's per-frame counts of the reference's own fixture."""
     import numpy as np
-    import adnm_oracle as O
     from adnm_hip.validate import aggregate
-    from util import load_npz
-    z = load_npz("evaluator_b3_t5")
-    thr, scale = [20, 30, 35, 40], float(z["value_scale"])
-    counts, mae, mse = O.evaluator_counts(z["truth"], z["pred"], scale, thr)
-    ssim = O.evaluator_ssim(z["truth"], z["pred"], scale)
-    hw, area = 48 * 48, 38 * 38
-    tab = np.zeros((5, 4 * 4 + 3))
-    for k, t in enumerate(thr):
-        tab[:, 4 * k:4 * k + 4] = counts[t].double().sum(0).numpy()     # (B, T, [TP, FN, FP, TN]) summed over the samples
-    tab[:, 16], tab[:, 17], tab[:, 18] = (mae.double() * hw).sum(0).numpy(), (mse.double() * hw).sum(0).numpy(), (ssim.double() * area).sum(0).numpy()
+    z, thr, hw, area, tab = _fixture_block()
     res = aggregate(np.concatenate([[1.25, 2, 3, 0], tab.ravel()]), thr, 5, hw, area)
     for t in thr:
         m = res["threshold_metrics"][t]
@@ -127,3 +141,49 @@ def test_aggregate_of_a_block_built_by_the_oracle_matches_the_reference_fixture(
     assert abs(res["MAE"] - float(z["mae"].mean())) <= 1e-5 * float(z["mae"].mean())
     assert (res["loss_sum"], res["loss_mean"], res["batches"], res["samples"], res["nonfinite"]) == (1.25, 0.625, 2, 3, 0)
     assert aggregate(np.concatenate([[0, 0, 3, 0], tab.ravel()]), thr, 5, hw, None)["SSIM"] is None
+
+
+def test_contingency_metrics_is_the_one_statement_both_evaluators_use():
+    """evaluator.contingency_metrics on the counts of the reference's fixture gives what aggregate() gives on the block above, value for
+    value (NaN with NaN), and GpuEvaluator.done() goes through it too: its tables are filled by hand with CPU tensors (done() only
+    reads them)."""
+    import numpy as np
+    import torch
+    from adnm_hip import evaluator
+    from adnm_hip.validate import aggregate
+    z, thr, hw, area, tab = _fixture_block()
+    same = lambda a, b: a == b or (np.isnan(a) and np.isnan(b))
+    sums = tab[:, :16].sum(axis=0)
+    metrics, far = evaluator.contingency_metrics(sums, thr)
+    res = aggregate(np.concatenate([[1.25, 2, 3, 0], tab.ravel()]), thr, 5, hw, area)
+    assert list(metrics) == list(res["threshold_metrics"]) == thr and len(far) == 4
+    for t in thr:
+        assert metrics[t].keys() == res["threshold_metrics"][t].keys()
+        assert all(same(metrics[t][k], res["threshold_metrics"][t][k]) for k in metrics[t]), t
+        for k in ("TP", "TN", "FP", "FN"):
+            assert metrics[t][k] == float(z[f"{k}.{t}"]), (t, k)
+        for k in ("CSI", "POD", "HSS"):
+            assert abs(metrics[t][k] - float(z[f"{k}.{t}"])) <= 1e-9, (t, k)
+    assert same(float(np.mean(far)), res["FAR"]) and abs(res["FAR"] - float(z["FAR"])) <= 1e-9
+    # GpuEvaluator.done(): one (B, T, 4 * nthr + 2) fp32 table per evaluate() call; the same counts spread over two calls
+    ev = evaluator.GpuEvaluator(5, float(z["value_scale"]), thr)
+    a, b = torch.zeros(2, 5, 18), torch.zeros(1, 5, 18)
+    a[1, 2, :16], b[0, 4, :16] = torch.from_numpy(sums - 7.0).float(), 7.0
+    a[..., 17], b[..., 17] = 3.0, 5.0
+    assert torch.equal(a[1, 2, :16].double() + 7.0, torch.from_numpy(sums)), "the fixture's counts are not exact in fp32: nothing is tested"
+    ev._tables, ev._ssim = [(a, hw), (b, hw)], []
+    done = ev.done()
+    assert list(done["threshold_metrics"]) == thr
+    for t in thr:
+        assert all(same(done["threshold_metrics"][t][k], metrics[t][k]) for k in metrics[t]), t
+    assert same(done["FAR"], res["FAR"]) and done["SSIM"] is None
+    # a threshold nothing crosses: 0 / 0 without a warning, and a non-integer key kept as it is
+    m0, f0 = evaluator.contingency_metrics(np.array([0.0, 0.0, 0.0, 10.0]), [2.5])
+    assert list(m0) == [2.5] and np.isnan(m0[2.5]["CSI"]) and np.isnan(m0[2.5]["POD"]) and np.isnan(f0[0]) and m0[2.5]["TN"] == 10.0
+    calls = []
+    real, evaluator.contingency_metrics = evaluator.contingency_metrics, lambda s, th: calls.append(1) or real(s, th)
+    try:
+        ev.done()
+    finally:
+        evaluator.contingency_metrics = real
+    assert calls == [1], "GpuEvaluator.done() does not go through contingency_metrics"
