@@ -1116,6 +1116,21 @@ def k_wt_level(x, B, H, W, C, cx, taps, K, flip=False):
     return sub, tag
 
 
+def k_wt_level_base(x, B, H, W, C, taps, base_wt, base_bias, K, flip=False):
+    """Level 0 of a WTConv2d module and the module's base depthwise conv of the same input in one launch: x (B*H*W, C) fp32 row view ->
+    (sub, tag, ybase); sub, tag as k_wt_level(cx=1), ybase (B*H*W, C) = conv(x, base_wt) + base_bias (flip: the flipped base taps, no bias:
+    the base conv's input gradient) — bitwise what k_dwconv_fwd / k_dwconv_bwd's dx give."""
+    _need_gpu(x)
+    h2, w2 = (H + 1) // 2, (W + 1) // 2
+    sub = torch.empty((B * h2 * w2, 4 * C), dtype=torch.float32, device=x.device)
+    tag = torch.empty_like(sub)
+    ybase = torch.empty((B * H * W, C), dtype=torch.float32, device=x.device)
+    px, ldx = _rows(x)
+    lib.call("adnm_wt_level_base", px, ldx, _f32(taps).data_ptr(), _f32(base_wt).data_ptr(), _p(_f32(base_bias)), sub.data_ptr(), tag.data_ptr(),
+             ybase.data_ptr(), B, H, W, C, K, int(flip), _stream())
+    return sub, tag, ybase
+
+
 def k_haar_idwt(s, ll_add, B, H, W, C, y_add=(), up=()):
     """s: (B*h2*w2, 4C) contiguous (+ ll_add (B*h2*w2, C)) -> (B*H*W, C) [+ up to two contiguous (B*H*W, C) addends].
     up: the sub-band tensors of the next one / two coarser levels — the cascade in one launch; ll_add then belongs to the coarsest."""
@@ -1508,9 +1523,12 @@ class WTConvFn(torch.autograd.Function):
         shapes, subs, tags = [], [], []
         cur, cx, h, w = x2, 1, H, W
         fused = x2.dtype == torch.float32 and K in (3, 5)   # DWT + the level's stencil in one launch (csrc/wtlevel.hip)
+        ybase = None   # the base conv (+ bias): level 0's launch reads x once for both
         for i in range(levels):
             shapes.append((h, w))
-            if fused:
+            if fused and i == 0:
+                sub, tag, ybase = k_wt_level_base(cur, B, h, w, C, level_wt[0], base_wt, base_bias, K)
+            elif fused:
                 sub, tag = k_wt_level(cur, B, h, w, C, cx, level_wt[i], K)
             else:
                 sub = k_haar_dwt(cur, B, h, w, C, cx)  # (B*h2*w2, 4C); its LL band (column c*4) feeds the next level
@@ -1519,8 +1537,11 @@ class WTConvFn(torch.autograd.Function):
             subs.append(sub)
             tags.append(tag)
             cur, cx = sub, 4
-        nxt = k_haar_synthesis(tags, shapes, B, C) if levels else None
-        y = k_dwconv_fwd(x2, base_wt, base_bias, B, H, W, C, K, lib.ACT_NONE, addend=nxt)
+        if ybase is not None:   # the finest synthesis launch adds the base conv: the same two operands as below, one launch fewer
+            y = k_haar_synthesis(tags, shapes, B, C, y_add=(ybase,))
+        else:
+            nxt = k_haar_synthesis(tags, shapes, B, C) if levels else None
+            y = k_dwconv_fwd(x2, base_wt, base_bias, B, H, W, C, K, lib.ACT_NONE, addend=nxt)
         ctx.save_for_backward(x2, base_wt, base_bias, *level_wt, *subs)
         ctx.dims = (B, H, W, C, K, levels, shapes)
         ctx.set_materialize_grads(False)
@@ -1537,16 +1558,21 @@ class WTConvFn(torch.autograd.Function):
             return (dalias if need_dx else None, None, None, None, None, None, *([None] * levels))
         dy2 = dy.reshape(B * H * W, C)
         dy2 = dy2 if dy2.stride(-1) == 1 else dy2.contiguous()
-        dxb, dbase, dbb = k_dwconv_bwd(dy2, x2, base_wt, base_bias, B, H, W, C, K, lib.ACT_NONE, want_bias=base_bias is not None, want_dx=need_dx)
+        fused = need_dx and dy2.dtype == torch.float32 and K in (3, 5)
+        # the base conv: its tap / bias gradients are a leaf; its input gradient comes out of level 0's launch below where there is one
+        dxb, dbase, dbb = k_dwconv_bwd(dy2, x2, base_wt, base_bias, B, H, W, C, K, lib.ACT_NONE, want_bias=base_bias is not None,
+                                       want_dx=need_dx and not (fused and levels))
         # the reconstruction's backward walks down: d(merged_i) = DWT(d r_{i-1}); its LL band is d r_i.  With an input gradient wanted, the
         # same launch also yields d sub_i = conv^T(d merged_i) (the fused level kernel on the flipped taps)
         dtags, dsubs = [], []
         cur, cx = dy2, 1
-        fused = need_dx and dy2.dtype == torch.float32 and K in (3, 5)
         for i in range(levels):
             hh, ww = shapes[i]
             if fused:
-                dm, dsub = k_wt_level(cur, B, hh, ww, C, cx, level_wt[i], K, flip=True)
+                if i == 0:
+                    dm, dsub, dxb = k_wt_level_base(cur, B, hh, ww, C, level_wt[0], base_wt, None, K, flip=True)
+                else:
+                    dm, dsub = k_wt_level(cur, B, hh, ww, C, cx, level_wt[i], K, flip=True)
                 dsubs.append(dsub)
             else:
                 dm = k_haar_dwt(cur, B, hh, ww, C, cx)

@@ -5,9 +5,14 @@ wavelet_scale.i.weight), executed by hand-written HIP kernels on the channels-la
 Reference behaviour (WTConv2d.py:100-153): a `wt_levels`-deep Haar (db1) pyramid; at each level a
 depthwise KxK conv + per-channel scale on the 4C sub-bands of the RAW low-pass of the level above;
 reconstruction from the deepest level, adding the deeper reconstruction to the convolved LL band;
-plus base_scale * base_conv(x).  Here: adnm_haar_dwt / adnm_dwconv_fwd / adnm_haar_idwt through
-adnm_hip.ops.WTConvFn (hand-written backward).  The per-channel scales are folded into the conv taps
-(tiny differentiable parameter ops), so no scale pass over the activations exists.
+plus base_scale * base_conv(x).  Here, through adnm_hip.ops.WTConvFn (hand-written backward), on fp32 tokens:
+level 0's DWT + stencil AND the base conv of the same input in one launch (adnm_wt_level_base: x is read once),
+one launch per coarser level (adnm_wt_level),
+then the synthesis cascade (adnm_haar_idwt), whose finest launch adds the base conv's output.  The backward
+runs the same launches on the flipped taps: level 0's also yields the base conv's input gradient, so of
+adnm_dwconv_bwd only the tap / bias gradient leaf remains.  (bf16 tokens: adnm_haar_dwt / adnm_dwconv_fwd
+per level.)  The per-channel scales are folded into the conv taps (tiny differentiable parameter ops), so no
+scale pass over the activations exists.
 """
 import math
 import torch

@@ -224,6 +224,12 @@ int adnm_haar_dwt(const void* x, int64_t ldx, int64_t cx, void* y, int64_t B, in
  * contiguous fp32, OVERWRITTEN.  flip != 0: flipped taps — one level of the backward pass (dm = DWT(d r), d sub = conv^T(dm)).  K in {3, 5}. */
 int adnm_wt_level(const float* x, int64_t ldx, int64_t cx, const float* taps, float* sub, float* tag, int64_t B, int64_t H, int64_t W,
                   int64_t C, int K, int flip, adnm_stream_t stream);
+/* Level 0 of a WTConv2d module (cx = 1) together with the module's base depthwise KxK conv of the same input, in one launch: sub and tag as
+ * adnm_wt_level; ybase (B,H,W,C) contiguous fp32, OVERWRITTEN, = conv(x, base_taps) + base_bias (base_taps (K*K, C) tap-major fp32, base_bias
+ * (C) or NULL) — or, flip != 0, the correlation with the flipped base taps and no bias (the base conv's input gradient).  Bit for bit what
+ * adnm_dwconv_fwd (no activation, no addend) / the input-gradient launch of adnm_dwconv_bwd write for the same operands. */
+int adnm_wt_level_base(const float* x, int64_t ldx, const float* taps, const float* base_taps, const float* base_bias, float* sub, float* tag,
+                       float* ybase, int64_t B, int64_t H, int64_t W, int64_t C, int K, int flip, adnm_stream_t stream);
 /* y_add1 / y_add2 (optional, (B,H,W,C) like y): added to the result in the same pass — WTConv2d's backward sums its input-gradient
  * paths (pyramid + base conv + the input's other consumer) there instead of in separate adds.
  * up1 / up2 (optional): the sub-band tensors of the next one / two COARSER levels ((B, ceil(h/2), ceil(w/2), 4C) with h, w the sub-band
