@@ -387,7 +387,7 @@ class GradRegistry:
                 if second:
                     self._multi[owner].add(ptr)
         if second:   # autograd is about to ADD this contribution to the first one: both must be complete when it does
-            FOLDS.flush(device, on_main=True)
+            FOLDS.flush(device)
             FOLDS.hold(device)   # ... so the producer of this one must not defer its fold either
         return torch.empty(tuple(shape), dtype=dtype, device=device)
 
@@ -439,7 +439,7 @@ class FoldRegistry:
         something else references is not adopted by autograd's AccumulateGrad but cloned on the spot, i.e. before the fold ran."""
         ent = self._q.get(device.index)
         if ent is not None and ent.pop("hold", False):
-            ent = None   # (a call that is not deferred is not moved to the side stream either: SIDE.submit checks deferring())
+            ent = None
         return _Deferred(ent, keep, self._lock)
 
     def abort(self, device):
@@ -461,26 +461,12 @@ class FoldRegistry:
             with self._lock:
                 ent["keep"].clear()
 
-    def flush(self, device, on_main=False):
-        """Issue the queued leaf launches and folds.  With the side stream on (SideStreams) they go THERE — forked from the current stream's
-        present, joined only at the end of the backward pass — unless the caller reads the results on the current stream right away
-        (on_main: a second claim of a gradient slice); the parameter-prep backward nodes, the other readers, move to the side stream
-        themselves (late())."""
+    def flush(self, device):
+        """Issue the queued leaf launches and folds on the current stream, then let go of the workspaces and operands kept for them."""
         ent = self._q.get(device.index)
         if ent is None:
             return
-        sent = None if on_main else SIDE.live(device)
         with torch.cuda.device(device):
-            if sent is not None:
-                SIDE._launch(sent)   # what was collected for the side stream first, in submission order
-                SIDE.fork(sent)      # everything the queued launches read exists on the current stream by now
-                with torch.cuda.stream(sent["stream"]):
-                    self._issue(ent)
-                with self._lock:     # the workspaces / operands of what now runs beside the main stream: alive until the join
-                    sent["keep"].extend(ent["keep"])
-                    ent["keep"].clear()
-                return
-            SIDE.join(device)   # queued folds (and whoever asked for the flush) read what weight-gradient kernels wrote on the side stream
             self._issue(ent)
         with self._lock:
             ent["keep"].clear()
@@ -491,29 +477,6 @@ class FoldRegistry:
             lib.call("adnm_leafq_flush", ent["lh"], _stream())   # the grouped leaf launches first: the folds read their partials
         if lib.query("adnm_foldq_pending", ent["h"]) > 0:
             lib.call("adnm_foldq_flush", ent["h"], _stream())
-
-    def late(self, device):
-        """with FOLDS.late(dev): <launch a kernel that reads deferred fold results and writes only parameter gradients> — the flush and the
-        body run on the side stream when it is on (the parameter-prep backward nodes), else on the current stream."""
-        return _Late(self, device)
-
-
-class _Late:
-    def __init__(self, reg, device):
-        self.reg, self.device, self.ctx = reg, device, None
-
-    def __enter__(self):
-        self.reg.flush(self.device)
-        sent = SIDE.live(self.device)
-        if sent is not None:
-            self.ctx = torch.cuda.stream(sent["stream"])
-            self.ctx.__enter__()
-            sent["dirty"] = True
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
-        return False
 
 
 class _Active:
@@ -534,9 +497,6 @@ class _Deferred:
     def __init__(self, ent, keep, lock):
         self.ent, self.keep, self.lock = (ent if ent is not None and ent["on"] else None), keep, lock
 
-    def deferring(self):
-        return self.ent is not None
-
     def __enter__(self):
         if self.ent is not None:
             lib.load().adnm_foldq_bind(self.ent["h"])
@@ -550,131 +510,6 @@ class _Deferred:
             lib.load().adnm_leafq_bind(None)
             with self.lock:
                 self.ent["keep"].extend(t for t in self.keep if t is not None)
-        return False
-
-
-class SideStreams:
-    """Weight-gradient kernels off the critical path.  In backward the input-gradient chain (dY -> dX -> the layer below) is one long
-    dependency chain of mostly small grids, while each layer's weight gradient (dW = dY^T X, depthwise / dense conv tap gradients) is
-    a leaf that nothing reads before the optimiser.  A trainer turns this on around its backward pass; the weight-gradient wrappers then
-    SUBMIT their library call instead of making it: calls are collected and, every `batch` of them, launched together on a second HIP
-    stream that forks from the current stream there (one event: every operand of the batch exists by then) and joins it again before
-    anything reads the results: every FOLDS.flush (the second-stage folds read the partials those kernels wrote) and the end of the
-    pass.  Under hipGraph capture the fork / join events become graph edges, i.e. parallel branches of the replayed graph; a fork costs
-    several microseconds on both streams, hence the batching.
-    Operands and workspaces are allocated on the MAIN stream before the fork and kept alive here until the join, so the caching
-    allocator cannot hand their memory to a later main-stream tensor while the side kernel still runs.  The OUTPUTS are never kept (a
-    second reference would make autograd's AccumulateGrad clone a gradient instead of adopting it — on the main stream, before the side
-    kernel ran): they are parameter gradients that stay referenced by autograd, or tap gradients consumed by a parameter-prep node
-    whose first action is FOLDS.flush.
-    Off (the default, plain autograd use): every call is made at once on the current stream."""
-
-    def __init__(self):
-        self._lock = threading.Lock()
-        self._s = {}   # device index -> {"stream", "on", "dirty", "keep", "pending"}
-        self.batch = int(os.environ.get("ADNM_SIDE_BATCH", "16"))
-
-    def active(self, device, on=True):
-        return _SideActive(self, device, on and device.type == "cuda" and os.environ.get("ADNM_SIDE_STREAM", "1") != "0")
-
-    def _ent(self, device):
-        with self._lock:
-            ent = self._s.get(device.index)
-            if ent is None:
-                ent = self._s[device.index] = {"stream": torch.cuda.Stream(device=device), "on": False, "dirty": False, "keep": [], "pending": []}
-        return ent
-
-    def live(self, device):
-        """the device's entry while the side stream is ON (inside a trainer's backward pass), else None"""
-        ent = self._s.get(device.index)
-        return ent if ent is not None and ent["on"] else None
-
-    def keep(self, device, *tensors):
-        """hold tensors a side-stream kernel reads until the join (no-op with the side stream off)"""
-        ent = self.live(device)
-        if ent is not None:
-            with self._lock:
-                for t in tensors:
-                    if isinstance(t, (list, tuple)):
-                        ent["keep"].extend(x for x in t if x is not None)
-                    elif t is not None:
-                        ent["keep"].append(t)
-
-    def fork(self, ent):
-        """the side stream waits for everything enqueued on the current stream so far"""
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(ent["stream"].device))
-        ent["stream"].wait_event(ev)
-        ent["dirty"] = True
-
-    def submit(self, device, keep, deferred, fn):
-        """fn() makes the library call on torch's CURRENT stream (it must read _stream() itself) inside `deferred` (a FOLDS.defer(...)
-        context, created by the caller so that a pending hold is honoured now)."""
-        ent = self._s.get(device.index)
-        if ent is None or not ent["on"] or not deferred.deferring():
-            with deferred:
-                fn()
-            return
-        with self._lock:
-            ent["pending"].append((deferred, fn))
-            ent["keep"].extend(t for t in keep if t is not None)
-            full = len(ent["pending"]) >= self.batch
-        if full:
-            self._launch(ent)
-
-    def _launch(self, ent):
-        with self._lock:
-            todo, ent["pending"] = ent["pending"], []
-        if not todo:
-            return
-        side = ent["stream"]
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(side.device))   # fork: the operands of every collected call exist on the main stream by now
-        side.wait_event(ev)
-        with torch.cuda.stream(side):
-            for deferred, fn in todo:
-                with deferred:
-                    fn()
-        ent["dirty"] = True
-
-    def abort(self, device):
-        """after an exception: forget what was collected (nothing is launched), switch off"""
-        ent = self._s.get(device.index)
-        if ent is None:
-            return
-        with self._lock:
-            ent["on"] = False
-            ent["pending"] = []
-            ent["keep"].clear()
-
-    def join(self, device):
-        """launch what is still collected, then the current stream waits for everything on the side stream"""
-        ent = self._s.get(device.index)
-        if ent is None:
-            return
-        self._launch(ent)
-        if not ent["dirty"]:
-            return
-        ev = torch.cuda.Event()
-        ev.record(ent["stream"])
-        torch.cuda.current_stream(device).wait_event(ev)
-        with self._lock:
-            ent["dirty"] = False
-            ent["keep"].clear()
-
-
-class _SideActive:
-    def __init__(self, reg, device, on):
-        self.reg, self.device, self.on = reg, device, on
-
-    def __enter__(self):
-        if self.on:
-            self.reg._ent(self.device)["on"] = True
-
-    def __exit__(self, *exc):
-        if self.on:
-            self.reg._ent(self.device)["on"] = False
-            self.reg.join(self.device)
         return False
 
 
@@ -942,14 +777,10 @@ FOLDS = FoldRegistry()
 SPLITWS = SplitWorkspaces()
 SHADOWS = ShadowRegistry()
 GRADS = GradRegistry()
-SIDE = SideStreams()
 grad_dst = GRADS.take
 
 
 class _NoDefer:
-    def deferring(self):
-        return False
-
     def __enter__(self):
         return False
 
@@ -1086,11 +917,10 @@ def k_dwconv_bwd(dy, x, wt, bias, B, H, W, C, K, act, dx=None, want_bias=False, 
         lib.call("adnm_dwconv_bwd", pdy, lddy, px, ldx, _p(wt), _p(bias), _p(dpre), pdx, lddx, None, None, ws.data_ptr(),
                  nb, B, H, W, C, K, K, act, int(chan_major), _dt(x), _stream())
     g, ldg = (dpre.data_ptr(), C) if dpre is not None else (pdy, lddy)
-    pdw, pdb, dt_ = _p(dwt), _p(db), _dt(x)
     # taps / bias gradients: parameters, or prep intermediates flushed at the prep node
     # (the operands are kept with the workspace: under a bound leaf queue the launch itself waits for the grouped flush)
-    SIDE.submit(dev, (dy, x, dpre), FOLDS.defer(dev, ws, dy, x, dpre), lambda: lib.call(
-        "adnm_dwconv_wgrad", g, ldg, px, ldx, pdw, pdb, ws.data_ptr(), nb, B, H, W, C, K, K, int(chan_major), dt_, _stream()))
+    with FOLDS.defer(dev, ws, dy, x, dpre):
+        lib.call("adnm_dwconv_wgrad", g, ldg, px, ldx, _p(dwt), _p(db), ws.data_ptr(), nb, B, H, W, C, K, K, int(chan_major), _dt(x), _stream())
     return dx, dwt, db
 
 
@@ -1950,15 +1780,15 @@ class AdnPrepFn(torch.autograd.Function):
         params = ctx.saved_tensors
         dm, di, gn, P = ctx.dims
         cx = di + 2 * gn
-        with FOLDS.late(params[0].device):   # the incoming gradients are (deferred) fold results of the mixer's backward
-            g_w_in, g_taps, g_ln_w, g_ln_b, g_w_out = (g.contiguous() for g in (g_w_in, g_taps, g_ln_w, g_ln_b, g_w_out))
-            gouts = [g_w_in, g_taps[:, di:], g_taps[:, :di], g_ln_w, g_ln_b, g_w_out]
-            dparams = [grad_dst(p.data_ptr(), p.shape, p.device, p.dtype) for p in params]
-            nb = lib.query("adnm_adnprep_bwd_ws_bytes")
-            ws = _ws(nb, params[0].device)
-            with FOLDS.defer(params[0].device, ws, g_w_in, g_taps, g_ln_w, g_ln_b, g_w_out):
-                lib.call("adnm_adnprep_bwd", lib.ptr_table(params), lib.ptr_table(gouts), lib.ptr_table(dparams), dm, di, gn, P, di + cx,
-                         ws.data_ptr(), nb, _stream())
+        FOLDS.flush(params[0].device)   # the incoming gradients are (deferred) fold results of the mixer's backward
+        g_w_in, g_taps, g_ln_w, g_ln_b, g_w_out = (g.contiguous() for g in (g_w_in, g_taps, g_ln_w, g_ln_b, g_w_out))
+        gouts = [g_w_in, g_taps[:, di:], g_taps[:, :di], g_ln_w, g_ln_b, g_w_out]
+        dparams = [grad_dst(p.data_ptr(), p.shape, p.device, p.dtype) for p in params]
+        nb = lib.query("adnm_adnprep_bwd_ws_bytes")
+        ws = _ws(nb, params[0].device)
+        with FOLDS.defer(params[0].device, ws, g_w_in, g_taps, g_ln_w, g_ln_b, g_w_out):
+            lib.call("adnm_adnprep_bwd", lib.ptr_table(params), lib.ptr_table(gouts), lib.ptr_table(dparams), dm, di, gn, P, di + cx,
+                     ws.data_ptr(), nb, _stream())
         return (None, None, None, None, *dparams)
 
 
@@ -1990,16 +1820,15 @@ class WtPrepFn(torch.autograd.Function):
         n = 1 + levels
         saved = ctx.saved_tensors
         bias, w, s = saved[0], saved[1:1 + n], saved[1 + n:]
-        with FOLDS.late(w[0].device):   # the incoming tap gradients are (deferred) fold results of the depthwise weight-gradient kernels
-            gtaps = [g.contiguous() for g in gtaps]
-            dw = [torch.empty_like(t) for t in w]
-            ds = [torch.empty_like(t) for t in s]
-            dbias = torch.empty_like(bias) if bias is not None else None
-            if bias is not None:
-                gbias_t = gbias_t.contiguous() if gbias_t is not None else torch.zeros(Cp, dtype=torch.float32, device=bias.device)
-            lib.call("adnm_wtprep_bwd", lib.ptr_table(w), lib.ptr_table(s), _p(bias), lib.ptr_table(gtaps), _p(gbias_t) if bias is not None else None,
-                     lib.ptr_table(dw), lib.ptr_table(ds), _p(dbias), C, Cp, K, levels, _stream())
-            SIDE.keep(w[0].device, gtaps, gbias_t)
+        FOLDS.flush(w[0].device)   # the incoming tap gradients are (deferred) fold results of the depthwise weight-gradient kernels
+        gtaps = [g.contiguous() for g in gtaps]
+        dw = [torch.empty_like(t) for t in w]
+        ds = [torch.empty_like(t) for t in s]
+        dbias = torch.empty_like(bias) if bias is not None else None
+        if bias is not None:
+            gbias_t = gbias_t.contiguous() if gbias_t is not None else torch.zeros(Cp, dtype=torch.float32, device=bias.device)
+        lib.call("adnm_wtprep_bwd", lib.ptr_table(w), lib.ptr_table(s), _p(bias), lib.ptr_table(gtaps), _p(gbias_t) if bias is not None else None,
+                 lib.ptr_table(dw), lib.ptr_table(ds), _p(dbias), C, Cp, K, levels, _stream())
         return (None, None, None, None, dbias, *dw, *ds)
 
 
@@ -2075,22 +1904,22 @@ class AdnPrepMultiFn(torch.autograd.Function):
         dims = ctx.dims
         n = len(dims)
         dev = params[0].device
-        with FOLDS.late(dev):   # the incoming gradients are (deferred) fold results of the mixers' backward
-            gtab, dflat, keep = [], [], []
-            for i, (dm, di, gn, P) in enumerate(dims):
-                nh, cx = di // P, di + 2 * gn
-                shapes = [(2 * di + 2 * gn + nh, dm), (9, di + cx), (di,), (di,), (dm, 2 * di)]
-                gi = [t.contiguous() if t is not None else torch.zeros(shp, dtype=torch.float32, device=dev) for t, shp in zip(g[9 * i:9 * i + 5], shapes)]
-                keep += gi
-                g_w_in, g_taps, g_ln_w, g_ln_b, g_w_out = gi
-                gtab += [g_w_in, g_taps[:, di:], g_taps[:, :di], g_ln_w, g_ln_b, g_w_out]
-                dflat += [dm, di, gn, P, 2 * di + 2 * gn]
-            dparams = [grad_dst(p.data_ptr(), p.shape, dev, p.dtype) for p in params]
-            nb = lib.query("adnm_adnprep_bwd_multi_ws_bytes", n)
-            ws = _ws(nb, dev)
-            with FOLDS.defer(dev, ws, *keep):
-                lib.call("adnm_adnprep_bwd_multi", n, lib.ptr_table(params), lib.ptr_table(gtab), lib.ptr_table(dparams), lib.i64_table(dflat),
-                         ws.data_ptr(), nb, _stream())
+        FOLDS.flush(dev)   # the incoming gradients are (deferred) fold results of the mixers' backward
+        gtab, dflat, keep = [], [], []
+        for i, (dm, di, gn, P) in enumerate(dims):
+            nh, cx = di // P, di + 2 * gn
+            shapes = [(2 * di + 2 * gn + nh, dm), (9, di + cx), (di,), (di,), (dm, 2 * di)]
+            gi = [t.contiguous() if t is not None else torch.zeros(shp, dtype=torch.float32, device=dev) for t, shp in zip(g[9 * i:9 * i + 5], shapes)]
+            keep += gi
+            g_w_in, g_taps, g_ln_w, g_ln_b, g_w_out = gi
+            gtab += [g_w_in, g_taps[:, di:], g_taps[:, :di], g_ln_w, g_ln_b, g_w_out]
+            dflat += [dm, di, gn, P, 2 * di + 2 * gn]
+        dparams = [grad_dst(p.data_ptr(), p.shape, dev, p.dtype) for p in params]
+        nb = lib.query("adnm_adnprep_bwd_multi_ws_bytes", n)
+        ws = _ws(nb, dev)
+        with FOLDS.defer(dev, ws, *keep):
+            lib.call("adnm_adnprep_bwd_multi", n, lib.ptr_table(params), lib.ptr_table(gtab), lib.ptr_table(dparams), lib.i64_table(dflat),
+                     ws.data_ptr(), nb, _stream())
         return (None, *dparams)
 
 
@@ -2129,26 +1958,25 @@ class WtPrepMultiFn(torch.autograd.Function):
         dims = ctx.dims
         saved = ctx.saved_tensors
         dev = saved[0].device
-        with FOLDS.late(dev):   # the incoming tap gradients are (deferred) fold results of the depthwise weight-gradient kernels
-            w, s, bias, gtaps, gbias_t, dw, ds, dbias, dflat, grads = [], [], [], [], [], [], [], [], [], []
-            si, gi = iter(saved), iter(g)
-            for C, Cp, K, levels, has_bias in dims:
-                n1 = 1 + levels
-                b = next(si) if has_bias else None
-                ws_ = [next(si) for _ in range(n1)]
-                ss = [next(si) for _ in range(n1)]
-                gb = next(gi).contiguous() if has_bias else None
-                gt = [next(gi).contiguous() for _ in range(n1)]
-                dws, dss = [torch.empty_like(t) for t in ws_], [torch.empty_like(t) for t in ss]
-                db = torch.empty_like(b) if has_bias else None
-                pad = [None] * (5 - n1)
-                w += list(ws_) + pad; s += list(ss) + pad; gtaps += gt + pad; dw += dws + pad; ds += dss + pad
-                bias.append(b); gbias_t.append(gb); dbias.append(db)
-                dflat += [C, Cp, K, levels]
-                grads += ([db] if has_bias else []) + dws + dss
-            lib.call("adnm_wtprep_bwd_multi", len(dims), lib.ptr_table(w), lib.ptr_table(s), lib.ptr_table(bias), lib.ptr_table(gtaps), lib.ptr_table(gbias_t),
-                     lib.ptr_table(dw), lib.ptr_table(ds), lib.ptr_table(dbias), lib.i64_table(dflat), _stream())
-            SIDE.keep(dev, gtaps, gbias_t)
+        FOLDS.flush(dev)   # the incoming tap gradients are (deferred) fold results of the depthwise weight-gradient kernels
+        w, s, bias, gtaps, gbias_t, dw, ds, dbias, dflat, grads = [], [], [], [], [], [], [], [], [], []
+        si, gi = iter(saved), iter(g)
+        for C, Cp, K, levels, has_bias in dims:
+            n1 = 1 + levels
+            b = next(si) if has_bias else None
+            ws_ = [next(si) for _ in range(n1)]
+            ss = [next(si) for _ in range(n1)]
+            gb = next(gi).contiguous() if has_bias else None
+            gt = [next(gi).contiguous() for _ in range(n1)]
+            dws, dss = [torch.empty_like(t) for t in ws_], [torch.empty_like(t) for t in ss]
+            db = torch.empty_like(b) if has_bias else None
+            pad = [None] * (5 - n1)
+            w += list(ws_) + pad; s += list(ss) + pad; gtaps += gt + pad; dw += dws + pad; ds += dss + pad
+            bias.append(b); gbias_t.append(gb); dbias.append(db)
+            dflat += [C, Cp, K, levels]
+            grads += ([db] if has_bias else []) + dws + dss
+        lib.call("adnm_wtprep_bwd_multi", len(dims), lib.ptr_table(w), lib.ptr_table(s), lib.ptr_table(bias), lib.ptr_table(gtaps), lib.ptr_table(gbias_t),
+                 lib.ptr_table(dw), lib.ptr_table(ds), lib.ptr_table(dbias), lib.i64_table(dflat), _stream())
         return (None, *grads)
 
 
@@ -2272,7 +2100,7 @@ def _sk_operand(t, what):
     return t
 
 
-def _skgemm(op, a, b, bias, c, dbias, M, N, K, defer=False, side=False, q=None, role="f", narrow=None):
+def _skgemm(op, a, b, bias, c, dbias, M, N, K, defer=False, q=None, role="f", narrow=None):
     """narrow = (pointer, b_dtype, scale tensor | None): read the weight operand from its narrow shadow (ShadowRegistry / the mixer prep's
     narrow copies) instead of the fp32 tensor b, which then only provides the shape and row stride"""
     if lib.query("adnm_skgemm_supported", op, M, N, K) != 1:
@@ -2301,8 +2129,6 @@ def _skgemm(op, a, b, bias, c, dbias, M, N, K, defer=False, side=False, q=None, 
     else:
         ws = _ws(nb, a.device)
         wsp, wsn = ws.data_ptr(), nb
-    # only the weight-gradient op (TN) may wait for its split-K fold, and only it leaves the critical path for the side stream
-    pc, ldc, pdb = c.data_ptr(), c.stride(0), _p(dbias)   # (the outputs are not captured: see SideStreams)
     if op == SK_TN:   # the weight gradient: bf16 operands in the fp8 configuration, no record
         prec, qp = (1 if MFMA_PREC[0] == 2 or QUANT.calibrating else MFMA_PREC[0]), None
     else:
@@ -2315,14 +2141,12 @@ def _skgemm(op, a, b, bias, c, dbias, M, N, K, defer=False, side=False, q=None, 
             bp, bdt = narrow[0], 1
         elif narrow[1] == 2 and prec in (2, 3):
             bp, bdt, bsc = narrow[0], 2, narrow[2]
-    ldb = b.stride(0)
-    call = lambda: lib.call("adnm_skgemm", op, a.data_ptr(), a.stride(0), bp, ldb, bdt, _p(bsc), _p(bias), pc, ldc, pdb,
-                            wsp, wsn, ucp, ucn, M, N, K, prec, qp, _stream())
-    if side:   # (a, b are kept with the workspace: under a bound leaf queue the launch itself waits for the grouped flush)
-        SIDE.submit(a.device, (a, b), FOLDS.defer(a.device, ws, a, b) if defer else _NODEFER, call)
-    else:
-        with FOLDS.defer(a.device, ws) if defer else _NODEFER:
-            call()
+    # only the weight-gradient op (TN) may wait for its split-K fold; under a bound leaf queue its launch itself waits for the grouped
+    # flush, so a and b are kept with the workspace
+    keep = (ws, a, b) if op == SK_TN else (ws,)
+    with FOLDS.defer(a.device, *keep) if defer else _NODEFER:
+        lib.call("adnm_skgemm", op, a.data_ptr(), a.stride(0), bp, b.stride(0), bdt, _p(bsc), _p(bias), c.data_ptr(), c.stride(0), _p(dbias),
+                 wsp, wsn, ucp, ucn, M, N, K, prec, qp, _stream())
 
 
 def _out_view_ok(out):
@@ -2418,14 +2242,13 @@ def k_linear_dw(dy2, x2, want_bias, w_ptr=0, b_ptr=0, dw_out=None, now=False):
     if ts_ok_tn(M, N, K, x2):
         nb = lib.query("adnm_tsgemm_tn_ws_bytes", M, N, K)
         ws = _ws(nb, dev)
-        pdw, pdb = dw.data_ptr(), _p(db)
-        dty, dtx = _dt(dy2), _dt(x2)
         # (the operands stay referenced until the flush: under the leaf queue the GEMM itself is deferred, not just its fold)
-        SIDE.submit(dev, (dy2, x2), FOLDS.defer(dev, ws, dy2, x2), lambda: lib.call(
-            "adnm_tsgemm_tn", dy2.data_ptr(), dy2.stride(0), x2.data_ptr(), x2.stride(0), pdw, pdb, ws.data_ptr(), nb, M, N, K, dty, dtx, _stream()))
+        with FOLDS.defer(dev, ws, dy2, x2):
+            lib.call("adnm_tsgemm_tn", dy2.data_ptr(), dy2.stride(0), x2.data_ptr(), x2.stride(0), dw.data_ptr(), _p(db), ws.data_ptr(), nb, M, N, K,
+                     _dt(dy2), _dt(x2), _stream())
         return dw, db
     dy2, x2 = _sk_operand(dy2, "output gradient"), _sk_operand(x2, "input")
-    _skgemm(SK_TN, dy2, x2, None, dw, db, M, N, K, defer=True, side=True)
+    _skgemm(SK_TN, dy2, x2, None, dw, db, M, N, K, defer=True)
     return dw, db
 
 
@@ -2606,10 +2429,10 @@ class Conv3Fn(torch.autograd.Function):
         db = grad_dst(b_ptr, (N,), dev) if has_bias else None
         nb = lib.query("adnm_conv3_wgrad_ws_bytes", B, H, W, K, N)
         wsb = _ws(nb, dev)
-        pg, pdb, prec = g.data_ptr(), _p(db), (1 if MFMA_PREC[0] == 2 or QUANT.calibrating else MFMA_PREC[0])   # fp8 configuration: bf16 operands here
-        SIDE.submit(dev, (dy2, pre, x2), FOLDS.defer(dev, wsb), lambda: lib.call(
-            "adnm_conv3_wgrad", dy2.data_ptr(), dy2.stride(0), _p(pre), N, act, x2.data_ptr(), x2.stride(0), pg, pdb,
-            wsb.data_ptr(), nb, B, H, W, K, N, prec, _stream()))
+        prec = 1 if MFMA_PREC[0] == 2 or QUANT.calibrating else MFMA_PREC[0]   # fp8 configuration: bf16 operands here
+        with FOLDS.defer(dev, wsb):
+            lib.call("adnm_conv3_wgrad", dy2.data_ptr(), dy2.stride(0), _p(pre), N, act, x2.data_ptr(), x2.stride(0), g.data_ptr(), _p(db),
+                     wsb.data_ptr(), nb, B, H, W, K, N, prec, _stream())
         return dx, g, db, None, None, None
 
 

@@ -32,22 +32,6 @@ import torch.distributed as dist
 from . import lib, ops
 
 
-class _Both:
-    """enter a then b, leave b then a"""
-
-    def __init__(self, a, b):
-        self.a, self.b = a, b
-
-    def __enter__(self):
-        self.a.__enter__()
-        self.b.__enter__()
-
-    def __exit__(self, *exc):
-        self.b.__exit__(*exc)
-        self.a.__exit__(*exc)
-        return False
-
-
 class FlatTrainer:
     def __init__(self, model, loss_fn, lr=1e-3, betas=(0.9, 0.999), eps=1e-9, weight_decay=1e-2, max_norm=0.0,
                  process_group=None, use_graph=True, fused=True, overlap="auto", reduce_dtype="f32", stages=None, defer_folds=True, side_stream=False,
@@ -92,10 +76,9 @@ class FlatTrainer:
         assert reduce_dtype in ("f32", "bf16")
         self.reduce_dtype = reduce_dtype
         self.defer_folds = defer_folds
-        # weight-gradient kernels on a second stream beside the input-gradient chain (ops.SIDE).  Off by default: measured on MI355X /
-        # ROCm 7.2 the forked branches of the replayed hipGraph buy nothing and every fork costs (11.4 ms/step off, 12.1 with a fork per
-        # 16 weight gradients, 13.1 with one per weight gradient); bitwise neutral either way (tests/test_trainer_gpu.py)
-        self.side_stream = side_stream
+        if side_stream:   # the keyword survives for callers that pass False; the lane it switched on measured slower and was removed
+            raise ValueError("FlatTrainer(side_stream=True): the side-stream lane for weight gradients was removed (it measured slower, "
+                             "see DESIGN.md); pass side_stream=False or leave the argument out")
         self._steps = 0
         # gradient accumulation: micro-steps per optimiser step, micro-steps done in the running cycle, the fp32 sum (only when k > 1)
         self._accum_steps = self._check_accum(accum_steps)
@@ -207,11 +190,10 @@ class FlatTrainer:
         return loss
 
     def _deferred(self):
-        """the context of a backward pass: second-stage folds of the parameter gradients batched (ops.FOLDS), weight-gradient kernels
-        on a side stream beside the input-gradient chain (ops.SIDE); both are joined / flushed on the way out"""
+        """the context of a backward pass: second-stage folds of the parameter gradients batched (ops.FOLDS), flushed on the way out"""
         on = self.defer_folds and self.used is not None and self.flat_g.is_cuda
         dev = self.flat_g.device if self.used is not None else torch.device("cpu")
-        return _Both(ops.SIDE.active(dev, on and self.side_stream), ops.FOLDS.active(dev, on))
+        return ops.FOLDS.active(dev, on)
 
     @torch.no_grad()
     def _flatten(self):
@@ -467,19 +449,18 @@ class FlatTrainer:
 
     def _abort_prepare(self):
         """After an exception in prepare(): torch.cuda.graph's __exit__ has already ended a capture in flight; what is left is
-        OUR state — the thread's fold-queue binding (a kernel wrapper may have died between bind and unbind), the deferral /
-        side-stream switches of this device, and what the captures own (_release_captures), which must not survive half-captured."""
+        OUR state — the thread's fold-queue binding (a kernel wrapper may have died between bind and unbind), the deferral
+        switch of this device, and what the captures own (_release_captures), which must not survive half-captured."""
         try:
             lib.load().adnm_foldq_bind(None)
         except Exception:
             pass
         dev = self.flat_g.device if self.flat_g is not None else None
         if dev is not None and dev.type == "cuda":
-            for reg in (ops.FOLDS, ops.SIDE):
-                try:
-                    reg.abort(dev)
-                except Exception:
-                    pass
+            try:
+                ops.FOLDS.abort(dev)
+            except Exception:
+                pass
         self._release_captures()
 
     def _prepare(self, x, tgt):

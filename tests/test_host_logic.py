@@ -60,6 +60,19 @@ def test_prepare_exception_path_restores_state():
     assert owner not in ops.GRADS._claimed and not any(o == owner for o, _ in ops.GRADS._dst.values())
 
 
+def test_side_stream_keyword_is_accepted_false_and_refused_true():
+    """The side-stream lane for weight gradients is gone (DESIGN.md keeps the measurements): callers that still pass side_stream=False
+    construct as before, side_stream=True is refused at construction with a message that names the removal, and ops no longer has the lane's singleton."""
+    from adnm_hip import ops
+    from adnm_hip.trainer import FlatTrainer
+    loss_fn = lambda o, t: (o - t).pow(2).mean()
+    tr = FlatTrainer(_Toy(), loss_fn, use_graph=False, fused=False, side_stream=False)
+    assert not hasattr(tr, "side_stream")
+    with pytest.raises(ValueError, match="removed"):
+        FlatTrainer(_Toy(), loss_fn, use_graph=False, fused=False, side_stream=True)
+    assert not hasattr(ops, "SIDE")
+
+
 def test_grad_registry_drop_is_lock_free_and_reentrant():
     """drop() is what a finaliser calls: it must not take the registry lock (the cyclic collector can run while register() / take()
     hold it on the same thread)."""

@@ -27,10 +27,10 @@ orig = ops._skgemm
 log = []
 
 
-def probe(op, a, b, bias, c, dbias, M, N, K, defer=False, side=False, q=None, role="f", narrow=None):
+def probe(op, a, b, bias, c, dbias, M, N, K, defer=False, q=None, role="f", narrow=None):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    orig(op, a, b, bias, c, dbias, M, N, K, defer=defer, side=side, q=q, role=role, narrow=narrow)
+    orig(op, a, b, bias, c, dbias, M, N, K, defer=defer, q=q, role=role, narrow=narrow)
     e1.record()
     log.append(((("NT", "NN", "TN")[op], M, N, K, a.stride(0), c.stride(0), bool(c.is_contiguous()), type(b).__name__, bias is not None), e0, e1))
 
