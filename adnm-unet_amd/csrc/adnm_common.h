@@ -80,6 +80,7 @@ int adnm_tsgemm_tn_launch_multi(const AdnmLeaf* const* items, int n, hipStream_t
 // device, and the reference's nn.DataParallel flow, train.py:99-102, drives several devices from one process).  `done` is the
 // call site's own bitmask of devices already opted in; setting the attribute twice is harmless, so a race only repeats the call.
 #include <atomic>
+#include <initializer_list>
 static inline int adnm_allow_lds(const void* fn, size_t smem, std::atomic<uint64_t>& done, const char* name) {
   if (smem <= 64 * 1024) return ADNM_OK;
   int dev = 0;
@@ -101,6 +102,13 @@ static inline int adnm_allow_lds(const void* fn, size_t smem, std::atomic<uint64
   } while (0)
 
 static inline int64_t adnm_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// Io<T>::ld4 / st4 (below) move four elements per access: 16 bytes of fp32, 8 of bf16.  True when every base pointer given (null ones
+// pass) is aligned to that; with a row stride that is a multiple of 4 elements every row start then is as well.
+static inline bool adnm_quad_aligned(int dtype, std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= (uintptr_t)p;
+  return bits % (dtype == ADNM_BF16 ? 8 : 16) == 0;
+}
 static inline int64_t adnm_align(int64_t a, int64_t b) { return adnm_cdiv(a, b) * b; }
 
 // ---- storage types -------------------------------------------------------------------------

@@ -229,6 +229,7 @@ extern "C" int adnm_gate_fwd(const void* h, int64_t ldh, void* y, int64_t ldy, i
   ADNM_REQUIRE(M > 0 && F > 0 && F % 4 == 0 && ldh >= 2 * F && ldy >= F && ldh % 4 == 0 && ldy % 4 == 0, "gate_fwd: bad shape M=%lld F=%lld",
                (long long)M, (long long)F);
   ADNM_REQUIRE(dtype == ADNM_F32 || dtype == ADNM_BF16, "gate_fwd: bad dtype %d", dtype);
+  ADNM_REQUIRE(adnm_quad_aligned(dtype, {h, y}), "gate_fwd: h and y must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)");
   hipStream_t st = (hipStream_t)stream;
   if (dtype == ADNM_F32) { ADNM_PROF("gate_fwd", st, 4.0 * M * F * 3); gate_fwd_kernel<float><<<grid_for(M * F / 4), kBlock, 0, st>>>((const float*)h, ldh, (float*)y, ldy, M, (int)F); }
   else { ADNM_PROF("gate_fwd", st, 2.0 * M * F * 3); gate_fwd_kernel<uint16_t><<<grid_for(M * F / 4), kBlock, 0, st>>>((const uint16_t*)h, ldh, (uint16_t*)y, ldy, M, (int)F); }
@@ -242,6 +243,7 @@ extern "C" int adnm_gate_bwd(const void* dy, int64_t lddy, const void* h, int64_
   ADNM_REQUIRE(M > 0 && F > 0 && F % 4 == 0 && ldh >= 2 * F && lddh >= 2 * F && lddy >= F && ldh % 4 == 0 && lddh % 4 == 0 && lddy % 4 == 0,
                "gate_bwd: bad shape M=%lld F=%lld", (long long)M, (long long)F);
   ADNM_REQUIRE(dtype == ADNM_F32 || dtype == ADNM_BF16, "gate_bwd: bad dtype %d", dtype);
+  ADNM_REQUIRE(adnm_quad_aligned(dtype, {dy, h, dh}), "gate_bwd: dy, h and dh must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)");
   hipStream_t st = (hipStream_t)stream;
   if (dtype == ADNM_F32)
     { ADNM_PROF("gate_bwd", st, 4.0 * M * F * 5); gate_bwd_kernel<float><<<grid_for(M * F / 4), kBlock, 0, st>>>((const float*)dy, lddy, (const float*)h, ldh, (float*)dh, lddh, M, (int)F); }
@@ -476,6 +478,7 @@ int catmix_check(const char* who, const void* x, int64_t ldx, const void* r, int
   ADNM_REQUIRE(M > 0 && d >= 4 && d % 4 == 0, "%s: d=%lld must be a positive multiple of 4", who, (long long)d);
   ADNM_REQUIRE(ldx >= d && ldr >= d && ldx % 4 == 0 && ldr % 4 == 0 && (!f || (ldf >= d && ldf % 4 == 0)), "%s: bad row stride", who);
   ADNM_REQUIRE(dtype == ADNM_F32 || dtype == ADNM_BF16, "%s: bad dtype %d", who, dtype);
+  ADNM_REQUIRE(adnm_quad_aligned(dtype, {x, r, f}), "%s: the operands must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)", who);
   return ADNM_OK;
 }
 }  // namespace
@@ -483,7 +486,7 @@ int catmix_check(const char* who, const void* x, int64_t ldx, const void* r, int
 extern "C" int adnm_catmix_fwd(const void* x, int64_t ldx, const void* r, int64_t ldr, const void* f, int64_t ldf, const float* a1, const float* a2,
                                const float* a3, const float* a4, void* y, int64_t M, int64_t d, int dtype, adnm_stream_t stream) {
   if (int rc = catmix_check("catmix_fwd", x, ldx, r, ldr, f, ldf, M, d, dtype)) return rc;
-  ADNM_REQUIRE(y, "catmix_fwd: null output");
+  ADNM_REQUIRE(y && adnm_quad_aligned(dtype, {y}), "catmix_fwd: the output must be non-null and aligned to 4 elements");
   hipStream_t st = (hipStream_t)stream;
   const double es = dtype == ADNM_F32 ? 4.0 : 2.0;
   ADNM_PROF("catmix_fwd", st, es * M * d * (f ? 5 : 4));
@@ -504,6 +507,7 @@ extern "C" int adnm_catmix_bwd(const void* dy, int64_t lddy, const void* x, int6
                                void* ws, int64_t ws_bytes, int64_t M, int64_t d, int dtype, adnm_stream_t stream) {
   if (int rc = catmix_check("catmix_bwd", x, ldx, r, ldr, f, ldf, M, d, dtype)) return rc;
   ADNM_REQUIRE(dy && da && lddy >= 2 * d && lddy % 4 == 0, "catmix_bwd: dy must be (M, 2d) with a row stride that is a multiple of 4");
+  ADNM_REQUIRE(adnm_quad_aligned(dtype, {dy, dx, dr, df}), "catmix_bwd: dy and the gradients must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)");
   if (!ws || ws_bytes < adnm_catmix_bwd_ws_bytes(M, d)) {
     adnm_set_error("catmix_bwd: workspace too small");
     return ADNM_EWORKSPACE;

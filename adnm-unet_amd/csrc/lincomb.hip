@@ -198,6 +198,7 @@ int check(const char* who, const void* x0, int64_t ld0, const void* x1, int64_t 
   ADNM_REQUIRE(ld0 >= C && ld0 % 4 == 0 && (!x1 || (ld1 >= C && ld1 % 4 == 0)) && (!x2 || (ld2 >= C && ld2 % 4 == 0)),
                "%s: row strides must be >= C and multiples of 4", who);
   ADNM_REQUIRE(dtype == ADNM_F32 || dtype == ADNM_BF16, "%s: bad dtype %d", who, dtype);
+  ADNM_REQUIRE(adnm_quad_aligned(dtype, {x0, x1, x2}), "%s: the operands must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)", who);
   return ADNM_OK;
 }
 
@@ -208,6 +209,7 @@ extern "C" int adnm_lincomb_fwd(const void* x0, int64_t ld0, const void* x1, int
                                 adnm_stream_t stream) {
   if (int rc = check("lincomb_fwd", x0, ld0, x1, ld1, x2, ld2, M, C, dtype)) return rc;
   ADNM_REQUIRE(y && ldy >= C && ldy % 4 == 0, "lincomb_fwd: bad output");
+  ADNM_REQUIRE(adnm_quad_aligned(dtype, {y}), "lincomb_fwd: the output must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)");
   Ops o{{x0, x1, x2}, {ld0, ld1, ld2}, {s0, s1, s2}};
   const int K = count_ops(x0, x1, x2);
   hipStream_t st = (hipStream_t)stream;
@@ -225,7 +227,9 @@ extern "C" int adnm_lincomb_bwd(const void* dy, int64_t lddy, const void* x0, in
                                 int64_t ws_bytes, int64_t M, int64_t C, int dtype, adnm_stream_t stream) {
   if (int rc = check("lincomb_bwd", x0, ld0, x1, ld1, x2, ld2, M, C, dtype)) return rc;
   ADNM_REQUIRE(dy && lddy >= C && lddy % 4 == 0, "lincomb_bwd: bad dy");
-  ADNM_REQUIRE((!dx0 || lddx0 >= C) && (!dx1 || lddx1 >= C) && (!dx2 || lddx2 >= C), "lincomb_bwd: bad gradient strides");
+  ADNM_REQUIRE((!dx0 || (lddx0 >= C && lddx0 % 4 == 0)) && (!dx1 || (lddx1 >= C && lddx1 % 4 == 0)) && (!dx2 || (lddx2 >= C && lddx2 % 4 == 0)),
+               "lincomb_bwd: gradient row strides must be >= C and multiples of 4");
+  ADNM_REQUIRE(adnm_quad_aligned(dtype, {dy, dx0, dx1, dx2}), "lincomb_bwd: dy and the gradients must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)");
   if (!ws || ws_bytes < adnm_lincomb_bwd_ws_bytes(M, C)) {
     adnm_set_error("lincomb_bwd: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)adnm_lincomb_bwd_ws_bytes(M, C));
     return ADNM_EWORKSPACE;

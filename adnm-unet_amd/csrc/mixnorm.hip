@@ -231,6 +231,7 @@ int check(const char* who, const float* x0, int64_t ld0, const float* x1, int64_
   ADNM_REQUIRE(x0 && x1, "%s: null operand", who);
   ADNM_REQUIRE(M > 0 && d >= 4 && d % 4 == 0 && d <= 1024, "%s: d=%lld must be a multiple of 4 in [4, 1024]", who, (long long)d);
   ADNM_REQUIRE(ld0 >= d && ld1 >= d && ld0 % 4 == 0 && ld1 % 4 == 0, "%s: row strides must be >= d and multiples of 4", who);
+  ADNM_REQUIRE(adnm_quad_aligned(ADNM_F32, {x0, x1}), "%s: the operands must be 16-byte aligned", who);
   return ADNM_OK;
 }
 }  // namespace
@@ -241,6 +242,7 @@ extern "C" int adnm_mixnorm_fwd(const float* x0, int64_t ld0, const float* x1, i
   if (int rc = check("mixnorm_fwd", x0, ld0, x1, ld1, M, d)) return rc;
   ADNM_REQUIRE(w && ymix && yn && rstd && (!subtract_mean || mu), "mixnorm_fwd: null pointer");
   ADNM_REQUIRE(ldm >= d && ldn >= d && ldm % 4 == 0 && ldn % 4 == 0, "mixnorm_fwd: output row strides must be >= d and multiples of 4");
+  ADNM_REQUIRE(adnm_quad_aligned(ADNM_F32, {ymix, yn}), "mixnorm_fwd: the outputs must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int lpr = lanes_per_row(d);
   const int it = (int)adnm_cdiv(d, (int64_t)lpr * 4);
@@ -277,6 +279,7 @@ extern "C" int adnm_mixnorm_bwd(const float* dyn, int64_t lddyn, const float* dr
   ADNM_REQUIRE(dyn && w && rstd && (!subtract_mean || mu), "mixnorm_bwd: null pointer");
   ADNM_REQUIRE(lddyn >= d && lddyn % 4 == 0 && (!dres || (lddres >= d && lddres % 4 == 0)), "mixnorm_bwd: bad gradient strides");
   ADNM_REQUIRE((!dx0 || (lddx0 >= d && lddx0 % 4 == 0)) && (!dx1 || (lddx1 >= d && lddx1 % 4 == 0)), "mixnorm_bwd: bad input-gradient strides");
+  ADNM_REQUIRE(adnm_quad_aligned(ADNM_F32, {dyn, dres, dx0, dx1}), "mixnorm_bwd: the gradients must be 16-byte aligned");
   if (!ws || ws_bytes < adnm_mixnorm_bwd_ws_bytes(M, d)) {
     adnm_set_error("mixnorm_bwd: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)adnm_mixnorm_bwd_ws_bytes(M, d));
     return ADNM_EWORKSPACE;

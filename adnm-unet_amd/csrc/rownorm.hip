@@ -242,6 +242,7 @@ extern "C" int adnm_rownorm_fwd(const void* x, int64_t ldx, const float* w, cons
   ADNM_REQUIRE(M >= 0 && d >= 4 && d % 4 == 0 && d <= 4096, "rownorm_fwd: d=%lld must be a multiple of 4 in [4,4096]", (long long)d);
   ADNM_REQUIRE(ldx >= d && ldy >= d && ldx % 4 == 0 && ldy % 4 == 0, "rownorm_fwd: row strides must be >= d and multiples of 4");
   ADNM_REQUIRE(dtype == ADNM_F32 || dtype == ADNM_BF16, "rownorm_fwd: bad dtype %d", dtype);
+  ADNM_REQUIRE(adnm_quad_aligned(dtype, {x, y}), "rownorm_fwd: x and y must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)");
   if (M == 0) return ADNM_OK;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == ADNM_F32)
@@ -268,6 +269,8 @@ extern "C" int adnm_rownorm_bwd(const void* dy, int64_t lddy, const void* x, int
                "rownorm_bwd: row strides must be >= d and multiples of 4");
   ADNM_REQUIRE(dtype == ADNM_F32 || dtype == ADNM_BF16, "rownorm_bwd: bad dtype %d", dtype);
   ADNM_REQUIRE(!dres || (lddres >= d && lddres % 4 == 0), "rownorm_bwd: bad residual-gradient stride");
+  ADNM_REQUIRE(adnm_quad_aligned(dtype, {dy, x, dx, dres}),
+               "rownorm_bwd: dy, x, dx and the residual gradient must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)");
   if (ws_bytes < adnm_rownorm_bwd_ws_bytes(M, d) || !ws) {
     adnm_set_error("rownorm_bwd: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)adnm_rownorm_bwd_ws_bytes(M, d));
     return ADNM_EWORKSPACE;

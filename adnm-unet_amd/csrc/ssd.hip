@@ -714,6 +714,8 @@ extern "C" int adnm_ssd_reduce_fwd(const void* x, int64_t ldx, const void* Bm, i
   ADNM_REQUIRE(ldx >= H * P && ldy >= H * P && ldb >= G * N && ldc >= G * N && lddt >= (H - 1) * dt_hstride + 1,
                "ssd_reduce_fwd: row strides smaller than the rows they address");
   ADNM_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0, "ssd_reduce_fwd: row strides must be multiples of 4");
+  ADNM_REQUIRE(adnm_quad_aligned(dtype, {x, Bm, Cm, y, yn}),
+               "ssd_reduce_fwd: x, B, C, y and the LayerNorm output must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)");
   if (yn) {
     ADNM_REQUIRE(H * P == kCols, "ssd_reduce_fwd: the fused LayerNorm epilogue needs the token row to be one head block (H*P == 64), got %lld",
                  (long long)(H * P));
@@ -756,6 +758,9 @@ extern "C" int adnm_ssd_reduce_bwd(const void* dy, int64_t lddy, const void* x, 
                "ssd_reduce_bwd: row strides smaller than the rows they address");
   ADNM_REQUIRE(ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && lddb % 4 == 0 && lddc % 4 == 0,
                "ssd_reduce_bwd: row strides must be multiples of 4");
+  ADNM_REQUIRE(lddt >= (H - 1) * dt_hstride + 1 && ldddt >= (H - 1) * dt_hstride + 1, "ssd_reduce_bwd: dt row strides smaller than the rows they address");
+  ADNM_REQUIRE(adnm_quad_aligned(dtype, {dy, x, Bm, Cm, dx, dBm, dCm}),
+               "ssd_reduce_bwd: dy, x, B, C and their gradients must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)");
   const Ws w = carve(ws, B, L, H, P, N, G);
   if (!ws || ws_bytes < w.bytes) {
     adnm_set_error("ssd_reduce_bwd: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)w.bytes);

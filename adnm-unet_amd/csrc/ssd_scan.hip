@@ -340,6 +340,9 @@ extern "C" int adnm_ssd_scan_fwd(const void* x, int64_t ldx, int64_t x_hstride, 
                                  adnm_stream_t stream) {
   if (int rc = check("ssd_scan_fwd", B, L, H, Pp, N, G, chunk, dtype)) return rc;
   ADNM_REQUIRE(x && Bm && Cm && dt_raw && dt_bias && A_log && D && y && S_in, "ssd_scan_fwd: null pointer");
+  ADNM_REQUIRE(x_hstride >= Pp && y_hstride >= Pp && dt_hstride >= 1 && p_hstride >= 1, "ssd_scan_fwd: head strides smaller than a head");
+  ADNM_REQUIRE(ldx >= (H - 1) * x_hstride + Pp && ldy >= (H - 1) * y_hstride + Pp && lddt >= (H - 1) * dt_hstride + 1 && ldb >= G * N && ldc >= G * N,
+               "ssd_scan_fwd: row strides smaller than the rows they address");
   const int64_t NC = adnm_cdiv(L, chunk);
   const ScanWs w = carve(ws, B, L, H, N, NC, false);
   if (!ws || ws_bytes < w.bytes) {
@@ -373,6 +376,11 @@ extern "C" int adnm_ssd_scan_bwd(const void* dy, int64_t lddy, int64_t dy_hstrid
   if (int rc = check("ssd_scan_bwd", B, L, H, Pp, N, G, chunk, dtype)) return rc;
   ADNM_REQUIRE(dy && x && Bm && Cm && dt_raw && dt_bias && A_log && D && S_in && dx && dBm && dCm && ddt_raw && ddt_bias && dA_log && dD,
                "ssd_scan_bwd: null pointer");
+  ADNM_REQUIRE(x_hstride >= Pp && dy_hstride >= Pp && dx_hstride >= Pp && dt_hstride >= 1 && ddt_hstride >= 1 && p_hstride >= 1,
+               "ssd_scan_bwd: head strides smaller than a head");
+  ADNM_REQUIRE(ldx >= (H - 1) * x_hstride + Pp && lddy >= (H - 1) * dy_hstride + Pp && lddx >= (H - 1) * dx_hstride + Pp &&
+                   lddt >= (H - 1) * dt_hstride + 1 && ldddt >= (H - 1) * ddt_hstride + 1 && ldb >= G * N && ldc >= G * N && lddb >= G * N && lddc >= G * N,
+               "ssd_scan_bwd: row strides smaller than the rows they address");
   const int64_t NC = adnm_cdiv(L, chunk);
   const ScanWs w = carve(ws, B, L, H, N, NC, true);
   if (!ws || ws_bytes < w.bytes) {

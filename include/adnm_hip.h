@@ -19,6 +19,12 @@
  *    keeps between stages (ADNMUNet.py:119, model_untils.py:21-27);
  *  - `dtype` selects the storage type of activations: ADNM_F32 (0) or ADNM_BF16 (1);
  *    parameters, statistics, reductions and workspaces are always fp32;
+ *  - a row operand is (pointer, row stride in elements): a column slice of a wider buffer is passed as it lies.  The row
+ *    kernels (rownorm, ssd_reduce, gate, catmix, lincomb, mixnorm, dwconv) move 4 elements per access, so they ask for a row
+ *    stride >= the width and a multiple of 4, and a base pointer aligned to 4 elements (16 bytes of fp32, 8 of bf16; dwconv:
+ *    16 bytes for both); operands read element by element (dt_raw, everything of ssd_scan) only need rows and head strides
+ *    that hold what they address.  A row operand that breaks this is rejected (parameter vectors, also read 16 bytes at a
+ *    time, are taken as the allocator hands them out and are not checked);
  *  - return value 0 = launched; negative = rejected (nothing launched), text via
  *    adnm_last_error() (thread-local).  The compute entry points keep no global mutable state: they are re-entrant
  *    per thread / stream / device (the reference's nn.DataParallel calls them from one thread per device).  The only

@@ -299,3 +299,33 @@ def test_shadow_staleness_rule_on_cpu_tensors(monkeypatch):
 
     reg.drop("trainer")
     assert reg.lookup(w, 1) is None and reg.sets() == []
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_embed_helper_reports_the_first_touched_pad(dtype):
+    """tests/util.py embed / assert_pads_untouched (the strided-view GPU tests stand on them): a clean buffer passes, one overwritten pad
+    element — the first pad column right of the view, last row — is reported at that position; fp32 and bf16 alike."""
+    from util import embed, assert_pads_untouched, bits
+    M, C, left, right = 5, 8, 8, 16
+    t = (torch.arange(M * C, dtype=torch.float32).reshape(M, C) / 7).to(dtype)
+    buf, view = embed(t, left, right, poison="bits")
+    assert buf.shape == (M, left + C + right) and buf.dtype == dtype and view.stride() == (left + C + right, 1)
+    assert view.data_ptr() == buf.data_ptr() + left * buf.element_size() and torch.equal(view, t)
+    assert bool(torch.isnan(buf[:, :left]).all()) and bool(torch.isnan(buf[:, left + C:]).all())
+    assert_pads_untouched(buf, left, C, "clean")
+    view.mul_(2.0)   # writes inside the view are not the helper's business
+    assert_pads_untouched(buf, left, C, "payload rewritten")
+    buf[M - 1, left + C] = 0.0
+    with pytest.raises(AssertionError, match=rf"row {M - 1}, column {left + C}\)"):
+        assert_pads_untouched(buf, left, C, "one pad element")
+    # a canonical NaN (what arithmetic on a poisoned neighbour would store) is not the poison either
+    buf2, _ = embed(t, left, right, poison="bits")
+    buf2[0, 0] = float("nan")
+    with pytest.raises(AssertionError, match=r"row 0, column 0\)"):
+        assert_pads_untouched(buf2, left, C, "canonical NaN")
+    # input poison: plain NaN everywhere outside the view, and the integer view sees any change
+    ibuf, iview = embed(t, 0, 8, poison="nan")
+    snap = bits(ibuf).clone()
+    assert bool(torch.isnan(ibuf[:, C:]).all()) and torch.equal(iview, t) and torch.equal(bits(ibuf), snap)
+    ibuf[2, C + 1] = 1.0
+    assert not torch.equal(bits(ibuf), snap)

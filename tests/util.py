@@ -66,3 +66,46 @@ def check_update_deltas(z, names, deltas, lr=1e-3):
 def _e4m3_bytes(t):
     """e4m3 bytes of an fp32 tensor (saturating), as the kernels write them"""
     return t.clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+# ------------------------------------------------------------------------------------------- column views of wider buffers
+# A quiet NaN with a recognisable payload, per element width: arithmetic produces the canonical NaN (payload 0), never this one, so
+# "the kernel left this element alone" is an exact comparison of bits — through an integer view, for fp32 and bf16 alike.
+_POISON_BITS = {torch.float32: (torch.int32, 0x7FC5A5A5), torch.bfloat16: (torch.int16, 0x7FE5)}
+
+
+def bits(t):
+    """integer view of an fp32 / bf16 tensor (same shape, same memory)"""
+    return t.view(_POISON_BITS[t.dtype][0])
+
+
+def poison_bits(dtype):
+    """the output poison of embed() as the integer bits() shows it"""
+    return _POISON_BITS[dtype][1]
+
+
+def embed(t, left, right, *, poison):
+    """(M, C) tensor t -> (buf, view): buf a fresh (M, left + C + right) tensor of t's dtype and device, view = buf[:, left:left + C]
+    holding t, every other column poisoned: poison="nan" for an input operand (a result may not depend on a neighbour in any way, not
+    even multiplied by zero), poison="bits" for an output (the payload NaN above: assert_pads_untouched compares it bit for bit)."""
+    assert t.dim() == 2 and poison in ("nan", "bits")
+    M, C = t.shape
+    buf = torch.empty((M, left + C + right), dtype=t.dtype, device=t.device)
+    if poison == "nan":
+        buf.fill_(float("nan"))
+    else:
+        bits(buf).fill_(_POISON_BITS[t.dtype][1])
+    view = buf[:, left:left + C]
+    view.copy_(t)
+    return buf, view
+
+
+def assert_pads_untouched(buf, left, C, what):
+    """every column of buf outside [left, left + C) still holds the output poison of embed(); names the first touched (row, column)"""
+    want = _POISON_BITS[buf.dtype][1]
+    touched = bits(buf) != want
+    touched[:, left:left + C] = False
+    if bool(touched.any()):
+        r, c = (int(v) for v in touched.nonzero()[0])
+        raise AssertionError(f"{what}: pad element (row {r}, column {c}) of a {tuple(buf.shape)} buffer was written "
+                             f"(payload columns {left}..{left + C - 1}, bits {int(bits(buf)[r, c]) & (0xFFFFFFFF if buf.dtype == torch.float32 else 0xFFFF):#x})")
