@@ -2304,8 +2304,8 @@ class ActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, act):
         _need_gpu(x)
-        if x.dtype != torch.float32 or x.numel() % 4:
-            _unsupported("act", f"needs fp32 tokens with a multiple of 4 elements, got {x.dtype} x {x.numel()}")
+        if x.dtype != torch.float32 or x.numel() == 0:
+            _unsupported("act", f"needs non-empty fp32 tokens, got {x.dtype} x {x.numel()}")
         xc = x.contiguous()
         y = torch.empty_like(xc)
         lib.call("adnm_act_fwd", xc.data_ptr(), y.data_ptr(), xc.numel(), act, _stream())
@@ -2366,9 +2366,6 @@ def _conv3_wstrides(w):
     return sn, skw, sk
 
 
-_CONV3_DPRE_ONCE = [os.environ.get("ADNM_CONV3_DPRE_ONCE", "1") != "0"]   # (measurement aid: 0 = the gradient kernels apply act' themselves)
-
-
 class Conv3Fn(torch.autograd.Function):
     """nn.Conv2d(k=3, s=1, p=1) [+ bias] [+ GELU] on (B, H*W, Cin) tokens (csrc/conv3.hip): implicit GEMM on MFMA, bias and
     activation in the epilogue; the pre-activation is saved for backward exactly as autograd saves it for a separate GELU."""
@@ -2405,21 +2402,23 @@ class Conv3Fn(torch.autograd.Function):
         dev = x2.device
         dy2 = dy.reshape(B * H * W, N)
         dy2 = dy2 if dy2.stride(-1) == 1 else dy2.contiguous()
-        if act != lib.ACT_NONE and _CONV3_DPRE_ONCE[0] and dy2.is_contiguous() and (B * H * W * N) % 4 == 0:
-            # dpre = dy * act'(pre) ONCE, as one elementwise pass: both gradient kernels stage this product tile by tile — the input gradient
-            # once per output-channel group, the weight gradient once per 16-channel input chunk (4 x for a 64 -> 64 conv) — and their
-            # loads (two arrays + the erf) are ~half of their time (profiles/r04_conv3_phases.txt).  Same fp32 product, same rounding after.
+        if act != lib.ACT_NONE:
+            # dpre = dy * act'(pre) ONCE, as one elementwise pass (a strided cotangent is copied first): both gradient kernels stage this
+            # operand tile by tile — the input gradient once per output-channel group, the weight gradient once per 16-channel input chunk
+            # (4 x for a 64 -> 64 conv) — and with the product formed in their load path (two arrays + the erf) the loads were ~half of
+            # their time (profiles/r04_conv3_phases.txt).  Without an activation the cotangent goes to the kernels as it lies.
+            dy2 = dy2.contiguous()
             dpre = torch.empty_like(pre)
             lib.call("adnm_act_bwd", dy2.data_ptr(), pre.data_ptr(), dpre.data_ptr(), pre.numel(), act, _stream())
-            dy2, pre, act = dpre, None, lib.ACT_NONE
+            dy2 = dpre
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty((B * H * W, K), dtype=torch.float32, device=dev)
             nb = lib.query("adnm_conv3_ws_bytes", B, H, W, N, K)
             wsb = _ws(nb, dev)
             prec, qp = _gemm_prec(QUANT.record(dev, w.data_ptr(), "gc3", B * H * W), "g")
-            lib.call("adnm_conv3_dgrad", dy2.data_ptr(), dy2.stride(0), _p(pre), N, act, w.data_ptr(), ws_[0], ws_[1], ws_[2], dx.data_ptr(), K,
-                     wsb.data_ptr(), nb, B, H, W, K, N, prec, qp, _stream())
+            lib.call("adnm_conv3_dgrad", dy2.data_ptr(), dy2.stride(0), w.data_ptr(), ws_[0], ws_[1], ws_[2], dx.data_ptr(), K, wsb.data_ptr(), nb,
+                     B, H, W, K, N, prec, qp, _stream())
             dx = dx.view(B, H * W, K)
         # the weight gradient is produced in (Cout, 3, 3, Cin) memory order: the flat trainer's channels-last slice takes it as it lies
         # (a registered slice in any other layout is refused without being claimed: the trainer's gather then copies the gradient)
@@ -2431,8 +2430,8 @@ class Conv3Fn(torch.autograd.Function):
         wsb = _ws(nb, dev)
         prec = 1 if MFMA_PREC[0] == 2 or QUANT.calibrating else MFMA_PREC[0]   # fp8 configuration: bf16 operands here
         with FOLDS.defer(dev, wsb):
-            lib.call("adnm_conv3_wgrad", dy2.data_ptr(), dy2.stride(0), _p(pre), N, act, x2.data_ptr(), x2.stride(0), g.data_ptr(), _p(db),
-                     wsb.data_ptr(), nb, B, H, W, K, N, prec, _stream())
+            lib.call("adnm_conv3_wgrad", dy2.data_ptr(), dy2.stride(0), x2.data_ptr(), x2.stride(0), g.data_ptr(), _p(db), wsb.data_ptr(), nb,
+                     B, H, W, K, N, prec, _stream())
         return dx, g, db, None, None, None
 
 

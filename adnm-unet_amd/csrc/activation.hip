@@ -12,19 +12,25 @@ inline unsigned grid_for(int64_t n4) {
   return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
+// n4 = n / 4 float4 items grid-strided; the last n % 4 elements (index 4 n4 ..) by the first threads of workgroup 0, one scalar each
 template <int ACT>
-__global__ __launch_bounds__(kBlock) void act_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n4) {
+__global__ __launch_bounds__(kBlock) void act_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n4, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kBlock) {
     const float4 v = reinterpret_cast<const float4*>(x)[i];
     reinterpret_cast<float4*>(y)[i] = make_float4(act_fwd<ACT>(v.x), act_fwd<ACT>(v.y), act_fwd<ACT>(v.z), act_fwd<ACT>(v.w));
   }
+  const int64_t t = 4 * n4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) y[t] = act_fwd<ACT>(x[t]);
 }
 template <int ACT>
-__global__ __launch_bounds__(kBlock) void act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ pre, float* __restrict__ dpre, int64_t n4) {
+__global__ __launch_bounds__(kBlock) void act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ pre, float* __restrict__ dpre, int64_t n4,
+                                                         int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kBlock) {
     const float4 g = reinterpret_cast<const float4*>(dy)[i], p = reinterpret_cast<const float4*>(pre)[i];
     reinterpret_cast<float4*>(dpre)[i] = make_float4(g.x * act_grad<ACT>(p.x), g.y * act_grad<ACT>(p.y), g.z * act_grad<ACT>(p.z), g.w * act_grad<ACT>(p.w));
   }
+  const int64_t t = 4 * n4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) dpre[t] = dy[t] * act_grad<ACT>(pre[t]);
 }
 
 __global__ __launch_bounds__(kBlock) void swish_fwd_kernel(const float* __restrict__ x, const float* __restrict__ beta, float* __restrict__ y, int64_t n4) {
@@ -65,24 +71,24 @@ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace
 
 extern "C" int adnm_act_fwd(const float* x, float* y, int64_t n, int act, adnm_stream_t stream) {
-  ADNM_REQUIRE(x && y && n > 0 && n % 4 == 0 && al16(x) && al16(y), "act_fwd: needs 16-byte aligned fp32 arrays of a multiple of 4 elements (n=%lld)", (long long)n);
+  ADNM_REQUIRE(x && y && n > 0 && al16(x) && al16(y), "act_fwd: needs non-empty 16-byte aligned fp32 arrays (n=%lld)", (long long)n);
   ADNM_REQUIRE(act == ADNM_ACT_GELU || act == ADNM_ACT_SILU, "act_fwd: activation %d not in {silu, gelu}", act);
   hipStream_t st = (hipStream_t)stream;
   ADNM_PROF("act_fwd", st, 8.0 * n);
-  if (act == ADNM_ACT_GELU) act_fwd_kernel<ADNM_ACT_GELU><<<grid_for(n / 4), kBlock, 0, st>>>(x, y, n / 4);
-  else act_fwd_kernel<ADNM_ACT_SILU><<<grid_for(n / 4), kBlock, 0, st>>>(x, y, n / 4);
+  if (act == ADNM_ACT_GELU) act_fwd_kernel<ADNM_ACT_GELU><<<grid_for(n / 4), kBlock, 0, st>>>(x, y, n / 4, n);
+  else act_fwd_kernel<ADNM_ACT_SILU><<<grid_for(n / 4), kBlock, 0, st>>>(x, y, n / 4, n);
   ADNM_CHECK_LAUNCH("act_fwd");
   return ADNM_OK;
 }
 
 extern "C" int adnm_act_bwd(const float* dy, const float* pre, float* dpre, int64_t n, int act, adnm_stream_t stream) {
-  ADNM_REQUIRE(dy && pre && dpre && n > 0 && n % 4 == 0 && al16(dy) && al16(pre) && al16(dpre),
-               "act_bwd: needs 16-byte aligned fp32 arrays of a multiple of 4 elements (n=%lld)", (long long)n);
+  ADNM_REQUIRE(dy && pre && dpre && n > 0 && al16(dy) && al16(pre) && al16(dpre), "act_bwd: needs non-empty 16-byte aligned fp32 arrays (n=%lld)",
+               (long long)n);
   ADNM_REQUIRE(act == ADNM_ACT_GELU || act == ADNM_ACT_SILU, "act_bwd: activation %d not in {silu, gelu}", act);
   hipStream_t st = (hipStream_t)stream;
   ADNM_PROF("act_bwd", st, 12.0 * n);
-  if (act == ADNM_ACT_GELU) act_bwd_kernel<ADNM_ACT_GELU><<<grid_for(n / 4), kBlock, 0, st>>>(dy, pre, dpre, n / 4);
-  else act_bwd_kernel<ADNM_ACT_SILU><<<grid_for(n / 4), kBlock, 0, st>>>(dy, pre, dpre, n / 4);
+  if (act == ADNM_ACT_GELU) act_bwd_kernel<ADNM_ACT_GELU><<<grid_for(n / 4), kBlock, 0, st>>>(dy, pre, dpre, n / 4, n);
+  else act_bwd_kernel<ADNM_ACT_SILU><<<grid_for(n / 4), kBlock, 0, st>>>(dy, pre, dpre, n / 4, n);
   ADNM_CHECK_LAUNCH("act_bwd");
   return ADNM_OK;
 }

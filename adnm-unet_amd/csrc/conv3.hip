@@ -3,11 +3,11 @@
 // 64->32 (:376-387), OutProj.conv[0] 32->64 and conv2 20->20 (:818-849) — nn.Conv2d(k=3, s=1, p=1) [+ bias] [+ GELU].
 //
 //   forward   out[p, n]   = act( sum_{tap, k} in[p + tap, k] * W[n, tap, k] + bias[n] )       p = pixel, n = Cout, k = Cin
-//   dgrad     din[p, k]   = sum_{tap, n} dpre[p - tap, n] * W[n, tap, k]                      dpre = dout * act'(pre)
-//   wgrad     dW[n,tap,k] = sum_p dpre[p, n] * in[p + tap, k],   dbias[n] = sum_p dpre[p, n]
+//   dgrad     din[p, k]   = sum_{tap, n} dpre[p - tap, n] * W[n, tap, k]                      dpre = dout * act'(pre), formed by the
+//   wgrad     dW[n,tap,k] = sum_p dpre[p, n] * in[p + tap, k],   dbias[n] = sum_p dpre[p, n]   caller (adnm_act_bwd): a plain operand here
 //
 // One gather-GEMM kernel serves forward and dgrad (dgrad = the same conv over dpre with the weight read through swapped
-// strides and flipped taps); wgrad is a second kernel.  v_mfma_f32_16x16x4_f32 (exact fp32).  Layout choices:
+// strides and flipped taps) in every precision; wgrad is a second kernel.  v_mfma_f32_16x16x4_f32 (exact fp32).  Layout choices:
 //   * the batch is one TALL image: B images of H rows with ONE zero row between them, so "same" zero padding in y, image
 //     boundaries and small maps (4x4 ... 16x16: a 16-pixel MFMA block = 16/W rows x W columns) are all the same tile code;
 //   * a workgroup (4 waves) owns a tile of 8 pixel blocks and up to 64 output channels; the input tile + halo of a 16-channel
@@ -46,7 +46,6 @@ inline Geo make_geo(int64_t B, int64_t H, int64_t W) {
 
 struct ConvArgs {
   const float* in;  int64_t ldin;     // (B*H*W, K) pixel rows
-  const float* in2; int64_t ldin2;    // dgrad: pre-activation of the forward output; the staged value is in * act'(in2)
   const float* w; int64_t sn, st, sk; int flip;   // W(n, tap, k) = w[n*sn + (flip ? 8-tap : tap)*st + k*sk]
   const float* bias;
   float* out; int64_t ldo;            // act(acc + bias)
@@ -65,41 +64,88 @@ __device__ __forceinline__ int64_t pixel_of(int v, int x, int B, int H, int W, i
   return y < H ? ((int64_t)b * H + y) * W + x : -1;
 }
 
-// ---- stage the (TH+2) x (TW+2) tile of channels [c0, c0+16) of (in [* act'(in2)]) into LDS, zeros outside
-// (scale: the fp8 mode stages value * scale; amax: running max |value| of what this thread staged, before scaling)
-template <int ACT>
-__device__ __forceinline__ void stage_tile(const float* __restrict__ in, int64_t ldin, const float* __restrict__ in2, int64_t ldin2, bool vec,
-                                           int K, int B, int H, int W, int VR, int TW, int TH, float* sIn, int v0, int x0, int c0,
-                                           float scale = 1.f, float* amax = nullptr) {
-  const int TWp = TW + 2, PT = (TH + 2) * TWp;
-  for (int it = threadIdx.x; it < PT * 4; it += kBlock) {
-    const int pix = it >> 2, q = it & 3, r = pix / TWp, c = pix - r * TWp, ch = c0 + 4 * q;
-    const int64_t p = pixel_of(v0 - 1 + r, x0 - 1 + c, B, H, W, VR);
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (p >= 0 && ch < K) {
-      if (vec && ch + 3 < K) {
-        const float4 t = *reinterpret_cast<const float4*>(in + p * ldin + ch);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-        if (ACT != ADNM_ACT_NONE) {
-          const float4 u = *reinterpret_cast<const float4*>(in2 + p * ldin2 + ch);
-          v[0] *= act_grad<ACT>(u.x); v[1] *= act_grad<ACT>(u.y); v[2] *= act_grad<ACT>(u.z); v[3] *= act_grad<ACT>(u.w);
+// ---- the two gathers of a chunk from global memory into registers.  An item is V consecutive floats of the reduction axis: V = 4 for
+// fp32 LDS images, 8 for bf16 ones (same item count, twice the channels).  16-byte loads where legal, scalar loads on a ragged end; zeros
+// outside the images and from channel kend on.
+constexpr int kItIn = 4;   // halo-tile items per thread: (TH+2)(TW+2) pixels x 4 channel groups / 256 <= 3.2
+
+// item it = (pixel it >> 2 of the (TH+2) x (TW+2) halo tile at (v0 - 1, x0 - 1), channels c0 + V*(it & 3) .. + V) of the pixel rows `in`
+template <int V, class Args>
+__device__ __forceinline__ void gather_pixels(const Args& a, const float* in, int64_t ldin, int vec, int v0, int x0, int c0, int kend,
+                                              float (&reg)[kItIn][V]) {
+  const int TWp = a.TW + 2, PT = (a.TH + 2) * TWp;
+#pragma unroll
+  for (int u = 0; u < kItIn; ++u) {
+    const int it = threadIdx.x + u * kBlock;
+    const int pix = it >> 2, q = it & 3, r = pix / TWp, cc = pix - r * TWp, ch = c0 + V * q;
+    const int64_t p = it < PT * 4 ? pixel_of(v0 - 1 + r, x0 - 1 + cc, a.B, a.H, a.W, a.VR) : -1;
+    float v[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) v[e] = 0.f;
+    if (p >= 0 && ch < kend) {
+      if (vec && ch + V - 1 < kend) {
+#pragma unroll
+        for (int h = 0; h < V; h += 4) {
+          const float4 t = *reinterpret_cast<const float4*>(in + p * ldin + ch + h);
+          v[h] = t.x; v[h + 1] = t.y; v[h + 2] = t.z; v[h + 3] = t.w;
         }
       } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (ch + e < K) {
-            v[e] = in[p * ldin + ch + e];
-            if (ACT != ADNM_ACT_NONE) v[e] *= act_grad<ACT>(in2[p * ldin2 + ch + e]);
-          }
+        for (int e = 0; e < V; ++e)
+          if (ch + e < kend) v[e] = in[p * ldin + ch + e];
       }
     }
-    if (amax) *amax = adnm_amax4(*amax, v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4*>(sIn + pix * CKP + 4 * q) = make_float4(v[0] * scale, v[1] * scale, v[2] * scale, v[3] * scale);
+#pragma unroll
+    for (int e = 0; e < V; ++e) reg[u][e] = v[e];
   }
 }
 
+// item it = (tap it / (NB*64), output channel n0 + (it >> 2) % (NB*16), channels c0 + V*(it & 3) .. + V) of the weight
+template <int V, int NB, int NIT>
+__device__ __forceinline__ void gather_weights(const ConvArgs& a, int n0, int c0, int kend, float (&reg)[NIT][V]) {
+#pragma unroll
+  for (int u = 0; u < NIT; ++u) {
+    const int it = threadIdx.x + u * kBlock;
+    const int kq = it & 3, nl = (it >> 2) % (NB * 16), tap = it / (NB * 64);
+    const int n = n0 + nl, k0 = c0 + V * kq;
+    float v[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) v[e] = 0.f;
+    if (it < 9 * NB * 64 && n < a.N && k0 < kend) {
+      const float* wp = a.w + (int64_t)n * a.sn + (int64_t)(a.flip ? 8 - tap : tap) * a.st + (int64_t)k0 * a.sk;
+      if (a.vec_w && k0 + V - 1 < kend) {
+#pragma unroll
+        for (int h = 0; h < V; h += 4) {
+          const float4 t = *reinterpret_cast<const float4*>(wp + h);
+          v[h] = t.x; v[h + 1] = t.y; v[h + 2] = t.z; v[h + 3] = t.w;
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < V; ++e)
+          if (k0 + e < kend) v[e] = wp[(int64_t)e * a.sk];
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) reg[u][e] = v[e];
+  }
+}
+
+// a gathered item on its way to LDS (16 bytes either way): fp32 x scale, or rounded ONCE to bf16; and its max |value| before that
+template <int V>
+__device__ __forceinline__ void put_item(float* dst, const float (&v)[V], float scale) {
+  if constexpr (V == 8) *reinterpret_cast<adnm_bf16x8*>(dst) = adnm_pack_bf16x8(v);
+  else *reinterpret_cast<float4*>(dst) = make_float4(v[0] * scale, v[1] * scale, v[2] * scale, v[3] * scale);
+}
+template <int V>
+__device__ __forceinline__ float amax_item(float m, const float (&v)[V]) {
+  m = adnm_amax4(m, v[0], v[1], v[2], v[3]);
+  if constexpr (V == 8) m = adnm_amax4(m, v[4], v[5], v[6], v[7]);
+  return m;
+}
+
+
 // ================================================================================================ forward / dgrad
-// epilogue shared by the two gather-GEMM kernels: bias, activation, pre-activation copy, or the split run's partial tile.
+// epilogue of the gather-GEMM kernel: bias, activation, pre-activation copy, or the split run's partial tile.
 // (Measured, round 4: parking the tile in LDS to write whole pixel rows — NB*64 contiguous bytes instead of 64 — gained 4 us on the
 // full-resolution GELU convs and lost 1-2 us on every other one to its two barriers: not kept.  tools/kbench_conv.py)
 template <int NB, int ACT_OUT>
@@ -139,13 +185,24 @@ __device__ __forceinline__ void conv3_epilogue(const ConvArgs& a, const f32x4 (&
 }
 
 // LDS: [input tile (TH+2)(TW+2) x CKP] [weights of the chunk: 9 taps x NB*16 channels x CKP]
-// PREC = ADNM_MFMA_*; A_BF8: in the fp8 mode the pixel rows are a gradient (e5m2) — the dgrad use.
-template <int NB, int ACT_IN, int ACT_OUT, int PREC, bool A_BF8>
+// MODE = ADNM_MFMA_* (FP8_GRAD: the fp8 mode with the pixel rows a gradient, e5m2 — the dgrad use).  What depends on it:
+//   * F32 / FP8 / FP8_GRAD keep fp32 LDS images — a chunk is 16 channels, staged already multiplied by the per-tensor scales in the fp8
+//     modes (the accumulators are un-scaled before the epilogue) — and a lane forms its fragment of a 32-step MFMA group from two 16-byte
+//     LDS reads: the chunk's 16 channels of TWO taps (tap 8 runs on a zero upper half);
+//   * BF16 keeps bf16 IMAGES (round 4): with fp32 images every staged value was converted by each of the 9 taps (x the NB / MB blocks
+//     that share it).  Here a value is rounded ONCE when its chunk is staged; the same 80-byte pixel pitch holds 32 channels, a lane's
+//     fragment is ONE ds_read_b128 (8 channels of one tap; conflict-free as before: 5 is coprime with 16), a chunk is 32 channels of all
+//     nine taps (no half-empty step for the ninth) and there are half as many chunk rounds (two barriers each).  Same results as rounding
+//     per use up to the fp32 summation order inside the accumulator.
+template <int NB, int ACT_OUT, int MODE>
 __global__ __launch_bounds__(kBlock) void conv3_kernel(ConvArgs a) {
+  constexpr int PREC = MODE == ADNM_MFMA_FP8_GRAD ? ADNM_MFMA_FP8 : MODE;
+  constexpr bool A_BF8 = MODE == ADNM_MFMA_FP8_GRAD, BF_IMAGES = MODE == ADNM_MFMA_BF16;
+  constexpr int V = BF_IMAGES ? 8 : 4, CN = 4 * V;   // floats per gathered item, channels per chunk
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  // fp8: the tile and the weights are staged already multiplied by their per-tensor scales (the accumulators are un-scaled in the
-  // epilogue); rec_a / rec_b (workgroup-uniform): collect max |value| of the pixels / weights staged — the first channel group /
-  // first pixel tile only, so every element is seen once (halo pixels twice, harmless for a max)
+  // rec_a / rec_b (workgroup-uniform): collect max |value| of the pixels / weights staged — the first channel group / first pixel tile
+  // only, so every element is seen once (halo pixels twice, harmless for a max).  A calibrating pass of the fp8 configuration runs bf16
+  // operands and collects here as well.
   float q_sa = 1.f, q_sb = 1.f, amax_a = 0.f, amax_b = 0.f;
   bool rec_a = false, rec_b = false;
   if (a.q) {
@@ -168,121 +225,90 @@ __global__ __launch_bounds__(kBlock) void conv3_kernel(ConvArgs a) {
   for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) acc[nb][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nchunks = (a.K + CK - 1) / CK;
-  const int cbeg = blockIdx.z * a.chunks_per_split;
-  const int cend = cbeg + a.chunks_per_split < nchunks ? cbeg + a.chunks_per_split : nchunks;
-  // Register-staged pipeline over the 16-channel chunks: the global loads of chunk c+1 (input tile + halo, the chunk's weights) are
-  // issued right after chunk c went to LDS and fly under its 9-tap MFMA loop — one exposed memory round trip per workgroup instead of one
-  // per chunk (these kernels ran at ~1 TB/s on the 128x128 maps: 2-4 chunks x two barriers with the loads in between).
-  constexpr int kItIn = 4;                                   // input items per thread: (TH+2)(TW+2) pixels x 4 channel quads / 256 <= 3.2
-  constexpr int kItW = (9 * NB * 64 + kBlock - 1) / kBlock;   // weight items per thread
+  // this split's channel range (chunks_per_split counts 16-channel units and is even for split runs: plan_split)
+  const int kbeg = blockIdx.z * a.chunks_per_split * CK;
+  const int kend = kbeg + a.chunks_per_split * CK < a.K ? kbeg + a.chunks_per_split * CK : a.K;
+  // Register-staged pipeline over the chunks: the global loads of the next chunk (input tile + halo, the chunk's weights) are issued right
+  // after this one went to LDS and fly under its 9-tap MFMA loop — one exposed memory round trip per workgroup instead of one per chunk
+  // (these kernels ran at ~1 TB/s on the 128x128 maps: 2-4 chunks x two barriers with the loads in between).
+  constexpr int kItW = (9 * NB * 64 + kBlock - 1) / kBlock;   // weight items per thread: 9 taps x NB*16 output channels x 4 groups
   const int PT = (a.TH + 2) * TWp;
-  float rin[kItIn][4], rw[kItW][4];
-  auto load_chunk = [&](int c) {
-    const int c0 = c * CK;
-#pragma unroll
-    for (int u = 0; u < kItIn; ++u) {
-      const int it = threadIdx.x + u * kBlock;
-      const int pix = it >> 2, q = it & 3, r = pix / TWp, cc = pix - r * TWp, ch = c0 + 4 * q;
-      const int64_t p = it < PT * 4 ? pixel_of(v0 - 1 + r, x0 - 1 + cc, a.B, a.H, a.W, a.VR) : -1;
-      float v[4] = {0.f, 0.f, 0.f, 0.f};
-      if (p >= 0 && ch < a.K) {
-        if (a.vec_in && ch + 3 < a.K) {
-          const float4 t = *reinterpret_cast<const float4*>(a.in + p * a.ldin + ch);
-          v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-          if (ACT_IN != ADNM_ACT_NONE) {
-            const float4 g = *reinterpret_cast<const float4*>(a.in2 + p * a.ldin2 + ch);
-            v[0] *= act_grad<ACT_IN>(g.x); v[1] *= act_grad<ACT_IN>(g.y); v[2] *= act_grad<ACT_IN>(g.z); v[3] *= act_grad<ACT_IN>(g.w);
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (ch + e < a.K) {
-              v[e] = a.in[p * a.ldin + ch + e];
-              if (ACT_IN != ADNM_ACT_NONE) v[e] *= act_grad<ACT_IN>(a.in2[p * a.ldin2 + ch + e]);
-            }
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) rin[u][e] = v[e];
-    }
-    // weights of this chunk: sW[(tap*NB*16 + nl)*CKP + kq*4 .. +3] = W(n0 + nl, tap, c*16 + 4 kq ..)
-#pragma unroll
-    for (int u = 0; u < kItW; ++u) {
-      const int it = threadIdx.x + u * kBlock;
-      const int kq = it & 3, nl = (it >> 2) % (NB * 16), tap = it / (NB * 64);
-      const int n = n0 + nl, k0 = c0 + 4 * kq;
-      float v[4] = {0.f, 0.f, 0.f, 0.f};
-      if (it < 9 * NB * 64 && n < a.N && k0 < a.K) {
-        const float* wp = a.w + (int64_t)n * a.sn + (int64_t)(a.flip ? 8 - tap : tap) * a.st + (int64_t)k0 * a.sk;
-        if (a.vec_w && k0 + 3 < a.K) {
-          const float4 t = *reinterpret_cast<const float4*>(wp);
-          v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (k0 + e < a.K) v[e] = wp[(int64_t)e * a.sk];
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) rw[u][e] = v[e];
-    }
+  float rin[kItIn][V], rw[kItW][V];
+  auto load_chunk = [&](int c0) {
+    gather_pixels<V>(a, a.in, a.ldin, a.vec_in, v0, x0, c0, kend, rin);
+    gather_weights<V, NB>(a, n0, c0, kend, rw);
   };
   auto store_chunk = [&]() {
 #pragma unroll
     for (int u = 0; u < kItIn; ++u) {
       const int it = threadIdx.x + u * kBlock;
       if (it >= PT * 4) break;
-      if (rec_a) amax_a = adnm_amax4(amax_a, rin[u][0], rin[u][1], rin[u][2], rin[u][3]);
-      *reinterpret_cast<float4*>(sIn + (it >> 2) * CKP + 4 * (it & 3)) = make_float4(rin[u][0] * q_sa, rin[u][1] * q_sa, rin[u][2] * q_sa, rin[u][3] * q_sa);
+      if (rec_a) amax_a = amax_item<V>(amax_a, rin[u]);
+      put_item<V>(sIn + (it >> 2) * CKP + 4 * (it & 3), rin[u], q_sa);
     }
+    // sW[(tap*NB*16 + nl)*CKP + 4 kq]: the item W(n0 + nl, tap, c0 + V kq ..)
 #pragma unroll
     for (int u = 0; u < kItW; ++u) {
       const int it = threadIdx.x + u * kBlock;
       if (it >= 9 * NB * 64) break;
       const int kq = it & 3, nl = (it >> 2) % (NB * 16), tap = it / (NB * 64);
-      if (rec_b) amax_b = adnm_amax4(amax_b, rw[u][0], rw[u][1], rw[u][2], rw[u][3]);
-      *reinterpret_cast<float4*>(sW + (tap * NB * 16 + nl) * CKP + 4 * kq) = make_float4(rw[u][0] * q_sb, rw[u][1] * q_sb, rw[u][2] * q_sb, rw[u][3] * q_sb);
+      if (rec_b) amax_b = amax_item<V>(amax_b, rw[u]);
+      put_item<V>(sW + (tap * NB * 16 + nl) * CKP + 4 * kq, rw[u], q_sb);
     }
   };
-  if (cbeg < cend) load_chunk(cbeg);
-  for (int c = cbeg; c < cend; ++c) {
+  if (kbeg < kend) load_chunk(kbeg);
+  for (int c0 = kbeg; c0 < kend; c0 += CN) {
     __syncthreads();   // every wave has finished reading the previous chunk's LDS images
     store_chunk();
     __syncthreads();
-    if (c + 1 < cend) load_chunk(c + 1);   // in flight under this chunk's MFMAs
-    // one MFMA step = 32 reduction steps = the chunk's 16 channels of TWO taps (tap 8 runs on a zero upper half)
+    if (c0 + CN < kend) load_chunk(c0 + CN);   // in flight under this chunk's MFMAs
+    if constexpr (BF_IMAGES) {
 #pragma unroll
-    for (int tp = 0; tp < 9; tp += 2) {
-      float wa[NB][2][4], xb[MB][2][4];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int tap = tp + h < 9 ? tp + h : 8;
+      for (int tap = 0; tap < 9; ++tap) {
         const int toff = ((tap / 3) * TWp + (tap % 3)) * CKP;
+        adnm_bf16x8 fw[NB], fx[MB];
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-          const float4 t = *reinterpret_cast<const float4*>(sW + (tap * NB * 16 + nb * 16 + j) * CKP + 4 * kk);
-          wa[nb][h][0] = t.x; wa[nb][h][1] = t.y; wa[nb][h][2] = t.z; wa[nb][h][3] = t.w;
-        }
+        for (int nb = 0; nb < NB; ++nb) fw[nb] = *reinterpret_cast<const adnm_bf16x8*>(sW + (tap * NB * 16 + nb * 16 + j) * CKP + 4 * kk);
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb) {
-          const float4 t = *reinterpret_cast<const float4*>(sIn + base[mb] + toff);
-          xb[mb][h][0] = t.x; xb[mb][h][1] = t.y; xb[mb][h][2] = t.z; xb[mb][h][3] = t.w;
-        }
+        for (int mb = 0; mb < MB; ++mb) fx[mb] = *reinterpret_cast<const adnm_bf16x8*>(sIn + base[mb] + toff);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+          for (int mb = 0; mb < MB; ++mb) acc[nb][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[nb], fx[mb], acc[nb][mb], 0, 0, 0);
       }
-      const bool pair = tp + 1 < 9;
-      AdnmFrag<PREC> fw[NB], fx[MB];
+    } else {
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) fw[nb] = adnm_make_frag<PREC, false>(wa[nb][0], pair ? wa[nb][1] : nullptr, 1.f);   // (already scaled)
+      for (int tp = 0; tp < 9; tp += 2) {
+        float wa[NB][2][4], xb[MB][2][4];
 #pragma unroll
-      for (int mb = 0; mb < MB; ++mb) fx[mb] = adnm_make_frag<PREC, A_BF8>(xb[mb][0], pair ? xb[mb][1] : nullptr, 1.f);
+        for (int h = 0; h < 2; ++h) {
+          const int tap = tp + h < 9 ? tp + h : 8;
+          const int toff = ((tap / 3) * TWp + (tap % 3)) * CKP;
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
+          for (int nb = 0; nb < NB; ++nb) {
+            const float4 t = *reinterpret_cast<const float4*>(sW + (tap * NB * 16 + nb * 16 + j) * CKP + 4 * kk);
+            wa[nb][h][0] = t.x; wa[nb][h][1] = t.y; wa[nb][h][2] = t.z; wa[nb][h][3] = t.w;
+          }
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb) {
-          if (tp + 1 < 9) acc[nb][mb] = adnm_mma<PREC, false, A_BF8, false>(fw[nb], fx[mb], acc[nb][mb]);
-          else acc[nb][mb] = adnm_mma<PREC, false, A_BF8, true>(fw[nb], fx[mb], acc[nb][mb]);
+          for (int mb = 0; mb < MB; ++mb) {
+            const float4 t = *reinterpret_cast<const float4*>(sIn + base[mb] + toff);
+            xb[mb][h][0] = t.x; xb[mb][h][1] = t.y; xb[mb][h][2] = t.z; xb[mb][h][3] = t.w;
+          }
         }
+        const bool pair = tp + 1 < 9;
+        AdnmFrag<PREC> fw[NB], fx[MB];
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) fw[nb] = adnm_make_frag<PREC, false>(wa[nb][0], pair ? wa[nb][1] : nullptr, 1.f);   // (already scaled)
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb) fx[mb] = adnm_make_frag<PREC, A_BF8>(xb[mb][0], pair ? xb[mb][1] : nullptr, 1.f);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+          for (int mb = 0; mb < MB; ++mb) {
+            if (tp + 1 < 9) acc[nb][mb] = adnm_mma<PREC, false, A_BF8, false>(fw[nb], fx[mb], acc[nb][mb]);
+            else acc[nb][mb] = adnm_mma<PREC, false, A_BF8, true>(fw[nb], fx[mb], acc[nb][mb]);
+          }
+      }
     }
   }
   if (rec_a) adnm_amax_commit(&a.q->amax_a, amax_a);
@@ -297,135 +323,6 @@ __global__ __launch_bounds__(kBlock) void conv3_kernel(ConvArgs a) {
   conv3_epilogue<NB, ACT_OUT>(a, acc, wave, kk, dyj, dxj, x0, v0, n0);
 }
 
-// ---- the bf16 configuration: bf16 IMAGES in LDS (round 4).  conv3_kernel keeps fp32 images and rounds where a lane forms its fragment —
-// every staged value is read by 9 taps (x the NB / MB blocks that share it), so it was converted nine times over, and a fragment cost two
-// 16-byte LDS reads.  Here a value is rounded ONCE when its tile is staged; the same 80-byte pixel pitch now holds 32 channels, a lane's
-// fragment of a 32-step MFMA is ONE ds_read_b128 (8 channels of one tap; conflict-free as before: 5 is coprime with 16), a chunk is 32
-// channels of all nine taps (no half-empty step for the ninth tap), and there are half as many chunk rounds (two barriers each).
-// Same results as rounding per use up to the fp32 summation order inside the accumulator.
-template <int NB, int ACT_IN, int ACT_OUT>
-__global__ __launch_bounds__(kBlock) void conv3_bf16_kernel(ConvArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int CN = 2 * CK;   // channels per chunk
-  float amax_a = 0.f, amax_b = 0.f;
-  bool rec_a = false, rec_b = false;
-  if (a.q) {   // a calibrating pass of the fp8 configuration runs bf16 operands and collects the amax of what it staged
-    const bool rec = a.q->record != 0.f;
-    rec_a = rec && blockIdx.y == 0, rec_b = rec && blockIdx.x == 0;
-  }
-  const int TWp = a.TW + 2;
-  float* sIn = smem;
-  float* sW = smem + (a.TH + 2) * TWp * CKP;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, kk = lane >> 4;
-  const int tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x;
-  const int x0 = tx * a.TW, v0 = ty * a.TH, n0 = blockIdx.y * NB * 16;
-  const int dyj = j / a.TW, dxj = j - dyj * a.TW;
-  int base[MB];
-#pragma unroll
-  for (int mb = 0; mb < MB; ++mb) base[mb] = (((wave * MB + mb) * a.RB + dyj) * TWp + dxj) * CKP + 4 * kk;
-  f32x4 acc[NB][MB];
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb) acc[nb][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // this split's channel range (chunks_per_split counts 16-channel units and is even for split runs: plan_split)
-  const int kbeg = blockIdx.z * a.chunks_per_split * CK;
-  const int kend = kbeg + a.chunks_per_split * CK < a.K ? kbeg + a.chunks_per_split * CK : a.K;
-  constexpr int kItIn = 4;                                    // (TH+2)(TW+2) pixels x 4 channel octets / 256 <= 3.2
-  constexpr int kItW = (9 * NB * 64 + kBlock - 1) / kBlock;   // 9 taps x NB*16 output channels x 4 octets
-  const int PT = (a.TH + 2) * TWp;
-  float rin[kItIn][8], rw[kItW][8];
-  auto load_chunk = [&](int c0) {
-#pragma unroll
-    for (int u = 0; u < kItIn; ++u) {
-      const int it = threadIdx.x + u * kBlock;
-      const int pix = it >> 2, q = it & 3, r = pix / TWp, cc = pix - r * TWp, ch = c0 + 8 * q;
-      const int64_t p = it < PT * 4 ? pixel_of(v0 - 1 + r, x0 - 1 + cc, a.B, a.H, a.W, a.VR) : -1;
-      float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (p >= 0 && ch < kend) {
-        if (a.vec_in && ch + 7 < kend) {
-          const float4 t0 = *reinterpret_cast<const float4*>(a.in + p * a.ldin + ch), t1 = *reinterpret_cast<const float4*>(a.in + p * a.ldin + ch + 4);
-          v[0] = t0.x; v[1] = t0.y; v[2] = t0.z; v[3] = t0.w; v[4] = t1.x; v[5] = t1.y; v[6] = t1.z; v[7] = t1.w;
-          if (ACT_IN != ADNM_ACT_NONE) {   // (applied here, not when the chunk goes to LDS: between the barriers it was 35 % slower)
-            const float4 g0 = *reinterpret_cast<const float4*>(a.in2 + p * a.ldin2 + ch), g1 = *reinterpret_cast<const float4*>(a.in2 + p * a.ldin2 + ch + 4);
-            v[0] *= act_grad<ACT_IN>(g0.x); v[1] *= act_grad<ACT_IN>(g0.y); v[2] *= act_grad<ACT_IN>(g0.z); v[3] *= act_grad<ACT_IN>(g0.w);
-            v[4] *= act_grad<ACT_IN>(g1.x); v[5] *= act_grad<ACT_IN>(g1.y); v[6] *= act_grad<ACT_IN>(g1.z); v[7] *= act_grad<ACT_IN>(g1.w);
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            if (ch + e < kend) {
-              v[e] = a.in[p * a.ldin + ch + e];
-              if (ACT_IN != ADNM_ACT_NONE) v[e] *= act_grad<ACT_IN>(a.in2[p * a.ldin2 + ch + e]);
-            }
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) rin[u][e] = v[e];
-    }
-    // weights of this chunk: the octet at sW[(tap*NB*16 + nl)*CKP + 4 kq] = W(n0 + nl, tap, c0 + 8 kq ..)
-#pragma unroll
-    for (int u = 0; u < kItW; ++u) {
-      const int it = threadIdx.x + u * kBlock;
-      const int kq = it & 3, nl = (it >> 2) % (NB * 16), tap = it / (NB * 64);
-      const int n = n0 + nl, k0 = c0 + 8 * kq;
-      float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (it < 9 * NB * 64 && n < a.N && k0 < kend) {
-        const float* wp = a.w + (int64_t)n * a.sn + (int64_t)(a.flip ? 8 - tap : tap) * a.st + (int64_t)k0 * a.sk;
-        if (a.vec_w && k0 + 7 < kend) {
-          const float4 t0 = *reinterpret_cast<const float4*>(wp), t1 = *reinterpret_cast<const float4*>(wp + 4);
-          v[0] = t0.x; v[1] = t0.y; v[2] = t0.z; v[3] = t0.w; v[4] = t1.x; v[5] = t1.y; v[6] = t1.z; v[7] = t1.w;
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            if (k0 + e < kend) v[e] = wp[(int64_t)e * a.sk];
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) rw[u][e] = v[e];
-    }
-  };
-  auto store_chunk = [&]() {
-#pragma unroll
-    for (int u = 0; u < kItIn; ++u) {
-      const int it = threadIdx.x + u * kBlock;
-      if (it >= PT * 4) break;
-      if (rec_a) amax_a = adnm_amax4(adnm_amax4(amax_a, rin[u][0], rin[u][1], rin[u][2], rin[u][3]), rin[u][4], rin[u][5], rin[u][6], rin[u][7]);
-      *reinterpret_cast<adnm_bf16x8*>(sIn + (it >> 2) * CKP + 4 * (it & 3)) = adnm_pack_bf16x8(rin[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < kItW; ++u) {
-      const int it = threadIdx.x + u * kBlock;
-      if (it >= 9 * NB * 64) break;
-      const int kq = it & 3, nl = (it >> 2) % (NB * 16), tap = it / (NB * 64);
-      if (rec_b) amax_b = adnm_amax4(adnm_amax4(amax_b, rw[u][0], rw[u][1], rw[u][2], rw[u][3]), rw[u][4], rw[u][5], rw[u][6], rw[u][7]);
-      *reinterpret_cast<adnm_bf16x8*>(sW + (tap * NB * 16 + nl) * CKP + 4 * kq) = adnm_pack_bf16x8(rw[u]);
-    }
-  };
-  if (kbeg < kend) load_chunk(kbeg);
-  for (int c0 = kbeg; c0 < kend; c0 += CN) {
-    __syncthreads();   // every wave has finished reading the previous chunk's LDS images
-    store_chunk();
-    __syncthreads();
-    if (c0 + CN < kend) load_chunk(c0 + CN);   // in flight under this chunk's MFMAs
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int toff = ((tap / 3) * TWp + (tap % 3)) * CKP;
-      adnm_bf16x8 fw[NB], fx[MB];
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) fw[nb] = *reinterpret_cast<const adnm_bf16x8*>(sW + (tap * NB * 16 + nb * 16 + j) * CKP + 4 * kk);
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb) fx[mb] = *reinterpret_cast<const adnm_bf16x8*>(sIn + base[mb] + toff);
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) acc[nb][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[nb], fx[mb], acc[nb][mb], 0, 0, 0);
-    }
-  }
-  if (rec_a) adnm_amax_commit(&a.q->amax_a, amax_a);
-  if (rec_b) adnm_amax_commit(&a.q->amax_b, amax_b);
-  conv3_epilogue<NB, ACT_OUT>(a, acc, wave, kk, dyj, dxj, x0, v0, n0);
-}
 
 // split runs: out = act(sum_z part[z] + bias) (+ pre), one float4 per thread
 template <int ACT_OUT>
@@ -448,8 +345,7 @@ __global__ __launch_bounds__(256) void conv3_join_kernel(const float* __restrict
 
 // ================================================================================================ wgrad
 struct WgArgs {
-  const float* dout; int64_t lddo;    // (M, N)
-  const float* pre;  int64_t ldpre;   // pre-activation of the forward output (ACT != NONE)
+  const float* dout; int64_t lddo;    // (M, N): dpre
   const float* in;   int64_t ldin;    // (M, K)
   float* part; int64_t rowlen;        // partial rows [gridDim.x][N*9*K (+ N)]
   int want_bias;
@@ -458,7 +354,7 @@ struct WgArgs {
   int vec_in, vec_do;
 };
 
-template <int NB, int ACT, int PREC>   // PREC: fp32 or bf16 (the fp8 configuration keeps bf16 operands for the weight gradient)
+template <int NB, int PREC>   // PREC: fp32 or bf16 (the fp8 configuration keeps bf16 operands for the weight gradient)
 __global__ __launch_bounds__(kBlock) void conv3_wgrad_kernel(WgArgs a) {
   constexpr int DP = NB * 16 + 16;   // pitch of a dpre pixel row: (DP mod 32) == 16 -> conflict-free A-operand reads
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -473,32 +369,14 @@ __global__ __launch_bounds__(kBlock) void conv3_wgrad_kernel(WgArgs a) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) acc[t][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
   float bsum = 0.f;
-  // Register-staged pipeline over the pixel tiles (as in conv3_kernel): the loads of the NEXT tile (input tile + halo, dout [* act'(pre)])
+  // Register-staged pipeline over the pixel tiles (as in conv3_kernel): the loads of the NEXT tile (input tile + halo, dpre)
   // fly under the current tile's MFMAs.
-  constexpr int kItIn = 4, kItD = (kTilePix * NB * 4 + kBlock - 1) / kBlock;
+  constexpr int kItD = (kTilePix * NB * 4 + kBlock - 1) / kBlock;
   const int PT = (a.TH + 2) * TWp;
   float rin[kItIn][4], rd[kItD][4];
   auto load_tile = [&](int tile) {
     const int tx = tile % a.tiles_x, ty = tile / a.tiles_x, x0 = tx * a.TW, v0 = ty * a.TH;
-#pragma unroll
-    for (int u = 0; u < kItIn; ++u) {
-      const int it = threadIdx.x + u * kBlock;
-      const int pix = it >> 2, q = it & 3, r = pix / TWp, cc = pix - r * TWp, ch = c0 + 4 * q;
-      const int64_t p = it < PT * 4 ? pixel_of(v0 - 1 + r, x0 - 1 + cc, a.B, a.H, a.W, a.VR) : -1;
-      float v[4] = {0.f, 0.f, 0.f, 0.f};
-      if (p >= 0 && ch < a.K) {
-        if (a.vec_in && ch + 3 < a.K) {
-          const float4 t = *reinterpret_cast<const float4*>(a.in + p * a.ldin + ch);
-          v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (ch + e < a.K) v[e] = a.in[p * a.ldin + ch + e];
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) rin[u][e] = v[e];
-    }
+    gather_pixels<4>(a, a.in, a.ldin, a.vec_in, v0, x0, c0, a.K, rin);
     // dpre tile: pixel block pb (0..7), pixel jj of it -> row pb*16 + jj; NB*16 channels from n0
 #pragma unroll
     for (int u = 0; u < kItD; ++u) {
@@ -511,17 +389,10 @@ __global__ __launch_bounds__(kBlock) void conv3_wgrad_kernel(WgArgs a) {
         if (a.vec_do && n + 3 < a.N) {
           const float4 t = *reinterpret_cast<const float4*>(a.dout + p * a.lddo + n);
           v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-          if (ACT != ADNM_ACT_NONE) {
-            const float4 g = *reinterpret_cast<const float4*>(a.pre + p * a.ldpre + n);
-            v[0] *= act_grad<ACT>(g.x); v[1] *= act_grad<ACT>(g.y); v[2] *= act_grad<ACT>(g.z); v[3] *= act_grad<ACT>(g.w);
-          }
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            if (n + e < a.N) {
-              v[e] = a.dout[p * a.lddo + n + e];
-              if (ACT != ADNM_ACT_NONE) v[e] *= act_grad<ACT>(a.pre[p * a.ldpre + n + e]);
-            }
+            if (n + e < a.N) v[e] = a.dout[p * a.lddo + n + e];
         }
       }
 #pragma unroll
@@ -634,31 +505,26 @@ inline Split plan_split(const Geo& g, int64_t K, int64_t N) {
     if (want < 1) want = 1;
   }
   s.cps = (int)adnm_cdiv(nchunks, want);
-  if (want > 1 && (s.cps & 1)) ++s.cps;   // whole 32-channel chunks per split: the bf16 kernel's chunk is two of these units
+  if (want > 1 && (s.cps & 1)) ++s.cps;   // whole 32-channel chunks per split: the bf16 mode's chunk is two of these units
   s.nsplit = (int)adnm_cdiv(nchunks, s.cps);
   return s;
 }
 
-template <int ACT_IN, int ACT_OUT>
-int launch_conv(const ConvArgs& a, const Geo& g, const Split& s, int prec, hipStream_t st, const char* prof, double bytes) {
+template <int ACT_OUT>
+int launch_conv(const ConvArgs& a, const Geo& g, const Split& s, int mode, hipStream_t st, const char* prof, double bytes) {
   const size_t smem = sizeof(float) * ((size_t)(g.TH + 2) * (g.TW + 2) * CKP + (size_t)9 * s.nb * 16 * CKP);
   const dim3 grid((unsigned)(g.tiles_x * g.tiles_y), (unsigned)s.ngroups, (unsigned)s.nsplit);
   ADNM_PROF(prof, st, bytes);
-#define CV(PRECV, BF8V)                                                                                  \
-  do {                                                                                                   \
-    if (s.nb == 4) conv3_kernel<4, ACT_IN, ACT_OUT, PRECV, BF8V><<<grid, kBlock, smem, st>>>(a);         \
-    else if (s.nb == 2) conv3_kernel<2, ACT_IN, ACT_OUT, PRECV, BF8V><<<grid, kBlock, smem, st>>>(a);    \
-    else conv3_kernel<1, ACT_IN, ACT_OUT, PRECV, BF8V><<<grid, kBlock, smem, st>>>(a);                   \
+#define CV(ACTV, MODEV)                                                                        \
+  do {                                                                                         \
+    if (s.nb == 4) conv3_kernel<4, ACTV, MODEV><<<grid, kBlock, smem, st>>>(a);                \
+    else if (s.nb == 2) conv3_kernel<2, ACTV, MODEV><<<grid, kBlock, smem, st>>>(a);           \
+    else conv3_kernel<1, ACTV, MODEV><<<grid, kBlock, smem, st>>>(a);                          \
   } while (0)
-  static const bool fp32_images = getenv("ADNM_CONV3_FP32_IMAGES") && atoi(getenv("ADNM_CONV3_FP32_IMAGES")) != 0;   // measurement aid: the round-3 kernel
-  if (prec == ADNM_MFMA_BF16 && fp32_images) CV(ADNM_MFMA_BF16, false);
-  else if (prec == ADNM_MFMA_BF16) {
-    if (s.nb == 4) conv3_bf16_kernel<4, ACT_IN, ACT_OUT><<<grid, kBlock, smem, st>>>(a);
-    else if (s.nb == 2) conv3_bf16_kernel<2, ACT_IN, ACT_OUT><<<grid, kBlock, smem, st>>>(a);
-    else conv3_bf16_kernel<1, ACT_IN, ACT_OUT><<<grid, kBlock, smem, st>>>(a);
-  } else if (prec == ADNM_MFMA_FP8) CV(ADNM_MFMA_FP8, false);
-  else if (prec == ADNM_MFMA_FP8_GRAD) CV(ADNM_MFMA_FP8, true);
-  else CV(ADNM_MFMA_F32, false);
+  if (mode == ADNM_MFMA_BF16) CV(ACT_OUT, ADNM_MFMA_BF16);
+  else if (mode == ADNM_MFMA_FP8) CV(ACT_OUT, ADNM_MFMA_FP8);
+  else if (mode == ADNM_MFMA_FP8_GRAD) CV(ADNM_ACT_NONE, ADNM_MFMA_FP8_GRAD);   // the input gradient only: nothing is activated on its way out
+  else CV(ACT_OUT, ADNM_MFMA_F32);
 #undef CV
   return ADNM_OK;
 }
@@ -693,7 +559,7 @@ extern "C" int adnm_conv3_fwd(const float* in, int64_t ldin, const float* w, int
     return ADNM_EWORKSPACE;
   }
   ConvArgs a{};
-  a.in = in, a.ldin = ldin, a.in2 = nullptr, a.ldin2 = 0;
+  a.in = in, a.ldin = ldin;
   a.w = w, a.sn = ws_n, a.st = ws_tap, a.sk = ws_k, a.flip = 0;
   a.bias = bias, a.out = out, a.ldo = ldo, a.pre = pre, a.ldpre = ldpre, a.part = (float*)ws;
   a.B = (int)B, a.H = (int)H, a.W = (int)W, a.K = (int)K, a.N = (int)N, a.nsplit = s.nsplit, a.chunks_per_split = s.cps;
@@ -704,8 +570,8 @@ extern "C" int adnm_conv3_fwd(const float* in, int64_t ldin, const float* w, int
   a.q = reinterpret_cast<AdnmQuant*>(q);
   hipStream_t st = (hipStream_t)stream;
   const double bytes = 4.0 * ((double)B * H * W * (K + N * (pre ? 2 : 1)) + 9.0 * K * N);
-  if (act == ADNM_ACT_GELU && s.nsplit == 1) launch_conv<ADNM_ACT_NONE, ADNM_ACT_GELU>(a, g, s, prec, st, "conv3_fwd", bytes);
-  else launch_conv<ADNM_ACT_NONE, ADNM_ACT_NONE>(a, g, s, prec, st, "conv3_fwd", bytes);
+  if (act == ADNM_ACT_GELU && s.nsplit == 1) launch_conv<ADNM_ACT_GELU>(a, g, s, prec, st, "conv3_fwd", bytes);
+  else launch_conv<ADNM_ACT_NONE>(a, g, s, prec, st, "conv3_fwd", bytes);
   ADNM_CHECK_LAUNCH("conv3_fwd");
   if (s.nsplit > 1) {
     const int64_t M = B * H * W, nthreads = M * (N / 4);
@@ -719,17 +585,17 @@ extern "C" int adnm_conv3_fwd(const float* in, int64_t ldin, const float* w, int
   return ADNM_OK;
 }
 
-// din = conv3x3^T(dout * act'(pre), w): the input gradient of adnm_conv3_fwd (K = Cin, N = Cout of the forward conv, same w strides).
-extern "C" int adnm_conv3_dgrad(const float* dout, int64_t lddo, const float* pre, int64_t ldpre, int act, const float* w, int64_t ws_n,
-                                int64_t ws_tap, int64_t ws_k, float* din, int64_t lddin, void* ws, int64_t ws_bytes, int64_t B, int64_t H,
-                                int64_t W, int64_t K, int64_t N, int prec, float* q, adnm_stream_t stream) {
+// din = conv3x3^T(dout, w): the input gradient of adnm_conv3_fwd (K = Cin, N = Cout of the forward conv, same w strides); dout is the
+// gradient with respect to the conv's PRE-activation (an activated conv's caller forms it with adnm_act_bwd).
+extern "C" int adnm_conv3_dgrad(const float* dout, int64_t lddo, const float* w, int64_t ws_n, int64_t ws_tap, int64_t ws_k, float* din,
+                                int64_t lddin, void* ws, int64_t ws_bytes, int64_t B, int64_t H, int64_t W, int64_t K, int64_t N, int prec,
+                                float* q, adnm_stream_t stream) {
   if (int rc = check_shape("conv3_dgrad", B, H, W, K, N)) return rc;
   ADNM_REQUIRE(dout && w && din, "conv3_dgrad: null pointer");
   ADNM_REQUIRE(prec >= ADNM_MFMA_F32 && prec <= ADNM_MFMA_FP8_GRAD, "conv3_dgrad: bad prec %d", prec);
   ADNM_REQUIRE((prec != ADNM_MFMA_FP8 && prec != ADNM_MFMA_FP8_GRAD) || q, "conv3_dgrad: the fp8 modes need a quantisation record");
   if (prec == ADNM_MFMA_FP8) prec = ADNM_MFMA_FP8_GRAD;   // the pixel rows of this op are always a gradient
-  ADNM_REQUIRE(act == ADNM_ACT_NONE || (act == ADNM_ACT_GELU && pre), "conv3_dgrad: activation %d needs the saved pre-activation", act);
-  ADNM_REQUIRE(lddo >= N && lddin >= K && (!pre || ldpre >= N), "conv3_dgrad: row strides smaller than the rows");
+  ADNM_REQUIRE(lddo >= N && lddin >= K, "conv3_dgrad: row strides smaller than the rows");
   const Geo g = make_geo(B, H, W);
   const Split s = plan_split(g, N, K);   // reduction over the forward's output channels, K columns out
   if (s.nsplit > 1 && (!ws || ws_bytes < adnm_conv3_ws_bytes(B, H, W, N, K))) {
@@ -737,19 +603,17 @@ extern "C" int adnm_conv3_dgrad(const float* dout, int64_t lddo, const float* pr
     return ADNM_EWORKSPACE;
   }
   ConvArgs a{};
-  a.in = dout, a.ldin = lddo, a.in2 = pre, a.ldin2 = ldpre;
+  a.in = dout, a.ldin = lddo;
   a.w = w, a.sn = ws_k, a.st = ws_tap, a.sk = ws_n, a.flip = 1;   // W'(k, tap, n) = W(n, 8 - tap, k)
   a.bias = nullptr, a.out = din, a.ldo = lddin, a.pre = nullptr, a.ldpre = 0, a.part = (float*)ws;
   a.B = (int)B, a.H = (int)H, a.W = (int)W, a.K = (int)N, a.N = (int)K, a.nsplit = s.nsplit, a.chunks_per_split = s.cps;
   fill_geo(a, g);
-  a.vec_in = al16(dout) && lddo % 4 == 0 && N % 4 == 0 && (!pre || (al16(pre) && ldpre % 4 == 0));
+  a.vec_in = al16(dout) && lddo % 4 == 0 && N % 4 == 0;
   a.vec_w = a.sk == 1 && al16(w) && a.sn % 4 == 0 && a.st % 4 == 0 && N % 4 == 0;
   a.vec_out = al16(din) && lddin % 4 == 0 && K % 4 == 0;
   a.q = reinterpret_cast<AdnmQuant*>(q);
   hipStream_t st = (hipStream_t)stream;
-  const double bytes = 4.0 * ((double)B * H * W * (K + N * (act != ADNM_ACT_NONE ? 2 : 1)) + 9.0 * K * N);
-  if (act == ADNM_ACT_GELU) launch_conv<ADNM_ACT_GELU, ADNM_ACT_NONE>(a, g, s, prec, st, "conv3_dgrad", bytes);
-  else launch_conv<ADNM_ACT_NONE, ADNM_ACT_NONE>(a, g, s, prec, st, "conv3_dgrad", bytes);
+  launch_conv<ADNM_ACT_NONE>(a, g, s, prec, st, "conv3_dgrad", 4.0 * ((double)B * H * W * (K + N) + 9.0 * K * N));
   ADNM_CHECK_LAUNCH("conv3_dgrad");
   if (s.nsplit > 1) {
     const int64_t M = B * H * W, nthreads = M * (K / 4);
@@ -788,15 +652,14 @@ extern "C" int64_t adnm_conv3_wgrad_ws_bytes(int64_t B, int64_t H, int64_t W, in
   return (int64_t)p.rows * p.rowlen * (int64_t)sizeof(float);
 }
 
-// dw[n][tap][k] (contiguous, = the channels-last weight layout) and dbias[n] (optional) of adnm_conv3_fwd.  OVERWRITES both.
-extern "C" int adnm_conv3_wgrad(const float* dout, int64_t lddo, const float* pre, int64_t ldpre, int act, const float* in, int64_t ldin,
-                                float* dw, float* dbias, void* ws, int64_t ws_bytes, int64_t B, int64_t H, int64_t W, int64_t K, int64_t N,
-                                int prec, adnm_stream_t stream) {
+// dw[n][tap][k] (contiguous, = the channels-last weight layout) and dbias[n] (optional) of adnm_conv3_fwd from dout = the gradient with
+// respect to the conv's pre-activation, as in adnm_conv3_dgrad.  OVERWRITES both.
+extern "C" int adnm_conv3_wgrad(const float* dout, int64_t lddo, const float* in, int64_t ldin, float* dw, float* dbias, void* ws,
+                                int64_t ws_bytes, int64_t B, int64_t H, int64_t W, int64_t K, int64_t N, int prec, adnm_stream_t stream) {
   if (prec == ADNM_MFMA_FP8 || prec == ADNM_MFMA_FP8_GRAD) prec = ADNM_MFMA_BF16;   // the weight gradient keeps bf16 operands in the fp8 configuration
   if (int rc = check_shape("conv3_wgrad", B, H, W, K, N)) return rc;
   ADNM_REQUIRE(dout && in && dw, "conv3_wgrad: null pointer");
-  ADNM_REQUIRE(act == ADNM_ACT_NONE || (act == ADNM_ACT_GELU && pre), "conv3_wgrad: activation %d needs the saved pre-activation", act);
-  ADNM_REQUIRE(lddo >= N && ldin >= K && (!pre || ldpre >= N), "conv3_wgrad: row strides smaller than the rows");
+  ADNM_REQUIRE(lddo >= N && ldin >= K, "conv3_wgrad: row strides smaller than the rows");
   ADNM_REQUIRE(N * 9 * K + N < (1ll << 31), "conv3_wgrad: weight too large");
   const Geo g = make_geo(B, H, W);
   const WgPlan p = plan_wgrad(g, K, N, dbias != nullptr);
@@ -805,33 +668,27 @@ extern "C" int adnm_conv3_wgrad(const float* dout, int64_t lddo, const float* pr
     return ADNM_EWORKSPACE;
   }
   WgArgs a{};
-  a.dout = dout, a.lddo = lddo, a.pre = pre, a.ldpre = ldpre, a.in = in, a.ldin = ldin;
+  a.dout = dout, a.lddo = lddo, a.in = in, a.ldin = ldin;
   a.part = (float*)ws, a.rowlen = p.rowlen, a.want_bias = dbias != nullptr;
   a.B = (int)B, a.H = (int)H, a.W = (int)W, a.K = (int)K, a.N = (int)N, a.ntiles = g.tiles_x * g.tiles_y;
   a.TW = g.TW, a.RB = g.RB, a.TH = g.TH, a.VR = g.VR, a.tiles_x = g.tiles_x;
   a.vec_in = al16(in) && ldin % 4 == 0 && K % 4 == 0;
-  a.vec_do = al16(dout) && lddo % 4 == 0 && N % 4 == 0 && (!pre || (al16(pre) && ldpre % 4 == 0));
+  a.vec_do = al16(dout) && lddo % 4 == 0 && N % 4 == 0;
   hipStream_t st = (hipStream_t)stream;
   size_t smem = sizeof(float) * ((size_t)(g.TH + 2) * (g.TW + 2) * CKP + (size_t)kTilePix * (p.nb * 16 + 16));
   const size_t red = sizeof(float) * (size_t)kWaves * (9 * p.nb * 4 + 1) * 64;   // the cross-wave sum reuses the same LDS
   if (smem < red) smem = red;
   const dim3 grid((unsigned)p.rows, (unsigned)p.cichunks, (unsigned)p.cogroups);
   {
-    ADNM_PROF("conv3_wgrad", st, 4.0 * ((double)B * H * W * (K + N * (act != ADNM_ACT_NONE ? 2 : 1)) + 9.0 * K * N));
-#define WG1(NBV, ACTV, BFV)                                                                   \
+    ADNM_PROF("conv3_wgrad", st, 4.0 * ((double)B * H * W * (K + N) + 9.0 * K * N));
+#define WG(NBV, PRECV)                                                                        \
   do {                                                                                        \
-    ADNM_ALLOW_LDS((conv3_wgrad_kernel<NBV, ACTV, BFV>), smem, "conv3_wgrad");                \
-    conv3_wgrad_kernel<NBV, ACTV, BFV><<<grid, kBlock, smem, st>>>(a);                        \
+    ADNM_ALLOW_LDS((conv3_wgrad_kernel<NBV, PRECV>), smem, "conv3_wgrad");                    \
+    conv3_wgrad_kernel<NBV, PRECV><<<grid, kBlock, smem, st>>>(a);                            \
   } while (0)
-#define WG(NBV)                                                                               \
-  do {                                                                                        \
-    if (act == ADNM_ACT_GELU) { if (prec == ADNM_MFMA_BF16) WG1(NBV, ADNM_ACT_GELU, ADNM_MFMA_BF16); else WG1(NBV, ADNM_ACT_GELU, ADNM_MFMA_F32); } \
-    else { if (prec == ADNM_MFMA_BF16) WG1(NBV, ADNM_ACT_NONE, ADNM_MFMA_BF16); else WG1(NBV, ADNM_ACT_NONE, ADNM_MFMA_F32); }                     \
-  } while (0)
-    if (p.nb == 2) WG(2);
-    else WG(1);
+    if (p.nb == 2) { if (prec == ADNM_MFMA_BF16) WG(2, ADNM_MFMA_BF16); else WG(2, ADNM_MFMA_F32); }
+    else { if (prec == ADNM_MFMA_BF16) WG(1, ADNM_MFMA_BF16); else WG(1, ADNM_MFMA_F32); }
 #undef WG
-#undef WG1
   }
   ADNM_CHECK_LAUNCH("conv3_wgrad");
   adnm_launch_fold("conv3_wgrad_fold", (const float*)ws, p.rows, (int)p.rowlen, {dw, (int)(N * 9 * K)}, {dbias, dbias ? (int)N : 0}, {nullptr, 0},

@@ -544,22 +544,23 @@ int adnm_loss_stat(const float* loss, void* stats, adnm_stream_t stream);
  *   in:(B*H*W, K) pixel rows (row stride ldin), out:(B*H*W, N) (ldo); K = Cin, N = Cout (any sizes; 16-byte paths need % 4).
  *   w element (n, ky, kx, k) at w[n*ws_n + (ky*3+kx)*ws_tap + k*ws_k]: nn.Conv2d's own (Cout,Cin,3,3) layout is
  *   (ws_n, ws_tap, ws_k) = (9K, 1, 9), the channels-last one (Cout,3,3,Cin) is (9K, K, 1) — both are read in place.
- *   act: ADNM_ACT_NONE | ADNM_ACT_GELU applied in the epilogue; pre (optional, row stride ldpre) receives conv + bias BEFORE the
- *   activation — the tensor autograd would have saved for the reference's separate GELU; dgrad / wgrad take it back.
- *   dgrad: din = conv^T(dout * act'(pre));  wgrad: dw[n][tap][k] contiguous (= the channels-last weight layout), dbias optional;
- *   both OVERWRITE.  Workspaces: split-K partials of the deep maps (fwd / dgrad: adnm_conv3_ws_bytes with the (K, N) of THAT
- *   launch's reduction / output), per-wave partial rows (wgrad). */
+ *   act (fwd only): ADNM_ACT_NONE | ADNM_ACT_GELU applied in the epilogue; pre (optional, row stride ldpre) receives conv + bias BEFORE
+ *   the activation — the tensor autograd would have saved for the reference's separate GELU.
+ *   dgrad / wgrad: dout (row stride lddo) is the gradient with respect to the conv's PRE-activation: the output gradient itself without
+ *   an activation, else dpre = dy * act'(pre), which the caller forms once with adnm_act_bwd — the two kernels read a plain operand.
+ *   dgrad: din = conv^T(dout);  wgrad: dw[n][tap][k] contiguous (= the channels-last weight layout), dbias optional; both OVERWRITE.
+ *   Workspaces: split-K partials of the deep maps (fwd / dgrad: adnm_conv3_ws_bytes with the (K, N) of THAT launch's reduction /
+ *   output), per-wave partial rows (wgrad). */
 int64_t adnm_conv3_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t K, int64_t N);
 int adnm_conv3_fwd(const float* in, int64_t ldin, const float* w, int64_t ws_n, int64_t ws_tap, int64_t ws_k, const float* bias,
                    float* out, int64_t ldo, float* pre, int64_t ldpre, void* ws, int64_t ws_bytes, int64_t B, int64_t H, int64_t W,
                    int64_t K, int64_t N, int act, int prec, float* q, adnm_stream_t stream);
-int adnm_conv3_dgrad(const float* dout, int64_t lddo, const float* pre, int64_t ldpre, int act, const float* w, int64_t ws_n,
-                     int64_t ws_tap, int64_t ws_k, float* din, int64_t lddin, void* ws, int64_t ws_bytes, int64_t B, int64_t H,
-                     int64_t W, int64_t K, int64_t N, int prec, float* q, adnm_stream_t stream);
+int adnm_conv3_dgrad(const float* dout, int64_t lddo, const float* w, int64_t ws_n, int64_t ws_tap, int64_t ws_k, float* din,
+                     int64_t lddin, void* ws, int64_t ws_bytes, int64_t B, int64_t H, int64_t W, int64_t K, int64_t N, int prec,
+                     float* q, adnm_stream_t stream);
 int64_t adnm_conv3_wgrad_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t K, int64_t N);
-int adnm_conv3_wgrad(const float* dout, int64_t lddo, const float* pre, int64_t ldpre, int act, const float* in, int64_t ldin,
-                     float* dw, float* dbias, void* ws, int64_t ws_bytes, int64_t B, int64_t H, int64_t W, int64_t K, int64_t N,
-                     int prec, adnm_stream_t stream);
+int adnm_conv3_wgrad(const float* dout, int64_t lddo, const float* in, int64_t ldin, float* dw, float* dbias, void* ws,
+                     int64_t ws_bytes, int64_t B, int64_t H, int64_t W, int64_t K, int64_t N, int prec, adnm_stream_t stream);
 
 /* ---------------------------------------------------------------- stride-2 transposed conv of UpSample (K9)
  * nn.ConvTranspose2d(C, C, k=3, s=2, p=1, output_padding=1) (model_untils.py:120-158,490-520) = one GEMM over the input pixels
@@ -642,8 +643,9 @@ int adnm_forecast_render(const float* pred, uint8_t* fields, uint8_t* strip, con
                          int64_t frame_step, int64_t gap, adnm_stream_t stream);
 
 /* ---------------------------------------------------------------- stand-alone activations
- * act_fwd / act_bwd: y = act(x), dpre = dy * act'(pre) over flat fp32 arrays (n % 4 == 0), act in {ADNM_ACT_SILU, ADNM_ACT_GELU}: nn.GELU
- *   between Mlp.fc1 and fc2 (model_untils.py:52-70) and the backward of the GELUs fused into GEMM / conv epilogues.
+ * act_fwd / act_bwd: y = act(x), dpre = dy * act'(pre) over flat fp32 arrays (any n > 0, 16-byte aligned pointers: the last n % 4
+ *   elements go by scalar accesses in the same launch), act in {ADNM_ACT_SILU, ADNM_ACT_GELU}: nn.GELU between Mlp.fc1 and fc2
+ *   (model_untils.py:52-70) and the backward of the GELUs fused into GEMM / conv epilogues.
  * swish_fwd / bwd: Swish with a learnable slope, y = x * sigmoid(beta * x) (model_untils.py:162-169), beta a 1-element device tensor;
  *   bwd OVERWRITES dx and dbeta (1 element). */
 int adnm_act_fwd(const float* x, float* y, int64_t n, int act, adnm_stream_t stream);

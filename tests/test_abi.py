@@ -15,7 +15,7 @@ def test_header_parses_and_library_exports_every_symbol():
     so = ctypes.CDLL(lib.LIB_PATH)
     for name in protos:
         assert hasattr(so, name), f"{name} declared in include/adnm_hip.h but not exported"
-    assert lib.load().adnm_abi_version() == 10
+    assert lib.load().adnm_abi_version() == 11
 
 
 def test_ws_queries_are_pure_host_functions():
@@ -31,6 +31,19 @@ def test_argument_validation_happens_before_any_launch():
     assert rc == -1 and "multiple of 4" in lib.last_error()
     rc = lib.load().adnm_ssd_reduce_fwd(1, 64, 1, 16, 1, 16, 1, 16, 1, 1, 1, 1, 1, 1, 64, 1, None, None, None, 0, None, None, 0.0, 1, 0, 1, 4, 4, 16, 16, 1, 0, None)
     assert rc == -1 and "not in" in lib.last_error()
+
+
+def test_conv3_gradient_entry_points_take_dpre():
+    """adnm_conv3_dgrad / _wgrad read the gradient with respect to the pre-activation as a plain operand: no pre / ldpre / act arguments;
+    a null dout is refused on the host before any launch"""
+    protos = lib.parse_header()
+    assert len(protos["adnm_conv3_dgrad"][1]) == 18 and len(protos["adnm_conv3_wgrad"][1]) == 15
+    B, H, W, K, N = 1, 8, 8, 16, 16
+    some = 4096   # stands for a device address: only dout is null, and nothing is dereferenced or launched before the refusal
+    rc = lib.load().adnm_conv3_dgrad(None, N, some, 9 * K, K, 1, some, K, None, 0, B, H, W, K, N, 0, None, None)
+    assert rc == -1 and "conv3_dgrad: null pointer" in lib.last_error()
+    rc = lib.load().adnm_conv3_wgrad(None, N, some, K, some, None, None, 0, B, H, W, K, N, 0, None)
+    assert rc == -1 and "conv3_wgrad: null pointer" in lib.last_error()
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")

@@ -108,7 +108,7 @@ def test_entry_point_is_declared_and_exported_and_the_abi_version_stays():
     assert ret == "int" and args[-1] == "adnm_stream_t" and len(args) == 15
     assert args[:6] == ["const float*", "uint8_t*", "uint8_t*", "const float*", "const uint8_t*", "int64_t"]
     assert hasattr(ctypes.CDLL(lib.LIB_PATH), "adnm_forecast_render"), "declared but not exported"
-    assert lib.load().adnm_abi_version() == 10
+    assert lib.load().adnm_abi_version() == 11
 
 
 # ------------------------------------------------------------------------------------------------ 5. refusals before any launch

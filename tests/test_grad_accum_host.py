@@ -21,7 +21,7 @@ def test_entry_points_reject_bad_arguments_before_any_launch():
                        ((ok + 4, ok, None, 8, 0.5, None), "aligned"), ((ok, ok + 8, None, 8, 0.5, None), "aligned"),
                        ((ok, ok, ok + 2, 8, 0.5, None), "aligned"), ((ok, ok, ok, 6, 0.5, None), "multiple of 4")):
         assert L.adnm_grad_accum_final(*args) == -1 and word in lib.last_error(), (args, lib.last_error())
-    assert L.adnm_abi_version() == 10
+    assert L.adnm_abi_version() == 11
 
 
 class Net(nn.Module):

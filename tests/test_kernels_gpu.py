@@ -847,6 +847,8 @@ def test_unsupported_shapes_raise():
     (1, 64, 64, 20, 20, lib.ACT_NONE, False, True),     # OutProj.conv2: 20 -> 20
     (2, 7, 9, 8, 12, lib.ACT_GELU, True, False),        # odd sizes
     (1, 32, 32, 32, 200, lib.ACT_NONE, True, True),     # several output-channel groups
+    (1, 3, 5, 4, 5, lib.ACT_GELU, True, False),         # GELU with 75 output elements: the scalar tail of adnm_act_bwd; a map smaller than a tile
+    (1, 7, 9, 8, 6, lib.ACT_GELU, True, True),          # GELU with 378 output elements (378 % 4 = 2), ragged N in the epilogue
 ])
 def test_conv3(B, H, W, K, N, act, bias, cl):
     x, w, cot = T(f"c3.x{H}{K}", (B, H * W, K)), T(f"c3.w{N}{K}", (N, K, 3, 3), 0.2), T(f"c3.c{H}{N}", (B, H * W, N))
@@ -869,6 +871,31 @@ def test_conv3(B, H, W, K, N, act, bias, cl):
     assert_close(wg.grad, wo.grad, GRAD_TOL, "dw")
     if bias:
         assert_close(bg.grad, bo.grad, GRAD_TOL, "db")
+
+
+def _conv3_gelu_grads(x, w, b, H, W, cot):
+    xg, wg, bg = leaf(x, DEV), leaf(w, DEV), leaf(b, DEV)
+    ops.conv3(xg, wg, bg, H, W, lib.ACT_GELU).backward(cot)
+    return xg.grad, wg.grad.contiguous(), bg.grad
+
+
+def _check_conv3_gelu_strided_cotangent():
+    """the cotangent of a GELU conv as a column view of a wider buffer (NaN beside it): it is copied, dpre = dy * GELU'(pre) is the same
+    fp32 product as from the contiguous copy, so all three gradients are bit-identical"""
+    B, H, W, K, N = 2, 8, 8, 16, 24
+    x, w, b, cot = T("c3sv.x", (B, H * W, K)), T("c3sv.w", (N, K, 3, 3), 0.2), T("c3sv.b", (N,)), T("c3sv.c", (B * H * W, N))
+    wide = torch.full((B * H * W, 16 + N + 12), float("nan"), device=DEV)
+    wide[:, 16:16 + N] = cot.to(DEV)
+    cv = wide[:, 16:16 + N]
+    assert not cv.is_contiguous()
+    strided = _conv3_gelu_grads(x, w, b, H, W, cv.unflatten(0, (B, H * W)))
+    contig = _conv3_gelu_grads(x, w, b, H, W, cv.contiguous().unflatten(0, (B, H * W)))
+    for name, s, c in zip(("dx", "dw", "db"), strided, contig):
+        assert torch.isfinite(s).all() and torch.equal(s, c), f"{name}: the strided cotangent's result differs from the contiguous one's"
+
+
+def test_conv3_gelu_strided_cotangent():
+    _check_conv3_gelu_strided_cotangent()
 
 
 # ------------------------------------------------------------------------------------------- stride-2 transposed conv (K9)
@@ -895,7 +922,17 @@ def test_convt2x(B, H, W, C, cl):
 # ------------------------------------------------------------------------------------------- stand-alone activations
 @pytest.mark.parametrize("code,fn", [(lib.ACT_GELU, F.gelu), (lib.ACT_SILU, F.silu)])
 def test_act(code, fn):
-    x, cot = T("act.x", (3, 1000, 8), 3.0), T("act.c", (3, 1000, 8))
+    _check_act(code, fn, (3, 1000, 8))
+
+
+@pytest.mark.parametrize("code,fn", [(lib.ACT_GELU, F.gelu), (lib.ACT_SILU, F.silu)])
+def test_act_tail(code, fn):
+    """1003 elements: 250 float4 items and a 3-element scalar tail in the same launch, forward and backward"""
+    _check_act(code, fn, (1003,))
+
+
+def _check_act(code, fn, shape):
+    x, cot = T("act.x", shape, 3.0), T("act.c", shape)
     xo = leaf(x.double())
     yo = fn(xo)
     (yo * cot.double()).sum().backward()
@@ -1003,9 +1040,10 @@ def test_tsgemm_bf16_mfma(M, K, N, bf16_mfma):
 @pytest.mark.parametrize("B,H,W,K,N,act", [(2, 16, 16, 32, 64, "none"), (1, 32, 32, 5, 32, "gelu"), (2, 8, 8, 20, 20, "none"), (1, 16, 16, 128, 32, "gelu"),
                                            (4, 4, 4, 256, 64, "none"), (1, 8, 8, 144, 48, "gelu"), (2, 4, 4, 512, 128, "gelu"), (1, 24, 40, 72, 16, "none")])
 def test_conv3_bf16_mfma(B, H, W, K, N, act, bf16_mfma):
-    """bf16 configuration: forward and input gradient run on bf16 LDS images (csrc/conv3.hip: conv3_bf16_kernel — 32-channel chunks, one
-    rounding per staged value): EXACTLY (fp32 summation order) the conv of the bf16-rounded operands.  Shapes: one / several chunks, a
-    ragged last chunk (K = 5, 20, 72, 144), split reductions with the join kernel (4 x 4 maps), GELU in the epilogue / on the way in."""
+    """bf16 configuration: forward and input gradient run on bf16 LDS images (csrc/conv3.hip: conv3_kernel in its ADNM_MFMA_BF16 mode —
+    32-channel chunks, one rounding per staged value): EXACTLY (fp32 summation order) the conv of the bf16-rounded operands.  Shapes: one /
+    several chunks, a ragged last chunk (K = 5, 20, 72, 144), split reductions with the join kernel (4 x 4 maps), GELU in the epilogue /
+    its derivative in the gradient the kernels are handed."""
     a = lib.ACT_GELU if act == "gelu" else lib.ACT_NONE
     x, w, b, cot = T(f"bfc.x{K}", (B, H * W, K)), T(f"bfc.w{K}{N}", (N, K, 3, 3), 0.2), T(f"bfc.b{N}", (N,)), T(f"bfc.c{N}{H}", (B, H * W, N))
     xg, wg, bg = leaf(x, DEV), leaf(w, DEV), leaf(b, DEV)
@@ -1032,6 +1070,10 @@ def test_conv3_bf16_mfma(B, H, W, K, N, act, bf16_mfma):
     dwo = torch.nn.grad.conv2d_weight(xr.view(B, H, W, K).permute(0, 3, 1, 2), (N, K, 3, 3), dr.view(B, H, W, N).permute(0, 3, 1, 2), padding=1)
     assert_close(wg.grad, dwo, gt, "dw")
     assert_close(bg.grad, dpre.double().sum((0, 1)), 1e-5, "db (fp32 sums of the unrounded gradient)")
+
+
+def test_conv3_gelu_strided_cotangent_bf16(bf16_mfma):
+    _check_conv3_gelu_strided_cotangent()
 
 
 # ------------------------------------------------------------------------------------------- fp8 MFMA precision (BASELINE config 5)

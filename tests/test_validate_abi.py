@@ -1,5 +1,5 @@
 """The entry points of the on-device validation epoch at the C boundary, without a GPU: declared in include/adnm_hip.h, exported by the
-library, additive (the ABI version stays 10), and refusing shapes outside their limits before any launch."""
+library, additive (they left the ABI version as it was), and refusing shapes outside their limits before any launch."""
 import ctypes
 
 from adnm_hip import lib
@@ -18,7 +18,7 @@ def test_new_prototypes_are_declared_and_exported_and_the_abi_version_stays():
         assert protos[name][0] == "int" and protos[name][1][-1] == "adnm_stream_t"
     for name in QUERIES:
         assert protos[name][0] == "int64_t"
-    assert lib.load().adnm_abi_version() == 10
+    assert lib.load().adnm_abi_version() == 11
 
 
 def test_workspace_queries_refuse_what_the_kernels_cannot_take():

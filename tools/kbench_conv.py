@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""The dense 3x3 convolutions of one training step (config 2: B = 4, 128 x 128) one by one: forward and input gradient through the C ABI,
-graph-replayed with cold operands (each launch of a replay reads its own copy of the tokens).   python tools/kbench_conv.py [f32|bf16 ...]
-ADNM_CONV3_FP32_IMAGES=1 selects the round-3 kernel (fp32 LDS images) in the bf16 configuration."""
+"""The dense 3x3 convolutions of one training step (config 2: B = 4, 128 x 128) one by one: forward, input gradient and weight gradient
+through the C ABI, graph-replayed with cold operands (each launch of a replay reads its own copy of the tokens).  The gradient launches
+time the production operand: dpre, no activation (Conv3Fn.backward forms it once with adnm_act_bwd).
+python tools/kbench_conv.py [f32|bf16 ...]
+Also runs against a library from before ABI 11, whose gradient entry points still carry (pre, ldpre, act): the arity is read from the
+header and the old positions get (NULL, N, ACT_NONE)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "adnm-unet_amd"))
@@ -13,6 +16,7 @@ SHAPES = [(128, 128, 5, 64), (128, 128, 64, 64), (128, 128, 128, 32), (128, 128,
           (32, 32, 128, 256), (32, 32, 256, 64)]
 B, REPS = 4, 20
 PREC = {"f32": 0, "bf16": 1}
+OLD_ABI = len(lib.parse_header()["adnm_conv3_dgrad"][1]) == 21   # (dout, lddo, pre, ldpre, act, ...)
 
 
 def timed(fn):
@@ -55,10 +59,12 @@ for name in (sys.argv[1:] or ["f32", "bf16"]):
                 lib.call("adnm_conv3_fwd", x.data_ptr(), K, w.data_ptr(), 9 * K, K, 1, b.data_ptr(), y.data_ptr(), N, pre.data_ptr() if act else None, N,
                          wsf.data_ptr(), nbf, B, H, W, K, N, act, prec, None, st)
 
+        old = (None, N, lib.ACT_NONE) if OLD_ABI else ()
+
         def dgrad(st):
             for dy in dys:
-                lib.call("adnm_conv3_dgrad", dy.data_ptr(), N, pre.data_ptr() if act else None, N, act, w.data_ptr(), 9 * K, K, 1, dx.data_ptr(), K,
-                         wsd.data_ptr(), nbd, B, H, W, K, N, prec, None, st)
+                lib.call("adnm_conv3_dgrad", dy.data_ptr(), N, *old, w.data_ptr(), 9 * K, K, 1, dx.data_ptr(), K, wsd.data_ptr(), nbd, B, H, W, K, N,
+                         prec, None, st)
 
         nbw = lib.query("adnm_conv3_wgrad_ws_bytes", B, H, W, K, N)
         wsw = torch.empty(max(nbw, 16), dtype=torch.uint8, device=dev)
@@ -66,8 +72,8 @@ for name in (sys.argv[1:] or ["f32", "bf16"]):
 
         def wgrad(st):   # (kernel + its fold: launched directly here; a queued leaf + a batched fold under a trainer)
             for x, dy in zip(xs, dys):
-                lib.call("adnm_conv3_wgrad", dy.data_ptr(), N, pre.data_ptr() if act else None, N, act, x.data_ptr(), K, dw.data_ptr(), db.data_ptr(),
-                         wsw.data_ptr(), nbw, B, H, W, K, N, prec, st)
+                lib.call("adnm_conv3_wgrad", dy.data_ptr(), N, *old, x.data_ptr(), K, dw.data_ptr(), db.data_ptr(), wsw.data_ptr(), nbw, B, H, W, K, N,
+                         prec, st)
 
         t_f, t_d, t_w = timed(fwd), timed(dgrad), timed(wgrad)
         mb = 4.0 * M * (K + N) / 1e6
