@@ -136,6 +136,8 @@ class QuantTable:
         """1-element view of a record's scale_b (what the fp8 shadow of a weight was / will be multiplied by)"""
         return self._ent(device)["tab"][row, 1:2]
 
+    # site -> record role: "f" / "g" = first operand e4m3 activation rows / e5m2 gradient rows, then the op.  The transposed conv swaps the
+    # usual pairs: convt_fwd = NN with e4m3 rows (X . Wf), convt_dgrad = NT with e5m2 rows (dcols . Wf^T).
     ROLES = {"linear_fwd": "fnt", "linear_dgrad": "gnn", "conv3_fwd": "fc3", "conv3_dgrad": "gc3", "convt_fwd": "fnn", "convt_dgrad": "gnt"}
 
     def set(self, device, key, site, scale_a, scale_b, record=False):

@@ -8,7 +8,7 @@ import torch.nn.functional as F
 
 import adnm_oracle as O
 from adnm_hip import ops, lib, recipe
-from util import load_case, load_npz, assert_close, _e4m3_bytes
+from util import load_case, load_npz, assert_close, rel_l2, _e4m3_bytes
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -1086,8 +1086,28 @@ def _fp8_round(t, scale, grad=False):
     return q.float().double()
 
 
-def _scale_for(t, grad=False):
-    return F8MAX[grad] / (2.0 * float(t.abs().max()))   # one binade of headroom, as the delayed scaling leaves
+def _scale_for(t, grad=False, head=2.0):
+    """head = 2: one binade of headroom, as the delayed scaling leaves; head = 0.75: a tensor that grew by a third since its calibration —
+    every |value| above 0.75 max|t| (a quarter of a uniform draw) lands beyond fmax and must be clamped"""
+    return F8MAX[grad] / (head * float(t.abs().max()))
+
+
+def _scales_for(x, w, cot, head):
+    """(scale of the activations, of the weight, of the e5m2 gradient); head < 1: asserts, on the CPU and before a kernel sees them, that
+    between 10 % and 40 % of each operand's elements saturate"""
+    s = _scale_for(x, False, head), _scale_for(w, False, head), _scale_for(cot, True, head)
+    if head < 1.0:
+        for name, t, sc, grad in zip("xwc", (x, w, cot), s, (False, False, True)):
+            frac = float(((t.float() * sc).abs() > F8MAX[grad]).double().mean())
+            assert 0.10 <= frac <= 0.40, f"{name}: {frac:.3f} of the elements lie beyond +-{F8MAX[grad]:g}"
+    return s
+
+
+def _close(got, ref, tol, case, what):
+    """assert_close after printing the observed rel-L2 (pytest -s; profiles/fp8_paths_tests.txt is a copy of one run); non-finite fails"""
+    print(f"fp8-paths {case} {what}: rel-L2 {rel_l2(got.detach().cpu(), ref):.3e} (bound {tol:.0e})")
+    assert torch.isfinite(got).all(), f"{case} {what}: non-finite values"
+    assert_close(got, ref, tol, f"{case} {what}")
 
 
 @pytest.fixture
@@ -1109,39 +1129,180 @@ def test_linear_fp8_mfma(M, K, N, fp8_mfma):
     gradient stays on bf16 operands (tall-skinny shapes: exact fp32).  Covers the streaming, the LDS-tiled and the tall-skinny kernel.
     Tolerance 2e-5, not the bf16 test's 2e-6: the fp8 MFMA sums its 32 products per step in the hardware's own internal format
     (measured 6e-6 at K = 1024 against the fp64 sum of the same rounded operands); a wrong scale, format or lane map would be >= 1e-2."""
+    yg, x, w = _linear_fp8(M, K, N)
+    assert_close(yg, x.double() @ w.double().t(), 8e-2, "y vs the unrounded GEMM")
+
+
+def _linear_fp8(M, K, N, head=2.0):
+    """ops.linear forward + backward in the fp8 mode against the fp64 GEMMs of the rounded operands -> (y, x, w)"""
     x, w, cot = T(f"f8.x{M}{K}", (M, K)), T(f"f8.w{N}{K}", (N, K), 0.05), T(f"f8.c{M}{N}", (M, N))
+    sx, sw, sc = _scales_for(x, w, cot, head)
     xg, wg = leaf(x, DEV), leaf(w, DEV)
-    sx, sw, sc = _scale_for(x), _scale_for(w), _scale_for(cot, True)
     ops.QUANT.set(xg.device, wg.data_ptr(), "linear_fwd", sx, sw)
     ops.QUANT.set(xg.device, wg.data_ptr(), "linear_dgrad", sc, sw)
     yg = ops.linear(xg, wg, None)
     (yg * cot.to(DEV)).sum().backward()
     xq, wq, cq = _fp8_round(x, sx), _fp8_round(w, sw), _fp8_round(cot, sc, True)
-    assert_close(yg, (xq @ wq.t()) / (sx * sw), 2e-5, "y vs the GEMM of the fp8-rounded operands")
-    assert_close(yg, x.double() @ w.double().t(), 8e-2, "y vs the unrounded GEMM")
-    assert_close(xg.grad, (cq @ wq) / (sc * sw), 2e-5, "dx vs the GEMM of the e5m2 gradient and the e4m3 weight")
+    case = f"linear[{M}x{K}->{N} head {head}]"
+    _close(yg, (xq @ wq.t()) / (sx * sw), 2e-5, case, "y vs the GEMM of the fp8-rounded operands")
+    _close(xg.grad, (cq @ wq) / (sc * sw), 2e-5, case, "dx vs the GEMM of the e5m2 gradient and the e4m3 weight")
     big = M >= 32768
     cr, xr = (cot.double(), x.double()) if big else (_bf16_round(cot).double(), _bf16_round(x).double())
-    assert_close(wg.grad, cr.t() @ xr, 1e-5 if big else 2e-6, "dw (bf16 operands / exact fp32 for the tall-skinny shapes)")
+    _close(wg.grad, cr.t() @ xr, 1e-5 if big else 2e-6, case, "dw (bf16 operands / exact fp32 for the tall-skinny shapes)")
+    return yg, x, w
 
 
-def test_conv3_fp8_mfma(fp8_mfma):
-    B, H, W, K, N = 2, 16, 16, 32, 64
-    x, w, b, cot = T("f8c.x", (B, H * W, K)), T("f8c.w", (N, K, 3, 3), 0.2), T("f8c.b", (N,)), T("f8c.c", (B, H * W, N))
+C3_SHAPES = [(2, 16, 16, 32, 64), (1, 32, 32, 5, 32), (2, 8, 8, 20, 20), (1, 16, 16, 128, 32), (4, 4, 4, 256, 64), (1, 8, 8, 144, 48),
+             (2, 4, 4, 512, 128), (1, 24, 40, 72, 16)]            # test_conv3_bf16_mfma's
+C3_SPLIT = [(4, 4, 4, 256, 64), (2, 4, 4, 512, 128)]              # reduction split over blockIdx.z + conv3_join_kernel, forward AND input gradient
+
+
+def _conv3_fp8(B, H, W, K, N, act, head=2.0):
+    a = lib.ACT_GELU if act == "gelu" else lib.ACT_NONE
+    x, w, b, cot = T(f"f8c.x{K}{H}", (B, H * W, K)), T(f"f8c.w{K}{N}", (N, K, 3, 3), 0.2), T(f"f8c.b{N}", (N,)), T(f"f8c.c{N}{H}", (B, H * W, N))
+    sx, sw, sc = _scales_for(x, w, cot, head)
+    if (B, H, W, K, N) in C3_SPLIT:   # (the input gradient reduces over N and writes K columns)
+        assert lib.query("adnm_conv3_ws_bytes", B, H, W, K, N) > 16 and lib.query("adnm_conv3_ws_bytes", B, H, W, N, K) > 16, "plan_split no longer splits this shape"
     xg, wg, bg = leaf(x, DEV), leaf(w, DEV), leaf(b, DEV)
-    sx, sw, sc = _scale_for(x), _scale_for(w), _scale_for(cot, True)
     ops.QUANT.set(xg.device, wg.data_ptr(), "conv3_fwd", sx, sw)
     ops.QUANT.set(xg.device, wg.data_ptr(), "conv3_dgrad", sc, sw)
-    yg = ops.conv3(xg, wg, bg, H, W, lib.ACT_NONE)
+    yg = ops.conv3(xg, wg, bg, H, W, a)
     (yg * cot.to(DEV)).sum().backward()
     xq, wq, cq = _fp8_round(x, sx), _fp8_round(w, sw), _fp8_round(cot, sc, True)
     conv = lambda a, ww: F.conv2d(a.view(B, H, W, -1).permute(0, 3, 1, 2), ww, None, padding=1).permute(0, 2, 3, 1).reshape(B, H * W, -1)
-    assert_close(yg, conv(xq, wq) / (sx * sw) + b.double(), 2e-5, "y vs the conv of the fp8-rounded operands")
+    pre = conv(xq, wq) / (sx * sw) + b.double()
+    case = f"conv3[{B}x{H}x{W} {K}->{N} {act} head {head}]"
+    if act == "gelu":
+        _close(yg, F.gelu(pre), 2e-5, case, "y vs GELU of the conv of the fp8-rounded operands")
+        for name, g in (("dx", xg.grad), ("dw", wg.grad), ("db", bg.grad)):
+            assert torch.isfinite(g).all(), f"{case} {name}: non-finite values"
+        return
+    _close(yg, pre, 2e-5, case, "y vs the conv of the fp8-rounded operands")
     dx_ref = F.conv_transpose2d(cq.view(B, H, W, N).permute(0, 3, 1, 2), wq, None, padding=1).permute(0, 2, 3, 1).reshape(B, H * W, K) / (sc * sw)
-    assert_close(xg.grad, dx_ref, 2e-5, "dx vs the transposed conv of the e5m2 gradient and the e4m3 weight")
+    _close(xg.grad, dx_ref, 2e-5, case, "dx vs the transposed conv of the e5m2 gradient and the e4m3 weight")
     xo, wo = leaf(_bf16_round(x).double()), leaf(_bf16_round(w).double())
     (conv(xo, wo) * _bf16_round(cot).double()).sum().backward()
-    assert_close(wg.grad, wo.grad, 2e-6, "dw (bf16 operands)")
+    _close(wg.grad, wo.grad, 2e-6, case, "dw (bf16 operands)")
+    _close(bg.grad, cot.double().sum((0, 1)), 1e-5, case, "db (fp32 sums of the unrounded gradient)")
+
+
+@pytest.mark.parametrize("act", ["none", "gelu"])
+@pytest.mark.parametrize("B,H,W,K,N", C3_SHAPES + [(1, 7, 9, 8, 6)])
+def test_conv3_fp8_mfma(B, H, W, K, N, act, fp8_mfma):
+    """conv3_kernel in its FP8 (forward: e4m3 pixels) and FP8_GRAD (input gradient: e5m2 pixels) modes on the bf16 test's shapes — one /
+    several 16-channel chunks, a ragged last chunk (K = 5, 20, 72, 144), NB = 1 / 2 / 4, reductions split over blockIdx.z (un-scaled
+    partials + conv3_join_kernel, with and without GELU) — plus 8 -> 6 channels on a 7 x 9 map (N % 4 != 0: the scalar epilogue).
+    "none": y, dx EXACTLY (fp32 summation order) the fp64 conv of the fp8-rounded operands over the two scales, dw on bf16 operands, db
+    fp32 sums.  "gelu": y through the epilogue / the GELU join against F.gelu of the same pre-activation; the gradients only finite — the
+    gradient kernels take dpre and hold no activation (the "none" cases test exactly what the "gelu" backward runs), and the e5m2
+    rounding of a dpre formed from the fp32 pre-activation flips too often against an fp64 one to bound tightly."""
+    _conv3_fp8(B, H, W, K, N, act)
+
+
+SWAPPED_ROLE_SHAPES = [(64, 1024, 512), (1024, 256, 1216), (300, 20, 64), (64, 4096, 1024), (256, 1024, 2048),   # test_linear_fp8_mfma's below 32768 rows
+                       (256, 1024, 4672), (1024, 512, 2368), (16, 2048, 512)]                                     # + test_skgemm_narrow_weight_operand's
+
+
+@pytest.mark.parametrize("M,K,N", SWAPPED_ROLE_SHAPES)
+def test_skgemm_fp8_transposed_conv_roles(M, K, N, fp8_mfma):
+    """the two (op, first-operand format) pairs only the transposed conv uses: its input gradient is NT with e5m2 rows (k_linear, role
+    "g", record "gnt"), its forward NN with e4m3 rows (k_linear_dx, role "f", record "fnn") — test_linear_fp8_mfma and
+    test_skgemm_narrow_weight_operand reach NT + e4m3 and NN + e5m2.  Same shapes as those: the streaming kernel at its three tile shapes,
+    the LDS-tiled kernel, split or not (every entry is accepted by adnm_skgemm_supported in both roles).  The e4m3 shadow of the weight
+    gives bit for bit the fp32 weight's result."""
+    c, x, w = T(f"tr.c{M}{K}", (M, K)).to(DEV), T(f"tr.x{M}{N}", (M, N)).to(DEV), T(f"tr.w{N}{K}", (N, K), 0.05).to(DEV)
+    sx, sw, sc = _scales_for(x, w, c, 2.0)
+    ops.QUANT.set(w.device, w.data_ptr(), "convt_dgrad", sc, sw)
+    ops.QUANT.set(w.device, w.data_ptr(), "convt_fwd", sx, sw)
+    nt, nn = ops.k_linear(c, w, None, role="g"), ops.k_linear_dx(x, w, role="f")
+    wq = _fp8_round(w.cpu(), sw)
+    case = f"skgemm[{M},{K},{N}]"
+    _close(nt, _fp8_round(c.cpu(), sc, True) @ wq.t() / (sc * sw), 2e-5, case, "NT, e5m2 rows")
+    _close(nn, _fp8_round(x.cpu(), sx) @ wq / (sx * sw), 2e-5, case, "NN, e4m3 rows")
+    w8 = _e4m3_bytes(w * sw)
+    s_t = torch.tensor([sw], dtype=torch.float32, device=DEV)
+    nt8 = ops.k_linear(c, w, None, role="g", narrow=(w8.data_ptr(), 2, s_t))
+    nn8 = ops.k_linear_dx(x, w, role="f", narrow=(w8.data_ptr(), 2, s_t))
+    assert torch.equal(nt, nt8) and torch.equal(nn, nn8), "fp8 shadow"
+
+
+CONVT_SHAPES = [(2, 4, 4, 64),      # 32 rows: streaming plans
+                (1, 16, 16, 128),   # 256 rows, a 1152-step reduction in the input gradient: the LDS-tiled kernel, split
+                (2, 6, 10, 16)]     # ragged tiles
+
+
+def _convt_ref(x, w, cot, B, H, W):
+    """fp64 autograd pass of the transposed conv on tokens -> (y without bias, dx, dw) for cotangent cot"""
+    xo, wo = leaf(x), leaf(w)
+    y = F.conv_transpose2d(xo.view(B, H, W, -1).permute(0, 3, 1, 2), wo, None, stride=2, padding=1, output_padding=1)
+    y = y.permute(0, 2, 3, 1).reshape(B, 4 * H * W, -1)
+    y.backward(cot)
+    return y.detach(), xo.grad, wo.grad
+
+
+def _convt2x_run(B, H, W, C, cl, scales=None):
+    """ops.convt2x forward + backward on the seeded tensors -> (x, w, b, cot) on the CPU, (y, dx, dw, db) from the GPU"""
+    if (B, H, W, C) == (1, 16, 16, 128):   # the input gradient (NT, M = 256, N = C, K = 9 C) is meant as a split launch
+        assert lib.query("adnm_skgemm_ws_bytes", 0, B * H * W, C, 9 * C) > 16, "plan_critical no longer splits this shape"
+    x, w, b, cot = T(f"ctq.x{H}{C}", (B, H * W, C)), T(f"ctq.w{C}", (C, C, 3, 3), 0.2), T(f"ctq.b{C}", (C,)), T(f"ctq.c{H}{C}", (B, 4 * H * W, C))
+    s = scales(x, w, cot) if scales else None
+    xg, bg = leaf(x, DEV), leaf(b, DEV)
+    wg = w.to(DEV)
+    if cl:   # (Cin, 3, 3, Cout) memory order behind the logical (Cin, Cout, 3, 3) shape: the flat trainer's layout
+        wg = wg.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    wg = wg.detach().requires_grad_(True)
+    if s:
+        ops.QUANT.set(xg.device, wg.data_ptr(), "convt_fwd", s[0], s[1])
+        ops.QUANT.set(xg.device, wg.data_ptr(), "convt_dgrad", s[2], s[1])
+    yg = ops.convt2x(xg, wg, bg, H, W)
+    (yg * cot.to(DEV)).sum().backward()
+    return (x, w, b, cot), s, (yg, xg.grad, wg.grad, bg.grad)
+
+
+def _convt2x_fp8(B, H, W, C, cl, head=2.0):
+    (x, w, b, cot), (sx, sw, sc), (yg, dx, dw, db) = _convt2x_run(B, H, W, C, cl, lambda x, w, cot: _scales_for(x, w, cot, head))
+    # (col2im / im2col only move values: rounding the column matrix per tensor is rounding dy)
+    xq, wq, cq = _fp8_round(x, sx), _fp8_round(w, sw), _fp8_round(cot, sc, True)
+    y_ref, dx_ref, _ = _convt_ref(xq, wq, cq, B, H, W)
+    _, _, dw_ref = _convt_ref(_bf16_round(x).double(), wq, _bf16_round(cot).double(), B, H, W)
+    case = f"convt2x[{B}x{H}x{W} {C} cl={int(cl)} fp8 head {head}]"
+    _close(yg, y_ref / (sx * sw) + b.double(), 2e-5, case, "y vs the transposed conv of the e4m3 operands")
+    _close(dx, dx_ref / (sc * sw), 2e-5, case, "dx from the e5m2 gradient and the e4m3 weight")
+    _close(dw, dw_ref, 2e-6, case, "dw (bf16 operands)")
+    _close(db, cot.double().sum((0, 1)), 1e-5, case, "db (fp32 sums of the unrounded gradient)")
+
+
+@pytest.mark.parametrize("cl", [True, False])
+@pytest.mark.parametrize("B,H,W,C", CONVT_SHAPES)
+def test_convt2x_fp8_mfma(B, H, W, C, cl, fp8_mfma):
+    """ConvT2xFn in the fp8 mode: forward = the NN GEMM with e4m3 rows (record "fnn", keyed by the parameter), input gradient = the NT
+    GEMM with e5m2 rows ("gnt"), EXACTLY (fp32 summation order) the fp64 transposed conv of the rounded tensors over the two scales;
+    the weight gradient on bf16 operands, the bias gradient fp32 sums"""
+    _convt2x_fp8(B, H, W, C, cl)
+
+
+@pytest.mark.parametrize("cl", [True, False])
+@pytest.mark.parametrize("B,H,W,C", CONVT_SHAPES)
+def test_convt2x_bf16_mfma(B, H, W, C, cl, bf16_mfma):
+    """ConvT2xFn in the bf16 mode: all three GEMMs EXACTLY (fp32 summation order) the fp64 transposed conv of the bf16-rounded tensors"""
+    (x, w, b, cot), _, (yg, dx, dw, db) = _convt2x_run(B, H, W, C, cl)
+    y_ref, dx_ref, dw_ref = _convt_ref(_bf16_round(x).double(), _bf16_round(w).double(), _bf16_round(cot).double(), B, H, W)
+    case = f"convt2x[{B}x{H}x{W} {C} cl={int(cl)} bf16]"
+    _close(yg, y_ref + b.double(), 2e-6, case, "y")
+    _close(dx, dx_ref, 2e-6, case, "dx")
+    _close(dw, dw_ref, 2e-6, case, "dw")
+    _close(db, cot.double().sum((0, 1)), 1e-5, case, "db (fp32 sums of the unrounded gradient)")
+
+
+def test_fp8_saturating_scales(fp8_mfma):
+    """scales a third too large for every operand (a tensor that grew between two calibrations of the delayed scaling): a quarter of the
+    elements lie beyond fmax, the kernels clamp them (v_med3 before the conversion, which would give NaN), and the results are still
+    EXACTLY those of the rounded — now also clamped — operands: the streaming and the LDS-tiled GEMM, conv3 unsplit and split, convt2x"""
+    for M, K, N in [(64, 1024, 512), (1024, 256, 1216)]:
+        _linear_fp8(M, K, N, head=0.75)
+    for B, H, W, K, N in [(2, 8, 8, 20, 20), (4, 4, 4, 256, 64)]:
+        _conv3_fp8(B, H, W, K, N, "none", head=0.75)
+    _convt2x_fp8(2, 4, 4, 64, True, head=0.75)
 
 
 def test_fp8_amax_collection_and_update(fp8_mfma):
@@ -1165,6 +1326,48 @@ def test_fp8_amax_collection_and_update(fp8_mfma):
         ops.QUANT.update(xg.device)
         assert ops.QUANT.dump(xg.device)[(wg.data_ptr(), "fnt")][6] == 1.0   # step `period`: collect again
         ops.set_mfma_precision("f32")
+
+
+def _assert_calibrated(tab, key, role, first, w, what):
+    """the record of call site (key, role) after a calibration pass: scales from exactly max |first operand| and max |w|, amax slots
+    cleared, not recording"""
+    r, h = tab[(key, role)], ops.QUANT.headroom
+    fmax_a = F8MAX[role[0] == "g"]
+    assert abs(r[0] - fmax_a / (float(first.abs().max()) * h)) <= 1e-5 * r[0], (what, role, "scale_a", r)
+    assert abs(r[1] - 448.0 / (float(w.abs().max()) * h)) <= 1e-5 * r[1], (what, role, "scale_b", r)
+    assert r[2] == 0.0 and r[3] == 0.0 and r[6] == 0.0, (what, role, r)
+
+
+def _plant_max(*ts):
+    """each tensor with its LAST element (flat order: last row / pixel, last channel, last tap) set to 1.5 x its amplitude"""
+    for t in ts:
+        t.view(-1)[-1] = 1.5 * float(t.abs().max())
+    return ts
+
+
+def test_fp8_amax_collection_conv3_convt(fp8_mfma):
+    """as test_fp8_amax_collection_and_update, for the call sites with gates of their own: conv3 collects in the first channel group
+    (pixels) / first pixel tile (weights) of EVERY reduction split — (4,4,4,256,64) is split in both directions, (1,32,32,32,200) has
+    several channel groups and pixel tiles —, the transposed conv through the GEMM records "fnn" / "gnt" keyed by the parameter.  The
+    three tensors differ in scale (3.0 / 0.05 / 0.01), so a swapped slot shows.  Each tensor's maximum is PLANTED (_plant_max) in its
+    last element — the last pixel tile, the last reduction split and the last output-channel group in either direction — so a gate that
+    skips any of those ranges gives a scale a third too large, whatever the seeded draw holds."""
+    for B, H, W, K, N in [(2, 8, 8, 20, 20), (4, 4, 4, 256, 64), (1, 32, 32, 32, 200)]:
+        x, w, cot = _plant_max(T(f"amc.x{K}", (B, H * W, K), 3.0), T(f"amc.w{K}", (N, K, 3, 3), 0.05), T(f"amc.c{N}", (B, H * W, N), 0.01))
+        b = T(f"amc.b{N}", (N,))
+        xg, wg, bg = leaf(x, DEV), leaf(w, DEV), leaf(b, DEV)
+        ops.fp8_calibrate(xg.device, lambda: ops.conv3(xg, wg, bg, H, W, lib.ACT_NONE).mul(cot.to(DEV)).sum().backward())
+        tab = ops.QUANT.dump(xg.device)
+        _assert_calibrated(tab, wg.data_ptr(), "fc3", x, w, (B, H, W, K, N))
+        _assert_calibrated(tab, wg.data_ptr(), "gc3", cot, w, (B, H, W, K, N))
+    for B, H, W, C in [(2, 4, 4, 64), (1, 16, 16, 128)]:
+        x, w, cot = _plant_max(T(f"amt.x{C}", (B, H * W, C), 3.0), T(f"amt.w{C}", (C, C, 3, 3), 0.05), T(f"amt.c{C}", (B, 4 * H * W, C), 0.01))
+        b = T(f"amt.b{C}", (C,))
+        xg, wg, bg = leaf(x, DEV), leaf(w, DEV), leaf(b, DEV)
+        ops.fp8_calibrate(xg.device, lambda: ops.convt2x(xg, wg, bg, H, W).mul(cot.to(DEV)).sum().backward())
+        tab = ops.QUANT.dump(xg.device)
+        _assert_calibrated(tab, wg.data_ptr(), "fnn", x, w, (B, H, W, C))
+        _assert_calibrated(tab, wg.data_ptr(), "gnt", cot, w, (B, H, W, C))   # (every cotangent element lies in the column matrix)
 
 
 @pytest.mark.parametrize("B,Cs", [(4, [256, 512, 1024]), (2, [32, 64, 128, 128, 256, 512, 1024]), (7, [36, 20]), (16, [256, 512, 1024]), (19, [36, 20])])
