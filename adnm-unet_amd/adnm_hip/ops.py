@@ -793,6 +793,65 @@ class _NoDefer:
 _NODEFER = _NoDefer()
 
 
+class LaunchGroup:
+    """with GROUP: <the same step of several independent chains> — the library's launch group (include/adnm_hip.h: adnm_group_*).  Entry
+    points that know about groups (the NT / NN short GEMMs, the depthwise stencil forward / input gradient, the FeedForward gate, InstanceNorm,
+    igate_res) record their launches inside the bracket; leaving it issues them, the
+    problems of one kernel instantiation merged into one launch.  Everything else launches at once.  An exception inside the bracket
+    clears the group: nothing recorded is launched.
+    Rules for the code inside: the calls are mutually independent and read only what was enqueued before the bracket; no torch kernel
+    may consume a recorded result (k_linear / k_linear_dx are used without a trailing copy: asserted there).
+    What a recorded launch touches must outlive the bracket: keep() holds the operands, outputs and workspaces until the launch (the
+    caching allocator would otherwise hand a freed temporary to the next chain's call, and two problems of one launch would share it).
+    Two split GEMMs of one bracket get disjoint counter / slab ranges of the stream's split workspace: split_offsets()."""
+
+    def __init__(self):
+        self._tls = threading.local()
+
+    def _state(self):
+        return getattr(self._tls, "state", None)
+
+    @property
+    def open(self):
+        return self._state() is not None
+
+    def __enter__(self):
+        lib.call("adnm_group_begin")   # refuses a nested bracket before any state changes
+        self._tls.state = {"keep": [], "ctr": 0, "slab": 0}
+        return self
+
+    def __exit__(self, etype, exc, tb):
+        st = self._tls.state
+        self._tls.state = None
+        try:
+            if etype is not None:
+                lib.load().adnm_group_clear()
+            else:
+                lib.call("adnm_group_launch", _stream())
+        finally:
+            st["keep"].clear()
+        return False
+
+    def keep(self, *objs):
+        st = self._state()
+        if st is not None:
+            st["keep"].extend(o for o in objs if o is not None)
+
+    def split_offsets(self, counter_bytes, slab_bytes):
+        """-> (counter offset, slab offset) in bytes for one split GEMM, both multiples of 256; (0, 0) outside a bracket.  The offsets
+        start again at zero with every bracket: its launch is ordered behind the previous one on the stream."""
+        st = self._state()
+        if st is None:
+            return 0, 0
+        off = st["ctr"], st["slab"]
+        st["ctr"] += (int(counter_bytes) + 255) // 256 * 256
+        st["slab"] += (int(slab_bytes) + 255) // 256 * 256
+        return off
+
+
+GROUP = LaunchGroup()
+
+
 def _need_gpu(t):
     if not t.is_cuda:
         raise RuntimeError("adnm_hip kernels run on the GPU only (there is no CPU fallback); got a CPU tensor")
@@ -891,12 +950,20 @@ def k_dwconv_fwd(x, wt, bias, B, H, W, C, K, act, y=None, addend=None, chan_majo
     px, ldx = _rows(x)
     py, ldy = _rows(y)
     pa, lda = _rows(addend) if addend is not None else (None, 0)
+    GROUP.keep(x, wt, bias, addend, y)   # (an open launch group only records the launch)
     lib.call("adnm_dwconv_fwd", px, ldx, _p(_f32(wt)), _p(_f32(bias)), pa, lda, py, ldy, B, H, W, C, K, K, act, int(chan_major), _dt(x), _stream())
     return y
 
 
 def k_dwconv_bwd(dy, x, wt, bias, B, H, W, C, K, act, dx=None, want_bias=False, want_w=True, chan_major=False, want_dx=True):
     """want_dx=False (the input needs no gradient; only without activation, where the tap gradient reads dy itself): tap / bias gradients only."""
+    return k_dwconv_bwd_w(k_dwconv_bwd_dx(dy, x, wt, bias, B, H, W, C, K, act, dx=dx, want_bias=want_bias, want_w=want_w, chan_major=chan_major,
+                                          want_dx=want_dx))
+
+
+def k_dwconv_bwd_dx(dy, x, wt, bias, B, H, W, C, K, act, dx=None, want_bias=False, want_w=True, chan_major=False, want_dx=True):
+    """First half of k_dwconv_bwd: the allocations and the input gradient (with the pre-activation gradient it needs) on the current stream
+    — the launches an open launch group records.  -> the state k_dwconv_bwd_w finishes (it holds every buffer those launches touch)."""
     dev = x.device
     if not want_dx:
         assert act == lib.ACT_NONE and want_w
@@ -910,20 +977,30 @@ def k_dwconv_bwd(dy, x, wt, bias, B, H, W, C, K, act, dx=None, want_bias=False, 
     pdy, lddy = _rows(dy)
     px, ldx = _rows(x)
     pdx, lddx = _rows(dx) if dx is not None else (None, 0)
-    if not want_w:
+    GROUP.keep(ws, dy, x, wt, bias, dpre, dx)   # (an open launch group only records dpre and the input gradient)
+    if want_dx or not want_w:
         lib.call("adnm_dwconv_bwd", pdy, lddy, px, ldx, _p(wt), _p(bias), _p(dpre), pdx, lddx, None, None, ws.data_ptr(),
                  nb, B, H, W, C, K, K, act, int(chan_major), _dt(x), _stream())
-        return dx, dwt, db
-    # input gradient (and the pre-activation gradient it needs) on the current stream, the tap / bias gradients as a leaf beside it
-    if want_dx:
-        lib.call("adnm_dwconv_bwd", pdy, lddy, px, ldx, _p(wt), _p(bias), _p(dpre), pdx, lddx, None, None, ws.data_ptr(),
-                 nb, B, H, W, C, K, K, act, int(chan_major), _dt(x), _stream())
+    return dict(dy=dy, x=x, wt=wt, bias=bias, dx=dx, dwt=dwt, db=db, dpre=dpre, ws=ws, nb=nb, dims=(B, H, W, C, K), chan_major=chan_major,
+                want_w=want_w)
+
+
+def k_dwconv_bwd_w(s):
+    """Second half of k_dwconv_bwd: the tap / bias gradients, a leaf beside the input-gradient chain.  -> (dx, dwt, db)."""
+    if not s["want_w"]:
+        return s["dx"], s["dwt"], s["db"]
+    dy, x, dpre, ws, nb = s["dy"], s["x"], s["dpre"], s["ws"], s["nb"]
+    assert dpre is None or not GROUP.open, "k_dwconv_bwd_w inside a launch group: the tap gradient would read a dpre that is only recorded"
+    B, H, W, C, K = s["dims"]
+    pdy, lddy = _rows(dy)
+    px, ldx = _rows(x)
     g, ldg = (dpre.data_ptr(), C) if dpre is not None else (pdy, lddy)
     # taps / bias gradients: parameters, or prep intermediates flushed at the prep node
     # (the operands are kept with the workspace: under a bound leaf queue the launch itself waits for the grouped flush)
-    with FOLDS.defer(dev, ws, dy, x, dpre):
-        lib.call("adnm_dwconv_wgrad", g, ldg, px, ldx, _p(dwt), _p(db), ws.data_ptr(), nb, B, H, W, C, K, K, int(chan_major), _dt(x), _stream())
-    return dx, dwt, db
+    with FOLDS.defer(x.device, ws, dy, x, dpre):
+        lib.call("adnm_dwconv_wgrad", g, ldg, px, ldx, _p(s["dwt"]), _p(s["db"]), ws.data_ptr(), nb, B, H, W, C, K, K, int(s["chan_major"]), _dt(x),
+                 _stream())
+    return s["dx"], s["dwt"], s["db"]
 
 
 def k_haar_dwt(x, B, H, W, C, cx=1):
@@ -999,6 +1076,7 @@ def k_instnorm_fwd(x, scale, shift, B, HW, C, eps, act):
     rstd = torch.empty((B, C), dtype=torch.float32, device=dev)
     nb = lib.query("adnm_instnorm_ws_bytes", B, HW, C)
     ws = _ws(nb, dev)
+    GROUP.keep(ws, x, y, mu, rstd)   # (an open launch group only records the two launches)
     lib.call("adnm_instnorm_fwd", x.data_ptr(), _p(scale), _p(shift), y.data_ptr(), mu.data_ptr(), rstd.data_ptr(), ws.data_ptr(), nb,
              B, HW, C, float(eps), act, _dt(x), _stream())
     return y, mu, rstd
@@ -1012,6 +1090,7 @@ def k_instnorm_bwd(dy, x, scale, shift, mu, rstd, B, HW, C, act, want_affine=Tru
     dsh = grad_dst(shift.data_ptr() if shift is not None else 0, (), dev) if want_affine else None
     nb = lib.query("adnm_instnorm_ws_bytes", B, HW, C)
     ws = _ws(nb, dev)
+    GROUP.keep(ws, dy, x, dx, dsc, dsh)   # (an open launch group only records the two launches, and the fold when no queue is bound)
     with FOLDS.defer(dev, ws):   # d scale / d shift: parameter gradients (per-workgroup partials + the shared fold)
         lib.call("adnm_instnorm_bwd", dy.data_ptr(), x.data_ptr(), _p(scale), _p(shift), mu.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
                  _p(dsc), _p(dsh), ws.data_ptr(), nb, B, HW, C, act, _dt(x), _stream())
@@ -1053,6 +1132,7 @@ def k_gate_fwd(h, F):
     M = h.shape[0]
     y = torch.empty((M, F), dtype=h.dtype, device=h.device)
     ph, ldh = _rows(h)
+    GROUP.keep(h, y)   # (an open launch group only records the launch)
     lib.call("adnm_gate_fwd", ph, ldh, y.data_ptr(), F, M, F, _dt(h), _stream())
     return y
 
@@ -1062,6 +1142,7 @@ def k_gate_bwd(dy, h, F):
     dh = torch.empty((M, 2 * F), dtype=h.dtype, device=h.device)
     pdy, lddy = _rows(dy)
     ph, ldh = _rows(h)
+    GROUP.keep(dy, h, dh)   # (an open launch group only records the launch)
     lib.call("adnm_gate_bwd", pdy, lddy, ph, ldh, dh.data_ptr(), 2 * F, M, F, _dt(h), _stream())
     return dh
 
@@ -2113,7 +2194,11 @@ def _skgemm(op, a, b, bias, c, dbias, M, N, K, defer=False, q=None, role="f", na
     if op != SK_TN and nb > 16:
         # NT / NN split over workgroups: the slabs are combined inside the launch — arrival counters + uncached slab space of this stream
         # (or this capture scope: SplitWorkspaces); an un-scoped capture takes a torch workspace [zeroed counters | slabs], fenced protocol
-        reg = SPLITWS.take(a.device, nb, lib.query("adnm_skgemm_counter_bytes", op, M, N, K))
+        # (inside a launch-group bracket every split problem takes its own sub-range of the region: the problems of a merged launch run
+        # at the same time; the region is sized — through SplitWorkspaces._seen as always — for the whole bracket)
+        cb = lib.query("adnm_skgemm_counter_bytes", op, M, N, K)
+        coff, soff = GROUP.split_offsets(cb, nb)
+        reg = SPLITWS.take(a.device, soff + nb, coff + cb)
         if reg is None:
             ws = _ws((nb + 255) // 256 * 256 + 256, a.device)
             ws.zero_()
@@ -2121,13 +2206,13 @@ def _skgemm(op, a, b, bias, c, dbias, M, N, K, defer=False, q=None, role="f", na
             wsp, wsn = ws.data_ptr() + off, nb
         else:
             ws = reg
-            wsp, wsn = reg.counters.data_ptr(), reg.counters.numel() * 4
+            wsp, wsn = reg.counters.data_ptr() + coff, reg.counters.numel() * 4 - coff
             if os.environ.get("ADNM_SK_UC_SLABS", "1") == "0":   # measurement aid / test: the fenced protocol, slabs behind the counters
                 ws = (reg, _ws(nb + 256, a.device))
                 ws[1].zero_()
                 wsp, wsn = ws[1].data_ptr() + (-ws[1].data_ptr()) % 256, nb
             else:
-                ucp, ucn = reg.slabs.ptr, reg.slabs.nbytes
+                ucp, ucn = reg.slabs.ptr + soff, reg.slabs.nbytes - soff
     else:
         ws = _ws(nb, a.device)
         wsp, wsn = ws.data_ptr(), nb
@@ -2146,6 +2231,8 @@ def _skgemm(op, a, b, bias, c, dbias, M, N, K, defer=False, q=None, role="f", na
     # only the weight-gradient op (TN) may wait for its split-K fold; under a bound leaf queue its launch itself waits for the grouped
     # flush, so a and b are kept with the workspace
     keep = (ws, a, b) if op == SK_TN else (ws,)
+    if op != SK_TN:   # an NT / NN launch recorded by an open launch group reads and writes these when the bracket closes
+        GROUP.keep(ws, a, b, bias, c, bsc)
     with FOLDS.defer(a.device, *keep) if defer else _NODEFER:
         lib.call("adnm_skgemm", op, a.data_ptr(), a.stride(0), bp, b.stride(0), bdt, _p(bsc), _p(bias), c.data_ptr(), c.stride(0), _p(dbias),
                  wsp, wsn, ucp, ucn, M, N, K, prec, qp, _stream())
@@ -2186,6 +2273,7 @@ def k_linear(x2, w, bias, out=None, qkey=None, role="f", out_dtype=None, narrow=
     x2 = _sk_operand(x2, "input")
     w = _sk_operand(w, "weight") if narrow is None else _NarrowW(narrow, N, K, x2.device)
     y = out if out is not None and _out_view_ok(out) else torch.empty((M, N), dtype=x2.dtype, device=x2.device)
+    assert out is None or y is out or not GROUP.open, "k_linear inside a launch group: the trailing copy would read a result that is only recorded"
     _skgemm(SK_NT, x2, w, bias, y, None, M, N, K, q=q, role=role, narrow=narrow)
     if out is not None and y is not out:
         out.copy_(y)
@@ -2208,6 +2296,7 @@ def k_linear_dx(dy2, w, out=None, qkey=None, role="g", out_dtype=None, narrow=No
     dy2 = _sk_operand(dy2, "output gradient")
     w = _sk_operand(w, "weight") if narrow is None else _NarrowW(narrow, N, K, dy2.device)
     dx = out if out is not None and _out_view_ok(out) else torch.empty((M, K), dtype=dy2.dtype, device=dy2.device)
+    assert out is None or dx is out or not GROUP.open, "k_linear_dx inside a launch group: the trailing copy would read a result that is only recorded"
     _skgemm(SK_NN, dy2, w, None, dx, None, M, N, K, q=q, role=role, narrow=narrow)
     if out is not None and dx is not out:
         out.copy_(dx)
@@ -2662,6 +2751,7 @@ class IGateResFn(torch.autograd.Function):
         per_token = int(res.numel() == x.numel())   # the reference's own call form hands over the gate already expanded over the tokens
         x, r = x.contiguous(), (res.reshape(B, L, C) if per_token else res.reshape(B, C)).contiguous()
         y = torch.empty_like(x)
+        GROUP.keep(x, r, gama, enhance, threshold, y)   # (an open launch group only records the launch)
         lib.call("adnm_igate_res_fwd", x.data_ptr(), r.data_ptr(), per_token, gama.data_ptr(), enhance.data_ptr(), threshold.data_ptr(), y.data_ptr(),
                  B, L, C, _stream())
         ctx.save_for_backward(x, r, gama, enhance, threshold)
@@ -2678,6 +2768,7 @@ class IGateResFn(torch.autograd.Function):
         dg, de, dt = (grad_dst(p.data_ptr(), p.shape, dev) for p in (gama, enhance, threshold))
         nb = lib.query("adnm_igate_res_bwd_ws_bytes", B, L, C)
         ws = _ws(nb, dev)
+        GROUP.keep(ws, dy, x, r, dx, dres, dg, de, dt)   # (an open launch group only records the launch, and the fold when no queue is bound)
         with FOLDS.defer(dev, ws):   # d res is complete when the launch ends; only the three scalar gradients go through the fold
             lib.call("adnm_igate_res_bwd", dy.data_ptr(), x.data_ptr(), r.data_ptr(), ctx.per_token, gama.data_ptr(), enhance.data_ptr(), threshold.data_ptr(),
                      dx.data_ptr(), dres.data_ptr(), dg.data_ptr(), de.data_ptr(), dt.data_ptr(), ws.data_ptr(), nb, B, L, C, _stream())
@@ -2744,6 +2835,194 @@ def skipgate(x, h, w, params):
     if x.dtype != torch.float32 or x.dim() != 3 or x.shape[-1] % 4 or x.shape[1] != h * w:
         _unsupported("skipgate", f"needs fp32 (B, H*W, C) tokens with 4 | C, got {x.dtype} {tuple(x.shape)} for a {h}x{w} map")
     return SkipGateFn.apply(x, h, w, *params)
+
+
+class _SubCtx:
+    """Stands in for the autograd context when a node runs another node's forward / backward as plain code; it keeps what that node
+    saved (so every intermediate of the outer node lives as long as the outer node does: plain attributes, not autograd's saved-tensor
+    slots, so they are neither version-checked nor released by the backward itself).  needs_input_grad is all True: the inner node
+    computes every gradient it can, and autograd drops those of outer inputs that need none (a frozen parameter costs its gradient's
+    launch here, which it does not in the module's own forward)."""
+
+    def __init__(self, n_inputs):
+        self.needs_input_grad = (True,) * n_inputs
+        self.saved_tensors = ()
+
+    def save_for_backward(self, *tensors):
+        self.saved_tensors = tensors
+
+
+class E2DGroupFn(torch.autograd.Function):
+    """n independent EncoderToDecoder chains (models/model_untils.py) as ONE autograd node: the chains advance in lockstep, `for chain in
+    chains` per step, one GROUP bracket per step, so the i-th launch of every chain is one launch wherever the entry point records (the
+    short GEMMs, the depthwise stencils, the gates, InstanceNorm, igate_res; the skip kernels, GroupNorm and the weight-gradient leaves
+    launch as they do alone).  Forward and backward are the sequences of IGateResFn, InstNormFn / GroupNormFn,
+    SkipGateFn, FeedForwardFn, LinearFn and DWConvFn that EncoderToDecoder.forward builds, run through those nodes' own code: outputs and
+    every gradient are bitwise what n separate module calls give.  Inputs: metas = [(h, w, GroupNorm groups | 0, eps)] per chain, then
+    n skips, n gates, n x NP parameters in EncoderToDecoder.group_args()'s order.  The per-step brackets close inside this function, so the
+    queued folds and leaf launches of the parameter gradients stay behind them."""
+    NP = 37
+
+    @staticmethod
+    def forward(ctx, metas, *ts):
+        n, NP = len(metas), E2DGroupFn.NP
+        xs, gates = ts[:n], ts[n:2 * n]
+        P = [ts[2 * n + i * NP:2 * n + (i + 1) * NP] for i in range(n)]
+        C = [{} for _ in range(n)]   # per chain: the contexts of its steps
+
+        def sub(i, name, n_inputs=9):
+            C[i][name] = _SubCtx(n_inputs)
+            return C[i][name]
+
+        with GROUP:
+            cur = [IGateResFn.forward(sub(i, "igate"), xs[i], gates[i], *P[i][0:3]) for i in range(n)]
+        with GROUP:   # (a GroupNorm chain keeps its own launches: that entry point does not record)
+            for i, (h, w, groups, eps) in enumerate(metas):
+                if groups:
+                    cur[i] = GroupNormFn.forward(sub(i, "norm"), cur[i], groups, P[i][3], P[i][4], P[i][5], P[i][6], eps, lib.ACT_NONE)
+                else:
+                    cur[i] = InstNormFn.forward(sub(i, "norm"), cur[i], P[i][5], P[i][6], eps, lib.ACT_NONE)
+        cur = [SkipGateFn.forward(sub(i, "skip", 21), cur[i], metas[i][0], metas[i][1], *P[i][7:25]) for i in range(n)]
+        # FeedForwardFn.forward, step by step
+        F = []
+        for i in range(n):
+            w_in, b_in, dw, b_dw, w_out, b_out = P[i][25:31]
+            B, L, d = cur[i].shape
+            M, F4, F2 = B * L, w_in.shape[0], w_out.shape[1]
+            x2 = cur[i].reshape(M, d)
+            x2 = x2 if x2.is_contiguous() else x2.contiguous()
+            wt = dw.reshape(F4, 9)
+            if wt.dtype != torch.float32 or not wt.is_contiguous():
+                wt = wt.contiguous().float()
+            F.append(dict(x2=x2, w_in=w_in.contiguous(), b_in=b_in, wt=wt, b_dw=b_dw, w_out=w_out.contiguous(), b_out=b_out, dims=(B, L, d, M, F4, F2),
+                          dwshape=dw.shape, st=low_storage(M, [(F4, d), (d, F4), (d, F2), (F2, d)]), xdtype=cur[i].dtype))
+        with GROUP:
+            for f in F:
+                f["h1"] = k_linear(f["x2"], f["w_in"], f["b_in"], out_dtype=f["st"])
+        with GROUP:
+            for i, f in enumerate(F):
+                B, L, d, M, F4, F2 = f["dims"]
+                f["h2"] = k_dwconv_fwd(f["h1"], f["wt"], f["b_dw"], B, metas[i][0], metas[i][1], F4, 3, lib.ACT_NONE, chan_major=True)
+        with GROUP:
+            for f in F:
+                f["g"] = k_gate_fwd(f["h2"], f["dims"][5])
+        with GROUP:
+            for f in F:
+                f["out"] = k_linear(f["g"], f["w_out"], f["b_out"], out_dtype=f["xdtype"])
+        cur = [f["out"].view(f["dims"][0], f["dims"][1], f["w_out"].shape[0]) for f in F]
+        # ConvFFD: Linear, depthwise 3x3 + GELU, Linear
+        with GROUP:
+            cur = [LinearFn.forward(sub(i, "in_proj"), cur[i], P[i][31], P[i][32]) for i in range(n)]
+        with GROUP:
+            cur = [DWConvFn.forward(sub(i, "dwc"), cur[i], P[i][33], P[i][34], metas[i][0], metas[i][1], lib.ACT_GELU) for i in range(n)]
+        with GROUP:
+            cur = [LinearFn.forward(sub(i, "out_proj"), cur[i], P[i][35], P[i][36]) for i in range(n)]
+        ctx.chains, ctx.ffn, ctx.metas = C, F, metas
+        for f in F:
+            del f["out"]   # (an output of this node: not kept, the gated tensor g is what the backward reads)
+        return tuple(cur)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        C, F, metas = ctx.chains, ctx.ffn, ctx.metas
+        n = len(metas)
+        G = [[None] * E2DGroupFn.NP for _ in range(n)]   # parameter gradients, in the parameters' order
+        with GROUP:
+            r = [LinearFn.backward(C[i]["out_proj"], douts[i]) for i in range(n)]
+        for i in range(n):
+            G[i][35], G[i][36] = r[i][1], r[i][2]
+        # DWConvFn.backward in its two halves: dpre and the input gradient inside the bracket, the tap / bias gradients (which read dpre)
+        # behind its launch
+        S = []
+        with GROUP:
+            for i in range(n):
+                x2, wt, bias = C[i]["dwc"].saved_tensors
+                B, H, W, Cc, K, act, wshape = C[i]["dwc"].dims
+                dy2 = r[i][0].reshape(B * H * W, Cc)
+                dy2 = dy2 if dy2.stride(-1) == 1 else dy2.contiguous()
+                S.append(k_dwconv_bwd_dx(dy2, x2, wt, bias, B, H, W, Cc, K, act, want_bias=bias is not None, want_w=True, chan_major=True))
+        r = []
+        for i in range(n):
+            B, H, W, Cc, K, act, wshape = C[i]["dwc"].dims
+            dxc, dwt, G[i][34] = k_dwconv_bwd_w(S[i])
+            G[i][33] = dwt.view(wshape)
+            r.append((dxc.view(B, H * W, Cc),))
+        with GROUP:
+            r = [LinearFn.backward(C[i]["in_proj"], r[i][0]) for i in range(n)]
+        for i in range(n):
+            G[i][31], G[i][32] = r[i][1], r[i][2]
+        # FeedForwardFn.backward, step by step
+        do = []
+        for i, f in enumerate(F):
+            t = r[i][0].reshape(f["dims"][3], f["w_out"].shape[0])
+            do.append(t if t.is_contiguous() else t.contiguous())
+        dg, dh2, dh1, dx = [None] * n, [None] * n, [None] * n, [None] * n
+        with GROUP:
+            for i, f in enumerate(F):
+                b_out = f["b_out"]
+                dg[i] = k_linear_dx(do[i], f["w_out"], out_dtype=f["g"].dtype)
+                G[i][29], G[i][30] = k_linear_dw(do[i], f["g"], b_out is not None, f["w_out"].data_ptr(), b_out.data_ptr() if b_out is not None else 0)
+        with GROUP:
+            for i, f in enumerate(F):
+                dh2[i] = k_gate_bwd(dg[i], f["h2"], f["dims"][5])
+        S = []
+        with GROUP:
+            for i, f in enumerate(F):
+                B, L, d, M, F4, F2 = f["dims"]
+                S.append(k_dwconv_bwd_dx(dh2[i], f["h1"], f["wt"], f["b_dw"], B, metas[i][0], metas[i][1], F4, 3, lib.ACT_NONE,
+                                         want_bias=f["b_dw"] is not None, chan_major=True))
+        for i, f in enumerate(F):
+            dh1[i], dwt, G[i][28] = k_dwconv_bwd_w(S[i])
+            G[i][27] = dwt.view(f["dwshape"])
+        with GROUP:
+            for i, f in enumerate(F):
+                b_in = f["b_in"]
+                dx[i] = k_linear_dx(dh1[i], f["w_in"], out_dtype=f["x2"].dtype)
+                G[i][25], G[i][26] = k_linear_dw(dh1[i], f["x2"], b_in is not None, f["w_in"].data_ptr(), b_in.data_ptr() if b_in is not None else 0)
+        r = [SkipGateFn.backward(C[i]["skip"], dx[i].view(F[i]["dims"][0], F[i]["dims"][1], F[i]["dims"][2])) for i in range(n)]
+        for i in range(n):
+            G[i][7:25] = r[i][3:21]
+        d = [None] * n
+        with GROUP:
+            for i in range(n):
+                if metas[i][2]:
+                    d[i], _, G[i][3], G[i][4], G[i][5], G[i][6] = GroupNormFn.backward(C[i]["norm"], r[i][0])[:6]
+                else:
+                    d[i], G[i][5], G[i][6] = InstNormFn.backward(C[i]["norm"], r[i][0])[:3]
+        with GROUP:
+            r = [IGateResFn.backward(C[i]["igate"], d[i]) for i in range(n)]
+        for i in range(n):
+            G[i][0:3] = r[i][2:5]
+        return (None,) + tuple(x[0] for x in r) + tuple(x[1] for x in r) + tuple(g for gi in G for g in gi)
+
+
+def e2d_group(xs, gates, modules):
+    """[m(x=x, res=g) for x, g, m in zip(xs, gates, modules)] for EncoderToDecoder modules, as one autograd node whose chains advance in
+    lockstep, the same step of every chain in one launch group (E2DGroupFn: the short GEMMs, the depthwise stencils, the gates, InstanceNorm
+    and igate_res merge; the skip kernels and GroupNorm launch per chain).  -> the list of outputs."""
+    if not (len(xs) == len(gates) == len(modules)) or not xs:
+        raise RuntimeError("adnm_hip e2d_group: needs as many skips as gates and modules, at least one")
+    metas, params = [], []
+    for x, g, m in zip(xs, gates, modules):
+        _need_gpu(x)
+        B, L, C = x.shape
+        if x.dtype != torch.float32 or C % 4 or g.numel() not in (B * C, B * L * C):
+            _unsupported("e2d_group", f"needs fp32 (B, L, C) tokens with 4 | C and a (B, 1, C) or (B, L, C) gate, got {x.dtype} {tuple(x.shape)}, gate {tuple(g.shape)}")
+        meta, p = m.group_args(x)
+        if meta[0] * meta[1] != L:
+            _unsupported("e2d_group", f"needs a square map, got {L} tokens")
+        assert len(p) == E2DGroupFn.NP
+        # what feedforward() and linear() check before their nodes run (the grouped node runs those nodes' code without them)
+        w_in, dw, w_out, w_mi, w_mo = p[25], p[27], p[29], p[31], p[35]
+        F4, F2 = w_in.shape[0], w_out.shape[1]
+        if F4 != 2 * F2 or F2 % 4 or tuple(dw.shape) != (F4, 1, 3, 3) or w_in.shape[1] != C:
+            _unsupported("e2d_group", f"the FeedForward is 1x1 d->4d, depthwise 3x3, gate, 1x1 2d->d with 8 | 4d, got weights {tuple(w_in.shape)}, "
+                                      f"{tuple(dw.shape)}, {tuple(w_out.shape)} for d = {C}")
+        if w_mi.dim() != 2 or w_mo.dim() != 2 or w_mi.shape[0] % 4 or w_mo.shape[0] % 4:
+            _unsupported("e2d_group", f"the ConvFFD Linears need 2-D weights with 4 | out_features, got {tuple(w_mi.shape)}, {tuple(w_mo.shape)}")
+        metas.append(meta)
+        params += p
+    return list(E2DGroupFn.apply(metas, *xs, *gates, *params))
 
 
 class RainLossFn(torch.autograd.Function):

@@ -39,7 +39,7 @@ void adnm_launch_fold(const char* prof_name, const float* part, int rows, int n,
 int64_t adnm_lgemm_ws_bytes(int64_t I, int64_t J, int64_t R, int nbs);
 int adnm_lgemm_launch(bool b_oc, const float* a, int64_t lda, const void* b, int64_t ldb, int b_dtype, const float* b_scale, const float* bias, float* c,
                       int64_t ldc, void* ws, int64_t ws_bytes, void* slabs_uc, int64_t slabs_uc_bytes, int64_t I, int64_t J, int64_t R, int nbs, int prec,
-                      float* q, hipStream_t st);
+                      float* q, const char* prof, double prof_bytes, hipStream_t st);   // (launched, or recorded by an open group, under `prof`)
 static inline int64_t adnm_ticket_bytes(int64_t ntiles) { return (ntiles * 4 + 255) / 256 * 256; }
 
 // Deferred LEAF launches (core.hip, include/adnm_hip.h: adnm_leafq_*).  A weight-gradient kernel is a leaf of the backward pass: nothing reads
@@ -58,6 +58,65 @@ bool adnm_leafq_push(const AdnmLeaf& leaf);                                  // 
 int adnm_skgemm_tn_launch_multi(const AdnmLeaf* const* items, int n, hipStream_t st);   // skgemm.hip
 int adnm_dwconv_wgrad_launch_multi(const AdnmLeaf* const* items, int n, int K, hipStream_t st);   // dwconv.hip
 int adnm_tsgemm_tn_launch_multi(const AdnmLeaf* const* items, int n, hipStream_t st);   // tsgemm.hip
+
+// Launch GROUP (core.hip, include/adnm_hip.h: adnm_group_*).  Between adnm_group_begin and adnm_group_launch the calling thread makes
+// mutually independent calls (the i-th step of several identical chains); an entry point that knows about groups stores its fully prepared
+// launch here instead of making it, and adnm_group_launch merges the records of ONE kernel instantiation into one multi-problem launch
+// (descriptors in the kernel-argument segment, up to ADNM_GROUP_MAX per launch).  Every problem keeps the plan, the grid and the workgroup
+// arithmetic it has alone: results are bitwise those of separate launches.
+//   fn:   launches n <= ADNM_GROUP_MAX records of its own kernel instantiation (n == 1: the plain single-problem kernel) — one host
+//         function per instantiation, so the pointer is also the merge key;
+//   pos:  position inside the recording call: an entry point that issues several DEPENDENT launches numbers them 0, 1, ...; position p
+//         of every call is launched before position p + 1 of any;
+//   args: the kernel's argument struct, copied byte for byte.
+constexpr int ADNM_GROUP_MAX = 8;
+constexpr int ADNM_GROUP_POS_LAST = 1 << 20;   // the position of a recorded second-stage fold (adnm_launch_fold without a bound fold queue)
+struct AdnmGroupRec;
+typedef int (*AdnmGroupFn)(const AdnmGroupRec* const* recs, int n, hipStream_t st);
+struct AdnmGroupRec {
+  AdnmGroupFn fn;
+  int grid, pos;
+  const char* prof;
+  double bytes;
+  alignas(16) unsigned char args[232];
+};
+bool adnm_group_open();                        // is a group open on this thread (would a submit be recorded)?
+// adnm_launch_fold for an entry point whose launches go through adnm_group_submit: inside an open group (and without a bound fold queue)
+// the fold is recorded behind them instead of launched.  Every other fold inside a group is launched at once, behind producers that
+// were launched at once.
+void adnm_launch_fold_recorded(const char* prof_name, const float* part, int rows, int n, AdnmFoldSeg s0, AdnmFoldSeg s1, AdnmFoldSeg s2,
+                               AdnmFoldSeg s3, hipStream_t st);
+// open group: record; otherwise launch now under the record's profiler scope (prof == NULL: the launch opens its own)
+int adnm_group_submit(const AdnmGroupRec& rec, hipStream_t st);
+// the argument of a multi-problem kernel: blk_end = inclusive prefix of the problems' workgroup counts (unused entries repeat the total)
+template <typename Args>
+struct AdnmMulti {
+  int blk_end[ADNM_GROUP_MAX];
+  Args p[ADNM_GROUP_MAX];
+};
+template <typename Args>
+static inline unsigned adnm_group_pack(const AdnmGroupRec* const* r, int n, AdnmMulti<Args>& m) {
+  static_assert(sizeof(Args) <= sizeof(AdnmGroupRec::args), "the argument struct must fit a group record");
+  static_assert(sizeof(AdnmMulti<Args>) <= 4096, "the descriptor table must fit the kernel argument segment");
+  int blocks = 0;
+  for (int k = 0; k < ADNM_GROUP_MAX; ++k) {
+    if (k < n) memcpy(&m.p[k], r[k]->args, sizeof(Args)), blocks += r[k]->grid;
+    else m.p[k] = m.p[0];
+    m.blk_end[k] = blocks;
+  }
+  return (unsigned)blocks;
+}
+// which problem this workgroup belongs to: the prefix entries at or below blockIdx.x, counted with CONSTANT indices (scalar loads and
+// compares, as fold_rows_kernel does); *bid / *nblk: the workgroup's index inside its problem and that problem's workgroup count
+template <typename M>
+__device__ __forceinline__ int adnm_group_which(const M& m, int* bid, int* nblk) {
+  int k = 0;
+#pragma unroll
+  for (int i = 0; i < ADNM_GROUP_MAX - 1; ++i) k += (int)blockIdx.x >= m.blk_end[i] ? 1 : 0;
+  const int b0 = k ? m.blk_end[k - 1] : 0;
+  *bid = (int)blockIdx.x - b0, *nblk = m.blk_end[k] - b0;
+  return k;
+}
 
 #define ADNM_REQUIRE(cond, ...)            \
   do {                                     \

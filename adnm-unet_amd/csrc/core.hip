@@ -1,5 +1,6 @@
 // Error reporting, ABI version and the opt-in per-kernel HIP-event profiler of libadnm_hip.
 #include "adnm_common.h"
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <map>
@@ -298,6 +299,74 @@ void launch_folds(const FoldDesc* d, const char* const* names, int count, hipStr
 }
 }  // namespace
 
+// ---- launch group (adnm_common.h: AdnmGroupRec): a thread-local sibling of the leaf queue, for launches ON the critical path
+namespace {
+struct LaunchGroup {
+  bool open = false;
+  bool fold_follows = false;   // set around the fold of an entry point whose launches were recorded (adnm_launch_fold_recorded)
+  std::vector<AdnmGroupRec> recs;
+};
+thread_local LaunchGroup tls_group;
+}  // namespace
+bool adnm_group_open() { return tls_group.open; }
+int adnm_group_submit(const AdnmGroupRec& rec, hipStream_t st) {
+  if (tls_group.open) {
+    tls_group.recs.push_back(rec);
+    return ADNM_OK;
+  }
+  const AdnmGroupRec* one = &rec;
+  if (!rec.prof) return rec.fn(&one, 1, st);
+  ADNM_PROF(rec.prof, st, rec.bytes);
+  return rec.fn(&one, 1, st);
+}
+extern "C" int adnm_group_begin(void) {
+  ADNM_REQUIRE(!tls_group.open, "group_begin: a group is already open on this thread (groups do not nest)");
+  tls_group.recs.clear();
+  tls_group.open = true;
+  return ADNM_OK;
+}
+extern "C" int64_t adnm_group_pending(void) { return (int64_t)tls_group.recs.size(); }
+extern "C" int adnm_group_clear(void) {   // the caller's error path: the group is closed and nothing it recorded is launched
+  tls_group.recs.clear();
+  tls_group.open = false;
+  return ADNM_OK;
+}
+extern "C" int adnm_group_launch(adnm_stream_t stream) {
+  std::vector<AdnmGroupRec> recs;
+  recs.swap(tls_group.recs);
+  tls_group.open = false;
+  if (recs.empty()) return ADNM_OK;
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int> positions;
+  for (const AdnmGroupRec& r : recs) positions.push_back(r.pos);
+  std::sort(positions.begin(), positions.end());
+  positions.erase(std::unique(positions.begin(), positions.end()), positions.end());
+  std::vector<char> done(recs.size(), 0);
+  for (const int pos : positions) {
+    for (size_t i = 0; i < recs.size(); ++i) {
+      if (done[i] || recs[i].pos != pos) continue;
+      // this record and its partners: the later records of the position that run the same kernel instantiation
+      const AdnmGroupRec* sel[ADNM_GROUP_MAX];
+      int n = 0;
+      double bytes = 0;
+      for (size_t j = i; j < recs.size() && n < ADNM_GROUP_MAX; ++j) {
+        if (done[j] || recs[j].pos != pos || recs[j].fn != recs[i].fn) continue;
+        sel[n++] = &recs[j], bytes += recs[j].bytes, done[j] = 1;
+      }
+      int rc;
+      if (recs[i].prof) {
+        ADNM_PROF(recs[i].prof, st, bytes);
+        rc = recs[i].fn(sel, n, st);
+      } else {   // (a record without a scope name opens its own: the folds)
+        rc = recs[i].fn(sel, n, st);
+      }
+      if (rc != ADNM_OK) return rc;
+    }
+  }
+  ADNM_CHECK_LAUNCH("group_launch");
+  return ADNM_OK;
+}
+
 void adnm_launch_fold(const char* prof_name, const float* part, int rows, int n, AdnmFoldSeg s0, AdnmFoldSeg s1, AdnmFoldSeg s2,
                       AdnmFoldSeg s3, hipStream_t st) {
   FoldDesc fd;
@@ -319,7 +388,40 @@ void adnm_launch_fold(const char* prof_name, const float* part, int rows, int n,
     tls_foldq->names.push_back(prof_name);
     return;
   }
+  if (tls_group.open && tls_group.fold_follows) {
+    // the immediate fold of a group-aware entry point: its partials come from launches the group has only recorded, so it is recorded too, behind
+    // every other position; the folds of a group share one launch (the arithmetic per descriptor does not depend on batching)
+    struct FoldRec {
+      FoldDesc fd;
+      const char* name;
+    };
+    static_assert(sizeof(FoldRec) <= sizeof(AdnmGroupRec::args), "a fold descriptor must fit a group record");
+    AdnmGroupRec rec;
+    rec.fn = [](const AdnmGroupRec* const* r, int n, hipStream_t s) {
+      FoldDesc d[ADNM_GROUP_MAX];
+      const char* names[ADNM_GROUP_MAX];
+      for (int k = 0; k < n; ++k) {
+        FoldRec fr;
+        memcpy(&fr, r[k]->args, sizeof(FoldRec));
+        d[k] = fr.fd, names[k] = fr.name;
+      }
+      launch_folds(d, names, n, s);
+      return (int)ADNM_OK;
+    };
+    rec.grid = fold_blocks(fd), rec.pos = ADNM_GROUP_POS_LAST, rec.prof = nullptr, rec.bytes = 0;
+    const FoldRec fr{fd, prof_name};
+    memcpy(rec.args, &fr, sizeof(FoldRec));
+    tls_group.recs.push_back(rec);
+    return;
+  }
   launch_folds(&fd, &prof_name, 1, st);
+}
+
+void adnm_launch_fold_recorded(const char* prof_name, const float* part, int rows, int n, AdnmFoldSeg s0, AdnmFoldSeg s1, AdnmFoldSeg s2,
+                               AdnmFoldSeg s3, hipStream_t st) {
+  tls_group.fold_follows = true;
+  adnm_launch_fold(prof_name, part, rows, n, s0, s1, s2, s3, st);
+  tls_group.fold_follows = false;
 }
 
 extern "C" void* adnm_foldq_create(void) { return new FoldQueue(); }
@@ -345,6 +447,7 @@ extern "C" int adnm_foldq_accumulate_next(int mask) {
 }
 extern "C" int adnm_foldq_flush(void* q, adnm_stream_t stream) {
   ADNM_REQUIRE(q, "foldq_flush: null queue");
+  ADNM_REQUIRE(!tls_group.open, "foldq_flush: a launch group is open on this thread (its recorded launches may produce what the folds read)");
   FoldQueue* fq = (FoldQueue*)q;
   if (fq->pending.empty()) return ADNM_OK;
   // the overwriting folds first, then — in later launches, i.e. ordered behind them on the stream — the accumulating ones; two
@@ -408,6 +511,7 @@ extern "C" int adnm_leafq_clear(void* q) {
 }
 extern "C" int adnm_leafq_flush(void* q, adnm_stream_t stream) {
   ADNM_REQUIRE(q, "leafq_flush: null queue");
+  ADNM_REQUIRE(!tls_group.open, "leafq_flush: a launch group is open on this thread (its recorded launches may produce what the leaves read)");
   LeafQueue* lq = (LeafQueue*)q;
   if (lq->items.empty()) return ADNM_OK;
   int rc = ADNM_OK;

@@ -100,11 +100,28 @@ __device__ __forceinline__ void cv_add(CVec<T>& a, const CVec<T>& x) {
 // MODE 0: y = act(conv(x) + bias) (+ addend)         [forward]
 // MODE 1: y = dy * act'(conv(x) + bias)              [backward step (a); `aux` = dy with pixel stride ldaux]
 // MODE 2: y = conv_flipped(x)                        [backward step (b); x = dpre]
-template <typename T, int K, int MODE, bool WCM>
-__global__ __launch_bounds__(kBlock) void dwconv_kernel(const T* __restrict__ x, int64_t ldx, const float* __restrict__ wgt,
-                                                        const float* __restrict__ bias, const T* __restrict__ aux,
-                                                        int64_t ldaux, T* __restrict__ y, int64_t ldy, int B, int H, int W,
-                                                        int C, int act) {
+struct DwArgs {
+  const void* x;
+  int64_t ldx;
+  const float* wgt;
+  const float* bias;
+  const void* aux;
+  int64_t ldaux;
+  void* y;
+  int64_t ldy;
+  int B, H, W, C, act;
+};
+// (blk, nb): this workgroup's index and the workgroup count of ITS problem — blockIdx.x / gridDim.x of the single-problem launch, a block
+// range of a grouped one (dwconv_multi_kernel).  Args: DwArgs, possibly in the constant address space.
+template <typename T, int K, int MODE, bool WCM, typename Args>
+__device__ __forceinline__ void dwconv_body(const Args& p, const unsigned blk, const unsigned nb) {
+  const T* __restrict__ x = (const T*)p.x;
+  const float* __restrict__ wgt = p.wgt;
+  const float* __restrict__ bias = p.bias;
+  const T* __restrict__ aux = (const T*)p.aux;
+  T* __restrict__ y = (T*)p.y;
+  const int64_t ldx = p.ldx, ldaux = p.ldaux, ldy = p.ldy;
+  const int B = p.B, H = p.H, W = p.W, C = p.C, act = p.act;
   constexpr int R = K / 2, N = CVec<T>::N, Q = CVec<T>::Q;
   using V = CVec<T>;
   const int C4 = C / N;   // channel vectors per pixel
@@ -113,7 +130,7 @@ __global__ __launch_bounds__(kBlock) void dwconv_kernel(const T* __restrict__ x,
   // XCD-aware block order: consecutive blockIdx round-robin over the 8 XCDs (private L2 each), but the halo rows of a
   // stencil are shared by VERTICALLY adjacent tiles.  Give every XCD one contiguous band of tiles so that re-reads of
   // the K-1 halo rows hit that XCD's own L2 (bijective for any grid size).
-  const unsigned nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
+  const unsigned q8 = nb >> 3, r8 = nb & 7, xcd = blk & 7, loc = blk >> 3;
   const unsigned bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
   const int64_t idx = (int64_t)bid * kBlock + threadIdx.x;
   if (idx >= total) return;
@@ -189,6 +206,33 @@ __global__ __launch_bounds__(kBlock) void dwconv_kernel(const T* __restrict__ x,
     }
     cv_st(y + pix * ldy + c, v);
   }
+}
+template <typename T, int K, int MODE, bool WCM>
+__global__ __launch_bounds__(kBlock) void dwconv_kernel(DwArgs p) {
+  dwconv_body<T, K, MODE, WCM>(p, blockIdx.x, gridDim.x);
+}
+// up to ADNM_GROUP_MAX independent problems of one instantiation in one launch (adnm_common.h: launch group): every workgroup looks up its
+// problem in the descriptor table (kernel arguments) and runs the unchanged stencil on that problem's own block range
+template <typename T, int K, int MODE, bool WCM>
+__global__ __launch_bounds__(kBlock) void dwconv_multi_kernel(AdnmMulti<DwArgs> by_value) {
+  (void)by_value;
+  const auto& m = *(const __attribute__((address_space(4))) AdnmMulti<DwArgs>*)__builtin_amdgcn_kernarg_segment_ptr();
+  int bid, nblk;
+  const int k = adnm_group_which(m, &bid, &nblk);
+  dwconv_body<T, K, MODE, WCM>(m.p[k], (unsigned)bid, (unsigned)nblk);
+}
+template <typename T, int K, int MODE, bool WCM>
+int dw_group_fn(const AdnmGroupRec* const* r, int n, hipStream_t st) {
+  if (n == 1) {
+    DwArgs p;
+    memcpy(&p, r[0]->args, sizeof(DwArgs));
+    dwconv_kernel<T, K, MODE, WCM><<<(unsigned)r[0]->grid, kBlock, 0, st>>>(p);
+    return ADNM_OK;
+  }
+  AdnmMulti<DwArgs> m;
+  const unsigned blocks = adnm_group_pack(r, n, m);
+  dwconv_multi_kernel<T, K, MODE, WCM><<<blocks, kBlock, 0, st>>>(m);
+  return ADNM_OK;
 }
 
 // (c) weight / bias gradients.  block = K waves, wave i owns tap ROW i of every channel quad it sees, so a lane
@@ -658,23 +702,19 @@ int check(const char* who, const void* x, int64_t B, int64_t H, int64_t W, int64
   return ADNM_OK;
 }
 
+// pos: the launch's position inside the calling entry point (adnm_common.h: AdnmGroupRec) — made now, or recorded by an open launch group
 template <typename T, int MODE>
-void launch_conv(const void* x, int64_t ldx, const float* wgt, const float* bias, const void* aux, int64_t ldaux, void* y, int64_t ldy,
-                 int64_t B, int64_t H, int64_t W, int64_t C, int K, int act, int wcm, hipStream_t st) {
+int launch_conv(const void* x, int64_t ldx, const float* wgt, const float* bias, const void* aux, int64_t ldaux, void* y, int64_t ldy,
+                int64_t B, int64_t H, int64_t W, int64_t C, int K, int act, int wcm, int pos, hipStream_t st) {
   const int64_t total = B * H * adnm_cdiv(W, TW) * (C / CVec<T>::N);
-  const unsigned grid = (unsigned)adnm_cdiv(total, kBlock);
-#define ADNM_DWCONV(KK, WCMV)                                                                                                       \
-  dwconv_kernel<T, KK, MODE, WCMV><<<grid, kBlock, 0, st>>>((const T*)x, ldx, wgt, bias, (const T*)aux, ldaux, (T*)y, ldy, (int)B, (int)H, \
-                                                            (int)W, (int)C, act)
-  ADNM_PROF(K == 3 ? "dwconv_k3" : "dwconv_k5", st, (double)sizeof(T) * B * H * W * C * (MODE == 1 ? 3 : (aux ? 3 : 2)));
-  if (K == 3) {
-    if (wcm) ADNM_DWCONV(3, true);
-    else ADNM_DWCONV(3, false);
-  } else {
-    if (wcm) ADNM_DWCONV(5, true);
-    else ADNM_DWCONV(5, false);
-  }
-#undef ADNM_DWCONV
+  const DwArgs p{x, ldx, wgt, bias, aux, ldaux, y, ldy, (int)B, (int)H, (int)W, (int)C, act};
+  AdnmGroupRec rec;
+  rec.grid = (int)adnm_cdiv(total, kBlock), rec.pos = pos, rec.prof = K == 3 ? "dwconv_k3" : "dwconv_k5";
+  rec.bytes = (double)sizeof(T) * B * H * W * C * (MODE == 1 ? 3 : (aux ? 3 : 2));
+  memcpy(rec.args, &p, sizeof(DwArgs));
+  if (K == 3) rec.fn = wcm ? dw_group_fn<T, 3, MODE, true> : dw_group_fn<T, 3, MODE, false>;
+  else rec.fn = wcm ? dw_group_fn<T, 5, MODE, true> : dw_group_fn<T, 5, MODE, false>;
+  return adnm_group_submit(rec, st);
 }
 
 template <typename T>
@@ -733,8 +773,9 @@ extern "C" int adnm_dwconv_fwd(const void* x, int64_t ldx, const float* wgt, con
                    ((uintptr_t)x | (uintptr_t)y | (uintptr_t)addend) % 16 == 0,
                "dwconv_fwd: pixel strides must be >= C, rows and strides 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == ADNM_F32) launch_conv<float, 0>(x, ldx, wgt, bias, addend, ldadd, y, ldy, B, H, W, C, KH, act, wlayout, st);
-  else launch_conv<uint16_t, 0>(x, ldx, wgt, bias, addend, ldadd, y, ldy, B, H, W, C, KH, act, wlayout, st);
+  const int rc = dtype == ADNM_F32 ? launch_conv<float, 0>(x, ldx, wgt, bias, addend, ldadd, y, ldy, B, H, W, C, KH, act, wlayout, 0, st)
+                                   : launch_conv<uint16_t, 0>(x, ldx, wgt, bias, addend, ldadd, y, ldy, B, H, W, C, KH, act, wlayout, 0, st);
+  if (rc != ADNM_OK) return rc;
   ADNM_CHECK_LAUNCH("dwconv_fwd");
   return ADNM_OK;
 }
@@ -760,6 +801,8 @@ extern "C" int adnm_dwconv_bwd(const void* dy, int64_t lddy, const void* x, int6
   ADNM_REQUIRE(dy && wgt && dx, "dwconv_bwd: null pointer");
   ADNM_REQUIRE(wlayout == 0 || wlayout == 1, "dwconv_bwd: weight layout %d not in {0 tap-major, 1 channel-major}", wlayout);
   ADNM_REQUIRE(act == ADNM_ACT_NONE || dpre, "dwconv_bwd: dpre scratch required when an activation is fused");
+  ADNM_REQUIRE(!(dwgt && adnm_group_open()), "dwconv_bwd: inside a launch group the weight gradient is a call of its own (adnm_dwconv_wgrad) behind the "
+                                             "group's launch: it reads what the recorded launches produce");
   const int al = dtype == ADNM_BF16 ? 8 : 4;   // elements per 16-byte lane access
   ADNM_REQUIRE(ldx >= C && lddy >= C && lddx >= C && ldx % al == 0 && lddy % al == 0 && lddx % al == 0 &&
                    ((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)dpre) % 16 == 0,
@@ -773,17 +816,17 @@ extern "C" int adnm_dwconv_bwd(const void* dy, int64_t lddy, const void* x, int6
   int64_t ldg = lddy;
   if (dtype == ADNM_F32) {
     if (act != ADNM_ACT_NONE) {
-      launch_conv<float, 1>(x, ldx, wgt, bias, dy, lddy, dpre, C, B, H, W, C, KH, act, wlayout, st);
+      if (int rc = launch_conv<float, 1>(x, ldx, wgt, bias, dy, lddy, dpre, C, B, H, W, C, KH, act, wlayout, 0, st)) return rc;
       g = dpre; ldg = C;
     }
-    launch_conv<float, 2>(g, ldg, wgt, nullptr, nullptr, 0, dx, lddx, B, H, W, C, KH, 0, wlayout, st);
+    if (int rc = launch_conv<float, 2>(g, ldg, wgt, nullptr, nullptr, 0, dx, lddx, B, H, W, C, KH, 0, wlayout, act != ADNM_ACT_NONE ? 1 : 0, st)) return rc;
     if (dwgt) launch_wgrad<float>(g, ldg, x, ldx, (float*)ws, dwgt, dbias, B, H, W, C, KH, wlayout, st);
   } else {
     if (act != ADNM_ACT_NONE) {
-      launch_conv<uint16_t, 1>(x, ldx, wgt, bias, dy, lddy, dpre, C, B, H, W, C, KH, act, wlayout, st);
+      if (int rc = launch_conv<uint16_t, 1>(x, ldx, wgt, bias, dy, lddy, dpre, C, B, H, W, C, KH, act, wlayout, 0, st)) return rc;
       g = dpre; ldg = C;
     }
-    launch_conv<uint16_t, 2>(g, ldg, wgt, nullptr, nullptr, 0, dx, lddx, B, H, W, C, KH, 0, wlayout, st);
+    if (int rc = launch_conv<uint16_t, 2>(g, ldg, wgt, nullptr, nullptr, 0, dx, lddx, B, H, W, C, KH, 0, wlayout, act != ADNM_ACT_NONE ? 1 : 0, st)) return rc;
     if (dwgt) launch_wgrad<uint16_t>(g, ldg, x, ldx, (float*)ws, dwgt, dbias, B, H, W, C, KH, wlayout, st);
   }
   ADNM_CHECK_LAUNCH("dwconv_bwd");

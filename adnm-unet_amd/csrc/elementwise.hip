@@ -5,12 +5,27 @@ namespace {
 constexpr int kBlock = 256;
 
 // FeedForward gate (model_untils.py:194-195): y = gelu(x1) * sigmoid(x2), x1|x2 = column halves of h.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void gate_fwd_kernel(const T* __restrict__ h, int64_t ldh, T* __restrict__ y, int64_t ldy,
-                                                          int64_t M, int F) {
+// Both gate kernels take an argument struct and run on (bid, nblk) = the workgroup's index and the workgroup count of ITS problem: the
+// whole grid of the single-problem launch, a block range of a grouped one (adnm_common.h: launch group).
+struct GateArgs {
+  const void* dy;   // backward only
+  int64_t lddy;
+  const void* h;
+  int64_t ldh;
+  void* y;          // forward: y; backward: dh
+  int64_t ldy;
+  int64_t M;
+  int F;
+};
+template <typename T, typename Args>
+__device__ __forceinline__ void gate_fwd_body(const Args& p, const int bid, const int nblk) {
+  const T* __restrict__ h = (const T*)p.h;
+  T* __restrict__ y = (T*)p.y;
+  const int64_t ldh = p.ldh, ldy = p.ldy, M = p.M;
+  const int F = p.F;
   const int F4 = F >> 2;
   const int64_t total = M * F4;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
+  for (int64_t i = (int64_t)bid * kBlock + threadIdx.x; i < total; i += (int64_t)nblk * kBlock) {
     const int64_t m = i / F4;
     const int f = (int)(i % F4) * 4;
     const float4 a = Io<T>::ld4(h + m * ldh + f), b = Io<T>::ld4(h + m * ldh + F + f);
@@ -19,12 +34,16 @@ __global__ __launch_bounds__(kBlock) void gate_fwd_kernel(const T* __restrict__ 
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kBlock) void gate_bwd_kernel(const T* __restrict__ dy, int64_t lddy, const T* __restrict__ h, int64_t ldh,
-                                                          T* __restrict__ dh, int64_t lddh, int64_t M, int F) {
+template <typename T, typename Args>
+__device__ __forceinline__ void gate_bwd_body(const Args& p, const int bid, const int nblk) {
+  const T* __restrict__ dy = (const T*)p.dy;
+  const T* __restrict__ h = (const T*)p.h;
+  T* __restrict__ dh = (T*)p.y;
+  const int64_t lddy = p.lddy, ldh = p.ldh, lddh = p.ldy, M = p.M;
+  const int F = p.F;
   const int F4 = F >> 2;
   const int64_t total = M * F4;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
+  for (int64_t i = (int64_t)bid * kBlock + threadIdx.x; i < total; i += (int64_t)nblk * kBlock) {
     const int64_t m = i / F4;
     const int f = (int)(i % F4) * 4;
     const float4 a = Io<T>::ld4(h + m * ldh + f), b = Io<T>::ld4(h + m * ldh + F + f), g = Io<T>::ld4(dy + m * lddy + f);
@@ -39,6 +58,34 @@ __global__ __launch_bounds__(kBlock) void gate_bwd_kernel(const T* __restrict__ 
     Io<T>::st4(dh + m * lddh + f, make_float4(d1[0], d1[1], d1[2], d1[3]));
     Io<T>::st4(dh + m * lddh + F + f, make_float4(d2[0], d2[1], d2[2], d2[3]));
   }
+}
+
+template <typename T, bool BWD>
+__global__ __launch_bounds__(kBlock) void gate_kernel(GateArgs p) {
+  if (BWD) gate_bwd_body<T>(p, (int)blockIdx.x, (int)gridDim.x);
+  else gate_fwd_body<T>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+template <typename T, bool BWD>
+__global__ __launch_bounds__(kBlock) void gate_multi_kernel(AdnmMulti<GateArgs> by_value) {
+  (void)by_value;
+  const auto& m = *(const __attribute__((address_space(4))) AdnmMulti<GateArgs>*)__builtin_amdgcn_kernarg_segment_ptr();
+  int bid, nblk;
+  const int k = adnm_group_which(m, &bid, &nblk);
+  if (BWD) gate_bwd_body<T>(m.p[k], bid, nblk);
+  else gate_fwd_body<T>(m.p[k], bid, nblk);
+}
+template <typename T, bool BWD>
+int gate_group_fn(const AdnmGroupRec* const* r, int n, hipStream_t st) {
+  if (n == 1) {
+    GateArgs p;
+    memcpy(&p, r[0]->args, sizeof(GateArgs));
+    gate_kernel<T, BWD><<<(unsigned)r[0]->grid, kBlock, 0, st>>>(p);
+    return ADNM_OK;
+  }
+  AdnmMulti<GateArgs> m;
+  const unsigned blocks = adnm_group_pack(r, n, m);
+  gate_multi_kernel<T, BWD><<<blocks, kBlock, 0, st>>>(m);
+  return ADNM_OK;
 }
 
 // IntensityGate (model_untils.py:523-532): y = silu(enhance * (x - threshold)), both learnable scalars.
@@ -231,8 +278,12 @@ extern "C" int adnm_gate_fwd(const void* h, int64_t ldh, void* y, int64_t ldy, i
   ADNM_REQUIRE(dtype == ADNM_F32 || dtype == ADNM_BF16, "gate_fwd: bad dtype %d", dtype);
   ADNM_REQUIRE(adnm_quad_aligned(dtype, {h, y}), "gate_fwd: h and y must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == ADNM_F32) { ADNM_PROF("gate_fwd", st, 4.0 * M * F * 3); gate_fwd_kernel<float><<<grid_for(M * F / 4), kBlock, 0, st>>>((const float*)h, ldh, (float*)y, ldy, M, (int)F); }
-  else { ADNM_PROF("gate_fwd", st, 2.0 * M * F * 3); gate_fwd_kernel<uint16_t><<<grid_for(M * F / 4), kBlock, 0, st>>>((const uint16_t*)h, ldh, (uint16_t*)y, ldy, M, (int)F); }
+  const GateArgs p{nullptr, 0, h, ldh, y, ldy, M, (int)F};
+  AdnmGroupRec rec;   // launched now, or recorded by an open launch group
+  rec.grid = (int)grid_for(M * F / 4), rec.pos = 0, rec.prof = "gate_fwd", rec.bytes = (dtype == ADNM_F32 ? 4.0 : 2.0) * M * F * 3;
+  rec.fn = dtype == ADNM_F32 ? gate_group_fn<float, false> : gate_group_fn<uint16_t, false>;
+  memcpy(rec.args, &p, sizeof(GateArgs));
+  if (int rc = adnm_group_submit(rec, st)) return rc;
   ADNM_CHECK_LAUNCH("gate_fwd");
   return ADNM_OK;
 }
@@ -245,10 +296,12 @@ extern "C" int adnm_gate_bwd(const void* dy, int64_t lddy, const void* h, int64_
   ADNM_REQUIRE(dtype == ADNM_F32 || dtype == ADNM_BF16, "gate_bwd: bad dtype %d", dtype);
   ADNM_REQUIRE(adnm_quad_aligned(dtype, {dy, h, dh}), "gate_bwd: dy, h and dh must be aligned to 4 elements (16 bytes of fp32, 8 of bf16)");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == ADNM_F32)
-    { ADNM_PROF("gate_bwd", st, 4.0 * M * F * 5); gate_bwd_kernel<float><<<grid_for(M * F / 4), kBlock, 0, st>>>((const float*)dy, lddy, (const float*)h, ldh, (float*)dh, lddh, M, (int)F); }
-  else
-    { ADNM_PROF("gate_bwd", st, 2.0 * M * F * 5); gate_bwd_kernel<uint16_t><<<grid_for(M * F / 4), kBlock, 0, st>>>((const uint16_t*)dy, lddy, (const uint16_t*)h, ldh, (uint16_t*)dh, lddh, M, (int)F); }
+  const GateArgs p{dy, lddy, h, ldh, dh, lddh, M, (int)F};
+  AdnmGroupRec rec;   // launched now, or recorded by an open launch group
+  rec.grid = (int)grid_for(M * F / 4), rec.pos = 0, rec.prof = "gate_bwd", rec.bytes = (dtype == ADNM_F32 ? 4.0 : 2.0) * M * F * 5;
+  rec.fn = dtype == ADNM_F32 ? gate_group_fn<float, true> : gate_group_fn<uint16_t, true>;
+  memcpy(rec.args, &p, sizeof(GateArgs));
+  if (int rc = adnm_group_submit(rec, st)) return rc;
   ADNM_CHECK_LAUNCH("gate_bwd");
   return ADNM_OK;
 }
@@ -293,12 +346,29 @@ extern "C" int adnm_igate_bwd(const void* dy, const void* x, const float* enhanc
 // the skip, one value per (sample, channel) broadcast over the L tokens: y[b,l,c] = silu(enh * (x[b,l,c] + gama * res[b,c] - thr)).
 // One pass each way instead of the reference's mul / add / sub / mul / silu chain and autograd's broadcast reductions.
 namespace {
-__global__ __launch_bounds__(kBlock) void igate_res_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ gama,
-                                                               const float* __restrict__ enh, const float* __restrict__ thr, float* __restrict__ y,
-                                                               int B, int L, int C4, int per_token) {
-  const float a = *enh, t = *thr, gm = *gama;
+// Both kernels take an argument struct and run on (bid, nblk) = the workgroup's index and the workgroup count of ITS problem: the whole
+// grid of the single-problem launch, a block range of a grouped one (adnm_common.h: launch group).
+struct IgrArgs {
+  const float* dy;   // backward only
+  const float* x;
+  const float* res;
+  const float* gama;
+  const float* enh;
+  const float* thr;
+  float* y;          // forward: y; backward: dx
+  float* dres;       // backward only
+  float* spart;      // backward only
+  int B, L, C4, per_token;
+};
+template <typename Args>
+__device__ __forceinline__ void igate_res_fwd_body(const Args& p, const int bid, const int nblk) {
+  const float* __restrict__ x = p.x;
+  const float* __restrict__ res = p.res;
+  float* __restrict__ y = p.y;
+  const int B = p.B, L = p.L, C4 = p.C4, per_token = p.per_token;
+  const float a = *p.enh, t = *p.thr, gm = *p.gama;
   const int64_t n4 = (int64_t)B * L * C4;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kBlock) {
+  for (int64_t i = (int64_t)bid * kBlock + threadIdx.x; i < n4; i += (int64_t)nblk * kBlock) {
     const int c = (int)(i % C4), b = (int)(i / ((int64_t)L * C4));
     const float4 v = Io<float>::ld4(x + i * 4), r = Io<float>::ld4(res + (per_token ? i : (int64_t)b * C4 + c) * 4);
     Io<float>::st4(y + i * 4, make_float4(siluf_(a * (fmaf(gm, r.x, v.x) - t)), siluf_(a * (fmaf(gm, r.y, v.y) - t)),
@@ -309,16 +379,21 @@ __global__ __launch_bounds__(kBlock) void igate_res_fwd_kernel(const float* __re
 // workgroup = (sample b, 16 channel quads) x 16 token slices: thread (sl, cl) takes tokens sl, sl+16, ... of its quad; the 16 slices are
 // summed through LDS, so d res (already times gama) is complete when the launch ends — the bridge's backward reads it next — and only
 // the three scalar gradients {d gama, d enhance, d threshold} go through per-workgroup partials and the (deferrable) fold.
-__global__ __launch_bounds__(kBlock) void igate_res_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ res,
-                                                               const float* __restrict__ gama, const float* __restrict__ enh,
-                                                               const float* __restrict__ thr, float* __restrict__ dx, float* __restrict__ dres,
-                                                               float* __restrict__ spart, int B, int L, int C4, int per_token) {
+template <typename Args>
+__device__ __forceinline__ void igate_res_bwd_body(const Args& p, const int bid) {
   __shared__ float4 sm[16][16];
   __shared__ float ss[3][kBlock / 64];
-  const float a = *enh, t = *thr, gm = *gama;
+  const float* __restrict__ dy = p.dy;
+  const float* __restrict__ x = p.x;
+  const float* __restrict__ res = p.res;
+  float* __restrict__ dx = p.y;
+  float* __restrict__ dres = p.dres;
+  float* __restrict__ spart = p.spart;
+  const int L = p.L, C4 = p.C4, per_token = p.per_token;
+  const float a = *p.enh, t = *p.thr, gm = *p.gama;
   const int chunks = (C4 + 15) / 16;
-  const int b = blockIdx.x / chunks, cl = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int cq = (blockIdx.x % chunks) * 16 + cl;
+  const int b = bid / chunks, cl = threadIdx.x & 15, sl = threadIdx.x >> 4;
+  const int cq = (bid % chunks) * 16 + cl;
   const bool valid = cq < C4;
   const int c = valid ? cq : 0;
   float4 r4 = Io<float>::ld4(res + (per_token ? 0 : ((int64_t)b * C4 + c) * 4));
@@ -353,12 +428,39 @@ __global__ __launch_bounds__(kBlock) void igate_res_bwd_kernel(const float* __re
     Io<float>::st4(dres + ((int64_t)b * C4 + c) * 4, make_float4(gm * acc.x, gm * acc.y, gm * acc.z, gm * acc.w));
   }
   if (threadIdx.x == 0) {
-    float* sp = spart + (int64_t)blockIdx.x * 4;
+    float* sp = spart + (int64_t)bid * 4;
     sp[0] = (ss[0][0] + ss[0][1]) + (ss[0][2] + ss[0][3]);
     sp[1] = (ss[1][0] + ss[1][1]) + (ss[1][2] + ss[1][3]);
     sp[2] = -a * ((ss[2][0] + ss[2][1]) + (ss[2][2] + ss[2][3]));
     sp[3] = 0.f;
   }
+}
+template <bool BWD>
+__global__ __launch_bounds__(kBlock) void igate_res_kernel(IgrArgs p) {
+  if constexpr (BWD) igate_res_bwd_body(p, (int)blockIdx.x);
+  else igate_res_fwd_body(p, (int)blockIdx.x, (int)gridDim.x);
+}
+template <bool BWD>
+__global__ __launch_bounds__(kBlock) void igate_res_multi_kernel(AdnmMulti<IgrArgs> by_value) {
+  (void)by_value;
+  const auto& m = *(const __attribute__((address_space(4))) AdnmMulti<IgrArgs>*)__builtin_amdgcn_kernarg_segment_ptr();
+  int bid, nblk;
+  const int k = adnm_group_which(m, &bid, &nblk);
+  if constexpr (BWD) igate_res_bwd_body(m.p[k], bid);
+  else igate_res_fwd_body(m.p[k], bid, nblk);
+}
+template <bool BWD>
+int igate_res_group_fn(const AdnmGroupRec* const* r, int n, hipStream_t st) {
+  if (n == 1) {
+    IgrArgs p;
+    memcpy(&p, r[0]->args, sizeof(IgrArgs));
+    igate_res_kernel<BWD><<<(unsigned)r[0]->grid, kBlock, 0, st>>>(p);
+    return ADNM_OK;
+  }
+  AdnmMulti<IgrArgs> m;
+  const unsigned blocks = adnm_group_pack(r, n, m);
+  igate_res_multi_kernel<BWD><<<blocks, kBlock, 0, st>>>(m);
+  return ADNM_OK;
 }
 int64_t igate_res_blocks(int64_t B, int64_t C) { return B * adnm_cdiv(C / 4, 16); }
 }  // namespace
@@ -374,8 +476,11 @@ extern "C" int adnm_igate_res_fwd(const float* x, const float* res, int per_toke
   ADNM_REQUIRE(B > 0 && L > 0 && C > 0 && C % 4 == 0 && B * L * C < (1ll << 31), "igate_res_fwd: bad shape B=%lld L=%lld C=%lld (4 | C)", (long long)B,
                (long long)L, (long long)C);
   hipStream_t st = (hipStream_t)stream;
-  ADNM_PROF("igate_fwd", st, 4.0 * (2.0 * B * L * C + B * C));
-  igate_res_fwd_kernel<<<grid_for(B * L * C / 4), kBlock, 0, st>>>(x, res, gama, enhance, threshold, y, (int)B, (int)L, (int)(C / 4), per_token);
+  const IgrArgs p{nullptr, x, res, gama, enhance, threshold, y, nullptr, nullptr, (int)B, (int)L, (int)(C / 4), per_token};
+  AdnmGroupRec rec;   // launched now, or recorded by an open launch group
+  rec.fn = igate_res_group_fn<false>, rec.grid = (int)grid_for(B * L * C / 4), rec.pos = 0, rec.prof = "igate_fwd", rec.bytes = 4.0 * (2.0 * B * L * C + B * C);
+  memcpy(rec.args, &p, sizeof(IgrArgs));
+  if (int rc = adnm_group_submit(rec, st)) return rc;
   ADNM_CHECK_LAUNCH("igate_res_fwd");
   return ADNM_OK;
 }
@@ -394,12 +499,14 @@ extern "C" int adnm_igate_res_bwd(const float* dy, const float* x, const float* 
   const int64_t blocks = igate_res_blocks(B, C);
   float* spart = (float*)ws;
   {
-    ADNM_PROF("igate_bwd", st, 4.0 * (3.0 * B * L * C + 2.0 * B * C));
-    igate_res_bwd_kernel<<<(unsigned)blocks, kBlock, 0, st>>>(dy, x, res, gama, enhance, threshold, dx, dres, spart, (int)B, (int)L, (int)(C / 4),
-                                                               per_token);
+    const IgrArgs p{dy, x, res, gama, enhance, threshold, dx, dres, spart, (int)B, (int)L, (int)(C / 4), per_token};
+    AdnmGroupRec rec;   // launched now, or recorded by an open launch group (the fold below then waits in its queue, or is recorded behind it)
+    rec.fn = igate_res_group_fn<true>, rec.grid = (int)blocks, rec.pos = 0, rec.prof = "igate_bwd", rec.bytes = 4.0 * (3.0 * B * L * C + 2.0 * B * C);
+    memcpy(rec.args, &p, sizeof(IgrArgs));
+    if (int rc = adnm_group_submit(rec, st)) return rc;
   }
   ADNM_CHECK_LAUNCH("igate_res_bwd");
-  adnm_launch_fold("igate_bwd_fold", spart, (int)blocks, 4, {dgama, 1}, {denhance, 1}, {dthreshold, 1}, {nullptr, 0}, st);   // deferrable
+  adnm_launch_fold_recorded("igate_bwd_fold", spart, (int)blocks, 4, {dgama, 1}, {denhance, 1}, {dthreshold, 1}, {nullptr, 0}, st);   // deferrable
   ADNM_CHECK_LAUNCH("igate_res_bwd");
   return ADNM_OK;
 }

@@ -67,8 +67,32 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf2));
 }
 
-template <bool B_OC, int PREC, bool A_BF8, int D, int BT>
-__global__ __launch_bounds__(kThreads) void lgemm_kernel(LgArgs p) {
+// One kernel in two forms.  MULTI = false: one problem, the argument is its LgArgs and the workgroup's place is blockIdx.x of gridDim.x.
+// MULTI = true: up to ADNM_GROUP_MAX independent problems of one instantiation in one launch (adnm_common.h: launch group): every workgroup
+// looks up its problem in the descriptor table (kernel arguments, read in the constant address space) and runs the same tile code on that
+// problem's own block range — the XCD remap and the (tile, slice) decode see the problem's block index and count, so each problem computes
+// what it computes alone.  The two forms are ONE __global__ template on purpose: with the tile code in a __device__ function under two
+// shells, the fp8 NN instantiations that read an fp32 weight came out 6-7 VGPRs heavier (one a wave of occupancy lower) than this form,
+// which gives the single-problem kernels the register counts they had before there was a second form.
+template <bool MULTI>
+struct LgPick;
+template <>
+struct LgPick<false> {
+  using Arg = LgArgs;
+  static __device__ __forceinline__ const LgArgs& get(const LgArgs& a, int*, int*) { return a; }
+};
+template <>
+struct LgPick<true> {
+  using Arg = AdnmMulti<LgArgs>;
+  static __device__ __forceinline__ const __attribute__((address_space(4))) LgArgs& get(const Arg&, int* bid, int* nblk) {
+    const auto& m = *(const __attribute__((address_space(4))) Arg*)__builtin_amdgcn_kernarg_segment_ptr();
+    return m.p[adnm_group_which(m, bid, nblk)];
+  }
+};
+template <bool B_OC, int PREC, bool A_BF8, int D, int BT, bool MULTI>
+__global__ __launch_bounds__(kThreads) void lgemm_kernel(typename LgPick<MULTI>::Arg arg) {
+  int bid_ = 0, nblk_ = 0;
+  const auto& p = LgPick<MULTI>::get(arg, &bid_, &nblk_);
   static_assert(BT == ADNM_B_F32 || (BT == ADNM_B_BF16 && PREC == ADNM_MFMA_BF16) || (BT == ADNM_B_FP8 && PREC == ADNM_MFMA_FP8),
                 "a narrow weight shadow feeds the matrix-core precision it was made for");
   constexpr bool BF16 = PREC == ADNM_MFMA_BF16, FP8 = PREC == ADNM_MFMA_FP8;
@@ -83,8 +107,9 @@ __global__ __launch_bounds__(kThreads) void lgemm_kernel(LgArgs p) {
   // workgroup -> (tile, slice).  Workgroups go round-robin over the 8 XCDs: give each XCD a contiguous run of (tile, slice) pairs, so the
   // slices of a tile (whose slabs the last of them reads back) and neighbouring tiles (which share A rows) meet in one L2.  A speed
   // choice only: the combine is correct for any placement.
-  int lin = blockIdx.x;
-  const int nblk = gridDim.x;
+  int lin = MULTI ? bid_ : (int)blockIdx.x;
+  const int nblk = MULTI ? nblk_ : (int)gridDim.x;
+  if (MULTI) __builtin_assume(lin >= 0 && nblk > 0 && lin < nblk);   // (what the compiler knows of blockIdx.x / gridDim.x themselves)
   if ((nblk & 7) == 0) lin = (lin & 7) * (nblk >> 3) + (lin >> 3);
   const int tile = lin / p.nbs, slice = lin - tile * p.nbs;
   const int i0 = (tile / p.tiles_j) * kTile, j0 = (tile % p.tiles_j) * kTile;
@@ -405,6 +430,20 @@ __global__ __launch_bounds__(kThreads) void lgemm_kernel(LgArgs p) {
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 constexpr int kRingDepth = 4;
 
+template <bool B_OC, int PREC, bool A_BF8, int BT>
+int lg_group_fn(const AdnmGroupRec* const* r, int n, hipStream_t st) {
+  if (n == 1) {
+    LgArgs p;
+    memcpy(&p, r[0]->args, sizeof(LgArgs));
+    lgemm_kernel<B_OC, PREC, A_BF8, kRingDepth, BT, false><<<(unsigned)r[0]->grid, kThreads, 0, st>>>(p);
+    return ADNM_OK;
+  }
+  AdnmMulti<LgArgs> m;
+  const unsigned blocks = adnm_group_pack(r, n, m);
+  lgemm_kernel<B_OC, PREC, A_BF8, kRingDepth, BT, true><<<blocks, kThreads, 0, st>>>(m);
+  return ADNM_OK;
+}
+
 struct LgPlan {
   int tiles_i, tiles_j, ntiles, nkt, nbs, kt_per_slice;
 };
@@ -432,7 +471,7 @@ int64_t adnm_lgemm_ws_bytes(int64_t I, int64_t J, int64_t R, int nbs) {
 
 int adnm_lgemm_launch(bool b_oc, const float* a, int64_t lda, const void* b, int64_t ldb, int b_dtype, const float* b_scale, const float* bias, float* c,
                       int64_t ldc, void* ws, int64_t ws_bytes, void* slabs_uc, int64_t slabs_uc_bytes, int64_t I, int64_t J, int64_t R, int nbs, int prec,
-                      float* q, hipStream_t st) {
+                      float* q, const char* prof, double prof_bytes, hipStream_t st) {
   const LgPlan pl = make_plan(I, J, R, nbs);
   LgArgs p;
   p.A = a, p.lda = lda, p.B = b, p.ldb = ldb, p.b_scale = b_scale, p.bias = bias, p.C = c, p.ldc = ldc;
@@ -456,19 +495,23 @@ int adnm_lgemm_launch(bool b_oc, const float* a, int64_t lda, const void* b, int
     p.slab = uc ? (float*)slabs_uc : (float*)((char*)ws + adnm_ticket_bytes(pl.ntiles));
     p.uc = uc ? 1 : 0;
   }
-  const unsigned grid = (unsigned)(pl.ntiles * pl.nbs);
-#define LG(OC)                                                                                                                             \
-  do {                                                                                                                                     \
-    if (b_dtype == ADNM_B_BF16) lgemm_kernel<OC, ADNM_MFMA_BF16, false, kRingDepth, ADNM_B_BF16><<<grid, kThreads, 0, st>>>(p);             \
-    else if (b_dtype == ADNM_B_FP8 && prec == ADNM_MFMA_FP8) lgemm_kernel<OC, ADNM_MFMA_FP8, false, kRingDepth, ADNM_B_FP8><<<grid, kThreads, 0, st>>>(p); \
-    else if (b_dtype == ADNM_B_FP8) lgemm_kernel<OC, ADNM_MFMA_FP8, true, kRingDepth, ADNM_B_FP8><<<grid, kThreads, 0, st>>>(p);            \
-    else if (prec == ADNM_MFMA_BF16) lgemm_kernel<OC, ADNM_MFMA_BF16, false, kRingDepth, ADNM_B_F32><<<grid, kThreads, 0, st>>>(p);         \
-    else if (prec == ADNM_MFMA_FP8) lgemm_kernel<OC, ADNM_MFMA_FP8, false, kRingDepth, ADNM_B_F32><<<grid, kThreads, 0, st>>>(p);           \
-    else if (prec == ADNM_MFMA_FP8_GRAD) lgemm_kernel<OC, ADNM_MFMA_FP8, true, kRingDepth, ADNM_B_F32><<<grid, kThreads, 0, st>>>(p);       \
-    else lgemm_kernel<OC, ADNM_MFMA_F32, false, kRingDepth, ADNM_B_F32><<<grid, kThreads, 0, st>>>(p);                                      \
+  // the launch as a group record: made now, or — inside an open launch group — stored and merged with its partners of the same instantiation
+  static_assert(sizeof(LgArgs) <= sizeof(AdnmGroupRec::args), "LgArgs must fit a group record");
+  AdnmGroupRec rec;
+  rec.grid = pl.ntiles * pl.nbs, rec.pos = 0, rec.prof = prof, rec.bytes = prof_bytes;
+  memcpy(rec.args, &p, sizeof(LgArgs));
+#define LG(OC)                                                                                              \
+  do {                                                                                                      \
+    if (b_dtype == ADNM_B_BF16) rec.fn = lg_group_fn<OC, ADNM_MFMA_BF16, false, ADNM_B_BF16>;               \
+    else if (b_dtype == ADNM_B_FP8 && prec == ADNM_MFMA_FP8) rec.fn = lg_group_fn<OC, ADNM_MFMA_FP8, false, ADNM_B_FP8>; \
+    else if (b_dtype == ADNM_B_FP8) rec.fn = lg_group_fn<OC, ADNM_MFMA_FP8, true, ADNM_B_FP8>;              \
+    else if (prec == ADNM_MFMA_BF16) rec.fn = lg_group_fn<OC, ADNM_MFMA_BF16, false, ADNM_B_F32>;           \
+    else if (prec == ADNM_MFMA_FP8) rec.fn = lg_group_fn<OC, ADNM_MFMA_FP8, false, ADNM_B_F32>;             \
+    else if (prec == ADNM_MFMA_FP8_GRAD) rec.fn = lg_group_fn<OC, ADNM_MFMA_FP8, true, ADNM_B_F32>;         \
+    else rec.fn = lg_group_fn<OC, ADNM_MFMA_F32, false, ADNM_B_F32>;                                        \
   } while (0)
   if (!b_oc) LG(false);
   else LG(true);
 #undef LG
-  return ADNM_OK;
+  return adnm_group_submit(rec, st);
 }

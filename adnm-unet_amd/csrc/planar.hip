@@ -304,20 +304,22 @@ __device__ __forceinline__ void merge_partials(const float* __restrict__ part, i
 // pass 1 of forward: shifted sums.  part[(b,chunk), {S1,S2}, c] with shift K = x[b,0,c] (cpg == 0: InstanceNorm) or, for GroupNorm,
 // K = x[b,0,first channel of c's group]: one shift per group, so the S1 / S2 of a group's channels may simply be added.
 template <typename T>
-__device__ __forceinline__ void shifted_sums(const T* __restrict__ x, float* __restrict__ part, int64_t HW, int C, int cpg, int cgb, int ppc) {
+// (bx, by, bz, gy): the workgroup's (channel block, chunk, sample) and the chunk count — blockIdx / gridDim.y of the single-problem launch
+__device__ __forceinline__ void shifted_sums(const T* __restrict__ x, float* __restrict__ part, int64_t HW, int C, int cpg, int cgb, int ppc,
+                                             const int bx, const int by, const int bz, const int gy) {
   __shared__ __attribute__((aligned(16))) float smem[3 * 2 * 64 * 4];
   const int C4 = C >> 2;
   const int cgl = threadIdx.x & (cgb - 1), slot = threadIdx.x / cgb, slots = kBlock / cgb;
-  const int cg = blockIdx.x * cgb + cgl;
+  const int cg = bx * cgb + cgl;
   const bool cv = cg < C4;
   const int c = cv ? cg * 4 : 0;
-  const int b = blockIdx.z;
+  const int b = bz;
   const T* xb = x + (int64_t)b * HW * C + c;
   float4 K;
   if (cpg) K.x = K.y = K.z = K.w = Io<T>::ld(xb - c % cpg);
   else K = Io<T>::ld4(xb);
   float4 acc[2] = {f4zero(), f4zero()};
-  const int64_t p0 = (int64_t)blockIdx.y * ppc;
+  const int64_t p0 = (int64_t)by * ppc;
   const int64_t p1 = p0 + ppc < HW ? p0 + ppc : HW;
   if (cv)
     for (int64_t p = p0 + slot; p < p1; p += slots) {
@@ -329,20 +331,37 @@ __device__ __forceinline__ void shifted_sums(const T* __restrict__ x, float* __r
     }
   fold_slots<2>(acc, cgb, smem);
   if ((threadIdx.x >> 6) == 0 && (threadIdx.x & 63) < cgb && cv) {
-    float* dst = part + ((int64_t)b * gridDim.y + blockIdx.y) * 2 * C;
+    float* dst = part + ((int64_t)b * gy + by) * 2 * C;
     *reinterpret_cast<float4*>(dst + c) = acc[0];
     *reinterpret_cast<float4*>(dst + C + c) = acc[1];
   }
 }
-template <typename T>
-__global__ __launch_bounds__(kBlock) void instnorm_stats_kernel(const T* __restrict__ x, float* __restrict__ part, int64_t HW, int C,
-                                                                int cgb, int ppc) {
-  shifted_sums<T>(x, part, HW, C, 0, cgb, ppc);
+// The four InstanceNorm kernels take one argument struct and run on (bx, by, bz) = the workgroup's (channel block, chunk, sample) of ITS
+// problem: blockIdx of the single-problem launch (grid gx x nchunk x B), decoded from a block range of a grouped one (adnm_common.h:
+// launch group).
+struct InArgs {
+  const void* x;
+  const void* dy;       // backward only
+  void* y;              // forward: y; backward: dx
+  float* part;
+  float* spart;         // backward stats: per-workgroup scalar partials, or NULL
+  const float* scale;
+  const float* shift;
+  float* mu;            // written by the forward apply, read by the backward
+  float* rstd;
+  int64_t HW;
+  int C, cgb, ppc, nchunk, gx, B;
+  float eps;
+  int act;
+};
+template <typename T, typename Args>
+__device__ __forceinline__ void instnorm_stats_body(const Args& p, const int bx, const int by, const int bz) {
+  shifted_sums<T>((const T*)p.x, p.part, p.HW, p.C, 0, p.cgb, p.ppc, bx, by, bz, p.nchunk);
 }
 template <typename T>
 __global__ __launch_bounds__(kBlock) void groupnorm_stats_kernel(const T* __restrict__ x, float* __restrict__ part, int64_t HW, int C,
                                                                  int cpg, int cgb, int ppc) {
-  shifted_sums<T>(x, part, HW, C, cpg, cgb, ppc);
+  shifted_sums<T>(x, part, HW, C, cpg, cgb, ppc, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y);
 }
 
 __device__ __forceinline__ float4 act4(float4 v, int act) {
@@ -357,18 +376,24 @@ __device__ __forceinline__ float4 actg4(float4 v, int act) {
 }
 
 // pass 2 of forward: merge chunk partials -> mu,rstd (chunk 0 of each (b, channel block) saves them), normalise.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void instnorm_apply_kernel(const T* __restrict__ x, const float* __restrict__ part,
-                                                                const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                T* __restrict__ y, float* __restrict__ mu_out,
-                                                                float* __restrict__ rstd_out, int64_t HW, int C, int cgb, int ppc,
-                                                                int nchunk, float eps, int act) {
+template <typename T, typename Args>
+__device__ __forceinline__ void instnorm_apply_body(const Args& p, const int bx, const int by, const int bz) {
+  const T* __restrict__ x = (const T*)p.x;
+  const float* __restrict__ part = p.part;
+  const float* __restrict__ scale = p.scale;
+  const float* __restrict__ shift = p.shift;
+  T* __restrict__ y = (T*)p.y;
+  float* __restrict__ mu_out = p.mu;
+  float* __restrict__ rstd_out = p.rstd;
+  const int64_t HW = p.HW;
+  const int C = p.C, cgb = p.cgb, ppc = p.ppc, nchunk = p.nchunk, act = p.act;
+  const float eps = p.eps;
   const int C4 = C >> 2;
   const int cgl = threadIdx.x & (cgb - 1), slot = threadIdx.x / cgb, slots = kBlock / cgb;
-  const int cg = blockIdx.x * cgb + cgl;
+  const int cg = bx * cgb + cgl;
   const bool cv = cg < C4;
   const int c = cv ? cg * 4 : 0;
-  const int b = blockIdx.z;
+  const int b = bz;
   float4 s1, s2;
   merge_partials(part, b, nchunk, C, c, cv, cgb, s1, s2);
   if (!cv) return;
@@ -383,12 +408,12 @@ __global__ __launch_bounds__(kBlock) void instnorm_apply_kernel(const T* __restr
   rstd.y = rsqrtf(fmaxf(s2.y * inv - m.y * m.y, 0.f) + eps);
   rstd.z = rsqrtf(fmaxf(s2.z * inv - m.z * m.z, 0.f) + eps);
   rstd.w = rsqrtf(fmaxf(s2.w * inv - m.w * m.w, 0.f) + eps);
-  if (blockIdx.y == 0 && slot == 0) {
+  if (by == 0 && slot == 0) {
     *reinterpret_cast<float4*>(mu_out + (int64_t)b * C + c) = mu;
     *reinterpret_cast<float4*>(rstd_out + (int64_t)b * C + c) = rstd;
   }
   const float sc = scale ? *scale : 1.f, sh = shift ? *shift : 0.f;
-  const int64_t p0 = (int64_t)blockIdx.y * ppc;
+  const int64_t p0 = (int64_t)by * ppc;
   const int64_t p1 = p0 + ppc < HW ? p0 + ppc : HW;
   for (int64_t p = p0 + slot; p < p1; p += slots) {
     const float4 v = Io<T>::ld4(xb + p * C);
@@ -399,26 +424,32 @@ __global__ __launch_bounds__(kBlock) void instnorm_apply_kernel(const T* __restr
 }
 
 // backward pass 1: per (b,chunk,c) sums of dpre and dpre*xhat, dpre = dy * act'(scale*xhat+shift)
-template <typename T>
-__global__ __launch_bounds__(kBlock) void instnorm_bwd_stats_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                                                    const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                    const float* __restrict__ mu_in, const float* __restrict__ rstd_in,
-                                                                    float* __restrict__ part, float* __restrict__ spart, int64_t HW, int C,
-                                                                    int cgb, int ppc, int act) {
+template <typename T, typename Args>
+__device__ __forceinline__ void instnorm_bwd_stats_body(const Args& p, const int bx, const int by, const int bz) {
   __shared__ __attribute__((aligned(16))) float smem[3 * 2 * 64 * 4];
+  const T* __restrict__ dy = (const T*)p.dy;
+  const T* __restrict__ x = (const T*)p.x;
+  const float* __restrict__ scale = p.scale;
+  const float* __restrict__ shift = p.shift;
+  const float* __restrict__ mu_in = p.mu;
+  const float* __restrict__ rstd_in = p.rstd;
+  float* __restrict__ part = p.part;
+  float* __restrict__ spart = p.spart;
+  const int64_t HW = p.HW;
+  const int C = p.C, cgb = p.cgb, ppc = p.ppc, act = p.act, gy = p.nchunk, gx = p.gx;
   const int C4 = C >> 2;
   const int cgl = threadIdx.x & (cgb - 1), slot = threadIdx.x / cgb, slots = kBlock / cgb;
-  const int cg = blockIdx.x * cgb + cgl;
+  const int cg = bx * cgb + cgl;
   const bool cv = cg < C4;
   const int c = cv ? cg * 4 : 0;
-  const int b = blockIdx.z;
+  const int b = bz;
   const T* xb = x + (int64_t)b * HW * C + c;
   const T* db = dy + (int64_t)b * HW * C + c;
   const float4 mu = *reinterpret_cast<const float4*>(mu_in + (int64_t)b * C + c);
   const float4 rs = *reinterpret_cast<const float4*>(rstd_in + (int64_t)b * C + c);
   const float sc = scale ? *scale : 1.f, sh = shift ? *shift : 0.f;
   float4 acc[2] = {f4zero(), f4zero()};
-  const int64_t p0 = (int64_t)blockIdx.y * ppc;
+  const int64_t p0 = (int64_t)by * ppc;
   const int64_t p1 = p0 + ppc < HW ? p0 + ppc : HW;
   if (cv)
     for (int64_t p = p0 + slot; p < p1; p += slots) {
@@ -434,7 +465,7 @@ __global__ __launch_bounds__(kBlock) void instnorm_bwd_stats_kernel(const T* __r
   if ((threadIdx.x >> 6) == 0) {
     const bool mine = (threadIdx.x & 63) < cgb && cv;
     if (mine) {
-      float* dst = part + ((int64_t)b * gridDim.y + blockIdx.y) * 2 * C;
+      float* dst = part + ((int64_t)b * gy + by) * 2 * C;
       *reinterpret_cast<float4*>(dst + c) = acc[0];
       *reinterpret_cast<float4*>(dst + C + c) = acc[1];
     }
@@ -444,7 +475,7 @@ __global__ __launch_bounds__(kBlock) void instnorm_bwd_stats_kernel(const T* __r
       float a = mine ? (acc[0].x + acc[0].y) + (acc[0].z + acc[0].w) : 0.f, q = mine ? (acc[1].x + acc[1].y) + (acc[1].z + acc[1].w) : 0.f;
       a = wave_sum(a), q = wave_sum(q);
       if (threadIdx.x == 0) {
-        float* sp = spart + (((int64_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2;
+        float* sp = spart + (((int64_t)b * gy + by) * gx + bx) * 2;
         sp[0] = a, sp[1] = q;
       }
     }
@@ -452,18 +483,24 @@ __global__ __launch_bounds__(kBlock) void instnorm_bwd_stats_kernel(const T* __r
 }
 
 // backward pass 2: dx = rstd*scale*(dpre - mean(dpre) - xhat*mean(dpre*xhat))
-template <typename T>
-__global__ __launch_bounds__(kBlock) void instnorm_bwd_apply_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                                                    const float* __restrict__ part, const float* __restrict__ scale,
-                                                                    const float* __restrict__ shift, const float* __restrict__ mu_in,
-                                                                    const float* __restrict__ rstd_in, T* __restrict__ dx, int64_t HW,
-                                                                    int C, int cgb, int ppc, int nchunk, int act) {
+template <typename T, typename Args>
+__device__ __forceinline__ void instnorm_bwd_apply_body(const Args& p, const int bx, const int by, const int bz) {
+  const T* __restrict__ dy = (const T*)p.dy;
+  const T* __restrict__ x = (const T*)p.x;
+  const float* __restrict__ part = p.part;
+  const float* __restrict__ scale = p.scale;
+  const float* __restrict__ shift = p.shift;
+  const float* __restrict__ mu_in = p.mu;
+  const float* __restrict__ rstd_in = p.rstd;
+  T* __restrict__ dx = (T*)p.y;
+  const int64_t HW = p.HW;
+  const int C = p.C, cgb = p.cgb, ppc = p.ppc, nchunk = p.nchunk, act = p.act;
   const int C4 = C >> 2;
   const int cgl = threadIdx.x & (cgb - 1), slot = threadIdx.x / cgb, slots = kBlock / cgb;
-  const int cg = blockIdx.x * cgb + cgl;
+  const int cg = bx * cgb + cgl;
   const bool cv = cg < C4;
   const int c = cv ? cg * 4 : 0;
-  const int b = blockIdx.z;
+  const int b = bz;
   float4 s1, s2;
   merge_partials(part, b, nchunk, C, c, cv, cgb, s1, s2);
   if (!cv) return;
@@ -476,7 +513,7 @@ __global__ __launch_bounds__(kBlock) void instnorm_bwd_apply_kernel(const T* __r
   const float inv = 1.0f / (float)HW;
   s1.x *= inv; s1.y *= inv; s1.z *= inv; s1.w *= inv;
   s2.x *= inv; s2.y *= inv; s2.z *= inv; s2.w *= inv;
-  const int64_t p0 = (int64_t)blockIdx.y * ppc;
+  const int64_t p0 = (int64_t)by * ppc;
   const int64_t p1 = p0 + ppc < HW ? p0 + ppc : HW;
   for (int64_t p = p0 + slot; p < p1; p += slots) {
     const float4 v = Io<T>::ld4(xb + p * C), g = Io<T>::ld4(db + p * C);
@@ -491,6 +528,50 @@ __global__ __launch_bounds__(kBlock) void instnorm_bwd_apply_kernel(const T* __r
   }
 }
 
+
+// WHICH: 0 forward stats, 1 forward apply, 2 backward stats, 3 backward apply
+template <typename T, int WHICH, typename Args>
+__device__ __forceinline__ void instnorm_body(const Args& p, const int bx, const int by, const int bz) {
+  if constexpr (WHICH == 0) instnorm_stats_body<T>(p, bx, by, bz);
+  else if constexpr (WHICH == 1) instnorm_apply_body<T>(p, bx, by, bz);
+  else if constexpr (WHICH == 2) instnorm_bwd_stats_body<T>(p, bx, by, bz);
+  else instnorm_bwd_apply_body<T>(p, bx, by, bz);
+}
+template <typename T, int WHICH>
+__global__ __launch_bounds__(kBlock) void instnorm_kernel(InArgs p) {
+  instnorm_body<T, WHICH>(p, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
+}
+template <typename T, int WHICH>
+__global__ __launch_bounds__(kBlock) void instnorm_multi_kernel(AdnmMulti<InArgs> by_value) {
+  (void)by_value;
+  const auto& m = *(const __attribute__((address_space(4))) AdnmMulti<InArgs>*)__builtin_amdgcn_kernarg_segment_ptr();
+  int bid, nblk;
+  const int k = adnm_group_which(m, &bid, &nblk);
+  const int gx = m.p[k].gx, gy = m.p[k].nchunk;   // the problem's own (gx, nchunk, B) grid, linearised x fastest
+  const int t = bid / gx;
+  instnorm_body<T, WHICH>(m.p[k], bid - t * gx, t % gy, t / gy);
+}
+template <typename T, int WHICH>
+int instnorm_group_fn(const AdnmGroupRec* const* r, int n, hipStream_t st) {
+  if (n == 1) {
+    InArgs p;
+    memcpy(&p, r[0]->args, sizeof(InArgs));
+    instnorm_kernel<T, WHICH><<<dim3(p.gx, p.nchunk, (unsigned)p.B), kBlock, 0, st>>>(p);
+    return ADNM_OK;
+  }
+  AdnmMulti<InArgs> m;
+  const unsigned blocks = adnm_group_pack(r, n, m);
+  instnorm_multi_kernel<T, WHICH><<<blocks, kBlock, 0, st>>>(m);
+  return ADNM_OK;
+}
+template <typename T>
+int instnorm_submit(int which, int pos, const char* prof, double bytes, const InArgs& p, hipStream_t st) {
+  AdnmGroupRec rec;   // launched now, or recorded by an open launch group
+  rec.fn = which == 0 ? instnorm_group_fn<T, 0> : (which == 1 ? instnorm_group_fn<T, 1> : (which == 2 ? instnorm_group_fn<T, 2> : instnorm_group_fn<T, 3>));
+  rec.grid = p.gx * p.nchunk * p.B, rec.pos = pos, rec.prof = prof, rec.bytes = bytes;
+  memcpy(rec.args, &p, sizeof(InArgs));
+  return adnm_group_submit(rec, st);
+}
 
 // ---------------------------------------------------------------------------------------------- GroupNorm
 // nn.GroupNorm(G, C) with its per-channel gamma / beta, the layer's scalar scale / shift and the activation, on InstanceNorm's grid and
@@ -795,18 +876,18 @@ extern "C" int adnm_instnorm_fwd(const void* x, const float* scale, const float*
   ADNM_REQUIRE(x && y && mu && rstd, "instnorm_fwd: null pointer");
   if (int rc = instnorm_check("instnorm_fwd", B, HW, C, act, dtype, ws, ws_bytes)) return rc;
   const IGeo g = igeo(HW, C);
-  const dim3 grid(g.gx, g.nchunk, (unsigned)B);
   hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)ws;
+  const InArgs p{x, nullptr, y, (float*)ws, nullptr, scale, shift, mu, rstd, HW, (int)C, g.cgb, g.pix_per_chunk, g.nchunk, g.gx, (int)B, eps, act};
+  const double es = dtype == ADNM_F32 ? 4.0 : 2.0;
+  int rc;
   if (dtype == ADNM_F32) {
-    { ADNM_PROF("instnorm_stats", st, 4.0 * B * HW * C); instnorm_stats_kernel<float><<<grid, kBlock, 0, st>>>((const float*)x, part, HW, (int)C, g.cgb, g.pix_per_chunk); }
-    { ADNM_PROF("instnorm_apply", st, 4.0 * B * HW * C * 2); instnorm_apply_kernel<float><<<grid, kBlock, 0, st>>>((const float*)x, part, scale, shift, (float*)y, mu, rstd, HW, (int)C, g.cgb,
-                                                          g.pix_per_chunk, g.nchunk, eps, act); }
+    rc = instnorm_submit<float>(0, 0, "instnorm_stats", es * B * HW * C, p, st);
+    if (rc == ADNM_OK) rc = instnorm_submit<float>(1, 1, "instnorm_apply", es * B * HW * C * 2, p, st);
   } else {
-    { ADNM_PROF("instnorm_stats", st, 2.0 * B * HW * C); instnorm_stats_kernel<uint16_t><<<grid, kBlock, 0, st>>>((const uint16_t*)x, part, HW, (int)C, g.cgb, g.pix_per_chunk); }
-    { ADNM_PROF("instnorm_apply", st, 2.0 * B * HW * C * 2); instnorm_apply_kernel<uint16_t><<<grid, kBlock, 0, st>>>((const uint16_t*)x, part, scale, shift, (uint16_t*)y, mu, rstd, HW, (int)C,
-                                                             g.cgb, g.pix_per_chunk, g.nchunk, eps, act); }
+    rc = instnorm_submit<uint16_t>(0, 0, "instnorm_stats", es * B * HW * C, p, st);
+    if (rc == ADNM_OK) rc = instnorm_submit<uint16_t>(1, 1, "instnorm_apply", es * B * HW * C * 2, p, st);
   }
+  if (rc != ADNM_OK) return rc;
   ADNM_CHECK_LAUNCH("instnorm_fwd");
   return ADNM_OK;
 }
@@ -817,24 +898,24 @@ extern "C" int adnm_instnorm_bwd(const void* dy, const void* x, const float* sca
   ADNM_REQUIRE(dy && x && mu && rstd && dx, "instnorm_bwd: null pointer");
   if (int rc = instnorm_check("instnorm_bwd", B, HW, C, act, dtype, ws, ws_bytes)) return rc;
   const IGeo g = igeo(HW, C);
-  const dim3 grid(g.gx, g.nchunk, (unsigned)B);
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)ws;
   float* spart = (dscale || dshift) ? part + B * g.nchunk * 2 * C : nullptr;
+  const InArgs p{x, dy, dx, part, spart, scale, shift, const_cast<float*>(mu), const_cast<float*>(rstd), HW, (int)C, g.cgb, g.pix_per_chunk, g.nchunk, g.gx, (int)B,
+                 0.f, act};
+  const double es = dtype == ADNM_F32 ? 4.0 : 2.0;
+  int rc;
   if (dtype == ADNM_F32) {
-    { ADNM_PROF("instnorm_bwd_stats", st, 4.0 * B * HW * C * 2); instnorm_bwd_stats_kernel<float><<<grid, kBlock, 0, st>>>((const float*)dy, (const float*)x, scale, shift, mu, rstd, part, spart, HW, (int)C,
-                                                              g.cgb, g.pix_per_chunk, act); }
-    { ADNM_PROF("instnorm_bwd_apply", st, 4.0 * B * HW * C * 3); instnorm_bwd_apply_kernel<float><<<grid, kBlock, 0, st>>>((const float*)dy, (const float*)x, part, scale, shift, mu, rstd, (float*)dx,
-                                                              HW, (int)C, g.cgb, g.pix_per_chunk, g.nchunk, act); }
+    rc = instnorm_submit<float>(2, 0, "instnorm_bwd_stats", es * B * HW * C * 2, p, st);
+    if (rc == ADNM_OK) rc = instnorm_submit<float>(3, 1, "instnorm_bwd_apply", es * B * HW * C * 3, p, st);
   } else {
-    { ADNM_PROF("instnorm_bwd_stats", st, 2.0 * B * HW * C * 2); instnorm_bwd_stats_kernel<uint16_t><<<grid, kBlock, 0, st>>>((const uint16_t*)dy, (const uint16_t*)x, scale, shift, mu, rstd, part, spart, HW,
-                                                                 (int)C, g.cgb, g.pix_per_chunk, act); }
-    { ADNM_PROF("instnorm_bwd_apply", st, 2.0 * B * HW * C * 3); instnorm_bwd_apply_kernel<uint16_t><<<grid, kBlock, 0, st>>>((const uint16_t*)dy, (const uint16_t*)x, part, scale, shift, mu, rstd,
-                                                                 (uint16_t*)dx, HW, (int)C, g.cgb, g.pix_per_chunk, g.nchunk, act); }
+    rc = instnorm_submit<uint16_t>(2, 0, "instnorm_bwd_stats", es * B * HW * C * 2, p, st);
+    if (rc == ADNM_OK) rc = instnorm_submit<uint16_t>(3, 1, "instnorm_bwd_apply", es * B * HW * C * 3, p, st);
   }
+  if (rc != ADNM_OK) return rc;
   ADNM_CHECK_LAUNCH("instnorm_bwd");
   // d shift / d scale: parameter gradients through the shared fold (deferrable: the caller may have bound a fold queue)
-  if (spart) adnm_launch_fold("instnorm_bwd_scalar", spart, (int)(B * g.nchunk * g.gx), 2, {dshift, 1}, {dscale, 1}, {nullptr, 0}, {nullptr, 0}, st);
+  if (spart) adnm_launch_fold_recorded("instnorm_bwd_scalar", spart, (int)(B * g.nchunk * g.gx), 2, {dshift, 1}, {dscale, 1}, {nullptr, 0}, {nullptr, 0}, st);
   ADNM_CHECK_LAUNCH("instnorm_bwd");
   return ADNM_OK;
 }

@@ -362,6 +362,17 @@ __global__ __launch_bounds__(kBlock) void skgemm_kernel(SkArgs p) {
   skgemm_body<A_RC, B_RC, PREC, A_BF8, TM, TN, KC, BT>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// NT / NN problems recorded by an open launch group (adnm_common.h): up to ADNM_GROUP_MAX of one instantiation in one launch.  Every
+// workgroup looks up its problem in the descriptor table and runs the unchanged tile code on that problem's own block range.
+template <bool A_RC, bool B_RC, int PREC, bool A_BF8, int TM, int TN, int KC, int BT>
+__global__ __launch_bounds__(kBlock) void skgemm_multi_kernel(AdnmMulti<SkArgs> by_value) {
+  (void)by_value;
+  const auto& m = *(const __attribute__((address_space(4))) AdnmMulti<SkArgs>*)__builtin_amdgcn_kernarg_segment_ptr();
+  int bid, nblk;
+  const int k = adnm_group_which(m, &bid, &nblk);
+  skgemm_body<A_RC, B_RC, PREC, A_BF8, TM, TN, KC, BT>(m.p[k], bid, nblk);
+}
+
 // Grouped weight gradients: the TN problems of a backward pass are leaves (nothing reads dW before the optimiser) and individually small
 // (a few tiles x a few reduction slices: 70 launches of ~10 us at config 2), so a caller that has bound a leaf queue gets them QUEUED and
 // launched up to kMaxSk at a time — every workgroup looks up its problem in the descriptor table (kernel arguments, constant address space)
@@ -553,15 +564,34 @@ void dims(int op, int64_t M, int64_t N, int64_t K, int64_t* I, int64_t* J, int64
   else *I = N, *J = K, *R = M;
 }
 
+// one host function per kernel instantiation (adnm_common.h: AdnmGroupFn): n == 1 is the plain launch, n > 1 the merged one of an open
+// launch group.  Only NT / NN (A_RC) problems are ever recorded; a weight gradient waits in the leaf queue or is launched at once.
+template <bool A_RC, bool B_RC, int PREC, bool A_BF8, int TM, int TN, int KC, int BT>
+int sk_group_fn(const AdnmGroupRec* const* r, int n, hipStream_t st) {
+  if constexpr (A_RC) {
+    if (n > 1) {
+      AdnmMulti<SkArgs> m;
+      const unsigned blocks = adnm_group_pack(r, n, m);
+      skgemm_multi_kernel<A_RC, B_RC, PREC, A_BF8, TM, TN, KC, BT><<<blocks, kBlock, 0, st>>>(m);
+      return ADNM_OK;
+    }
+  }
+  for (int k = 0; k < n; ++k) {
+    SkArgs p;
+    memcpy(&p, r[k]->args, sizeof(SkArgs));
+    skgemm_kernel<A_RC, B_RC, PREC, A_BF8, TM, TN, KC, BT><<<(unsigned)r[k]->grid, kBlock, 0, st>>>(p);
+  }
+  return ADNM_OK;
+}
 template <bool A_RC, bool B_RC, int TM, int TN, int KC>
-void launch(int prec, int bt, unsigned grid, hipStream_t st, const SkArgs& p) {
-  if (bt == ADNM_B_BF16) skgemm_kernel<A_RC, B_RC, ADNM_MFMA_BF16, false, TM, TN, KC, ADNM_B_BF16><<<grid, kBlock, 0, st>>>(p);
-  else if (bt == ADNM_B_FP8 && prec == ADNM_MFMA_FP8) skgemm_kernel<A_RC, B_RC, ADNM_MFMA_FP8, false, TM, TN, KC, ADNM_B_FP8><<<grid, kBlock, 0, st>>>(p);
-  else if (bt == ADNM_B_FP8) skgemm_kernel<A_RC, B_RC, ADNM_MFMA_FP8, true, TM, TN, KC, ADNM_B_FP8><<<grid, kBlock, 0, st>>>(p);
-  else if (prec == ADNM_MFMA_BF16) skgemm_kernel<A_RC, B_RC, ADNM_MFMA_BF16, false, TM, TN, KC, ADNM_B_F32><<<grid, kBlock, 0, st>>>(p);
-  else if (prec == ADNM_MFMA_FP8) skgemm_kernel<A_RC, B_RC, ADNM_MFMA_FP8, false, TM, TN, KC, ADNM_B_F32><<<grid, kBlock, 0, st>>>(p);
-  else if (prec == ADNM_MFMA_FP8_GRAD) skgemm_kernel<A_RC, B_RC, ADNM_MFMA_FP8, true, TM, TN, KC, ADNM_B_F32><<<grid, kBlock, 0, st>>>(p);
-  else skgemm_kernel<A_RC, B_RC, ADNM_MFMA_F32, false, TM, TN, KC, ADNM_B_F32><<<grid, kBlock, 0, st>>>(p);
+AdnmGroupFn pick(int prec, int bt) {
+  if (bt == ADNM_B_BF16) return sk_group_fn<A_RC, B_RC, ADNM_MFMA_BF16, false, TM, TN, KC, ADNM_B_BF16>;
+  if (bt == ADNM_B_FP8 && prec == ADNM_MFMA_FP8) return sk_group_fn<A_RC, B_RC, ADNM_MFMA_FP8, false, TM, TN, KC, ADNM_B_FP8>;
+  if (bt == ADNM_B_FP8) return sk_group_fn<A_RC, B_RC, ADNM_MFMA_FP8, true, TM, TN, KC, ADNM_B_FP8>;
+  if (prec == ADNM_MFMA_BF16) return sk_group_fn<A_RC, B_RC, ADNM_MFMA_BF16, false, TM, TN, KC, ADNM_B_F32>;
+  if (prec == ADNM_MFMA_FP8) return sk_group_fn<A_RC, B_RC, ADNM_MFMA_FP8, false, TM, TN, KC, ADNM_B_F32>;
+  if (prec == ADNM_MFMA_FP8_GRAD) return sk_group_fn<A_RC, B_RC, ADNM_MFMA_FP8, true, TM, TN, KC, ADNM_B_F32>;
+  return sk_group_fn<A_RC, B_RC, ADNM_MFMA_F32, false, TM, TN, KC, ADNM_B_F32>;
 }
 }  // namespace
 
@@ -636,8 +666,8 @@ extern "C" int adnm_skgemm(int op, const float* a, int64_t lda, const void* b, i
   // algorithmic bytes: activations in and out in fp32, the weight in the storage it is read from (fp32 / bf16 shadow / fp8 shadow)
   const double algo_bytes = 4.0 * (double)M * (K + N) + (b_dtype == ADNM_B_BF16 ? 2.0 : (b_dtype == ADNM_B_FP8 ? 1.0 : 4.0)) * (double)N * K;
   if (pl.kernel == KERNEL_LDS) {
-    ADNM_PROF(scope, st, algo_bytes);
-    const int rc = adnm_lgemm_launch(op == ADNM_SKGEMM_NN, a, lda, b, ldb, b_dtype, b_scale, bias, c, ldc, ws, ws_bytes, slabs_uc, slabs_uc_bytes, I, J, R, pl.nbs, prec, q, st);
+    const int rc = adnm_lgemm_launch(op == ADNM_SKGEMM_NN, a, lda, b, ldb, b_dtype, b_scale, bias, c, ldc, ws, ws_bytes, slabs_uc, slabs_uc_bytes, I, J, R, pl.nbs, prec, q,
+                                     scope, algo_bytes, st);
     if (rc != ADNM_OK) return rc;
     ADNM_CHECK_LAUNCH("skgemm");
     return ADNM_OK;
@@ -685,17 +715,27 @@ extern "C" int adnm_skgemm(int op, const float* a, int64_t lda, const void* b, i
     queued = adnm_leafq_push(leaf);
   }
   if (!queued) {
-    ADNM_PROF(scope, st, algo_bytes);
+    static_assert(sizeof(SkArgs) <= sizeof(AdnmGroupRec::args), "SkArgs must fit a group record");
+    AdnmGroupRec rec;
+    rec.grid = (int)grid, rec.pos = 0, rec.prof = scope, rec.bytes = algo_bytes;
+    memcpy(rec.args, &p, sizeof(SkArgs));
     if (op == ADNM_SKGEMM_NT) {
-      if (pl.tm == 1) launch<true, true, 1, 1, 4>(prec, b_dtype, grid, st, p);
-      else if (pl.tm == 2) launch<true, true, 2, 2, 2>(prec, b_dtype, grid, st, p);
-      else launch<true, true, 4, 4, 1>(prec, b_dtype, grid, st, p);
+      if (pl.tm == 1) rec.fn = pick<true, true, 1, 1, 4>(prec, b_dtype);
+      else if (pl.tm == 2) rec.fn = pick<true, true, 2, 2, 2>(prec, b_dtype);
+      else rec.fn = pick<true, true, 4, 4, 1>(prec, b_dtype);
     } else if (op == ADNM_SKGEMM_NN) {
-      if (pl.tm == 1) launch<true, false, 1, 4, 2>(prec, b_dtype, grid, st, p);
-      else if (pl.tm == 2) launch<true, false, 2, 4, 2>(prec, b_dtype, grid, st, p);
-      else launch<true, false, 4, 4, 1>(prec, b_dtype, grid, st, p);
+      if (pl.tm == 1) rec.fn = pick<true, false, 1, 4, 2>(prec, b_dtype);
+      else if (pl.tm == 2) rec.fn = pick<true, false, 2, 4, 2>(prec, b_dtype);
+      else rec.fn = pick<true, false, 4, 4, 1>(prec, b_dtype);
     } else {
-      launch<false, false, 4, 4, 1>(prec, b_dtype, grid, st, p);
+      rec.fn = pick<false, false, 4, 4, 1>(prec, b_dtype);
+    }
+    if (op == ADNM_SKGEMM_TN) {   // a weight gradient never waits in a launch group (its fold below follows it at once)
+      const AdnmGroupRec* one = &rec;
+      ADNM_PROF(scope, st, algo_bytes);
+      rec.fn(&one, 1, st);
+    } else if (int rc = adnm_group_submit(rec, st)) {
+      return rc;
     }
   }
   ADNM_CHECK_LAUNCH("skgemm");

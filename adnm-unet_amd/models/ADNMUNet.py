@@ -294,7 +294,10 @@ class Decoder(nn.Module):
         aliases = []
         gates = self.fusion(skips, live=None if dead else {4, 5, 6}, alias_out=aliases)
         skips = aliases   # same tensors; their gradients now meet the bridge pool's inside one kernel
-        feats = [self.e2ds[i](x=skips[6 - i], res=gates[6 - i]) for i in range(7 if dead else 3)]
+        # the chains are independent and structurally identical: one autograd node runs them step by step, the same step of every
+        # chain inside one launch group (ops.e2d_group) — bit for bit [self.e2ds[i](x=skips[6 - i], res=gates[6 - i]) for i in ...]
+        n = 7 if dead else 3
+        feats = ops.e2d_group([skips[6 - i] for i in range(n)], [gates[6 - i] for i in range(n)], [self.e2ds[i] for i in range(n)])
         return skips, feats
 
     def forward_blocks(self, x, skips, feats):

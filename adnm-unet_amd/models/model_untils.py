@@ -580,6 +580,28 @@ class EncoderToDecoder(nn.Module):
             self.alpha1, self.alpha2, self.alpha3, self.gamma))
         return self.mlp(self.ffd.forward_tokens(xp, h, w))
 
+    def group_args(self, x):
+        """-> ((h, w, GroupNorm groups or 0, eps), the 37 parameter tensors forward() hands to its kernels, in forward()'s order): what
+        ops.e2d_group needs to run this module as one chain of a grouped node.  Same checks as forward()."""
+        b, l, d = x.shape
+        h, w = _hw(l)
+        n = self.norm
+        group = _hip_groupnorm(n, d)
+        if not (group or isinstance(n, nn.InstanceNorm2d) and d % 4 == 0):
+            raise RuntimeError(f"EncoderToDecoder: the HIP kernels take InstanceNorm2d, or GroupNorm with a multiple of 4 channels per group, "
+                               f"and a multiple of 4 channels, got {n}, dim {d} (the HIP path has no PyTorch fallback)")
+        f13, f33 = self.ffd13.conv, self.ffd33.conv
+        pi, dc, po = self.ffd.project_in.conv, self.ffd.dwconv.conv, self.ffd.project_out.conv
+        m = self.mlp
+        params = [self.gama, self.act.enhance, self.act.threshold, n.weight if group else None, n.bias if group else None, self.scale, self.shift,
+                  self.conv13pool.conv.weight, self.conv13pool.conv.bias, self.conv31pool.conv.weight, self.conv31pool.conv.bias,
+                  self.conv33pool.conv.weight, self.conv33pool.conv.bias, f13.weight.reshape(-1), f13.bias, f33.weight.reshape(-1), f33.bias,
+                  self.act_func13.enhance, self.act_func13.threshold, self.act_func33.enhance, self.act_func33.threshold,
+                  self.alpha1, self.alpha2, self.alpha3, self.gamma,
+                  pi.weight.reshape(pi.out_channels, -1), pi.bias, dc.weight, dc.bias, po.weight.reshape(po.out_channels, -1), po.bias,
+                  m.in_proj.weight, m.in_proj.bias, m.dw_conv.conv.weight, m.dw_conv.conv.bias, m.out_proj.weight, m.out_proj.bias]
+        return (h, w, n.num_groups if group else 0, n.eps), params
+
 
 class OutProj(nn.Module):
     def __init__(self, num_frames=3, embed_dim=256, img_size=[256, 256], act_func=Swish, wt_levels=2, ls_init_value=1,

@@ -116,6 +116,26 @@ int64_t adnm_leafq_pending(void* q);
 int adnm_leafq_flush(void* q, adnm_stream_t stream);
 int adnm_leafq_clear(void* q);
 
+/* Launch group: the same step of several INDEPENDENT, structurally identical chains as one launch (EncoderToDecoder's three skip
+ * chains: each of their kernels fills a small part of the chip, and the runtime does not overlap independent launches).
+ * Contract: the calls the thread makes between adnm_group_begin and adnm_group_launch are mutually independent problems, each of which
+ * depends only on work enqueued before adnm_group_begin.  An entry point that knows about groups — adnm_skgemm with ops NT and NN (both of
+ * its kernels), adnm_dwconv_fwd, adnm_dwconv_bwd (dpre and the input gradient: two positions; with a weight-gradient destination it is
+ * refused inside a group, adnm_dwconv_wgrad is a call of its own behind the launch), adnm_gate_fwd / _bwd, adnm_instnorm_fwd / _bwd (two
+ * positions each; without a bound fold queue the fold of the scalar gradients is recorded behind them), adnm_igate_res_fwd / _bwd (likewise)
+ * — then stores its fully prepared launch instead of making it (operands, outputs and workspaces must stay alive, and two
+ * split problems need DISJOINT counter / slab ranges); every other entry point launches at once, which the contract allows.
+ * adnm_group_launch issues the stored launches on `stream`: those of one kernel instantiation merged into one multi-problem launch (up to 8
+ * problems; descriptors in the kernel-argument segment), a record without a partner alone.  Every problem keeps the plan, the grid and
+ * the workgroup arithmetic it has alone: results are bitwise those of separate launches.  A merged launch is one profiler event under the
+ * entry point's own scope name with the summed bytes.
+ * Groups are per thread and do not nest (a second begin: EINVAL); adnm_foldq_flush / adnm_leafq_flush are refused while one is open;
+ * a launch with nothing recorded is ADNM_OK; adnm_group_clear closes the group and forgets what it recorded (the error path). */
+int adnm_group_begin(void);
+int adnm_group_launch(adnm_stream_t stream);
+int adnm_group_clear(void);
+int64_t adnm_group_pending(void);
+
 /* ---------------------------------------------------------------- row norms (K2, K7)
  * y = scale * ( xhat * w + b ) + shift,  xhat = (x - mu) * rstd
  *   RMSNorm   (mamba_ssm RMSNorm bound at ADNMUNet.py:278, used ADNMUNet.py:149,155): subtract_mean=0, b=NULL
