@@ -118,7 +118,8 @@ class GraphedForward:
                     ops.QUANT.restore(x.device, snap)
         for s in ent["shadows"]:
             s.ensure_current()
-        ent["sx"].copy_(x, non_blocking=True)
+        if x is not ent["sx"]:   # (a client that filled the static input in place hands it back: no copy onto itself)
+            ent["sx"].copy_(x, non_blocking=True)
         ent["graph"].replay()
         return ent
 

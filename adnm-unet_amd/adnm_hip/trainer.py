@@ -25,6 +25,7 @@ refiner -> decoder -> e2ds / fusion -> encoder4-6 -> encoder1-3; or the older tw
     bf16, the 1/world average and the return to fp32 happen in one HIP pass.
 """
 import gc
+import weakref
 
 import torch
 import torch.distributed as dist
@@ -97,7 +98,7 @@ class FlatTrainer:
         # what the captures own (_prepare); _release_captures() is the one place that gives it back
         self.graph = self.graph2 = self.tail = None
         self.graphs = []
-        self.static_loss = self._carry = self._cuts = self.sx = self.st = None
+        self.static_loss = self._carry = self._cuts = self.sx = self.st = self._feed = None
         self.hyper = self._hyper_host = None   # [lr, max_norm] as the tail graph reads them, and the host's copy
         self._splitws = None                   # the split-K capture scope of all graphs (ops.SPLITWS)
         self._pin = None                       # the pin on the fp8 table (ops.QUANT.pinned)
@@ -337,6 +338,7 @@ class FlatTrainer:
         self.static_loss = None
         self._carry = self._cuts = None
         self.sx = self.st = None
+        self._feed = None   # (step_from's checked feed: checked against THESE static buffers)
         self.hyper = self._hyper_host = None
         self._splitws = None
         pin, self._pin = self._pin, None
@@ -705,6 +707,24 @@ class FlatTrainer:
         if not self._skip_host:   # (fused: always; the device's own counter, state[0], is the one a skipped step leaves alone)
             self._steps += 1
         return loss
+
+    def step_from(self, feed, eager=False):
+        """step() on the next batch of a dataio.ResidentDataset; returns what step() returns.  Prepared with graphs: ONE launch writes the
+        batch into the static buffers the graphs read (self.sx / self.st) and step() runs on them, so that its pointer test skips both
+        copies.  The first call (it prepares), use_graph=False and eager=True fetch into tensors of their own.  With accum_steps = k
+        every micro-step takes the feed's next batch."""
+        if self.graph is None or eager:
+            x, tgt = feed.fetch()
+            return self.step(x, tgt, eager=eager)
+        if self._feed is None or self._feed() is not feed:   # once per feed: the static buffers are what the feed writes
+            if tuple(self.sx.shape) != tuple(feed.x_shape) or tuple(self.st.shape) != tuple(feed.tgt_shape) or self.sx.device != feed.device:
+                raise RuntimeError(f"FlatTrainer.step_from: prepared for x {tuple(self.sx.shape)} / tgt {tuple(self.st.shape)} on {self.sx.device}, the "
+                                   f"feed gives {tuple(feed.x_shape)} / {tuple(feed.tgt_shape)} on {feed.device}")
+            feed._check(self.sx, feed.x_shape, "the trainer's static input")
+            feed._check(self.st, feed.tgt_shape, "the trainer's static target")
+            self._feed = weakref.ref(feed)
+        feed._launch(self.sx, self.st)
+        return self.step(self.sx, self.st)
 
     # ------------------------------------------------------------------ monitor=True: statistics and the skipped step
     STAT_FIELDS = ("steps", "skipped", "norm_sum", "norm_max", "last_norm", "clip_count", "loss_sum", "loss_nonfinite")

@@ -134,16 +134,36 @@ class Validator(ForwardClient):
         if tgt.shape[0] != x.shape[0] or tgt.device != x.device:
             raise RuntimeError(f"Validator: input {tuple(x.shape)} on {x.device} and target {tuple(tgt.shape)} on {tgt.device} do not belong together")
         shape = (tgt.shape[0], tgt.shape[1], tgt.shape[-2], tgt.shape[-1])
-        if self._frame is None:
-            self._frame = shape[2:]
-        elif self._frame != shape[2:]:
-            raise RuntimeError(f"Validator: frames of {shape[2]} x {shape[3]} in an epoch of {self._frame[0]} x {self._frame[1]} frames (done(reset=True) first)")
-        self._block_for(x.device)
+        self._begin(shape, x.device)
         ent = self._fwd.entry(x)
         if ent["shape"] != shape:
             raise RuntimeError(f"Validator: input {tuple(x.shape)} came with a target of {ent['shape']} before, now {shape}")
         ent["tgt"].view(tgt.shape).copy_(tgt, non_blocking=True)
         return self._fwd.replay(ent, x)["out"]
+
+    def _begin(self, shape, device):
+        """a batch of (B, T, H, W) targets enters the epoch: its frames are the epoch's, the block is on its device"""
+        if self._frame is None:
+            self._frame = shape[2:]
+        elif self._frame != shape[2:]:
+            raise RuntimeError(f"Validator: frames of {shape[2]} x {shape[3]} in an epoch of {self._frame[0]} x {self._frame[1]} frames (done(reset=True) first)")
+        self._block_for(device)
+
+    def step_from(self, feed):
+        """step() on the next batch of a dataio.ResidentDataset.  Once the feed's shape has a captured graph, the batch is fetched
+        straight into that graph's static input and target (one launch; no copy of either, and none of a buffer onto itself); before
+        that (the first batch of a shape) into tensors of its own, which step() copies while it captures."""
+        B, T, _, H, W = feed.tgt_shape
+        if T != self.seq_len:
+            raise RuntimeError(f"Validator: the feed has {T} target frames per sample, seq_len is {self.seq_len}")
+        ent = self._fwd._graphs.get((tuple(feed.x_shape), torch.float32, feed.device))
+        if ent is None or ent["graph"] is None:
+            return self.step(*feed.fetch())
+        if ent["shape"] != (B, T, H, W):
+            raise RuntimeError(f"Validator: input {feed.x_shape} came with a target of {ent['shape']} before, the feed gives {(B, T, H, W)}")
+        self._begin((B, T, H, W), feed.device)
+        feed.fetch_into(ent["sx"], ent["tgt"])
+        return self._fwd.replay(ent, ent["sx"])["out"]
 
     @property
     def last_loss(self):

@@ -265,6 +265,79 @@ extern "C" int adnm_radar_ingest(const void* src_u8, float* dst, int64_t frames,
   return ADNM_OK;
 }
 
+// ---- the resident split: one batch out of the store (include/adnm_hip.h: adnm_batch_fetch) ----
+namespace {
+constexpr int kFetchUnroll = 4;       // pieces a lane keeps in flight per trip
+constexpr int kFetchMaxBlocks = 2048; // workgroups of a launch, all samples together (a streaming grid: the rest is grid-strided)
+constexpr int64_t kFetchMaxBatch = 65535;
+
+// gridDim.y = the batch: a workgroup stays inside sample b = blockIdx.y, whose index order[pos + b] is one uniform load.  An index
+// outside [0, n_samples) is never turned into an address: the sample's rows are filled with quiet NaNs instead (a uniform branch).
+// V = float4: `per` (= T*hw) and `split` (= T_in*hw) count 16-byte pieces, so that no piece straddles the x / tgt boundary; V = float:
+// they count floats.  A lane's pieces lie `stride` apart; it loads kFetchUnroll of them before it stores the first, then the ragged rest
+// one by one.
+__device__ __forceinline__ void fetch_nan(float& v) { v = __int_as_float(0x7fc00000); }
+__device__ __forceinline__ void fetch_nan(float4& v) { v.x = v.y = v.z = v.w = __int_as_float(0x7fc00000); }
+
+template <typename V>
+__global__ __launch_bounds__(kBlock) void batch_fetch_kernel(const V* __restrict__ store, const int32_t* __restrict__ order, int64_t pos, int n_samples,
+                                                             int64_t per, int64_t split, V* __restrict__ x, V* __restrict__ tgt) {
+  const int64_t b = blockIdx.y;
+  const int s = order[pos + b];
+  V* dx = x + b * split;
+  V* dt = tgt + b * (per - split) - split;   // piece i >= split of the sample -> dt[i]
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (s < 0 || s >= n_samples) {
+    V nan;
+    fetch_nan(nan);
+    for (; i < per; i += stride) (i < split ? dx : dt)[i] = nan;
+    return;
+  }
+  const V* src = store + (int64_t)s * per;
+  for (; i + (kFetchUnroll - 1) * stride < per; i += kFetchUnroll * stride) {
+    V v[kFetchUnroll];
+#pragma unroll
+    for (int k = 0; k < kFetchUnroll; ++k) v[k] = src[i + k * stride];
+#pragma unroll
+    for (int k = 0; k < kFetchUnroll; ++k) (i + k * stride < split ? dx : dt)[i + k * stride] = v[k];
+  }
+  for (; i < per; i += stride) (i < split ? dx : dt)[i] = src[i];
+}
+}  // namespace
+
+extern "C" int adnm_batch_fetch(const float* store, int64_t n_samples, int64_t T, int64_t hw, const int32_t* order, int64_t order_len, int64_t pos, float* x,
+                                float* tgt, int64_t B, int64_t T_in, adnm_stream_t stream) {
+  ADNM_REQUIRE(store && order && x && tgt, "batch_fetch: null pointer");
+  ADNM_REQUIRE(((uintptr_t)store | (uintptr_t)order | (uintptr_t)x | (uintptr_t)tgt) % 4 == 0, "batch_fetch: store, order, x and tgt must be 4-byte aligned");
+  ADNM_REQUIRE(B >= 1 && B <= kFetchMaxBatch, "batch_fetch: the batch must be in [1, %lld] (one grid row per sample), got %lld", (long long)kFetchMaxBatch, (long long)B);
+  ADNM_REQUIRE(hw >= 1 && hw < (1ll << 31) && T < (1ll << 31), "batch_fetch: bad shape (1 <= hw < 2^31, T < 2^31), got T %lld hw %lld", (long long)T, (long long)hw);
+  ADNM_REQUIRE(T_in >= 1 && T_in < T, "batch_fetch: T_in must be in [1, T), got T_in %lld of T %lld", (long long)T_in, (long long)T);
+  ADNM_REQUIRE(n_samples >= 1 && n_samples < (1ll << 31) && order_len >= 1 && order_len < (1ll << 31),
+               "batch_fetch: n_samples and order_len must be in [1, 2^31), got %lld and %lld", (long long)n_samples, (long long)order_len);
+  ADNM_REQUIRE(pos >= 0 && pos <= order_len - B, "batch_fetch: %lld positions from %lld on lie outside an order of %lld", (long long)B, (long long)pos,
+               (long long)order_len);
+  const int64_t per = T * hw, split = T_in * hw;
+  // 16-byte accesses need every sample start in the store (stride `per`), both halves' starts in x and tgt (strides `split`, `per - split`)
+  // and the three bases aligned; anything else (an odd S, a 4-byte aligned slice of a larger buffer) takes the scalar path: same result
+  const bool vec = per % 4 == 0 && split % 4 == 0 && adnm_quad_aligned(ADNM_F32, {store, x, tgt});
+  const int64_t units = vec ? per / 4 : per;
+  int64_t gx = adnm_cdiv(units, (int64_t)kBlock * kFetchUnroll), cap = kFetchMaxBlocks / B;
+  cap = cap < 1 ? 1 : cap;
+  gx = gx > cap ? cap : gx;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ADNM_PROF("batch_fetch", st, 8.0 * B * T * hw);
+    if (vec)
+      batch_fetch_kernel<float4><<<dim3((unsigned)gx, (unsigned)B), kBlock, 0, st>>>((const float4*)store, order, pos, (int)n_samples, per / 4, split / 4,
+                                                                                     (float4*)x, (float4*)tgt);
+    else
+      batch_fetch_kernel<float><<<dim3((unsigned)gx, (unsigned)B), kBlock, 0, st>>>(store, order, pos, (int)n_samples, per, split, x, tgt);
+  }
+  ADNM_CHECK_LAUNCH("batch_fetch");
+  return ADNM_OK;
+}
+
 extern "C" int64_t adnm_eval_counts_ws_bytes(int64_t frames, int64_t hw, int64_t nthr) {
   if (frames <= 0 || hw <= 0 || nthr <= 0 || nthr > kMaxThr) return 0;
   return (int64_t)eval_blocks(hw) * frames * (4 * nthr + 2) * (int64_t)sizeof(float);

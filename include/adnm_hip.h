@@ -602,6 +602,19 @@ int adnm_convt_im2col(const float* dout, int64_t lddo, float* dcols, int64_t ldc
  *   uint16(clip(x,0,1) * value_scale) fields (truth = "obs", pred = "sim") and sum |d|, sum d^2 of the scaled clipped float fields.
  *   thresholds_host: nthr <= 8 floats in HOST memory (they become kernel arguments).  out: (frames, 4*nthr + 2) fp32, OVERWRITTEN. */
 int adnm_radar_ingest(const void* src_u8, float* dst, int64_t frames, int64_t H0, int64_t W0, int64_t S, float mul, adnm_stream_t stream);
+/* adnm_batch_fetch: the DataLoader's collate + copy (train.py:44-57,132-134) for a split that lives on the device.  store: (n_samples, T, hw)
+ *   fp32 contiguous; order: order_len int32 sample indices, both in DEVICE memory (the kernel reads the indices: none passes through the
+ *   host).  For b < B, s = order[pos + b]:  x[b] = store[s, :T_in] as (B, T_in, hw),  tgt[b] = store[s, T_in:] as (B, T - T_in, hw),
+ *   both contiguous, a pure copy (bit exact).  One launch, gridDim.y = B.
+ *   An index outside [0, n_samples) is NOT dereferenced: that sample's x and tgt rows are filled with quiet NaNs (0x7fc00000) and the
+ *   launch succeeds, so a bad order shows as a non-finite loss (which a monitored step skips and counts), never as a stray read.
+ *   Refused before any launch (ADNM_EINVAL): a null pointer; B outside [1, 65535] (the grid's second dimension); T_in < 1 or T_in >= T;
+ *   hw < 1 (or hw, T >= 2^31); pos < 0 or pos + B > order_len; n_samples or order_len outside [1, 2^31); a pointer that is not 4-byte
+ *   aligned.  Alignment beyond that is the entry point's business: with T*hw and T_in*hw multiples of 4 and store, x and tgt 16-byte
+ *   aligned the copy moves 16 bytes per access, otherwise (an odd frame side, x or tgt a 4-byte aligned slice of a larger buffer) it
+ *   moves floats one by one with the SAME result: such a call is served, not refused. */
+int adnm_batch_fetch(const float* store, int64_t n_samples, int64_t T, int64_t hw, const int32_t* order, int64_t order_len, int64_t pos,
+                     float* x, float* tgt, int64_t B, int64_t T_in, adnm_stream_t stream);
 int64_t adnm_eval_counts_ws_bytes(int64_t frames, int64_t hw, int64_t nthr);
 int adnm_eval_counts(const float* truth, const float* pred, float* out, const float* thresholds_host, int64_t nthr, float value_scale,
                      void* ws, int64_t ws_bytes, int64_t frames, int64_t hw, adnm_stream_t stream);
