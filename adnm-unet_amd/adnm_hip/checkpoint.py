@@ -110,8 +110,8 @@ def to_torch_adamw_state(trainer, sd=None):
 
 def from_torch_adamw_state(trainer, opt_sd, strict=True):
     """Take over a torch.optim.AdamW.state_dict() (one param group over model.parameters()): moments, step count and lr; betas, eps and
-    weight_decay must be the trainer's (strict=False: the trainer keeps its own).  max_norm, an accumulation cycle, the monitor block
-    and the fp8 table are not torch's to give and stay as they are.  Like load_state_dict: in place on a prepared trainer, kept for
+    weight_decay must be the trainer's (strict=False: the trainer keeps its own).  max_norm, an accumulation cycle, the monitor block,
+    the fp8 table and the average of the weights (ema_decay) are not torch's to give and stay as they are.  Like load_state_dict: in place on a prepared trainer, kept for
     the flat layout on a fresh one."""
     groups = opt_sd["param_groups"]
     if len(groups) != 1:
@@ -137,4 +137,4 @@ def from_torch_adamw_state(trainer, opt_sd, strict=True):
     sd = trainer._scalars()
     sd.update(steps=int(step), lr=float(g["lr"]), betas=tuple(float(b) for b in g["betas"]), eps=float(g["eps"]),
               weight_decay=float(g["weight_decay"]), micro_step=0, state_bits=bits.view(torch.int32), params=per, monitor=None, fp8=None)
-    trainer._load(sd, strict, quant=False)
+    trainer._load(sd, strict, quant=False, ema=False)

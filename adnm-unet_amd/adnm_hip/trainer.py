@@ -24,6 +24,7 @@ refiner -> decoder -> e2ds / fusion -> encoder4-6 -> encoder1-3; or the older tw
   * reduce_dtype="bf16": the wire format of the collective is bf16 (146 MB instead of 292 MB); sums are formed by RCCL in
     bf16, the 1/world average and the return to fp32 happen in one HIP pass.
 """
+import contextlib
 import gc
 import weakref
 
@@ -36,7 +37,7 @@ from . import lib, ops
 class FlatTrainer:
     def __init__(self, model, loss_fn, lr=1e-3, betas=(0.9, 0.999), eps=1e-9, weight_decay=1e-2, max_norm=0.0,
                  process_group=None, use_graph=True, fused=True, overlap="auto", reduce_dtype="f32", stages=None, defer_folds=True, side_stream=False,
-                 nstages=None, accum_steps=1, monitor=False):
+                 nstages=None, accum_steps=1, monitor=False, ema_decay=None, ema_warmup=True):
         """overlap: cut the backward at the model's stage boundaries and all-reduce every stage's gradients while the backward of the
         stages before it runs.  "auto" = whenever there is more than one rank.  `stages` is the older name of the same switch
         (True / False).  nstages: None = every stage the model offers (forward_stages(): 5 for ADNM-UNet); 2 = the two-stage cut
@@ -46,7 +47,12 @@ class FlatTrainer:
         monitor: keep the epoch's statistics (train.py:140-153: gradient norms, clip count, summed loss) in device memory — stats()
         reads them with ONE synchronising copy per epoch instead of two .item() per step — and SKIP every optimiser step whose
         gradient is not finite (parameters, moments, step counter, shadow and fp8 table stay as they were).  False: nothing of this
-        exists, the step is launch for launch what it was."""
+        exists, the step is launch for launch what it was.
+        ema_decay: a float in [0, 1] keeps an exponential moving average of the parameters in a second flat fp32 buffer (self.ema, 4 bytes
+        per parameter: ~0.29 GB for ADNM-UNet), moved by one HIP pass behind every APPLIED optimiser step (once per accumulation cycle; a
+        skipped step leaves it alone): ema = d * ema + (1 - d) * p with d = ema_decay, or, ema_warmup=True, min(ema_decay, (1 + t) /
+        (10 + t)) at optimiser step t, so that a young average is not dominated by the initial weights.  ema_weights() makes the model
+        compute with it, ema_info() reads the decay in use and the number of updates.  None: nothing of this exists."""
         self.model, self.loss_fn = model, loss_fn
         self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_norm
         self.group = process_group
@@ -111,6 +117,12 @@ class FlatTrainer:
         # a state loaded before the flat buffers exist (load_state_dict): applied as the last act of _flatten; its fp8 part after the
         # calibration of prepare() has made the table's rows
         self._pending = self._pending_quant = None
+        self._pending_ema = True
+        # ema_decay is not None: the average (laid out like flat_p, allocated with it), [the d of the last update, updates applied] as
+        # adnm_ema_update keeps them, and whether ema_weights() is open (flat_p and ema then hold each other's values)
+        self.ema_decay, self.ema_warmup = self._check_ema_decay(ema_decay), bool(ema_warmup)
+        self.ema = self._ema_info = None
+        self._ema_open = False
 
     # ------------------------------------------------------------------ gradient accumulation
     @staticmethod
@@ -281,9 +293,12 @@ class FlatTrainer:
             self._accumulator()
         if self.monitor:
             self._stats_block()
+        if self.ema_decay is not None:   # starts as a copy of the parameters (padding included: zero, and zero it stays)
+            self.ema = self.flat_p.clone()
+            self._ema_info = torch.zeros(2, dtype=torch.float32, device=dev)
         if self._pending is not None:   # a state loaded before the first backward: now there is a layout to write it into
             sd, self._pending = self._pending, None
-            self._apply_state(sd, quant=False)
+            self._apply_state(sd, quant=False, ema=self._pending_ema)
 
     def bucket_report(self):
         """[(bucket index in all-reduce order, first element, last element + 1, bytes on the wire)]: what each stage's collective moves —
@@ -437,6 +452,7 @@ class FlatTrainer:
         Ownership: objects with device-side destructors that died earlier (old trainers, graphs of failed runs) are collected
         BEFORE anything starts, and the cyclic collector stays off until the last capture has ended (see close()); an exception
         on the way — inside a capture included — unbinds the fold queue, drops the half-built graphs and re-raises."""
+        self._not_under_ema("prepare")
         gc.collect()
         gc_was_on = gc.isenabled()
         gc.disable()
@@ -550,7 +566,9 @@ class FlatTrainer:
         self.hyper = torch.tensor([self.lr, self.max_norm], dtype=torch.float32, device=x.device)
         self._hyper_host = (float(self.lr), float(self.max_norm))
         # (the statistics block of a monitored run among them: the warm-up's guard counted one step, prepare() leaves the block zero)
-        live = [t for t in (self.flat_p, self.exp_avg, self.exp_avg_sq, self.state, self.flat_g, self.shadow, self._stats) if t is not None]
+        # (and the average with its two floats: adnm_ema_update's first launch happens in this warm-up, not inside the capture)
+        live = [t for t in (self.flat_p, self.exp_avg, self.exp_avg_sq, self.state, self.flat_g, self.shadow, self._stats, self.ema,
+                            self._ema_info) if t is not None]
         keep = [t.clone() for t in live]
         qsave = ops.QUANT.snapshot(x.device) if self.fp8 else None
         try:
@@ -582,8 +600,8 @@ class FlatTrainer:
         self._update(hyper=True)
 
     def _update(self, hyper=False):
-        """the end of a step, on gradients that are final: (monitor: guard + statistics ->) fp8 table update -> clip + AdamW (+ shadow).
-        Eagerly and as the body of the tail graph.
+        """the end of a step, on gradients that are final: (monitor: guard + statistics ->) fp8 table update -> clip + AdamW (+ shadow)
+        (-> the moving average of the parameters).  Eagerly and as the body of the tail graph.
         monitor, more than one rank: the guard runs AFTER the all-reduce, on a flat_g that holds the same bits on every rank (the
         collective leaves one result everywhere — fp32 sums and, on the bf16 wire, the bf16 sums every rank casts back with the same
         kernel), so every rank takes the same decision from the same state[1]: the ranks skip or apply together without exchanging
@@ -597,6 +615,8 @@ class FlatTrainer:
             # the e4m3 shadow of the updated weights with the scales the next step's GEMMs will read
             ops.QUANT.update(self.flat_g.device, guard=guard)
         self._optimizer_step(hyper=hyper)
+        if self.ema is not None:
+            self._ema_update()
 
     def _run_eager(self, x, tgt, between=None):
         """between(j): called after part j (its bucket is complete) while parts remain — the N > 1 flow starts the bucket's all-reduce there"""
@@ -658,6 +678,7 @@ class FlatTrainer:
         monitor=True: every call adds its loss to the statistics; the optimiser step (once per cycle, on the averaged gradient — a
         non-finite micro-gradient reaches it through the accumulator) is skipped when that gradient is not finite.  A skipped cycle ends
         like any other: micro_step is 0 again and the next cycle overwrites the accumulator."""
+        self._not_under_ema("step")
         if self.used is None:
             self.prepare(x, tgt)
         elif self._shadow is not None and self._shadow.stale():   # a write outside the optimiser (a checkpoint load, an in-place op)
@@ -713,6 +734,7 @@ class FlatTrainer:
         batch into the static buffers the graphs read (self.sx / self.st) and step() runs on them, so that its pointer test skips both
         copies.  The first call (it prepares), use_graph=False and eager=True fetch into tensors of their own.  With accum_steps = k
         every micro-step takes the feed's next batch."""
+        self._not_under_ema("step_from")
         if self.graph is None or eager:
             x, tgt = feed.fetch()
             return self.step(x, tgt, eager=eager)
@@ -803,6 +825,102 @@ class FlatTrainer:
         max_norm = float(torch.tensor(self.max_norm, dtype=torch.float32))   # (the kernel compares in fp32)
         if max_norm > 0 and norm > max_norm:
             s[5] += 1
+
+    # ------------------------------------------------------------------ ema_decay: the moving average of the parameters
+    @staticmethod
+    def _check_ema_decay(d):
+        if d is None:
+            return None
+        if isinstance(d, bool) or not isinstance(d, (int, float)) or not 0.0 <= float(d) <= 1.0:
+            raise ValueError(f"FlatTrainer: ema_decay={d!r} must be None or a number in [0, 1]")
+        return float(d)
+
+    def _require_ema(self, what):
+        if self.ema_decay is None:
+            raise RuntimeError(f"FlatTrainer.{what}: this trainer was built without ema_decay and keeps no average of the weights")
+
+    def _not_under_ema(self, what):
+        if self._ema_open:
+            raise RuntimeError(f"FlatTrainer.{what}: not inside ema_weights() (the parameters hold the averaged weights; leave the context first)")
+
+    @torch.no_grad()
+    def _ema_update(self):
+        """ema = d * ema + (1 - d) * p behind the optimiser pass (adnm_ema_update; d from the device's step counter); the same statement
+        in torch on the CPU test path, where the step counter is the host's"""
+        if self.fused:
+            lib.call("adnm_ema_update", self.flat_p.data_ptr(), self.ema.data_ptr(), self.n, self.state.data_ptr(), self.ema_decay,
+                     int(self.ema_warmup), self._ema_info.data_ptr(), self._stats.data_ptr() if self.monitor else None,
+                     torch.cuda.current_stream().cuda_stream)
+        elif not self._skip_host:
+            self._torch_ema_for_tests()
+
+    @torch.no_grad()
+    def _torch_ema_for_tests(self):
+        """adnm_ema_update in torch ops, for the CPU (gloo) tests: d and w in fp32, w * p rounded to fp32, then d * ema + (w * p) formed
+        in fp64 (the product is exact there) and rounded once: the kernel's fmaf"""
+        d = torch.tensor(self.ema_decay, dtype=torch.float32)
+        if self.ema_warmup:
+            t = torch.tensor(float(self._steps + 1), dtype=torch.float32)   # (the step this update belongs to: state[0] on the device)
+            d = torch.minimum(d, (1.0 + t) / (10.0 + t))
+        w = 1.0 - d
+        wp = self.flat_p * w.to(self.flat_p.device)
+        self.ema.copy_((self.ema.double() * float(d) + wp.double()).float())
+        self._ema_info[0] = d
+        self._ema_info[1] += 1
+
+    def ema_info(self):
+        """{"decay": the d the last update used (0.0 before the first), "updates": updates applied}.  SYNCHRONISES: one small device ->
+        host read that waits for every step enqueued so far."""
+        self._require_ema("ema_info")
+        v = self._ema_info.tolist() if self._ema_info is not None else [0.0, 0.0]   # (no step yet: nothing applied)
+        return {"decay": v[0], "updates": int(v[1])}
+
+    @torch.no_grad()
+    def _ema_swap(self):
+        if self.fused:
+            lib.call("adnm_ema_swap", self.flat_p.data_ptr(), self.ema.data_ptr(), self.n, torch.cuda.current_stream().cuda_stream)
+        else:
+            keep = self.flat_p.clone()
+            self.flat_p.copy_(self.ema)
+            self.ema.copy_(keep)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """with trainer.ema_weights(): the model computes with the averaged weights — model.state_dict(), checkpoint.save_reference_checkpoint,
+        Validator.step / step_from, Forecaster, eager forwards and GraphedForward graphs captured before (no pointer moves) — and the run
+        goes on afterwards as if nothing had happened.  Entry: (fp8: the quantisation table is saved,) flat_p and ema exchange their
+        contents in one HIP pass, the narrow shadow is rewritten from the parameters as they now are (fp8: weight scales re-derived).
+        Exit, also after an exception: exchanged back, (fp8: the table restored,) the shadow written from the restored parameters with
+        the restored scales: flat_p, the shadow and the table are bit for bit what they were.  The raw HIP writes move none of torch's
+        version counters, so both ends rewrite the shadow themselves.  Between steps only: not inside a capture, not with an
+        accumulation cycle open; step(), step_from(), prepare(), state_dict(), load_state_dict(), snapshot() and a nested ema_weights()
+        raise inside."""
+        self._require_ema("ema_weights")
+        self._require_state("ema_weights")
+        self._not_under_ema("ema_weights")
+        if self._micro != 0:
+            raise RuntimeError(f"FlatTrainer.ema_weights: an accumulation cycle is open (micro-step {self._micro} of {self._accum_steps}); "
+                               "finish it first")
+        dev = self.flat_p.device
+        qsave = ops.QUANT.snapshot(dev) if self.fp8 else None
+        self._ema_swap()
+        self._ema_open = True
+        try:
+            if self._shadow is not None:
+                self._shadow.refresh()
+            yield self
+        finally:
+            try:
+                self._ema_swap()
+                if qsave is not None:
+                    ops.QUANT.restore(dev, qsave)
+                if self._shadow is not None:
+                    self._shadow.write()
+                    if qsave is not None:   # (the shadow pass collects max |w| into the records whose flag is set: the table once more)
+                        ops.QUANT.restore(dev, qsave)
+                    self._shadow.mark_current()
+            finally:
+                self._ema_open = False
 
     def _optimizer_step(self, hyper=False):
         if self.fused:
@@ -898,15 +1016,18 @@ class FlatTrainer:
         return out
 
     def _scalars(self):
-        return {"version": self.STATE_VERSION, "precision": self._precision(), "steps": int(self._steps), "lr": float(self.lr),
-                "max_norm": float(self.max_norm), "betas": (float(self.betas[0]), float(self.betas[1])), "eps": float(self.eps),
-                "weight_decay": float(self.wd), "accum_steps": self._accum_steps, "micro_step": self._micro}
+        sc = {"version": self.STATE_VERSION, "precision": self._precision(), "steps": int(self._steps), "lr": float(self.lr),
+              "max_norm": float(self.max_norm), "betas": (float(self.betas[0]), float(self.betas[1])), "eps": float(self.eps),
+              "weight_decay": float(self.wd), "accum_steps": self._accum_steps, "micro_step": self._micro}
+        if self.ema_decay is not None:   # (a trainer without the average writes the keys it always wrote, and no others)
+            sc["ema_decay"], sc["ema_warmup"] = self.ema_decay, self.ema_warmup
+        return sc
 
     def _live_buffers(self, params=False):
         """the device buffers a saved state is made of (None: this trainer has no such buffer)"""
         open_cycle = self._micro > 0 and self.acc is not None
         bufs = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "state": self.state, "acc": self.acc if open_cycle else None,
-                "stats": self._stats if self.monitor else None, "qtab": None, "qstate": None}
+                "stats": self._stats if self.monitor else None, "qtab": None, "qstate": None, "ema": self.ema, "ema_info": self._ema_info}
         if params:
             bufs["flat_p"] = self.flat_p
         if self.fp8:
@@ -930,6 +1051,9 @@ class FlatTrainer:
         sd["fp8"] = None
         if qrows is not None:
             sd["fp8"] = {"state": host["qstate"].clone(), "rows": {n: host["qtab"][r].clone() for n, r in qrows}}
+        if host.get("ema") is not None:
+            sd["ema"] = {name: self._logical(host["ema"], i).clone(memory_format=torch.contiguous_format) for i, name in enumerate(names)}
+            sd["ema_info"] = host["ema_info"].clone()
         if host.get("flat_p") is not None:
             sd["parameters"] = {name: self._logical(host["flat_p"], i).clone(memory_format=torch.contiguous_format) for i, name in enumerate(names)}
         return sd
@@ -947,15 +1071,18 @@ class FlatTrainer:
         parameter's logical shape, contiguous (NCHW for the conv weights the flat buffers hold channels-last), without padding, for the
         parameters that receive gradients; "state_bits": the four floats of `state` as int32; "steps", "lr", "max_norm", "betas", "eps",
         "weight_decay", "accum_steps", "micro_step", "precision", "version"; "monitor": the nine doubles of a monitored trainer or None;
-        "fp8": {"state", "rows": {"<parameter name>|<role>": the record's 8 floats}} or None.  SYNCHRONISES: one device -> host copy per
+        "fp8": {"state", "rows": {"<parameter name>|<role>": the record's 8 floats}} or None; with ema_decay also "ema": {parameter name: the
+        average, in logical shape like the moments}, "ema_info": adnm_ema_update's two floats, "ema_decay", "ema_warmup" (a trainer
+        without the average writes none of the four).  SYNCHRONISES: one device -> host copy per
         flat buffer (snapshot() is the form that does not stall the step).  fp8: NotImplementedError when a record of the table cannot
         be named by one of the model's parameters."""
         self._require_state("state_dict")
+        self._not_under_ema("state_dict")
         qrows = self._quant_rows() if self.fp8 else None
         host = {k: (None if v is None else v.detach().to("cpu", copy=True)) for k, v in self._live_buffers().items()}
         return self._pack_state(host, self._scalars(), qrows)
 
-    def _check_state(self, sd, strict):
+    def _check_state(self, sd, strict, ema=True):
         if not isinstance(sd, dict) or sd.get("version") != self.STATE_VERSION or "params" not in sd:
             raise RuntimeError(f"FlatTrainer.load_state_dict: not a trainer state of format version {self.STATE_VERSION} "
                                f"(version: {sd.get('version') if isinstance(sd, dict) else type(sd).__name__!r})")
@@ -964,6 +1091,8 @@ class FlatTrainer:
                                f"at {self._precision()!r}")
         if strict:
             mine = {"betas": (float(self.betas[0]), float(self.betas[1])), "eps": float(self.eps), "weight_decay": float(self.wd)}
+            if ema and self.ema_decay is not None and "ema" in sd:
+                mine.update(ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
             bad = [f"{k}: saved {tuple(sd[k]) if k == 'betas' else sd[k]!r}, trainer {v!r}" for k, v in mine.items()
                    if (tuple(sd[k]) if k == "betas" else sd[k]) != v]
             if bad:
@@ -977,6 +1106,21 @@ class FlatTrainer:
         if unknown:
             raise RuntimeError(f"FlatTrainer.load_state_dict: {len(unknown)} names of the state are no parameters of the model, e.g. {unknown[:3]}")
         self._check_shapes(sd, shapes)
+        if not ema:
+            return
+        if strict and self.ema_decay is not None and "ema" not in sd:
+            raise RuntimeError("FlatTrainer.load_state_dict: this trainer keeps an average of the weights (ema_decay), the state holds no 'ema'; "
+                               "strict=False loads the rest and starts the average anew from the loaded parameters")
+        if strict and self.ema_decay is None and "ema" in sd:
+            raise RuntimeError("FlatTrainer.load_state_dict: the state holds an average of the weights ('ema'), this trainer was built without "
+                               "ema_decay; strict=False ignores it")
+        if self.ema_decay is not None and "ema" in sd:
+            unknown = sorted(set(sd["ema"]) - set(shapes))
+            if unknown:
+                raise RuntimeError(f"FlatTrainer.load_state_dict: {len(unknown)} names of the state's 'ema' are no parameters of the model, e.g. {unknown[:3]}")
+            for n, t in sd["ema"].items():
+                if tuple(t.shape) != shapes[n]:
+                    raise RuntimeError(f"FlatTrainer.load_state_dict: ema of {n} has shape {tuple(t.shape)}, the parameter {shapes[n]}")
 
     @staticmethod
     def _check_shapes(sd, shapes):
@@ -993,6 +1137,9 @@ class FlatTrainer:
         """Take over a state_dict(): moments, `state`, step count, lr and max_norm (they reach the tail graph's device copy with the next
         step), an open accumulation cycle, the monitor block, the fp8 table's rows.  IN PLACE, on the current stream: no buffer moves, so
         the captured graphs of a prepared trainer stay valid.  Any flat layout loads any other: the parameter name is the only key.
+        The average of the weights: a state without 'ema' into a trainer with ema_decay raises (strict=False: the average starts anew as a
+        copy of the parameters as they are when the state is applied, its counters zero); a state with 'ema' into a trainer without
+        raises (strict=False: ignored); another ema_decay / ema_warmup counts as differing hyper-parameters.
         Raises on another set of names or another shape, on other betas / eps / weight_decay (strict=False: the trainer keeps its own),
         on another accum_steps while the saved cycle is open, on another precision, and in fp8 on a record that one side lacks.  The
         parameters themselves are model.state_dict()'s business: load them FIRST (checkpoint.load_training_state does both).
@@ -1000,21 +1147,23 @@ class FlatTrainer:
         when the layout is made; fp8 rows after prepare()'s calibration has created them."""
         self._load(sd, strict)
 
-    def _load(self, sd, strict=True, quant=True):
+    def _load(self, sd, strict=True, quant=True, ema=True):
+        """ema=False (checkpoint.from_torch_adamw_state): the state has no say about the average; it stays as it is"""
+        self._not_under_ema("load_state_dict")
         if self.used is not None and self.flat_p.is_cuda and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("FlatTrainer.load_state_dict: not inside a hipGraph capture")
-        self._check_state(sd, strict)
+        self._check_state(sd, strict, ema)
         if self.used is None:
             self._take_scalars(sd)
-            self._pending, self._pending_quant = sd, (sd.get("fp8") if quant else None)
+            self._pending, self._pending_quant, self._pending_ema = sd, (sd.get("fp8") if quant else None), ema
             return
-        self._apply_state(sd, quant=quant)
+        self._apply_state(sd, quant=quant, ema=ema)
 
     def _take_scalars(self, sd):
         self._steps, self._micro = int(sd["steps"]), int(sd["micro_step"])
         self.lr, self.max_norm = float(sd["lr"]), float(sd["max_norm"])
 
-    def _apply_state(self, sd, quant=True):
+    def _apply_state(self, sd, quant=True, ema=True):
         names = self._used_names()
         missing, unexpected = sorted(set(names) - set(sd["params"])), sorted(set(sd["params"]) - set(names))
         if missing or unexpected:
@@ -1025,17 +1174,30 @@ class FlatTrainer:
             rows = self._match_quant(sd.get("fp8"))   # (raises before anything is written)
         open_cycle = sd["micro_step"] > 0
 
+        with_ema = ema and self.ema is not None and "ema" in sd
+        if with_ema:
+            missing, unexpected = sorted(set(names) - set(sd["ema"])), sorted(set(sd["ema"]) - set(names))
+            if missing or unexpected:
+                raise RuntimeError(f"FlatTrainer.load_state_dict: the state's 'ema' does not match the parameters this trainer updates: "
+                                   f"{len(missing)} missing (e.g. {missing[:3]}), {len(unexpected)} unexpected (e.g. {unexpected[:3]})")
+
         def put(buf, key):
             # one host image of the whole flat buffer (padding zero, as the buffers are born), then ONE copy into the buffer where it is
             host = torch.zeros(self.n, dtype=buf.dtype)
             for i, name in enumerate(names):
-                self._logical(host, i).copy_(sd["params"][name][key])
+                self._logical(host, i).copy_(sd["ema"][name] if key == "ema" else sd["params"][name][key])
             buf.copy_(host)
         put(self.exp_avg, "exp_avg")
         put(self.exp_avg_sq, "exp_avg_sq")
         if open_cycle:
             put(self._accumulator(), "acc")
         self.state.copy_(sd["state_bits"].view(torch.float32))
+        if with_ema:
+            put(self.ema, "ema")
+            self._ema_info.copy_(sd["ema_info"])
+        elif ema and self.ema is not None:   # (strict=False, a state without the average: anew from the parameters as they are)
+            self.ema.copy_(self.flat_p)
+            self._ema_info.zero_()
         if self.monitor and sd.get("monitor") is not None:
             self._stats_block().copy_(sd["monitor"])
         self._take_scalars(sd)
@@ -1072,11 +1234,13 @@ class FlatTrainer:
     @torch.no_grad()
     def snapshot(self):
         """A consistent copy of the training state WITHOUT stalling the step: device-to-device copies of flat_p, exp_avg, exp_avg_sq,
-        state (and acc, the monitor block, the fp8 table where they exist) into buffers the snapshot owns, enqueued on the current stream
+        state (and acc, the monitor block, the fp8 table, the average of the weights where they exist) into buffers the snapshot owns, enqueued on the current stream
         behind the steps issued so far, then an event; returns at once.  Call it between steps, outside any capture; read it later with
         TrainerSnapshot.state_dict().  Costs one more copy of the optimiser-sized buffers in device memory while the snapshot lives
-        (3 x 4 bytes per parameter: ~0.9 GB for the 72 M parameters of ADNM-UNet); nothing is allocated before the first call."""
+        (3 x 4 bytes per parameter: ~0.9 GB for the 72 M parameters of ADNM-UNet; 4 x 4 with ema_decay); nothing is allocated before the
+        first call."""
         self._require_state("snapshot")
+        self._not_under_ema("snapshot")
         return TrainerSnapshot(self)
 
 

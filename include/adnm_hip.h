@@ -706,6 +706,21 @@ int adnm_cast_bf16_f32(const void* src, void* dst, int64_t n, float scale, adnm_
 int adnm_grad_accum(float* acc, const float* g, int64_t n, int first, adnm_stream_t stream);
 int adnm_grad_accum_final(const float* acc, float* g, void* wire_bf16, int64_t n, float scale, adnm_stream_t stream);
 
+/* Exponential moving average of the parameters (FlatTrainer(ema_decay=...)): a second flat fp32 buffer laid out like p.  Streaming
+ * passes: p, ema 16-byte aligned and disjoint, n > 0, n % 4 == 0; checked on entry.  <= 2048 workgroups of 256 lanes, two 16-byte quads
+ * per lane and trip, the rest by grid stride.
+ *   adnm_ema_update, behind the optimiser pass of the same step:  t = state[0] (adnm_adamw_step's step counter, after that pass),
+ *       d = warmup ? min(decay, (1 + t) / (10 + t)) : decay,  w = 1.0f - d,  ema[i] = fmaf(d, ema[i], w * p[i])   (two roundings;
+ *       12 B/element).  d is formed on the device, so a captured launch follows the counter.  decay in [0, 1]: 0 leaves ema == p,
+ *       1 leaves ema as it was.  info[0] = the d this call used, info[1] += 1 (updates applied); two device floats, 4-byte aligned.
+ *       stats: the statistics block of adnm_step_guard (8-byte aligned) or NULL; with its skip flag set every workgroup returns after
+ *       one uniform load and neither ema nor info is written (adnm_adamw_step_guarded's rule).
+ *   adnm_ema_swap: p and ema exchange their contents, bit pattern for bit pattern, in one pass without a temporary buffer
+ *       (16 B/element); twice is the identity. */
+int adnm_ema_update(const float* p, float* ema, int64_t n, const float* state, float decay, int warmup, float* info, const void* stats,
+                    adnm_stream_t stream);
+int adnm_ema_swap(float* p, float* ema, int64_t n, adnm_stream_t stream);
+
 /* ---------------------------------------------------------------- tall-skinny fp32 GEMMs on MFMA (K6)
  * The Linear / 1x1 projections of the full-resolution stages (ADNssd.py:309,461; model_untils.py:64,67,193,196,831;
  * ADNMUNet.py:634): M = B*H*W tokens, K,N <= 256.  v_mfma_f32_16x16x4_f32: exact fp32 (an fmaf chain).
