@@ -3240,6 +3240,72 @@ def attn4(qkv, heads, scale):
     return Attn4Fn.apply(qkv, heads, scale)
 
 
+# ======================================================================================= pooled contingency counts (csrc/dataio.hip: valid_pool_accum)
+MAX_POOLS, MAX_POOL_WINDOW = 4, 32
+
+
+def pool_pairs(pools):
+    """a sequence of ints p (= (p, p)) or (size, stride) pairs -> a tuple of (size, stride) int pairs, checked against
+    adnm_valid_pool_accum's limits that do not depend on the frame: 1 <= stride <= size <= 32, at most 4 pools, none twice.  None -> ()."""
+    if pools is None:
+        return ()
+
+    def whole(v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"pools: sizes and strides are integers, got {v!r}")
+        return int(v)
+    out = []
+    for p in pools:
+        if isinstance(p, (tuple, list)):
+            if len(p) != 2:
+                raise ValueError(f"pools: a pool is an integer or a (size, stride) pair, got {p!r}")
+            s, d = whole(p[0]), whole(p[1])
+        else:
+            s = d = whole(p)
+        if not 1 <= d <= s <= MAX_POOL_WINDOW:
+            raise ValueError(f"pools: a pool needs 1 <= stride <= size <= {MAX_POOL_WINDOW}, got size {s} stride {d}")
+        if (s, d) in out:
+            raise ValueError(f"pools: pool {(s, d)} is given twice")
+        out.append((s, d))
+    if len(out) > MAX_POOLS:
+        raise ValueError(f"pools: at most {MAX_POOLS} pools, got {len(out)}")
+    return tuple(out)
+
+
+def pool_table(pairs):
+    """(size, stride) pairs -> the host int64 array adnm_valid_pool_accum reads"""
+    return lib.i64_table([v for p in pairs for v in p])
+
+
+def pool_counts(truth, pred, thresholds, value_scale, pools):
+    """truth / pred: fp32 GPU tensors (..., H, W) of the same shape -> (frames, npool, 4 * nthr) float64 on the device: per frame and
+    pool (an int p = (p, p), or (size, stride): the windows of max_pool2d(kernel_size=size, stride=stride)) TP, FN, FP, TN per threshold,
+    counted per window on the fields quantised as adnm_eval_counts quantises them.  The one-shot use of adnm_valid_pool_accum (T = frames)."""
+    if not (torch.is_tensor(truth) and torch.is_tensor(pred)):
+        raise RuntimeError("pool_counts: needs GPU tensors")
+    _need_gpu(truth)
+    _need_gpu(pred)
+    if truth.dtype != torch.float32 or pred.dtype != torch.float32 or truth.shape != pred.shape or truth.dim() < 2 or truth.device != pred.device:
+        _unsupported("pool_counts", f"takes two fp32 tensors (..., H, W) of one shape, got {truth.dtype} {tuple(truth.shape)} and {pred.dtype} {tuple(pred.shape)}")
+    pairs = pool_pairs(pools)
+    thr = [float(t) for t in thresholds]
+    if not pairs or not 1 <= len(thr) <= 8:
+        raise ValueError("pool_counts: 1..4 pools and 1..8 thresholds")
+    H, W = truth.shape[-2:]
+    t, p = truth.contiguous(), pred.contiguous()
+    frames = t.numel() // (H * W) if H * W else 0
+    tab = pool_table(pairs)
+    nb = lib.query("adnm_valid_pool_accum_ws_bytes", frames, frames, H, W, len(thr), tab, len(pairs))
+    if nb < 0:
+        raise RuntimeError(f"pool_counts: {frames} frames of {H} x {W} with pools {pairs} are outside adnm_valid_pool_accum's limits "
+                           "(1 <= frames <= 65535, H*W < 2^24, no window larger than the frame)")
+    out = torch.zeros((frames, len(pairs), 4 * len(thr)), dtype=torch.float64, device=t.device)
+    ws = torch.empty(int(nb), dtype=torch.uint8, device=t.device)
+    lib.call("adnm_valid_pool_accum", p.data_ptr(), H * W, H * W, t.data_ptr(), out.data_ptr(), (ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale),
+             tab, len(pairs), ws.data_ptr(), int(nb), frames, frames, H, W, _stream())
+    return out
+
+
 # ======================================================================================= the output side (csrc/dataio.hip: forecast_render)
 def edges_up_f32(edges):
     """double edges -> float32, each rounded UP to the smallest float >= it: the kernel compares an fp32 value with fp32 edges where

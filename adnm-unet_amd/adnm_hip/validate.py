@@ -13,6 +13,11 @@ target) and valid_ssim_accum, both ADDING into one block of doubles that lives o
 include/adnm_hip.h, adnm_valid_accum).  done() reads that block — summed over the ranks of `process_group` with one all-reduce —
 and aggregates it exactly as GpuEvaluator.done() does.
 
+Validator(..., pools=(4, 16, (16, 8)), persistence=True) adds neighbourhood scores and the persistence baseline:
+csrc/dataio.hip::valid_pool_accum counts TP / FN / FP / TN per window of a spatial max-pool, for the forecast and for the last input
+frame held over the horizon, into tables that follow the block in the same allocation; done(per_lead=True) adds every score per frame
+index, from the rows the block always kept.  The defaults allocate and launch nothing new.
+
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
@@ -39,13 +44,48 @@ def reduce_block(block, process_group=None):
     return block
 
 
-def aggregate(block, thresholds, seq_len, hw, ssim_area):
-    """host: the block (a float64 array of HEADER + T * (4*nthr + 3) values) -> the dictionary of Validator.done().  The metrics are
-    SimplifiedEvaluator.done's (Shanghai_metrics.py:218-290) as GpuEvaluator.done() states them, from per-frame-index sums."""
+def baseline_pools(pools):
+    """the pools the persistence baseline is scored at: point-wise first, then every pool of the forecast"""
+    return ((1, 1),) + tuple(p for p in pools if p != (1, 1))
+
+
+def block_doubles(seq_len, nthr, pools=(), persistence=False):
+    """-> (doubles of the main block, of the forecast's pooled table, of the baseline's): the three parts of the ONE allocation, in order"""
+    cell = seq_len * 4 * nthr
+    return HEADER + seq_len * (4 * nthr + 3), cell * len(pools), cell * len(baseline_pools(pools)) if persistence else 0
+
+
+def _scores(counts, thresholds):
+    """(4 * nthr) counts summed over the horizon -> the two entries every scored field has"""
+    metrics, all_far = contingency_metrics(counts, thresholds)
+    return {"threshold_metrics": metrics, "FAR": float(np.mean(all_far))}
+
+
+def _lead_scores(rows, thresholds):
+    """(T, 4 * nthr) counts per frame index -> {thr: {TP, TN, FP, FN, CSI, POD, HSS, FAR}}, each a length-T array: contingency_metrics'
+    formulas applied to the rows (its sums[4k:4k+4] are then four length-T arrays)"""
+    metrics, all_far = contingency_metrics(rows.T, thresholds)
+    for m, far in zip(metrics.values(), all_far):
+        m["FAR"] = far
+    return metrics
+
+
+def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False):
+    """host: the block (a float64 array of HEADER + T * (4*nthr + 3) values; with `pools` (size, stride) pairs then the forecast's pooled
+    table (T, npool, 4*nthr), with `persistence` then the baseline's (T, len(baseline_pools(pools)), 4*nthr): include/adnm_hip.h) -> the
+    dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's (Shanghai_metrics.py:218-290) as GpuEvaluator.done()
+    states them, from per-frame-index sums; "pooled", "persistence" and "per_lead" apply the same formulas to the pooled tables, the
+    baseline's tables and the single rows."""
     nthr, T = len(thresholds), seq_len
+    pools = tuple(pools)
+    base = baseline_pools(pools) if persistence else ()
+    n0, n1, n2 = block_doubles(T, nthr, pools, persistence)
     blk = np.asarray(block, dtype=np.float64)
+    if blk.shape != (n0 + n1 + n2,):
+        raise ValueError(f"aggregate: a block of {n0 + n1 + n2} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
+                         f"persistence {bool(persistence)}; got {blk.shape}")
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
-    tab = blk[HEADER:].reshape(T, 4 * nthr + 3)
+    tab = blk[HEADER:n0].reshape(T, 4 * nthr + 3)
     metrics, all_far = contingency_metrics(tab[:, :4 * nthr].sum(axis=0), thresholds)
     with np.errstate(divide="ignore", invalid="ignore"):
         mse_t = tab[:, 4 * nthr + 1] / (hw * samples)            # per frame index: the mean over the samples of the frame's MSE
@@ -53,13 +93,32 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area):
         mae = float(tab[:, 4 * nthr].sum() / (hw * samples * T))
         ssim = None if ssim_area is None else float(tab[:, 4 * nthr + 2].sum() / (ssim_area * samples * T))
         finite = batches - nonfinite
-    return {"threshold_metrics": metrics, "FAR": float(np.mean(all_far)), "RMSE": rmse, "MAE": mae, "MSE": float(mse_t.mean()), "SSIM": ssim,
-            "LPIPS": None, "loss_sum": loss_sum, "loss_mean": loss_sum / finite if finite > 0 else float("nan"), "batches": int(batches),
-            "samples": int(samples), "nonfinite": int(nonfinite)}
+    res = {"threshold_metrics": metrics, "FAR": float(np.mean(all_far)), "RMSE": rmse, "MAE": mae, "MSE": float(mse_t.mean()), "SSIM": ssim,
+           "LPIPS": None, "loss_sum": loss_sum, "loss_mean": loss_sum / finite if finite > 0 else float("nan"), "batches": int(batches),
+           "samples": int(samples), "nonfinite": int(nonfinite)}
+    ftab = blk[n0:n0 + n1].reshape(T, len(pools), 4 * nthr)
+    btab = blk[n0 + n1:].reshape(T, len(base), 4 * nthr)
+    if pools:
+        res["pooled"] = {p: _scores(ftab[:, i].sum(axis=0), thresholds) for i, p in enumerate(pools)}
+    if persistence:
+        res["persistence"] = dict(_scores(btab[:, 0].sum(axis=0), thresholds),
+                                  pooled={p: _scores(btab[:, base.index(p)].sum(axis=0), thresholds) for p in pools})
+    if per_lead:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lead = {"RMSE": np.sqrt(mse_t), "MAE": tab[:, 4 * nthr] / (hw * samples),
+                    "SSIM": None if ssim_area is None else tab[:, 4 * nthr + 2] / (ssim_area * samples),
+                    "threshold_metrics": _lead_scores(tab[:, :4 * nthr], thresholds)}
+        if pools:
+            lead["pooled"] = {p: {"threshold_metrics": _lead_scores(ftab[:, i], thresholds)} for i, p in enumerate(pools)}
+        if persistence:
+            lead["persistence"] = {"threshold_metrics": _lead_scores(btab[:, 0], thresholds),
+                                   "pooled": {p: {"threshold_metrics": _lead_scores(btab[:, base.index(p)], thresholds)} for p in pools}}
+        res["per_lead"] = lead
+    return res
 
 
 class Validator(ForwardClient):
-    def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None):
+    def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -71,6 +130,12 @@ class Validator(ForwardClient):
         if self.seq_len < 1:
             raise ValueError("seq_len >= 1")
         self.ssim, self.process_group = bool(ssim), process_group
+        self.pools, self.persistence = ops.pool_pairs(pools), bool(persistence)   # (size, stride) pairs; ValueError on a bad entry
+        # the pooled passes: (key of the input in _launch, its pools), the forecast's first — their tables follow the main block in this order
+        self._passes = ([("pred", self.pools)] if self.pools else []) + ([("last", baseline_pools(self.pools))] if self.persistence else [])
+        if self.persistence and len(baseline_pools(self.pools)) > ops.MAX_POOLS:
+            raise ValueError(f"Validator: the persistence baseline is scored at (1, 1) and at every pool, which makes {len(self.pools) + 1} pools; "
+                             f"a pass takes {ops.MAX_POOLS} (give (1, 1) among the pools, or one pool fewer)")
         self._thr = (ctypes.c_float * len(self.thresholds))(*self.thresholds)
         self._fwd = GraphedForward(model, client=self, keep_quant=True)
         self._block = self._last = None    # the epoch's accumulator block and the last batch's fp32 loss: they outlive the graphs
@@ -78,15 +143,18 @@ class Validator(ForwardClient):
 
     # ---- device state
     def _block_for(self, device):
+        """ONE allocation: adnm_valid_accum's block, then the pooled tables (none by default); done() reduces it with one all-reduce"""
         if self._block is None:
             n = lib.query("adnm_valid_block_bytes", self.seq_len, len(self.thresholds))
-            self._block = torch.zeros(n // 8, dtype=torch.float64, device=device)
+            parts = block_doubles(self.seq_len, len(self.thresholds), self.pools, self.persistence)
+            assert n == 8 * parts[0]
+            self._block = torch.zeros(sum(parts), dtype=torch.float64, device=device)
             self._last = torch.zeros((), dtype=torch.float32, device=device)
         elif self._block.device != device:
             raise RuntimeError(f"Validator: one device per Validator (the block is on {self._block.device}, the batch on {device})")
         return self._block
 
-    def _launch(self, ent, pred, block, loss_out):
+    def _launch(self, ent, sx, pred, block, loss_out):
         B, T, H, W = ent["shape"]
         nthr, stream = len(self.thresholds), torch.cuda.current_stream().cuda_stream
         lib.call("adnm_valid_accum", pred.data_ptr(), ent["tgt"].data_ptr(), block.data_ptr(), loss_out.data_ptr(), self._thr, nthr, self.value_scale,
@@ -94,6 +162,16 @@ class Validator(ForwardClient):
         if ent["ws_ssim"] is not None:
             lib.call("adnm_valid_ssim_accum", pred.data_ptr(), ent["tgt"].data_ptr(), block.data_ptr(), nthr, self.value_scale, ent["ws_ssim"].data_ptr(),
                      ent["ws_ssim"].numel(), B * T, T, H, W, stream)
+        table = block.data_ptr() + 8 * block_doubles(T, nthr)[0]
+        for what, pools in self._passes:
+            if what == "pred":     # the forecast, contiguous
+                src, strides = pred.data_ptr(), (T * H * W, H * W)
+            else:                  # persistence: the last input frame of the sample, for every frame index
+                t_in = sx.shape[1]
+                src, strides = sx.data_ptr() + 4 * (t_in - 1) * H * W, (t_in * H * W, 0)
+            lib.call("adnm_valid_pool_accum", src, strides[0], strides[1], ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
+                     ops.pool_table(pools), len(pools), ent["ws_pool"].data_ptr(), ent["ws_pool"].numel(), B * T, T, H, W, stream)
+            table += 8 * T * len(pools) * 4 * nthr
 
     # ---- ForwardClient: what GraphedForward calls with the entry of one input shape
     def open(self, ent, x):
@@ -107,10 +185,23 @@ class Validator(ForwardClient):
         ws_ssim = None
         if self.ssim and H > 10 and W > 10:   # 11 x 11 windows need a valid region; smaller frames: SSIM is None
             ws_ssim = torch.empty(max(int(lib.query("adnm_valid_ssim_accum_ws_bytes", B * T, T, H, W, nthr)), 16), dtype=torch.uint8, device=dev)
+        ws_pool = None
+        if self._passes:
+            need = [lib.query("adnm_valid_pool_accum_ws_bytes", B * T, T, H, W, nthr, ops.pool_table(pools), len(pools)) for _, pools in self._passes]
+            if min(need) < 0:
+                raise RuntimeError(f"Validator: pools {self.pools} on {B * T} frames of {H} x {W} are outside adnm_valid_pool_accum's limits "
+                                   "(no window larger than the frame, H and W < 32768)")
+            ws_pool = torch.empty(max(need), dtype=torch.uint8, device=dev)   # the passes follow one another on one stream: one workspace
+        if self.persistence:
+            sx = ent["sx"]
+            if (sx.dtype != torch.float32 or sx.dim() not in (4, 5) or (sx.dim() == 5 and sx.shape[2] != 1) or tuple(sx.shape[-2:]) != (H, W)
+                    or sx.shape[1] < 1 or not sx.is_contiguous()):
+                raise RuntimeError(f"Validator: persistence needs the model's input as contiguous fp32 (B, T_in, 1, H, W) or (B, T_in, H, W) with the "
+                                   f"target's {H} x {W} frames, got {sx.dtype} {tuple(sx.shape)}")
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=torch.empty(max(int(nb), 16), dtype=torch.uint8, device=dev),
-                   ws_ssim=ws_ssim, loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
+                   ws_ssim=ws_ssim, ws_pool=ws_pool, loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
-        self._launch(ent, ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
+        self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
 
     def check(self, ent, out):
         B, T, H, W = ent["shape"]
@@ -119,7 +210,7 @@ class Validator(ForwardClient):
 
     def after(self, ent, sx, out):
         ent["pred"] = out.contiguous()   # (the model emits it contiguous; a copy made here belongs to the graph's pool and is kept with it)
-        self._launch(ent, ent["pred"], self._block, self._last)
+        self._launch(ent, sx, ent["pred"], self._block, self._last)
 
     # ---- the public surface
     def step(self, x, tgt):
@@ -170,17 +261,21 @@ class Validator(ForwardClient):
         """the fp32 loss of the last batch: a 0-dim device tensor (reading it synchronises; the epoch's sum is in done())"""
         return self._last
 
-    def done(self, reset=False):
+    def done(self, reset=False, per_lead=False):
         """-> what GpuEvaluator.done() returns (the same keys, the same aggregation; SSIM None when ssim=False or the frames are too small
         for the window) plus "loss_sum" (what train.py:163 / :201 accumulate and compare against `best`), "loss_mean" (over the finite
-        batches), "batches", "samples", "nonfinite".  With a process_group the blocks of all ranks are summed first.  The one host read."""
+        batches), "batches", "samples", "nonfinite".  With a process_group the blocks of all ranks are summed first.  The one host read.
+        pools: plus "pooled": {(size, stride): {"threshold_metrics", "FAR"}}, the same scores counted per max-pool window.
+        persistence: plus "persistence": {"threshold_metrics", "FAR", "pooled": {...}}, the last input frame held for every frame index,
+        scored on the same batches.  per_lead=True: plus "per_lead": length-T arrays "RMSE", "MAE", "SSIM" (or None) and
+        "threshold_metrics"[thr][TP | FN | FP | TN | CSI | POD | FAR | HSS], and the same under "pooled" / "persistence" where those exist."""
         if self._block is None or self._frame is None:
             raise RuntimeError("Validator.done: no batch since the last reset")
         blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
         host = blk.cpu().numpy()   # the one device -> host read
         H, W = self._frame
         area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
-        res = aggregate(host, self.thresholds, self.seq_len, H * W, area)
+        res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead)
         if reset:
             self.reset()
         return res

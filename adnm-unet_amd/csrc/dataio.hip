@@ -43,6 +43,11 @@ struct Thr {
   int n;
 };
 
+// The quantisation of a field value, stated ONCE for every kernel that counts events (EvalAcc::add and pool_bits below):
+// q(v) = floorf(fminf(fmaxf(v, 0), 1) * value_scale) in fp32 (Shanghai_metrics.py:45-47).  NaN -> 0 (fmaxf), -Inf -> 0, +Inf -> floor(scale).
+__device__ __forceinline__ float eval_scaled(float v, float value_scale) { return fminf(fmaxf(v, 0.f), 1.f) * value_scale; }
+__device__ __forceinline__ float eval_trunc(float scaled) { return floorf(scaled); }   // .astype(np.uint16) of a non-negative float: truncation
+
 // One lane's share of a frame's contingency counts and error sums, and the workgroup's fold of it: the arithmetic of eval_counts, stated
 // ONCE for eval_counts_kernel and valid_accum_kernel (the validation epoch's accumulating pass) so that their counts cannot drift apart.
 struct EvalAcc {
@@ -54,12 +59,11 @@ struct EvalAcc {
   }
   // clip to [0,1], scale, truncate, compare (Shanghai_metrics.py:45-47,103-120)
   __device__ __forceinline__ void add(float tv, float pv, float value_scale, const Thr& thr) {
-    const float tc = fminf(fmaxf(tv, 0.f), 1.f), pc = fminf(fmaxf(pv, 0.f), 1.f);
-    const float ts = tc * value_scale, ps = pc * value_scale;
+    const float ts = eval_scaled(tv, value_scale), ps = eval_scaled(pv, value_scale);
     const float d = ps - ts;
     sa += fabsf(d);
     sq = fmaf(d, d, sq);
-    const float ti = floorf(ts), pi = floorf(ps);   // .astype(np.uint16) of a non-negative float: truncation
+    const float ti = eval_trunc(ts), pi = eval_trunc(ps);
 #pragma unroll
     for (int k = 0; k < kMaxThr; ++k)
       if (k < thr.n) {
@@ -478,6 +482,221 @@ extern "C" int adnm_valid_ssim_accum(const float* pred, const float* target, voi
     valid_ssim_fold_kernel<<<1, kFoldBlock, 0, st>>>((const float*)ws, tx * ty, (int)frames, (int)T, (int)nthr, (double*)block);
   }
   ADNM_CHECK_LAUNCH("valid_ssim_fold");
+  return ADNM_OK;
+}
+
+// ---- neighbourhood (pooled) contingency counts (include/adnm_hip.h: adnm_valid_pool_accum) ----
+// A window of a pool (s, d) is an event at threshold k iff ANY pixel of it has q >= thr_k (thresholding commutes with the max), so a
+// pixel's whole state is one byte per field (bit k = q >= thr_k) and max-pooling is a windowed OR.  A workgroup owns the windows whose
+// top-left pixel lies in its 32 x 32 tile of one frame.  It stages the tile and the halo its windows reach into ONCE, as 2 bytes per
+// pixel in LDS (low byte target, high byte forecast), and serves every pool and every threshold from that image: OR along rows, then
+// along columns, then per bit the number of windows with the target bit, the forecast bit and both.  Those are wave ballots summed in
+// scalar registers: integers throughout.  part[frame][tile][pool][3*nthr] uint32; the fold turns (obs, sim, both) into TP, FN, FP, TN.
+namespace {
+constexpr int kPoolMax = 4, kPoolWin = 32, kPoolTile = 32;
+constexpr int kPoolSide = kPoolTile + kPoolWin;   // staged rows / columns at most: a window reaches at most s - 1 <= 31 past the tile
+constexpr int kPoolPitch = kPoolSide + 4;         // uint16 per staged row: 136 bytes, so that a row start stays 8-byte aligned
+struct Pools {
+  int s[kPoolMax], d[kPoolMax], n;
+};
+
+__device__ __forceinline__ uint32_t pool_bits(float tv, float pv, float value_scale, const Thr& thr) {
+  const float ti = eval_trunc(eval_scaled(tv, value_scale)), pi = eval_trunc(eval_scaled(pv, value_scale));
+  uint32_t m = 0;
+#pragma unroll
+  for (int k = 0; k < kMaxThr; ++k)
+    if (k < thr.n) m |= (ti >= thr.t[k] ? 1u << k : 0u) | (pi >= thr.t[k] ? 0x100u << k : 0u);
+  return m;
+}
+
+// grid (tiles, frames).  Frame f of the forecast starts at pred + (f / T) * sstride + (f % T) * fstride.  ext: how far past the tile the
+// staged image goes (host: the largest s - gcd(d, 32) of the pools; VEC: rounded up to 4).  VEC: W, both strides and both bases are
+// multiples of 4 floats, so every staged row piece is a 16-byte load.
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void pool_counts_kernel(const float* __restrict__ pred, int64_t sstride, int64_t fstride, const float* __restrict__ tgt,
+                                                             uint32_t* __restrict__ part, int T, int H, int W, int tiles_x, int ext, float value_scale,
+                                                             Thr thr, Pools pools) {
+  __shared__ __attribute__((aligned(8))) uint16_t img[kPoolSide][kPoolPitch];
+  __shared__ uint16_t rowor[kPoolSide][kPoolTile + 1];
+  __shared__ uint32_t red[kBlock / 64][3 * kMaxThr];
+  const int f = blockIdx.y, tile = blockIdx.x, oy = (tile / tiles_x) * kPoolTile, ox = (tile % tiles_x) * kPoolTile;
+  const int rh = min(kPoolTile + ext, H - oy), rw = min(kPoolTile + ext, W - ox);
+  const float* tp = tgt + (int64_t)f * H * W + (int64_t)oy * W + ox;
+  const float* pp = pred + (int64_t)(f / T) * sstride + (int64_t)(f % T) * fstride + (int64_t)oy * W + ox;
+  if (VEC) {
+    const int q = rw >> 2;   // rw is a multiple of 4: W, ox and 32 + ext are
+    for (int i = threadIdx.x; i < rh * q; i += kBlock) {
+      const int r = i / q, c = (i % q) * 4;
+      const float4 a = *(const float4*)(tp + (int64_t)r * W + c), b = *(const float4*)(pp + (int64_t)r * W + c);
+      const uint32_t m0 = pool_bits(a.x, b.x, value_scale, thr), m1 = pool_bits(a.y, b.y, value_scale, thr);
+      const uint32_t m2 = pool_bits(a.z, b.z, value_scale, thr), m3 = pool_bits(a.w, b.w, value_scale, thr);
+      *(uint2*)&img[r][c] = make_uint2(m0 | (m1 << 16), m2 | (m3 << 16));
+    }
+  } else {
+    for (int i = threadIdx.x; i < rh * rw; i += kBlock) {
+      const int r = i / rw, c = i % rw;
+      img[r][c] = (uint16_t)pool_bits(tp[(int64_t)r * W + c], pp[(int64_t)r * W + c], value_scale, thr);
+    }
+  }
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nout = 3 * thr.n;
+  for (int p = 0; p < pools.n; ++p) {
+    const int s = pools.s[p], d = pools.d[p];
+    // the windows anchored in this tile: indices [j0, j0 + na) along each axis, the first one at offset c0 from the tile's origin
+    const int jx0 = (ox + d - 1) / d, jy0 = (oy + d - 1) / d;
+    const int nax = max(0, min((W - s) / d + 1, (ox + kPoolTile + d - 1) / d) - jx0), nay = max(0, min((H - s) / d + 1, (oy + kPoolTile + d - 1) / d) - jy0);
+    const int cx0 = jx0 * d - ox, cy0 = jy0 * d - oy;
+    for (int i = threadIdx.x; i < rh * nax; i += kBlock) {
+      const int r = i / nax, j = i % nax;
+      const uint16_t* src = &img[r][cx0 + j * d];   // cx0 + j*d + s <= min(W - ox, 32 + ext) = rw
+      uint32_t m = 0;
+      for (int u = 0; u < s; ++u) m |= src[u];
+      rowor[r][j] = (uint16_t)m;
+    }
+    __syncthreads();
+    uint32_t cnt[3 * kMaxThr];   // wave-uniform: windows with the target bit k, the forecast bit k, both
+#pragma unroll
+    for (int k = 0; k < 3 * kMaxThr; ++k) cnt[k] = 0;
+    const int na = nax * nay;
+    for (int i0 = 0; i0 < na; i0 += kBlock) {   // the same trips for every lane: the ballots below see whole waves
+      const int i = i0 + threadIdx.x;
+      uint32_t m = 0;
+      if (i < na) {
+        const int r0 = cy0 + (i / nax) * d, j = i % nax;   // r0 + s <= rh
+        for (int u = 0; u < s; ++u) m |= rowor[r0 + u][j];
+      }
+      const uint32_t o = m & 0xffu, sim = m >> 8, v = o | (sim << 8) | ((o & sim) << 16);
+#pragma unroll
+      for (int k = 0; k < kMaxThr; ++k)
+        if (k < thr.n) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) cnt[3 * k + c] += (uint32_t)__popcll(__ballot((v >> (8 * c + k)) & 1u));
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 3 * kMaxThr; ++k)
+        if (k < nout) red[wave][k] = cnt[k];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nout)
+      part[(((int64_t)f * gridDim.x + tile) * pools.n + p) * nout + threadIdx.x] =
+          (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    __syncthreads();   // rowor and red are rewritten by the next pool
+  }
+}
+
+// One thread per (t, pool, threshold), a fixed order (samples ascending, tiles ascending: valid_fold_kernel's), double arithmetic on
+// integers: table[t][pool][4k .. 4k+3] += TP, FN, FP, TN of the batch, TN from the number of windows of the pool.
+__global__ __launch_bounds__(kFoldBlock) void pool_fold_kernel(const uint32_t* __restrict__ part, int tiles, int frames, int T, int nthr, int H, int W,
+                                                               Pools pools, double* __restrict__ table) {
+  const int np = pools.n, B = frames / T, i = blockIdx.x * kFoldBlock + threadIdx.x;
+  if (i >= T * np * nthr) return;
+  const int k = i % nthr, p = (i / nthr) % np, t = i / (nthr * np);
+  double obs = 0.0, sim = 0.0, both = 0.0;
+  for (int b = 0; b < B; ++b)
+    for (int tile = 0; tile < tiles; ++tile) {
+      const uint32_t* q = part + ((((int64_t)b * T + t) * tiles + tile) * np + p) * (3 * nthr) + 3 * k;
+      obs += (double)q[0], sim += (double)q[1], both += (double)q[2];
+    }
+  const double windows = (double)B * (double)((H - pools.s[p]) / pools.d[p] + 1) * (double)((W - pools.s[p]) / pools.d[p] + 1);
+  double* out = table + ((int64_t)t * np + p) * (4 * nthr) + 4 * k;
+  out[0] += both;
+  out[1] += obs - both;
+  out[2] += sim - both;
+  out[3] += windows - obs - sim + both;
+}
+
+int pool_gcd(int a, int b) { return b == 0 ? a : pool_gcd(b, a % b); }
+
+// the shape limits of the pooled pass; on refusal `why` names the limit
+bool pool_shape_ok(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* pools_host, int64_t npool, const char** why) {
+  const char* w = nullptr;
+  if (!pools_host) w = "null pointer";
+  else if (npool < 1 || npool > kPoolMax) w = "1..4 pools";
+  else if (nthr < 1 || nthr > kMaxThr) w = "1..8 thresholds";
+  else if (T < 1 || frames < 1 || frames % T != 0) w = "T >= 1 must divide frames";
+  else if (frames > 65535) w = "frames <= 65535";
+  else if (H < 1 || W < 1 || H >= 32768 || W >= 32768) w = "H and W must be in [1, 32768)";
+  else if (H * W >= (1ll << 24)) w = "pixels per frame < 2^24";
+  else
+    for (int64_t p = 0; p < npool && !w; ++p) {
+      const int64_t s = pools_host[2 * p], d = pools_host[2 * p + 1];
+      if (!(1 <= d && d <= s && s <= kPoolWin)) w = "a pool needs 1 <= stride <= size <= 32";
+      else if (s > (H < W ? H : W)) w = "a pool window is larger than the frame";
+    }
+  if (why) *why = w;
+  return w == nullptr;
+}
+inline int64_t pool_tiles(int64_t H, int64_t W) { return adnm_cdiv(H, kPoolTile) * adnm_cdiv(W, kPoolTile); }
+}  // namespace
+
+extern "C" int64_t adnm_valid_pool_block_bytes(int64_t T, int64_t nthr, int64_t npool) {
+  if (T < 1 || T > 65535 || nthr < 1 || nthr > kMaxThr || npool < 1 || npool > kPoolMax) return -1;
+  return (int64_t)sizeof(double) * T * npool * 4 * nthr;
+}
+
+extern "C" int64_t adnm_valid_pool_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* pools_host, int64_t npool) {
+  if (!pool_shape_ok(frames, T, H, W, nthr, pools_host, npool, nullptr)) return -1;
+  return frames * pool_tiles(H, W) * npool * 3 * nthr * (int64_t)sizeof(uint32_t);
+}
+
+extern "C" int adnm_valid_pool_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                                     const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* pools_host, int64_t npool, void* ws,
+                                     int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream) {
+  ADNM_REQUIRE(pred && target && table && thresholds_host && pools_host, "valid_pool_accum: null pointer");
+  ADNM_REQUIRE(((uintptr_t)pred | (uintptr_t)target) % 4 == 0, "valid_pool_accum: pred and target must be 4-byte aligned");
+  ADNM_REQUIRE((uintptr_t)table % 8 == 0, "valid_pool_accum: the table must be 8-byte aligned");
+  const char* why = nullptr;
+  if (!pool_shape_ok(frames, T, H, W, nthr, pools_host, npool, &why)) {
+    adnm_set_error("valid_pool_accum: %s (got frames %lld T %lld %lld x %lld nthr %lld npool %lld)", why, (long long)frames, (long long)T, (long long)H,
+                   (long long)W, (long long)nthr, (long long)npool);
+    return ADNM_EINVAL;
+  }
+  ADNM_REQUIRE(pred_frame_stride == 0 || pred_frame_stride >= H * W, "valid_pool_accum: pred_frame_stride must be 0 or >= H*W, got %lld",
+               (long long)pred_frame_stride);
+  ADNM_REQUIRE(pred_sample_stride >= 0, "valid_pool_accum: pred_sample_stride must be >= 0, got %lld", (long long)pred_sample_stride);
+  const int64_t need = adnm_valid_pool_accum_ws_bytes(frames, T, H, W, nthr, pools_host, npool);
+  if (!ws || ws_bytes < need) {
+    adnm_set_error("valid_pool_accum: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
+    return ADNM_EWORKSPACE;
+  }
+  Thr thr;
+  thr.n = (int)nthr;
+  for (int k = 0; k < kMaxThr; ++k) thr.t[k] = k < nthr ? thresholds_host[k] : 0.f;
+  Pools pools;
+  pools.n = (int)npool;
+  int ext = 0;
+  for (int p = 0; p < kPoolMax; ++p) {
+    pools.s[p] = p < npool ? (int)pools_host[2 * p] : 1;
+    pools.d[p] = p < npool ? (int)pools_host[2 * p + 1] : 1;
+    // windows start at multiples of d and tiles at multiples of 32: the last start in a tile is at most 32 - gcd(d, 32) into it
+    const int e = pools.s[p] - pool_gcd(pools.d[p], kPoolTile);
+    ext = e > ext ? e : ext;
+  }
+  // 16-byte loads need every frame and row start of both fields aligned; anything else (an odd W, a 4-byte aligned slice) takes the
+  // scalar path: same result
+  const bool vec = W % 4 == 0 && pred_sample_stride % 4 == 0 && pred_frame_stride % 4 == 0 && adnm_quad_aligned(ADNM_F32, {pred, target});
+  if (vec) ext = (int)adnm_align(ext, 4);
+  const int tiles_x = (int)adnm_cdiv(W, kPoolTile), tiles = (int)pool_tiles(H, W);
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ADNM_PROF("valid_pool", st, 8.0 * frames * H * W);
+    const dim3 grid((unsigned)tiles, (unsigned)frames);
+    if (vec)
+      pool_counts_kernel<true><<<grid, kBlock, 0, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (uint32_t*)ws, (int)T, (int)H, (int)W, tiles_x, ext,
+                                                        value_scale, thr, pools);
+    else
+      pool_counts_kernel<false><<<grid, kBlock, 0, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (uint32_t*)ws, (int)T, (int)H, (int)W, tiles_x, ext,
+                                                         value_scale, thr, pools);
+  }
+  ADNM_CHECK_LAUNCH("valid_pool_accum");
+  {
+    ADNM_PROF("valid_pool_fold", st, 4.0 * frames * tiles * npool * 3 * nthr);
+    pool_fold_kernel<<<(unsigned)adnm_cdiv(T * npool * nthr, kFoldBlock), kFoldBlock, 0, st>>>((const uint32_t*)ws, tiles, (int)frames, (int)T, (int)nthr, (int)H,
+                                                                                             (int)W, pools, (double*)table);
+  }
+  ADNM_CHECK_LAUNCH("valid_pool_fold");
   return ADNM_OK;
 }
 

@@ -651,6 +651,33 @@ int64_t adnm_valid_ssim_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int
 int adnm_valid_ssim_accum(const float* pred, const float* target, void* block, int64_t nthr, float value_scale, void* ws, int64_t ws_bytes,
                           int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
 
+/* Neighbourhood ("pooled") contingency counts: TP / FN / FP / TN per WINDOW of a spatial max-pool instead of per pixel.  The reference
+ * has no such score; the definitions are this project's and the yardstick is torch's max_pool2d on the quantised fields.
+ *   quantisation  q(v) = floorf(fminf(fmaxf(v, 0), 1) * value_scale) in fp32: adnm_eval_counts' (the same device function).
+ *   pool (s, d)   window size s, stride d, 1 <= d <= s <= 32; the windows of max_pool2d(kernel_size=s, stride=d, padding=0,
+ *                 ceil_mode=False): ((H-s)/d + 1) x ((W-s)/d + 1), anchored top-left; pixels no window covers take no part.
+ *   event         a window is an observed event at threshold k iff max q(target) over it >= thr_k, likewise the forecast; (1, 1) is
+ *                 the point-wise count of adnm_eval_counts.
+ * table: adnm_valid_pool_block_bytes(T, nthr, npool) bytes, 8-byte aligned, zeroed by the caller, all double, shape (T, npool, 4*nthr):
+ *   [t][p][4k .. 4k+3] = TP, FN, FP, TN at threshold k of pool p for frame index t (frame f of a batch belongs to row f mod T), summed
+ *   over every sample so far.  No header: batches and samples are in adnm_valid_accum's block.
+ * adnm_valid_pool_accum ADDS a batch.  target: contiguous (frames, H, W) fp32.  Frame f = b*T + t of the forecast starts at
+ *   pred + b*pred_sample_stride + t*pred_frame_stride (in elements; rows contiguous): a contiguous forecast is (T*H*W, H*W), a
+ *   persistence forecast is (T_in*H*W, 0) with pred at the last input frame.  thresholds_host (nthr floats) and pools_host (2*npool
+ *   int64: size, stride) are read on the host at call time and passed by value: the call can be captured.  With T = frames on a
+ *   zeroed table it is the one-shot per-frame form.  Two launches: each frame tile (32 x 32 window origins plus the halo its windows
+ *   reach into) is read once and serves every pool and threshold; integer per-workgroup partials go to ws, and one fold adds them in
+ *   a fixed order (samples, then tiles, ascending).  No atomics, no floating-point sums: exact and bit-reproducible.  Aligned shapes
+ *   (W, both strides multiples of 4, both bases 16-byte aligned) are read 16 bytes per access, all others float by float: same result.
+ * Limits, refused before any launch (ADNM_EINVAL): a null pointer; pred / target not 4-byte or table not 8-byte aligned; npool outside
+ *   1..4; a pool outside 1 <= d <= s <= 32 or with s > min(H, W); nthr outside 1..8; T < 1 or not dividing frames; frames > 65535;
+ *   H or W >= 32768; H*W >= 2^24; pred_frame_stride neither 0 nor >= H*W; pred_sample_stride < 0.  The *_bytes queries return -1. */
+int64_t adnm_valid_pool_block_bytes(int64_t T, int64_t nthr, int64_t npool);
+int64_t adnm_valid_pool_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* pools_host, int64_t npool);
+int adnm_valid_pool_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                          const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* pools_host, int64_t npool, void* ws,
+                          int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
+
 /* The output side (pic_results.py:104-184 of the reference): a forecast as the bytes a consumer keeps, in ONE launch.
  * adnm_forecast_render: pred contiguous fp32 (B, T, H, W), 4-byte aligned.  fields: (B, T, H, W) uint8 or NULL.  strip: (B, H, Ws, 4) uint8
  *   (RGBA, 4-byte aligned) or NULL, Ws = n*W + (n-1)*gap, holding the n = ceil((T - frame_start) / frame_step) frames frame_start,
