@@ -3300,7 +3300,7 @@ def pool_counts(truth, pred, thresholds, value_scale, pools):
         raise RuntimeError(f"pool_counts: {frames} frames of {H} x {W} with pools {pairs} are outside adnm_valid_pool_accum's limits "
                            "(1 <= frames <= 65535, H*W < 2^24, no window larger than the frame)")
     out = torch.zeros((frames, len(pairs), 4 * len(thr)), dtype=torch.float64, device=t.device)
-    ws = torch.empty(int(nb), dtype=torch.uint8, device=t.device)
+    ws = _ws(nb, t.device)
     lib.call("adnm_valid_pool_accum", p.data_ptr(), H * W, H * W, t.data_ptr(), out.data_ptr(), (ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale),
              tab, len(pairs), ws.data_ptr(), int(nb), frames, frames, H, W, _stream())
     return out

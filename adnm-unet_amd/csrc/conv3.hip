@@ -662,9 +662,12 @@ extern "C" int adnm_conv3_wgrad(const float* dout, int64_t lddo, const float* in
   ADNM_REQUIRE(lddo >= N && ldin >= K, "conv3_wgrad: row strides smaller than the rows");
   ADNM_REQUIRE(N * 9 * K + N < (1ll << 31), "conv3_wgrad: weight too large");
   const Geo g = make_geo(B, H, W);
-  const WgPlan p = plan_wgrad(g, K, N, dbias != nullptr);
-  if (!ws || ws_bytes < (int64_t)p.rows * p.rowlen * 4) {
-    adnm_set_error("conv3_wgrad: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)((int64_t)p.rows * p.rowlen * 4));
+  WgPlan p = plan_wgrad(g, K, N, dbias != nullptr);
+  // the partial-row count is the one the query sized the workspace for (its plan counts the bias sums into a row: without them the ~8 MB
+  // cap could admit one row more than the query's), and the workspace is held to the queried size
+  p.rows = plan_wgrad(g, K, N, true).rows;
+  if (!ws || ws_bytes < adnm_conv3_wgrad_ws_bytes(B, H, W, K, N)) {
+    adnm_set_error("conv3_wgrad: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)adnm_conv3_wgrad_ws_bytes(B, H, W, K, N));
     return ADNM_EWORKSPACE;
   }
   WgArgs a{};

@@ -662,6 +662,16 @@ extern "C" int adnm_skgemm(int op, const float* a, int64_t lda, const void* b, i
   // the deferred fold writes whole contiguous rows: a strided output (column slice of a wider buffer) takes no partials there
   if (op == ADNM_SKGEMM_TN && ldc != J) pl = make_plan(op, I, J, R, true, bf);
   ADNM_REQUIRE(pl.kernel >= 0, "skgemm: ADNM_SK_FORCE names a configuration this op has no kernel for");
+  // The workspace is held to the size the QUERY names (enough for the plan of either precision), not only to what this precision's plan
+  // touches: a split shape's workspace sized any other way is refused whatever the precision.  (NT / NN with uncached slab space: ws
+  // only holds the arrival counters, checked below.)
+  if (!(slabs_uc && op != ADNM_SKGEMM_TN)) {
+    const int64_t asked = adnm_skgemm_ws_bytes(op, M, N, K);
+    if (asked > 16 && (!ws || ws_bytes < asked)) {
+      adnm_set_error("skgemm: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)asked);
+      return ADNM_EWORKSPACE;
+    }
+  }
   const char* scope = op == ADNM_SKGEMM_NT ? "skgemm_nt" : (op == ADNM_SKGEMM_NN ? "skgemm_nn" : "skgemm_tn");
   // algorithmic bytes: activations in and out in fp32, the weight in the storage it is read from (fp32 / bf16 shadow / fp8 shadow)
   const double algo_bytes = 4.0 * (double)M * (K + N) + (b_dtype == ADNM_B_BF16 ? 2.0 : (b_dtype == ADNM_B_FP8 ? 1.0 : 4.0)) * (double)N * K;

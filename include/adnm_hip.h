@@ -430,6 +430,8 @@ int adnm_colsum(const float* x, float* out, int64_t rows, int64_t n, void* ws, i
  *   A narrow weight halves / quarters the bytes of the weight-streaming shapes and gives bit for bit the result of the fp32 operand
  *   rounded the same way.
  * Workspace (adnm_skgemm_ws_bytes; 16 = the shape is not split): a reduction that would leave CUs idle is split over workgroups.
+ *   The query covers the plan of either precision; a launch that keeps its slabs / partials in ws is refused (ADNM_EWORKSPACE) unless
+ *   ws_bytes is at least what the query names, whatever its own plan would touch.
  *   TN: ws holds fp32 partials for the shared fold — ordinary device memory.
  *   NT / NN: the slabs are combined INSIDE the launch (arrival counters; the last workgroup of a tile adds the slabs in slice order:
  *     bitwise reproducible).  ws = [arrival counters: one int per output tile, rounded up to 256 B | slabs], 256-byte aligned ordinary

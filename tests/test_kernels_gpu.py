@@ -849,6 +849,7 @@ def test_unsupported_shapes_raise():
     (1, 32, 32, 32, 200, lib.ACT_NONE, True, True),     # several output-channel groups
     (1, 3, 5, 4, 5, lib.ACT_GELU, True, False),         # GELU with 75 output elements: the scalar tail of adnm_act_bwd; a map smaller than a tile
     (1, 7, 9, 8, 6, lib.ACT_GELU, True, True),          # GELU with 378 output elements (378 % 4 = 2), ragged N in the epilogue
+    (2, 32, 32, 140, 104, lib.ACT_NONE, False, False),  # no bias, weight-gradient partials at the ~8 MB cap: 15 rows as the query sizes them, not 16
 ])
 def test_conv3(B, H, W, K, N, act, bias, cl):
     x, w, cot = T(f"c3.x{H}{K}", (B, H * W, K)), T(f"c3.w{N}{K}", (N, K, 3, 3), 0.2), T(f"c3.c{H}{N}", (B, H * W, N))

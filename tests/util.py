@@ -1,4 +1,6 @@
+import contextlib
 import os
+import sys
 import numpy as np
 import torch
 
@@ -109,3 +111,71 @@ def assert_pads_untouched(buf, left, C, what):
         r, c = (int(v) for v in touched.nonzero()[0])
         raise AssertionError(f"{what}: pad element (row {r}, column {c}) of a {tuple(buf.shape)} buffer was written "
                              f"(payload columns {left}..{left + C - 1}, bits {int(bits(buf)[r, c]) & (0xFFFFFFFF if buf.dtype == torch.float32 else 0xFFFF):#x})")
+
+
+# ------------------------------------------------------------------------------------------- guarded, poisoned workspaces
+# The scratch workspaces (ops._ws) are memory the kernels write and nothing else looks at: an overrun of the queried size lands in the
+# allocator's slack, a fold that reads a partial row nobody wrote finds last call's right numbers there.  Under guarded_workspaces every
+# workspace is its own buffer [front guard | payload | rear guard] filled with the output poison above (a payload NaN as fp32, garbage as
+# an arrival counter): an overrun changes a guard byte, an unwritten cell reaches the result as a NaN.
+_WS_POISON = _POISON_BITS[torch.float32][1]
+_WS_FRONT, _WS_PAGE, _WS_REAR_MAX = 4096, 4096, 1 << 20   # the front guard keeps the 256 / 512-byte alignment of a fresh allocation
+
+
+class GuardedWorkspaces:
+    def __init__(self):
+        self.records = []   # (buffer, payload bytes, requested bytes, caller)
+
+    @property
+    def calls(self):
+        return len(self.records)
+
+    @staticmethod
+    def rear_bytes(n):
+        return min(_WS_REAR_MAX, (max(_WS_PAGE, int(n)) + _WS_PAGE - 1) // _WS_PAGE * _WS_PAGE)
+
+    @staticmethod
+    def _caller():
+        f = sys._getframe(1)
+        while f is not None and f.f_code.co_filename == __file__:
+            f = f.f_back
+        if f is None:
+            return "?"
+        fn, self_ = f.f_code.co_name, f.f_locals.get("ctx", None)
+        cls = type(self_).__name__.replace("Backward", "") if self_ is not None and fn in ("forward", "backward") else ""
+        return f"{os.path.basename(f.f_code.co_filename)}:{f.f_lineno} {cls + '.' if cls else ''}{fn}"
+
+    def alloc(self, n, device, caller=None):
+        """`n` bytes (at least 16, as ops._ws hands out) of poisoned workspace between two poisoned guards"""
+        n = int(n)
+        pay = max(n, 16)
+        total = (_WS_FRONT + pay + self.rear_bytes(n) + 3) // 4 * 4
+        buf = torch.empty(total, dtype=torch.uint8, device=device)
+        buf.view(torch.int32).fill_(_WS_POISON)
+        self.records.append((buf, pay, n, caller or self._caller()))
+        return buf[_WS_FRONT:_WS_FRONT + pay]
+
+    def check(self):
+        """every guard byte of every workspace handed out still holds the poison"""
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        for buf, pay, n, caller in self.records:
+            want = torch.tensor([_WS_POISON], dtype=torch.int32, device=buf.device).view(torch.uint8).repeat(buf.numel() // 4)
+            touched = buf != want
+            touched[_WS_FRONT:_WS_FRONT + pay] = False
+            if bool(touched.any()):
+                at = int(touched.nonzero()[0])
+                off = at - (_WS_FRONT + pay)
+                raise AssertionError(f"workspace of {n} bytes taken by {caller}: guard byte at offset {off} from the end of the payload was written "
+                                     f"({'front guard' if off < 0 else 'rear guard'}, {int(touched.sum())} guard bytes touched in all)")
+
+
+@contextlib.contextmanager
+def guarded_workspaces(monkeypatch):
+    """with guarded_workspaces(monkeypatch) as g: every ops._ws inside is g.alloc; g.check() asserts the guards, g.calls counts the
+    workspaces handed out, g.alloc(n, device) serves a test that calls the C ABI itself.  Works on CPU tensors too."""
+    from adnm_hip import ops
+    g = GuardedWorkspaces()
+    with monkeypatch.context() as m:
+        m.setattr(ops, "_ws", lambda nbytes, device: g.alloc(nbytes, device))
+        yield g
