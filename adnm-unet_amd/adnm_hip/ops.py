@@ -3306,6 +3306,69 @@ def pool_counts(truth, pred, thresholds, value_scale, pools):
     return out
 
 
+# ======================================================================================= Fractions Skill Score sums (csrc/dataio.hip: valid_fss_accum)
+MAX_FSS_SCALES, MAX_FSS_SCALE = 4, 33
+
+
+def fss_scales(scales):
+    """an int or an iterable of ints -> a tuple of distinct odd ints in 1..33, at most 4: adnm_valid_fss_accum's limits that do not depend
+    on the frame (a 32 x 32 tile's sum of squared counts fits 32 bits up to n = 33).  ValueError on a bad entry.  None -> ()."""
+    if scales is None:
+        return ()
+    if isinstance(scales, (int, np.integer)) and not isinstance(scales, bool):
+        scales = (scales,)
+    if isinstance(scales, (str, bytes)) or not hasattr(scales, "__iter__"):
+        raise ValueError(f"fss: scales are an odd integer or an iterable of them, got {scales!r}")
+    out = []
+    for n in scales:
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise ValueError(f"fss: a scale is an integer, got {n!r}")
+        n = int(n)
+        if not 1 <= n <= MAX_FSS_SCALE or n % 2 == 0:
+            raise ValueError(f"fss: a scale is odd and in 1..{MAX_FSS_SCALE} (larger windows need 64-bit partials: out of scope), got {n}")
+        if n in out:
+            raise ValueError(f"fss: scale {n} is given twice")
+        out.append(n)
+    if len(out) > MAX_FSS_SCALES:
+        raise ValueError(f"fss: at most {MAX_FSS_SCALES} scales, got {len(out)}")
+    return tuple(out)
+
+
+def fss_table(scales):
+    """scales -> the host int64 array adnm_valid_fss_accum reads"""
+    return lib.i64_table(list(scales))
+
+
+def fss_sums(truth, pred, thresholds, value_scale, scales):
+    """truth / pred: fp32 GPU tensors (..., H, W) of the same shape -> (frames, nscale, 3 * nthr) float64 on the device: per frame and
+    scale n (odd, <= 33) A = sum c_o^2, F = sum c_f^2, C = sum c_o c_f per threshold, c the number of threshold pixels in the n x n window
+    centred on each pixel (zero outside the frame), on the fields quantised as adnm_eval_counts quantises them.  FSS = 2C / (A + F).
+    The one-shot use of adnm_valid_fss_accum (T = frames)."""
+    if not (torch.is_tensor(truth) and torch.is_tensor(pred)):
+        raise RuntimeError("fss_sums: needs GPU tensors")
+    _need_gpu(truth)
+    _need_gpu(pred)
+    if truth.dtype != torch.float32 or pred.dtype != torch.float32 or truth.shape != pred.shape or truth.dim() < 2 or truth.device != pred.device:
+        _unsupported("fss_sums", f"takes two fp32 tensors (..., H, W) of one shape, got {truth.dtype} {tuple(truth.shape)} and {pred.dtype} {tuple(pred.shape)}")
+    ns = fss_scales(scales)
+    thr = [float(t) for t in thresholds]
+    if not ns or not 1 <= len(thr) <= 8:
+        raise ValueError("fss_sums: 1..4 scales and 1..8 thresholds")
+    H, W = truth.shape[-2:]
+    t, p = truth.contiguous(), pred.contiguous()
+    frames = t.numel() // (H * W) if H * W else 0
+    tab = fss_table(ns)
+    nb = lib.query("adnm_valid_fss_accum_ws_bytes", frames, frames, H, W, len(thr), tab, len(ns))
+    if nb < 0:
+        raise RuntimeError(f"fss_sums: {frames} frames of {H} x {W} are outside adnm_valid_fss_accum's limits (1 <= frames <= 65535, H and W < 32768, "
+                           "H*W < 2^24)")
+    out = torch.zeros((frames, len(ns), 3 * len(thr)), dtype=torch.float64, device=t.device)
+    ws = _ws(nb, t.device)
+    lib.call("adnm_valid_fss_accum", p.data_ptr(), H * W, H * W, t.data_ptr(), out.data_ptr(), (ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale),
+             tab, len(ns), ws.data_ptr(), int(nb), frames, frames, H, W, _stream())
+    return out
+
+
 # ======================================================================================= the output side (csrc/dataio.hip: forecast_render)
 def edges_up_f32(edges):
     """double edges -> float32, each rounded UP to the smallest float >= it: the kernel compares an fp32 value with fp32 edges where

@@ -18,6 +18,10 @@ csrc/dataio.hip::valid_pool_accum counts TP / FN / FP / TN per window of a spati
 frame held over the horizon, into tables that follow the block in the same allocation; done(per_lead=True) adds every score per frame
 index, from the rows the block always kept.  The defaults allocate and launch nothing new.
 
+Validator(..., fss=(1, 5, 17, 33)) adds the Fractions Skill Score per scale and threshold (DESIGN.md §4i): csrc/dataio.hip::valid_fss_accum
+adds the integer sums A = sum c_o^2, F = sum c_f^2, C = sum c_o c_f of the windowed event counts into tables that follow the pooled
+ones (the forecast's, then with persistence the baseline's), and done() reports FSS = 2C / (A + F) from the summed rows.
+
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
@@ -55,6 +59,36 @@ def block_doubles(seq_len, nthr, pools=(), persistence=False):
     return HEADER + seq_len * (4 * nthr + 3), cell * len(pools), cell * len(baseline_pools(pools)) if persistence else 0
 
 
+def fss_doubles(seq_len, nthr, fss=(), persistence=False):
+    """-> (doubles of the forecast's FSS table, of the baseline's): they follow block_doubles' three parts in the ONE allocation"""
+    cell = seq_len * len(fss) * 3 * nthr
+    return cell, cell if persistence else 0
+
+
+def _fss(sums):
+    """(..., 3 * nthr) sums A, F, C -> (..., nthr) FSS = 2C / (A + F); NaN where A + F = 0 (no event in either field)"""
+    sums = np.asarray(sums, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return 2.0 * sums[..., 2::3] / (sums[..., 0::3] + sums[..., 1::3])
+
+
+def _thr_key(thr):
+    """the key contingency_metrics gives a threshold"""
+    return int(thr) if float(thr).is_integer() else thr
+
+
+def _fss_scores(tab, scales, thresholds):
+    """(T, nscale, 3 * nthr) -> {n: {thr: FSS over the horizon}}"""
+    score = _fss(tab.sum(axis=0))
+    return {n: {_thr_key(thr): float(score[i, k]) for k, thr in enumerate(thresholds)} for i, n in enumerate(scales)}
+
+
+def _fss_lead(tab, scales, thresholds):
+    """(T, nscale, 3 * nthr) -> {n: {thr: length-T array of FSS per frame index}}"""
+    score = _fss(tab)
+    return {n: {_thr_key(thr): score[:, i, k].copy() for k, thr in enumerate(thresholds)} for i, n in enumerate(scales)}
+
+
 def _scores(counts, thresholds):
     """(4 * nthr) counts summed over the horizon -> the two entries every scored field has"""
     metrics, all_far = contingency_metrics(counts, thresholds)
@@ -70,20 +104,23 @@ def _lead_scores(rows, thresholds):
     return metrics
 
 
-def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False):
+def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=()):
     """host: the block (a float64 array of HEADER + T * (4*nthr + 3) values; with `pools` (size, stride) pairs then the forecast's pooled
     table (T, npool, 4*nthr), with `persistence` then the baseline's (T, len(baseline_pools(pools)), 4*nthr): include/adnm_hip.h) -> the
     dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's (Shanghai_metrics.py:218-290) as GpuEvaluator.done()
     states them, from per-frame-index sums; "pooled", "persistence" and "per_lead" apply the same formulas to the pooled tables, the
-    baseline's tables and the single rows."""
+    baseline's tables and the single rows.  With `fss` (odd scales) the forecast's FSS table (T, nscale, 3*nthr) follows, with
+    `persistence` then the baseline's: "fss" {n: {thr: 2C / (A + F)}}, "fss_useful" {thr: 0.5 + f_o / 2} with f_o the observed event
+    fraction of the main table (the line above which a scale is called useful), and "fss" under "persistence" and "per_lead"."""
     nthr, T = len(thresholds), seq_len
-    pools = tuple(pools)
+    pools, fss = tuple(pools), tuple(fss)
     base = baseline_pools(pools) if persistence else ()
     n0, n1, n2 = block_doubles(T, nthr, pools, persistence)
+    n3, n4 = fss_doubles(T, nthr, fss, persistence)
     blk = np.asarray(block, dtype=np.float64)
-    if blk.shape != (n0 + n1 + n2,):
-        raise ValueError(f"aggregate: a block of {n0 + n1 + n2} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
-                         f"persistence {bool(persistence)}; got {blk.shape}")
+    if blk.shape != (n0 + n1 + n2 + n3 + n4,):
+        raise ValueError(f"aggregate: a block of {n0 + n1 + n2 + n3 + n4} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
+                         f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + f"; got {blk.shape}")
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
     tab = blk[HEADER:n0].reshape(T, 4 * nthr + 3)
     metrics, all_far = contingency_metrics(tab[:, :4 * nthr].sum(axis=0), thresholds)
@@ -97,12 +134,21 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
            "LPIPS": None, "loss_sum": loss_sum, "loss_mean": loss_sum / finite if finite > 0 else float("nan"), "batches": int(batches),
            "samples": int(samples), "nonfinite": int(nonfinite)}
     ftab = blk[n0:n0 + n1].reshape(T, len(pools), 4 * nthr)
-    btab = blk[n0 + n1:].reshape(T, len(base), 4 * nthr)
+    btab = blk[n0 + n1:n0 + n1 + n2].reshape(T, len(base), 4 * nthr)
+    fss_f = blk[n0 + n1 + n2:n0 + n1 + n2 + n3].reshape(T, len(fss), 3 * nthr)
+    fss_b = blk[n0 + n1 + n2 + n3:].reshape(T, len(fss) if persistence else 0, 3 * nthr)
     if pools:
         res["pooled"] = {p: _scores(ftab[:, i].sum(axis=0), thresholds) for i, p in enumerate(pools)}
     if persistence:
         res["persistence"] = dict(_scores(btab[:, 0].sum(axis=0), thresholds),
                                   pooled={p: _scores(btab[:, base.index(p)].sum(axis=0), thresholds) for p in pools})
+    if fss:
+        res["fss"] = _fss_scores(fss_f, fss, thresholds)
+        cells = tab[:, :4 * nthr].sum(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            res["fss_useful"] = {_thr_key(thr): float(0.5 + (cells[4 * k] + cells[4 * k + 1]) / cells[4 * k:4 * k + 4].sum() / 2.0) for k, thr in enumerate(thresholds)}
+        if persistence:
+            res["persistence"]["fss"] = _fss_scores(fss_b, fss, thresholds)
     if per_lead:
         with np.errstate(divide="ignore", invalid="ignore"):
             lead = {"RMSE": np.sqrt(mse_t), "MAE": tab[:, 4 * nthr] / (hw * samples),
@@ -113,12 +159,17 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
         if persistence:
             lead["persistence"] = {"threshold_metrics": _lead_scores(btab[:, 0], thresholds),
                                    "pooled": {p: {"threshold_metrics": _lead_scores(btab[:, base.index(p)], thresholds)} for p in pools}}
+        if fss:
+            lead["fss"] = _fss_lead(fss_f, fss, thresholds)
+            if persistence:
+                lead["persistence"]["fss"] = _fss_lead(fss_b, fss, thresholds)
         res["per_lead"] = lead
     return res
 
 
 class Validator(ForwardClient):
-    def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False):
+    def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False,
+                 fss=None):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -136,6 +187,9 @@ class Validator(ForwardClient):
         if self.persistence and len(baseline_pools(self.pools)) > ops.MAX_POOLS:
             raise ValueError(f"Validator: the persistence baseline is scored at (1, 1) and at every pool, which makes {len(self.pools) + 1} pools; "
                              f"a pass takes {ops.MAX_POOLS} (give (1, 1) among the pools, or one pool fewer)")
+        self.fss = ops.fss_scales(fss)   # distinct odd scales <= 33; ValueError on a bad entry
+        # the FSS passes, the forecast's first: their tables follow the pooled ones in this order
+        self._fss_passes = (["pred"] + (["last"] if self.persistence else [])) if self.fss else []
         self._thr = (ctypes.c_float * len(self.thresholds))(*self.thresholds)
         self._fwd = GraphedForward(model, client=self, keep_quant=True)
         self._block = self._last = None    # the epoch's accumulator block and the last batch's fp32 loss: they outlive the graphs
@@ -146,7 +200,8 @@ class Validator(ForwardClient):
         """ONE allocation: adnm_valid_accum's block, then the pooled tables (none by default); done() reduces it with one all-reduce"""
         if self._block is None:
             n = lib.query("adnm_valid_block_bytes", self.seq_len, len(self.thresholds))
-            parts = block_doubles(self.seq_len, len(self.thresholds), self.pools, self.persistence)
+            parts = (block_doubles(self.seq_len, len(self.thresholds), self.pools, self.persistence)
+                     + fss_doubles(self.seq_len, len(self.thresholds), self.fss, self.persistence))
             assert n == 8 * parts[0]
             self._block = torch.zeros(sum(parts), dtype=torch.float64, device=device)
             self._last = torch.zeros((), dtype=torch.float32, device=device)
@@ -163,15 +218,22 @@ class Validator(ForwardClient):
             lib.call("adnm_valid_ssim_accum", pred.data_ptr(), ent["tgt"].data_ptr(), block.data_ptr(), nthr, self.value_scale, ent["ws_ssim"].data_ptr(),
                      ent["ws_ssim"].numel(), B * T, T, H, W, stream)
         table = block.data_ptr() + 8 * block_doubles(T, nthr)[0]
-        for what, pools in self._passes:
+
+        def source(what):
             if what == "pred":     # the forecast, contiguous
-                src, strides = pred.data_ptr(), (T * H * W, H * W)
-            else:                  # persistence: the last input frame of the sample, for every frame index
-                t_in = sx.shape[1]
-                src, strides = sx.data_ptr() + 4 * (t_in - 1) * H * W, (t_in * H * W, 0)
+                return pred.data_ptr(), (T * H * W, H * W)
+            t_in = sx.shape[1]     # persistence: the last input frame of the sample, for every frame index
+            return sx.data_ptr() + 4 * (t_in - 1) * H * W, (t_in * H * W, 0)
+        for what, pools in self._passes:
+            src, strides = source(what)
             lib.call("adnm_valid_pool_accum", src, strides[0], strides[1], ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
                      ops.pool_table(pools), len(pools), ent["ws_pool"].data_ptr(), ent["ws_pool"].numel(), B * T, T, H, W, stream)
             table += 8 * T * len(pools) * 4 * nthr
+        for what in self._fss_passes:
+            src, strides = source(what)
+            lib.call("adnm_valid_fss_accum", src, strides[0], strides[1], ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
+                     ops.fss_table(self.fss), len(self.fss), ent["ws_fss"].data_ptr(), ent["ws_fss"].numel(), B * T, T, H, W, stream)
+            table += 8 * T * len(self.fss) * 3 * nthr
 
     # ---- ForwardClient: what GraphedForward calls with the entry of one input shape
     def open(self, ent, x):
@@ -192,6 +254,12 @@ class Validator(ForwardClient):
                 raise RuntimeError(f"Validator: pools {self.pools} on {B * T} frames of {H} x {W} are outside adnm_valid_pool_accum's limits "
                                    "(no window larger than the frame, H and W < 32768)")
             ws_pool = torch.empty(max(need), dtype=torch.uint8, device=dev)   # the passes follow one another on one stream: one workspace
+        ws_fss = None
+        if self.fss:
+            need = lib.query("adnm_valid_fss_accum_ws_bytes", B * T, T, H, W, nthr, ops.fss_table(self.fss), len(self.fss))
+            if need < 0:
+                raise RuntimeError(f"Validator: fss on {B * T} frames of {H} x {W} is outside adnm_valid_fss_accum's limits (H and W < 32768)")
+            ws_fss = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)   # the passes follow one another on one stream: one workspace
         if self.persistence:
             sx = ent["sx"]
             if (sx.dtype != torch.float32 or sx.dim() not in (4, 5) or (sx.dim() == 5 and sx.shape[2] != 1) or tuple(sx.shape[-2:]) != (H, W)
@@ -199,7 +267,7 @@ class Validator(ForwardClient):
                 raise RuntimeError(f"Validator: persistence needs the model's input as contiguous fp32 (B, T_in, 1, H, W) or (B, T_in, H, W) with the "
                                    f"target's {H} x {W} frames, got {sx.dtype} {tuple(sx.shape)}")
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=torch.empty(max(int(nb), 16), dtype=torch.uint8, device=dev),
-                   ws_ssim=ws_ssim, ws_pool=ws_pool, loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
+                   ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss, loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
         self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
 
@@ -268,14 +336,17 @@ class Validator(ForwardClient):
         pools: plus "pooled": {(size, stride): {"threshold_metrics", "FAR"}}, the same scores counted per max-pool window.
         persistence: plus "persistence": {"threshold_metrics", "FAR", "pooled": {...}}, the last input frame held for every frame index,
         scored on the same batches.  per_lead=True: plus "per_lead": length-T arrays "RMSE", "MAE", "SSIM" (or None) and
-        "threshold_metrics"[thr][TP | FN | FP | TN | CSI | POD | FAR | HSS], and the same under "pooled" / "persistence" where those exist."""
+        "threshold_metrics"[thr][TP | FN | FP | TN | CSI | POD | FAR | HSS], and the same under "pooled" / "persistence" where those exist.
+        fss: plus "fss": {n: {thr: FSS}} (NaN where neither field has an event), "fss_useful": {thr: 0.5 + f_o / 2}, and "fss" under
+        "persistence" and, as length-T arrays, under "per_lead" and "per_lead"/"persistence" where those exist."""
         if self._block is None or self._frame is None:
             raise RuntimeError("Validator.done: no batch since the last reset")
         blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
         host = blk.cpu().numpy()   # the one device -> host read
         H, W = self._frame
         area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
-        res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead)
+        res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead,
+                        fss=self.fss)
         if reset:
             self.reset()
         return res

@@ -680,6 +680,34 @@ int adnm_valid_pool_accum(const float* pred, int64_t pred_sample_stride, int64_t
                           const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* pools_host, int64_t npool, void* ws,
                           int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
 
+/* Fractions Skill Score (Roberts & Lean 2008) per scale, threshold and frame index, as three INTEGER sums.  The reference has no FSS;
+ * the definitions are this project's and the yardstick is conv2d with an all-ones kernel on the threshold bit fields.
+ *   quantisation  adnm_valid_pool_accum's (the same device functions): I_o = q(target) >= thr_k, I_f = q(forecast) >= thr_k.
+ *   scale n       odd, 1 <= n <= 33.  c_o(y, x) = the number of I_o pixels in the n x n window CENTRED on (y, x), for every pixel of the
+ *                 frame; pixels outside the frame count 0 (scipy.ndimage.uniform_filter(size=n, mode="constant", cval=0) times n^2:
+ *                 pysteps' convention); c_f likewise.  A window larger than the frame is allowed: the padding defines it.
+ *   sums          A = SUM c_o^2, F = SUM c_f^2, C = SUM c_o c_f over the H*W pixels.  FSS = 2C / (A + F) (the 1/n^4 cancel), NaN when
+ *                 A + F = 0: the caller's division.  n = 1: A = TP + FN, F = TP + FP, C = TP of the point-wise counts.
+ * table: adnm_valid_fss_block_bytes(T, nthr, nscale) bytes, 8-byte aligned, zeroed by the caller, all double, shape (T, nscale, 3*nthr):
+ *   [t][i][3k .. 3k+2] = A, F, C at threshold k of scale i for frame index t (frame f of a batch belongs to row f mod T), summed over
+ *   every sample so far.  No header.  Integers held in doubles: one 256 x 256 frame adds at most 65536 * 1089^2 = 7.8e10, so a row stays
+ *   exact (< 2^53) for more than 10^5 samples of such frames.
+ * adnm_valid_fss_accum ADDS a batch.  target, pred and the two strides: adnm_valid_pool_accum's meaning (persistence is (T_in*H*W, 0)).
+ *   thresholds_host (nthr floats) and scales_host (nscale int64) are read on the host at call time and passed by value: the call can be
+ *   captured.  With T = frames on a zeroed table it is the one-shot per-frame form.  Two launches: each 32 x 32 tile of window centres
+ *   plus a halo of max(n)/2 pixels on all four sides is read once, as threshold bits, and serves every scale and threshold (row sums,
+ *   then column sums); uint32 per-workgroup partials (a tile's is at most 1024 * 1089^2 < 2^32: why 33 is the limit) go to ws, and one
+ *   fold adds them in a fixed order (samples, then tiles, ascending).  No atomics, no floating-point sums: exact and bit-reproducible.
+ *   Aligned shapes (W, both strides multiples of 4, both bases 16-byte aligned) are read 16 bytes per access, all others float by float.
+ * Limits, refused before any launch (ADNM_EINVAL): a null pointer; pred / target not 4-byte or table not 8-byte aligned; nscale outside
+ *   1..4; a scale even or outside 1..33; a scale given twice; nthr outside 1..8; T < 1 or not dividing frames; frames > 65535; H or W
+ *   outside [1, 32768); H*W >= 2^24; pred_frame_stride neither 0 nor >= H*W; pred_sample_stride < 0.  The *_bytes queries return -1. */
+int64_t adnm_valid_fss_block_bytes(int64_t T, int64_t nthr, int64_t nscale);
+int64_t adnm_valid_fss_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* scales_host, int64_t nscale);
+int adnm_valid_fss_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                         const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* scales_host, int64_t nscale, void* ws,
+                         int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
+
 /* The output side (pic_results.py:104-184 of the reference): a forecast as the bytes a consumer keeps, in ONE launch.
  * adnm_forecast_render: pred contiguous fp32 (B, T, H, W), 4-byte aligned.  fields: (B, T, H, W) uint8 or NULL.  strip: (B, H, Ws, 4) uint8
  *   (RGBA, 4-byte aligned) or NULL, Ws = n*W + (n-1)*gap, holding the n = ceil((T - frame_start) / frame_step) frames frame_start,
