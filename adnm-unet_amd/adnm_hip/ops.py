@@ -796,7 +796,7 @@ _NODEFER = _NoDefer()
 class LaunchGroup:
     """with GROUP: <the same step of several independent chains> — the library's launch group (include/adnm_hip.h: adnm_group_*).  Entry
     points that know about groups (the NT / NN short GEMMs, the depthwise stencil forward / input gradient, the FeedForward gate, InstanceNorm,
-    igate_res) record their launches inside the bracket; leaving it issues them, the
+    igate_res, skipgate forward and backward) record their launches inside the bracket; leaving it issues them, the
     problems of one kernel instantiation merged into one launch.  Everything else launches at once.  An exception inside the bracket
     clears the group: nothing recorded is launched.
     Rules for the code inside: the calls are mutually independent and read only what was enqueued before the bracket; no torch kernel
@@ -2797,6 +2797,7 @@ class SkipGateFn(torch.autograd.Function):
         pooled = torch.empty((3, b, l, c), dtype=x.dtype, device=x.device)
         conv = torch.empty_like(pooled)
         out = torch.empty_like(x)
+        GROUP.keep(x, *params, pooled, conv, out)   # (an open launch group only records the two launches)
         lib.call("adnm_skipgate_fwd", x.data_ptr(), lib.ptr_table(params), pooled.data_ptr(), conv.data_ptr(), out.data_ptr(), b, h, w, c, _stream())
         ctx.save_for_backward(x, pooled, conv, *params)
         ctx.hw = (h, w)
@@ -2812,6 +2813,7 @@ class SkipGateFn(torch.autograd.Function):
         dp = torch.empty(int(lib.query("adnm_skipgate_grad_floats", c)), dtype=torch.float32, device=x.device)
         nb = lib.query("adnm_skipgate_bwd_ws_bytes", b, h, w, c)
         ws = _ws(nb, x.device)
+        GROUP.keep(ws, dout, x, pooled, conv, *params, dx, dp)   # (an open launch group only records the three launches, and the folds when no queue is bound)
         with FOLDS.defer(x.device, ws):   # every parameter of an EncoderToDecoder has this one node
             lib.call("adnm_skipgate_bwd", dout.data_ptr(), x.data_ptr(), lib.ptr_table(params), pooled.data_ptr(), conv.data_ptr(), dx.data_ptr(),
                      dp.data_ptr(), ws.data_ptr(), nb, b, h, w, c, _stream())
@@ -2855,8 +2857,8 @@ class _SubCtx:
 class E2DGroupFn(torch.autograd.Function):
     """n independent EncoderToDecoder chains (models/model_untils.py) as ONE autograd node: the chains advance in lockstep, `for chain in
     chains` per step, one GROUP bracket per step, so the i-th launch of every chain is one launch wherever the entry point records (the
-    short GEMMs, the depthwise stencils, the gates, InstanceNorm, igate_res; the skip kernels, GroupNorm and the weight-gradient leaves
-    launch as they do alone).  Forward and backward are the sequences of IGateResFn, InstNormFn / GroupNormFn,
+    short GEMMs, the depthwise stencils, the gates, InstanceNorm, igate_res, the five skip-gate kernels; GroupNorm and the
+    weight-gradient leaves launch as they do alone).  Forward and backward are the sequences of IGateResFn, InstNormFn / GroupNormFn,
     SkipGateFn, FeedForwardFn, LinearFn and DWConvFn that EncoderToDecoder.forward builds, run through those nodes' own code: outputs and
     every gradient are bitwise what n separate module calls give.  Inputs: metas = [(h, w, GroupNorm groups | 0, eps)] per chain, then
     n skips, n gates, n x NP parameters in EncoderToDecoder.group_args()'s order.  The per-step brackets close inside this function, so the
@@ -2882,7 +2884,8 @@ class E2DGroupFn(torch.autograd.Function):
                     cur[i] = GroupNormFn.forward(sub(i, "norm"), cur[i], groups, P[i][3], P[i][4], P[i][5], P[i][6], eps, lib.ACT_NONE)
                 else:
                     cur[i] = InstNormFn.forward(sub(i, "norm"), cur[i], P[i][5], P[i][6], eps, lib.ACT_NONE)
-        cur = [SkipGateFn.forward(sub(i, "skip", 21), cur[i], metas[i][0], metas[i][1], *P[i][7:25]) for i in range(n)]
+        with GROUP:
+            cur = [SkipGateFn.forward(sub(i, "skip", 21), cur[i], metas[i][0], metas[i][1], *P[i][7:25]) for i in range(n)]
         # FeedForwardFn.forward, step by step
         F = []
         for i in range(n):
@@ -2979,7 +2982,8 @@ class E2DGroupFn(torch.autograd.Function):
                 b_in = f["b_in"]
                 dx[i] = k_linear_dx(dh1[i], f["w_in"], out_dtype=f["x2"].dtype)
                 G[i][25], G[i][26] = k_linear_dw(dh1[i], f["x2"], b_in is not None, f["w_in"].data_ptr(), b_in.data_ptr() if b_in is not None else 0)
-        r = [SkipGateFn.backward(C[i]["skip"], dx[i].view(F[i]["dims"][0], F[i]["dims"][1], F[i]["dims"][2])) for i in range(n)]
+        with GROUP:
+            r = [SkipGateFn.backward(C[i]["skip"], dx[i].view(F[i]["dims"][0], F[i]["dims"][1], F[i]["dims"][2])) for i in range(n)]
         for i in range(n):
             G[i][7:25] = r[i][3:21]
         d = [None] * n
@@ -2998,8 +3002,8 @@ class E2DGroupFn(torch.autograd.Function):
 
 def e2d_group(xs, gates, modules):
     """[m(x=x, res=g) for x, g, m in zip(xs, gates, modules)] for EncoderToDecoder modules, as one autograd node whose chains advance in
-    lockstep, the same step of every chain in one launch group (E2DGroupFn: the short GEMMs, the depthwise stencils, the gates, InstanceNorm
-    and igate_res merge; the skip kernels and GroupNorm launch per chain).  -> the list of outputs."""
+    lockstep, the same step of every chain in one launch group (E2DGroupFn: the short GEMMs, the depthwise stencils, the gates, InstanceNorm,
+    igate_res and the skip-gate kernels merge; GroupNorm launches per chain).  -> the list of outputs."""
     if not (len(xs) == len(gates) == len(modules)) or not xs:
         raise RuntimeError("adnm_hip e2d_group: needs as many skips as gates and modules, at least one")
     metas, params = [], []

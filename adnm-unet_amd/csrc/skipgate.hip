@@ -24,9 +24,7 @@ struct Geo {
   int64_t npix;
 };
 
-struct Params {  // device pointers, order documented in include/adnm_hip.h (adnm_skipgate_fwd)
-  const float* w[3];
-  const float* b[3];
+struct GateParams {  // what the pointwise gate reads: everything but the conv weights and biases
   const float* fw[2];
   const float* fb[2];
   const float* enh[2];
@@ -34,6 +32,55 @@ struct Params {  // device pointers, order documented in include/adnm_hip.h (adn
   const float* alpha[3];
   const float* gamma;
 };
+struct Params {  // device pointers, order documented in include/adnm_hip.h (adnm_skipgate_fwd)
+  const float* w[3];
+  const float* b[3];
+  GateParams q;
+};
+
+// The kernels' argument structs, one per kernel, each also the payload of a launch-group record (adnm_common.h: AdnmGroupRec::args, 232
+// bytes).  The whole argument list of the earlier kernels (18 parameter pointers + geometry + up to 12 tensor pointers) does not fit
+// one, so every struct holds only the parameter pointers ITS kernel reads, and ONE base pointer per tensor family: pooled / conv are
+// (3, npix, C), the backward's workspace starts with seven (npix, C) tensors (d c_0..2, the direct d x term, g_0..2); branch k lies at
+// base + k * npix * C, derived from the geometry in the kernel.  The record stays at 232 bytes (the largest struct here is 208).
+struct PoolFwdArgs {
+  const float* x;
+  float* pooled;
+  Geo g;
+};
+struct BranchFwdArgs {
+  const float *x, *pooled;
+  Params P;
+  float *conv, *out;
+  Geo g;
+};
+struct BranchBwdArgs {
+  const float *dout, *x, *conv;
+  GateParams q;
+  float *ws, *vpart, *spart;   // ws: d c_0..2 and the direct d x term are written at ws + {0, 1, 2, 3} n
+  int S;
+  Geo g;
+};
+struct ConvBwdArgs {
+  const float* w[3];
+  const float* pooled;
+  float *ws, *dw;   // ws: reads d c_0..2 at ws + {0, 1, 2} n, writes g_0..2 at ws + {4, 5, 6} n;  dw: the weight gradient or its partial rows
+  int ndg, SW;
+  Geo g;
+};
+struct PoolBwdArgs {
+  const float* x;
+  const float* ws;   // reads the direct d x term at ws + 3 n and g_0..2 at ws + {4, 5, 6} n
+  float* dx;
+  Geo g;
+};
+// a problem's geometry out of its argument struct (in a multi-problem launch that struct lies in the kernel-argument segment)
+template <typename Args>
+__device__ __forceinline__ Geo geo_of(const Args& p) {
+  Geo g;
+  g.B = p.g.B, g.H = p.g.H, g.W = p.g.W, g.C = p.g.C, g.C4 = p.g.C4, g.npix = p.g.npix;
+  return g;
+}
 
 template <int K>
 struct Taps {
@@ -56,9 +103,19 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 __device__ __forceinline__ void st4(float* p, const float o[4]) { *reinterpret_cast<float4*>(p) = mk4(o); }
 
 // ------------------------------------------------------------------------------------------------ pools
-__global__ __launch_bounds__(kBlock) void skip_pool_fwd_kernel(const float* __restrict__ x, float* __restrict__ p0, float* __restrict__ p1,
-                                                               float* __restrict__ p2, Geo g) {
-  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+// Every kernel body below sees `bid`, the workgroup's index inside ITS problem: blockIdx.x in the single-problem kernel, the index
+// behind adnm_group_which in the multi-problem one (SKIP_KERNELS at the end of the device code).  A problem's block range is whole
+// workgroups, hence whole waves: the in-wave reductions and the "lanes past the end stay in their wave" logic hold per problem.  (The
+// problem's workgroup count is not passed on: no body here walks a grid-stride loop, each derives its extent from the geometry.)
+template <typename Args>
+__device__ __forceinline__ void skip_pool_fwd_body(const Args& p, const int bid) {
+  const Geo g = geo_of(p);
+  const int64_t n = g.npix * g.C;
+  const float* __restrict__ x = p.x;
+  float* __restrict__ p0 = p.pooled;
+  float* __restrict__ p1 = p0 + n;
+  float* __restrict__ p2 = p0 + 2 * n;
+  const int64_t idx = (int64_t)bid * kBlock + threadIdx.x;
   if (idx >= g.npix * g.C4) return;
   int b, h, w, cg;
   decode(idx, g, b, h, w, cg);
@@ -129,10 +186,17 @@ __device__ __forceinline__ void pool_bwd_one(const float (&xv)[5][5][4], const b
     }
 }
 
-__global__ __launch_bounds__(kBlock) void skip_pool_bwd_kernel(const float* __restrict__ x, const float* __restrict__ g0, const float* __restrict__ g1,
-                                                               const float* __restrict__ g2, const float* __restrict__ dxa, float* __restrict__ dx,
-                                                               Geo g) {
-  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+template <typename Args>
+__device__ __forceinline__ void skip_pool_bwd_body(const Args& p, const int bid) {
+  const Geo g = geo_of(p);
+  const int64_t n = g.npix * g.C;
+  const float* __restrict__ x = p.x;
+  const float* __restrict__ dxa = p.ws + 3 * n;
+  const float* __restrict__ g0 = p.ws + 4 * n;
+  const float* __restrict__ g1 = p.ws + 5 * n;
+  const float* __restrict__ g2 = p.ws + 6 * n;
+  float* __restrict__ dx = p.dx;
+  const int64_t idx = (int64_t)bid * kBlock + threadIdx.x;
   if (idx >= g.npix * g.C4) return;
   int b, h, w, cg;
   decode(idx, g, b, h, w, cg);
@@ -195,14 +259,23 @@ __device__ __forceinline__ void conv4(const float* __restrict__ p, const float* 
   }
 }
 
-__global__ __launch_bounds__(kBlock) void skip_branch_fwd_kernel(const float* __restrict__ x, const float* __restrict__ p0,
-                                                                 const float* __restrict__ p1, const float* __restrict__ p2, Params P,
-                                                                 float* __restrict__ c0, float* __restrict__ c1, float* __restrict__ c2,
-                                                                 float* __restrict__ out, Geo g) {
+template <typename Args>
+__device__ __forceinline__ void skip_branch_fwd_body(const Args& p, const int bid) {
   __shared__ float wlds[kGW * kWPitch];
+  const Geo g = geo_of(p);
+  const int64_t n = g.npix * g.C;
+  const float* __restrict__ x = p.x;
+  const float* __restrict__ p0 = p.pooled;
+  const float* __restrict__ p1 = p0 + n;
+  const float* __restrict__ p2 = p0 + 2 * n;
+  float* __restrict__ c0 = p.conv;
+  float* __restrict__ c1 = c0 + n;
+  float* __restrict__ c2 = c0 + 2 * n;
+  float* __restrict__ out = p.out;
+  const auto& P = p.P;
   const int nchunk = (g.C4 + kGW - 1) / kGW;
-  const int cg0 = ((int)blockIdx.x % nchunk) * kGW, cg = cg0 + (threadIdx.x & (kGW - 1));
-  const int64_t pix = (int64_t)((int)blockIdx.x / nchunk) * kGP + (threadIdx.x / kGW);
+  const int cg0 = (bid % nchunk) * kGW, cg = cg0 + (threadIdx.x & (kGW - 1));
+  const int64_t pix = (int64_t)(bid / nchunk) * kGP + (threadIdx.x / kGW);
   stage_weights<0>(P.w[0], cg0, g.C4, wlds);
   stage_weights<1>(P.w[1], cg0, g.C4, wlds);
   stage_weights<2>(P.w[2], cg0, g.C4, wlds);
@@ -217,14 +290,14 @@ __global__ __launch_bounds__(kBlock) void skip_branch_fwd_kernel(const float* __
   conv4<1>(p1, wl, P.b[1], g, b, h, w, cg, c[1]);
   conv4<2>(p2, wl, P.b[2], g, b, h, w, cg, c[2]);
   f4(ld4(x + idx * 4), xv);
-  f4(ld4(P.gamma + cg * 4), gam);
+  f4(ld4(P.q.gamma + cg * 4), gam);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int f = k >> 1;   // 0: ffd13 / act_func13, 1: ffd33 / act_func33
     float fw[4], fb[4];
-    f4(ld4(P.fw[f] + cg * 4), fw);
-    f4(ld4(P.fb[f] + cg * 4), fb);
-    const float enh = *P.enh[f], thr = *P.thr[f], al = *P.alpha[k];
+    f4(ld4(P.q.fw[f] + cg * 4), fw);
+    f4(ld4(P.q.fb[f] + cg * 4), fb);
+    const float enh = *P.q.enh[f], thr = *P.q.thr[f], al = *P.q.alpha[k];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float z = fmaf(xv[q] * geluf_(c[k][q]), fw[q], fb[q]);
@@ -242,12 +315,24 @@ __global__ __launch_bounds__(kBlock) void skip_branch_fwd_kernel(const float* __
 // ------------------------------------------------------------------------------------------------ gated branches, backward (pointwise)
 // thread = (pixel slice s, group cg); pixels s, s+S, ...  Writes d c_k, the direct d x term, and per-slice partials of the
 // 8 per-channel vectors; the 7 scalars are summed over the wave's 64 groups first (one slice per wave: C4 % 64 == 0).
-__global__ __launch_bounds__(kBlock) void skip_branch_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ x,
-                                                                 const float* __restrict__ c0, const float* __restrict__ c1,
-                                                                 const float* __restrict__ c2, Params P, float* __restrict__ dc0,
-                                                                 float* __restrict__ dc1, float* __restrict__ dc2, float* __restrict__ dxa,
-                                                                 float* __restrict__ vpart, float* __restrict__ spart, int S, Geo g) {
-  const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+template <typename Args>
+__device__ __forceinline__ void skip_branch_bwd_body(const Args& p, const int bid) {
+  const Geo g = geo_of(p);
+  const int64_t n = g.npix * g.C;
+  const float* __restrict__ dout = p.dout;
+  const float* __restrict__ x = p.x;
+  const float* __restrict__ c0 = p.conv;
+  const float* __restrict__ c1 = c0 + n;
+  const float* __restrict__ c2 = c0 + 2 * n;
+  float* __restrict__ dc0 = p.ws;
+  float* __restrict__ dc1 = dc0 + n;
+  float* __restrict__ dc2 = dc0 + 2 * n;
+  float* __restrict__ dxa = dc0 + 3 * n;
+  float* __restrict__ vpart = p.vpart;
+  float* __restrict__ spart = p.spart;
+  const int S = p.S;
+  const auto& P = p.q;
+  const int64_t tid = (int64_t)bid * kBlock + threadIdx.x;   // the lane's index inside its problem: slices, partial rows and validity
   const bool valid = tid < (int64_t)S * g.C4;   // an idle lane keeps going: its wave's scalar sums are shuffled across all 64 lanes
   const int cg = valid ? (int)(tid % g.C4) : 0, s = (int)(tid / g.C4);
   float gam[4], fw[2][4], fb[2][4], enh[2], thr[2], al[3];
@@ -379,19 +464,29 @@ __device__ __forceinline__ void wgrad_block(const float* __restrict__ dc, const 
   }
 }
 
-__global__ __launch_bounds__(kBlock) void skip_conv_bwd_kernel(const float* __restrict__ dc0, const float* __restrict__ dc1,
-                                                               const float* __restrict__ dc2, const float* __restrict__ p0,
-                                                               const float* __restrict__ p1, const float* __restrict__ p2, Params P,
-                                                               float* __restrict__ g0, float* __restrict__ g1, float* __restrict__ g2,
-                                                               float* __restrict__ dw, int ndg, int SW, Geo g) {
+template <typename Args>
+__device__ __forceinline__ void skip_conv_bwd_body(const Args& p, const int bid) {
   __shared__ float wlds[kGW * kWPitch];
-  if ((int)blockIdx.x < ndg) {   // workgroup = 16 groups x 16 pixels, the groups' weights staged in LDS (see stage_weights)
+  const Geo g = geo_of(p);
+  const int64_t n = g.npix * g.C;
+  const float* __restrict__ dc0 = p.ws;
+  const float* __restrict__ dc1 = dc0 + n;
+  const float* __restrict__ dc2 = dc0 + 2 * n;
+  const float* __restrict__ p0 = p.pooled;
+  const float* __restrict__ p1 = p0 + n;
+  const float* __restrict__ p2 = p0 + 2 * n;
+  float* __restrict__ g0 = p.ws + 4 * n;
+  float* __restrict__ g1 = p.ws + 5 * n;
+  float* __restrict__ g2 = p.ws + 6 * n;
+  float* __restrict__ dw = p.dw;
+  const int ndg = p.ndg, SW = p.SW;
+  if (bid < ndg) {   // workgroup = 16 groups x 16 pixels, the groups' weights staged in LDS (see stage_weights)
     const int nchunk = (g.C4 + kGW - 1) / kGW;
-    const int cg0 = ((int)blockIdx.x % nchunk) * kGW, cg = cg0 + (threadIdx.x & (kGW - 1));
-    const int64_t pix = (int64_t)((int)blockIdx.x / nchunk) * kGP + (threadIdx.x / kGW);
-    stage_weights<0>(P.w[0], cg0, g.C4, wlds);
-    stage_weights<1>(P.w[1], cg0, g.C4, wlds);
-    stage_weights<2>(P.w[2], cg0, g.C4, wlds);
+    const int cg0 = (bid % nchunk) * kGW, cg = cg0 + (threadIdx.x & (kGW - 1));
+    const int64_t pix = (int64_t)(bid / nchunk) * kGP + (threadIdx.x / kGW);
+    stage_weights<0>(p.w[0], cg0, g.C4, wlds);
+    stage_weights<1>(p.w[1], cg0, g.C4, wlds);
+    stage_weights<2>(p.w[2], cg0, g.C4, wlds);
     __syncthreads();
     if (cg >= g.C4 || pix >= g.npix) return;
     const int64_t idx = pix * g.C4 + cg;
@@ -409,7 +504,7 @@ __global__ __launch_bounds__(kBlock) void skip_conv_bwd_kernel(const float* __re
   }
   // weight-gradient role: block -> (branch, chunk of 16 groups, outer pixel slice); partial row `outer` of (SW, 60 C)
   const int nchunk = (g.C4 + 15) / 16;
-  int r = (int)blockIdx.x - ndg;
+  int r = bid - ndg;
   const int k = r / (nchunk * SW);
   r -= k * nchunk * SW;
   const int outer = r / nchunk, gchunk = r % nchunk;
@@ -417,6 +512,48 @@ __global__ __launch_bounds__(kBlock) void skip_conv_bwd_kernel(const float* __re
   if (k == 0) wgrad_block<0>(dc0, p0, row, g, gchunk, outer, SW);
   else if (k == 1) wgrad_block<1>(dc1, p1, row + (int64_t)g.C * 12, g, gchunk, outer, SW);
   else wgrad_block<2>(dc2, p2, row + (int64_t)g.C * 24, g, gchunk, outer, SW);
+}
+
+// ------------------------------------------------------------------------------------------------ the kernels, and their group functions
+// Per body: the single-problem kernel (its argument struct by value, blockIdx.x), the multi-problem kernel (up to ADNM_GROUP_MAX argument
+// structs in the kernel-argument segment, the problem and the problem-local block index from adnm_group_which), and the host function
+// that is the launch-group's merge key (adnm_common.h: AdnmGroupFn; n == 1 launches the single-problem kernel).
+#define SKIP_KERNELS(name, Args)                                                                                                  \
+  __global__ __launch_bounds__(kBlock) void name##_kernel(Args p) { name##_body(p, (int)blockIdx.x); }                             \
+  __global__ __launch_bounds__(kBlock) void name##_multi_kernel(AdnmMulti<Args> by_value) {                                        \
+    (void)by_value;                                                                                                               \
+    const auto& m = *(const __attribute__((address_space(4))) AdnmMulti<Args>*)__builtin_amdgcn_kernarg_segment_ptr();             \
+    int bid, nblk;                                                                                                                \
+    const int k = adnm_group_which(m, &bid, &nblk);                                                                               \
+    name##_body(m.p[k], bid);                                                                                                     \
+  }                                                                                                                               \
+  int name##_group_fn(const AdnmGroupRec* const* r, int n, hipStream_t st) {                                                       \
+    if (n == 1) {                                                                                                                 \
+      Args p;                                                                                                                     \
+      memcpy(&p, r[0]->args, sizeof(Args));                                                                                       \
+      name##_kernel<<<(unsigned)r[0]->grid, kBlock, 0, st>>>(p);                                                                   \
+      return ADNM_OK;                                                                                                             \
+    }                                                                                                                             \
+    AdnmMulti<Args> m;                                                                                                            \
+    const unsigned blocks = adnm_group_pack(r, n, m);                                                                             \
+    name##_multi_kernel<<<blocks, kBlock, 0, st>>>(m);                                                                             \
+    return ADNM_OK;                                                                                                               \
+  }
+SKIP_KERNELS(skip_pool_fwd, PoolFwdArgs)
+SKIP_KERNELS(skip_branch_fwd, BranchFwdArgs)
+SKIP_KERNELS(skip_branch_bwd, BranchBwdArgs)
+SKIP_KERNELS(skip_conv_bwd, ConvBwdArgs)
+SKIP_KERNELS(skip_pool_bwd, PoolBwdArgs)
+#undef SKIP_KERNELS
+
+// one launch of an entry point: made now under its profiler scope, or recorded at position `pos` by an open launch group
+template <typename Args>
+int submit(AdnmGroupFn fn, const Args& p, int64_t grid, int pos, const char* prof, double bytes, hipStream_t st) {
+  static_assert(sizeof(Args) <= sizeof(AdnmGroupRec::args), "the argument struct must fit a group record");
+  AdnmGroupRec rec;
+  rec.fn = fn, rec.grid = (int)grid, rec.pos = pos, rec.prof = prof, rec.bytes = bytes;
+  memcpy(rec.args, &p, sizeof(Args));
+  return adnm_group_submit(rec, st);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -432,10 +569,11 @@ int load_params(const char* who, const float* const* params, Params* P) {
   ADNM_REQUIRE(params, "%s: null parameter table", who);
   for (int i = 0; i < 18; ++i) ADNM_REQUIRE(params[i], "%s: parameter %d is null", who, i);
   for (int k = 0; k < 3; ++k) P->w[k] = params[2 * k], P->b[k] = params[2 * k + 1];
-  P->fw[0] = params[6], P->fb[0] = params[7], P->fw[1] = params[8], P->fb[1] = params[9];
-  P->enh[0] = params[10], P->thr[0] = params[11], P->enh[1] = params[12], P->thr[1] = params[13];
-  P->alpha[0] = params[14], P->alpha[1] = params[15], P->alpha[2] = params[16];
-  P->gamma = params[17];
+  GateParams& q = P->q;
+  q.fw[0] = params[6], q.fb[0] = params[7], q.fw[1] = params[8], q.fb[1] = params[9];
+  q.enh[0] = params[10], q.thr[0] = params[11], q.enh[1] = params[12], q.thr[1] = params[13];
+  q.alpha[0] = params[14], q.alpha[1] = params[15], q.alpha[2] = params[16];
+  q.gamma = params[17];
   return ADNM_OK;
 }
 int slices_pointwise(const Geo& g) {   // pixels per lane of the pointwise backward = npix / slices (ADNM_SKIP_PPL: measurement aid)
@@ -481,16 +619,11 @@ extern "C" int adnm_skipgate_fwd(const float* x, const float* const* params, flo
   if (int rc = load_params("skipgate_fwd", params, &P)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = g.npix * g.C;
-  const unsigned grid = (unsigned)adnm_cdiv(g.npix * g.C4, kBlock);
-  {
-    ADNM_PROF("skip_pool_fwd", st, 4.0 * 4 * n);
-    skip_pool_fwd_kernel<<<grid, kBlock, 0, st>>>(x, pooled, pooled + n, pooled + 2 * n, g);
-  }
-  {
-    ADNM_PROF("skip_branch_fwd", st, 4.0 * (8 * n + kWeightsPerChannel * C));
-    const unsigned gridb = (unsigned)(adnm_cdiv(g.C4, kGW) * adnm_cdiv(g.npix, kGP));
-    skip_branch_fwd_kernel<<<gridb, kBlock, 0, st>>>(x, pooled, pooled + n, pooled + 2 * n, P, conv, conv + n, conv + 2 * n, out, g);
-  }
+  // two dependent launches: positions 0 and 1 of an open launch group (all pools of a bracket, then all branches)
+  if (int rc = submit(skip_pool_fwd_group_fn, PoolFwdArgs{x, pooled, g}, adnm_cdiv(g.npix * g.C4, kBlock), 0, "skip_pool_fwd", 4.0 * 4 * n, st)) return rc;
+  if (int rc = submit(skip_branch_fwd_group_fn, BranchFwdArgs{x, pooled, P, conv, out, g}, adnm_cdiv(g.C4, kGW) * adnm_cdiv(g.npix, kGP), 1,
+                      "skip_branch_fwd", 4.0 * (8 * n + kWeightsPerChannel * C), st))
+    return rc;
   ADNM_CHECK_LAUNCH("skipgate_fwd");
   return ADNM_OK;
 }
@@ -511,29 +644,23 @@ extern "C" int adnm_skipgate_bwd(const float* dout, const float* x, const float*
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = g.npix * g.C;
   float* f = (float*)ws;
-  float *dc0 = f, *dc1 = f + n, *dc2 = f + 2 * n, *dxa = f + 3 * n, *g0 = f + 4 * n, *g1 = f + 5 * n, *g2 = f + 6 * n;
-  float *vpart = f + L.vpart, *spart = f + L.spart, *wpart = f + L.wpart;
+  float *vpart = f + L.vpart, *spart = f + L.spart, *wpart = f + L.wpart;   // (f itself: the seven (npix, C) tensors the kernels address as f + k n)
   const int S = slices_pointwise(g), SW = slices_wgrad(g);
   const int nwt = g.C * kWeightsPerChannel;
   float *dwgt = dparams, *dvec = dparams + nwt, *dscal = dvec + (int64_t)kVec * g.C;
-  {
-    ADNM_PROF("skip_branch_bwd", st, 4.0 * 9 * n);
-    skip_branch_bwd_kernel<<<(unsigned)adnm_cdiv((int64_t)S * g.C4, kBlock), kBlock, 0, st>>>(dout, x, conv, conv + n, conv + 2 * n, P, dc0, dc1, dc2,
-                                                                                             dxa, vpart, spart, S, g);
-  }
-  adnm_launch_fold("skip_vec_fold", vpart, S, kVec * g.C, {dvec, kVec * g.C}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}, st);
-  adnm_launch_fold("skip_scal_fold", spart, (int)scal_rows(g, S), kScal, {dscal, kScal}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}, st);
+  // three dependent launches: positions 0, 1, 2 of an open launch group.  The folds wait in a bound fold queue as ever; without one, an
+  // open group records them behind every position (their partials are regions of the workspace no later launch writes).
+  if (int rc = submit(skip_branch_bwd_group_fn, BranchBwdArgs{dout, x, conv, P.q, f, vpart, spart, S, g}, adnm_cdiv((int64_t)S * g.C4, kBlock), 0,
+                      "skip_branch_bwd", 4.0 * 9 * n, st))
+    return rc;
+  adnm_launch_fold_recorded("skip_vec_fold", vpart, S, kVec * g.C, {dvec, kVec * g.C}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}, st);
+  adnm_launch_fold_recorded("skip_scal_fold", spart, (int)scal_rows(g, S), kScal, {dscal, kScal}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}, st);
   const int ndg = (int)(adnm_cdiv(g.C4, kGW) * adnm_cdiv(g.npix, kGP));
-  {
-    ADNM_PROF("skip_conv_bwd", st, 4.0 * (9 * n + 2.0 * nwt));
-    skip_conv_bwd_kernel<<<(unsigned)(ndg + 3 * ((g.C4 + 15) / 16) * SW), kBlock, 0, st>>>(
-        dc0, dc1, dc2, pooled, pooled + n, pooled + 2 * n, P, g0, g1, g2, SW > 1 ? wpart : dwgt, ndg, SW, g);
-  }
-  if (SW > 1) adnm_launch_fold("skip_wgrad_fold", wpart, SW, nwt, {dwgt, nwt}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}, st);
-  {
-    ADNM_PROF("skip_pool_bwd", st, 4.0 * 6 * n);
-    skip_pool_bwd_kernel<<<(unsigned)adnm_cdiv(g.npix * g.C4, kBlock), kBlock, 0, st>>>(x, g0, g1, g2, dxa, dx, g);
-  }
+  if (int rc = submit(skip_conv_bwd_group_fn, ConvBwdArgs{{P.w[0], P.w[1], P.w[2]}, pooled, f, SW > 1 ? wpart : dwgt, ndg, SW, g},
+                      ndg + 3 * ((g.C4 + 15) / 16) * SW, 1, "skip_conv_bwd", 4.0 * (9 * n + 2.0 * nwt), st))
+    return rc;
+  if (SW > 1) adnm_launch_fold_recorded("skip_wgrad_fold", wpart, SW, nwt, {dwgt, nwt}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}, st);
+  if (int rc = submit(skip_pool_bwd_group_fn, PoolBwdArgs{x, f, dx, g}, adnm_cdiv(g.npix * g.C4, kBlock), 2, "skip_pool_bwd", 4.0 * 6 * n, st)) return rc;
   ADNM_CHECK_LAUNCH("skipgate_bwd");
   return ADNM_OK;
 }

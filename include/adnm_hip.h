@@ -122,7 +122,8 @@ int adnm_leafq_clear(void* q);
  * depends only on work enqueued before adnm_group_begin.  An entry point that knows about groups — adnm_skgemm with ops NT and NN (both of
  * its kernels), adnm_dwconv_fwd, adnm_dwconv_bwd (dpre and the input gradient: two positions; with a weight-gradient destination it is
  * refused inside a group, adnm_dwconv_wgrad is a call of its own behind the launch), adnm_gate_fwd / _bwd, adnm_instnorm_fwd / _bwd (two
- * positions each; without a bound fold queue the fold of the scalar gradients is recorded behind them), adnm_igate_res_fwd / _bwd (likewise)
+ * positions each; without a bound fold queue the fold of the scalar gradients is recorded behind them), adnm_igate_res_fwd / _bwd (likewise),
+ * adnm_skipgate_fwd (pools, then branches: two positions) / _bwd (pointwise gate, grouped conv, pools: three positions; its folds likewise)
  * — then stores its fully prepared launch instead of making it (operands, outputs and workspaces must stay alive, and two
  * split problems need DISJOINT counter / slab ranges); every other entry point launches at once, which the contract allows.
  * adnm_group_launch issues the stored launches on `stream`: those of one kernel instantiation merged into one multi-problem launch (up to 8
@@ -349,7 +350,11 @@ int adnm_igate_res_bwd(const float* dy, const float* x, const float* res, int pe
  * pooled, conv: (3, B, H, W, C) each, written by fwd and handed back to bwd.
  * dparams (OVERWRITTEN), adnm_skipgate_grad_floats(C) floats:
  *   [d w0 12C | d w1 12C | d w2 36C | d gamma | d ffd13.w | d ffd13.b | d ffd33.w | d ffd33.b | d b0 | d b1 | d b2 (C each) |
- *    d alpha1..3, d enh13, d thr13, d enh33, d thr33, pad] */
+ *    d alpha1..3, d enh13, d thr13, d enh33, d thr33, pad]
+ * Inside a launch group (adnm_group_*) both calls record their launches, fwd at positions 0 (pools) and 1 (branches), bwd at 0 (pointwise
+ * gate), 1 (grouped conv, both gradients) and 2 (pools); the device pointers behind params are read at the call, everything they point to
+ * (and pooled, conv, out, dx, dparams, ws) must stay alive until adnm_group_launch.  bwd's folds wait in a bound fold queue; without one an
+ * open group records them behind every position. */
 int adnm_skipgate_fwd(const float* x, const float* const* params, float* pooled, float* conv, float* out, int64_t B, int64_t H, int64_t W,
                       int64_t C, adnm_stream_t stream);
 int64_t adnm_skipgate_grad_floats(int64_t C);
