@@ -3373,6 +3373,92 @@ def fss_sums(truth, pred, thresholds, value_scale, scales):
     return out
 
 
+# ======================================================================================= block-matched motion and advection (csrc/advect.hip)
+TREC_BLOCKS, MAX_TREC_RADIUS = (8, 16, 32), 8
+
+
+def advection_spec(arg, thresholds):
+    """the Validator's `advection` argument -> (block, radius, echo) or None: True is (32, 4, max(1, int(min(thresholds)) // 2)) (a block
+    has an echo when `block` of its pixels reach half the lowest threshold); otherwise (block, radius) with that echo, or
+    (block, radius, echo).  Checked against adnm_trec_motion's limits that do not depend on the frame: block in {8, 16, 32}, radius in
+    1..8, echo in 1..255.  ValueError on a bad entry.  None / False -> None."""
+    if arg is None or arg is False:
+        return None
+    echo = max(1, int(min(float(t) for t in thresholds)) // 2)
+    if arg is True:
+        arg = (32, 4)
+    if isinstance(arg, (str, bytes)) or not hasattr(arg, "__iter__"):
+        raise ValueError(f"advection: True, (block, radius) or (block, radius, echo), got {arg!r}")
+    arg = tuple(arg)
+    if len(arg) not in (2, 3):
+        raise ValueError(f"advection: True, (block, radius) or (block, radius, echo), got {arg!r}")
+    for v in arg:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"advection: block, radius and echo are integers, got {v!r}")
+    block, radius, echo = int(arg[0]), int(arg[1]), int(arg[2]) if len(arg) == 3 else echo
+    if block not in TREC_BLOCKS:
+        raise ValueError(f"advection: block is one of {TREC_BLOCKS}, got {block}")
+    if not 1 <= radius <= MAX_TREC_RADIUS:
+        raise ValueError(f"advection: radius is in 1..{MAX_TREC_RADIUS}, got {radius}")
+    if not 1 <= echo <= 255:
+        raise ValueError(f"advection: echo is in 1..255 (a quantised value), got {echo}")
+    return block, radius, echo
+
+
+def _frames(op, t, what):
+    if not torch.is_tensor(t):
+        raise RuntimeError(f"{op}: needs GPU tensors")
+    _need_gpu(t)
+    if t.dtype != torch.float32 or t.dim() < 2:
+        _unsupported(op, f"takes {what} as an fp32 tensor (..., H, W), got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def trec_motion(prev, last, value_scale, block, radius, echo, return_costs=False):
+    """prev / last: fp32 GPU tensors (..., H, W) of one shape, the last two frames of n samples -> int32 (n, nby, nbx, 2) on the device:
+    (vy, vx) per block of `block` x `block` pixels, last(y, x) ~ prev(y - vy, x - vx), by block matching over [-radius, radius]^2 on the
+    fields quantised as adnm_eval_counts quantises them (include/adnm_hip.h: adnm_trec_motion).  return_costs: -> (motion, the cost tables
+    as int32 (n, nby, nbx, 2 radius + 1, 2 radius + 1))."""
+    p, l = _frames("trec_motion", prev, "prev"), _frames("trec_motion", last, "last")
+    if p.shape != l.shape or p.device != l.device:
+        _unsupported("trec_motion", f"takes two fp32 tensors (..., H, W) of one shape, got {tuple(prev.shape)} and {tuple(last.shape)}")
+    H, W = l.shape[-2:]
+    n = l.numel() // (H * W) if H * W else 0
+    block, radius, echo = int(block), int(radius), int(echo)
+    nb = lib.query("adnm_trec_ws_bytes", n, H, W, block, radius)
+    if nb < 0:
+        raise RuntimeError(f"trec_motion: {n} samples of {H} x {W} with block {block} and radius {radius} are outside adnm_trec_motion's limits "
+                           "(1 <= samples <= 65535, H and W < 32768, H*W < 2^24, block 8 / 16 / 32, radius 1..8)")
+    nby, nbx, D = -(-H // block), -(-W // block), 2 * radius + 1
+    motion = torch.empty((n, nby, nbx, 2), dtype=torch.int32, device=l.device)
+    costs = torch.empty((n, nby, nbx, D, D), dtype=torch.int32, device=l.device) if return_costs else None
+    ws = _ws(nb, l.device)
+    lib.call("adnm_trec_motion", p.data_ptr(), l.data_ptr(), H * W, motion.data_ptr(), None if costs is None else costs.data_ptr(), float(value_scale),
+             block, radius, echo, ws.data_ptr(), int(nb), n, H, W, _stream())
+    return (motion, costs) if return_costs else motion
+
+
+def advect(last, motion, block, T):
+    """last: fp32 GPU tensor (..., H, W), n samples; motion: int32 (n, nby, nbx, 2) of trec_motion at the same `block` -> fp32 (n, T, H, W):
+    frame t is `last` moved t + 1 times along its block's vector, last[y - (t+1) vy, x - (t+1) vx] bit for bit, +0.0 where that lies outside
+    the frame (include/adnm_hip.h: adnm_advect)."""
+    l = _frames("advect", last, "last")
+    H, W = l.shape[-2:]
+    n = l.numel() // (H * W) if H * W else 0
+    block, T = int(block), int(T)
+    if lib.query("adnm_trec_ws_bytes", n, H, W, block, 1) < 0 or T < 1:
+        raise RuntimeError(f"advect: {n} samples of {H} x {W} with block {block} and T {T} are outside adnm_advect's limits "
+                           "(1 <= samples <= 65535, H and W < 32768, H*W < 2^24, block 8 / 16 / 32, T >= 1)")
+    shape = (n, -(-H // block), -(-W // block), 2)
+    if not torch.is_tensor(motion) or motion.dtype != torch.int32 or tuple(motion.shape) != shape or motion.device != l.device:
+        _unsupported("advect", f"takes the motion as an int32 tensor {shape} on {l.device}, got "
+                               f"{(motion.dtype, tuple(motion.shape), motion.device) if torch.is_tensor(motion) else type(motion).__name__}")
+    m = motion.contiguous()
+    out = torch.empty((n, T, H, W), dtype=torch.float32, device=l.device)
+    lib.call("adnm_advect", l.data_ptr(), H * W, m.data_ptr(), out.data_ptr(), block, n, T, H, W, _stream())
+    return out
+
+
 # ======================================================================================= the output side (csrc/dataio.hip: forecast_render)
 def edges_up_f32(edges):
     """double edges -> float32, each rounded UP to the smallest float >= it: the kernel compares an fp32 value with fp32 edges where

@@ -22,6 +22,10 @@ Validator(..., fss=(1, 5, 17, 33)) adds the Fractions Skill Score per scale and 
 adds the integer sums A = sum c_o^2, F = sum c_f^2, C = sum c_o c_f of the windowed event counts into tables that follow the pooled
 ones (the forecast's, then with persistence the baseline's), and done() reports FSS = 2C / (A + F) from the summed rows.
 
+Validator(..., advection=True) adds the Lagrangian-persistence baseline (DESIGN.md §4j): csrc/advect.hip::trec_cost / trec_pick estimate one
+motion vector per block from the last two input frames, advect moves the last frame along it for every frame index, and that field is
+scored as a second baseline by the same pooled and FSS passes, into two tables APPENDED to the block (pooled, then FSS).
+
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
@@ -65,6 +69,13 @@ def fss_doubles(seq_len, nthr, fss=(), persistence=False):
     return cell, cell if persistence else 0
 
 
+def advection_doubles(seq_len, nthr, pools=(), fss=(), advection=False):
+    """-> (doubles of the advection baseline's pooled table, of its FSS table): they follow fss_doubles' two parts in the ONE allocation"""
+    if not advection:
+        return 0, 0
+    return seq_len * 4 * nthr * len(baseline_pools(pools)), seq_len * len(fss) * 3 * nthr
+
+
 def _fss(sums):
     """(..., 3 * nthr) sums A, F, C -> (..., nthr) FSS = 2C / (A + F); NaN where A + F = 0 (no event in either field)"""
     sums = np.asarray(sums, dtype=np.float64)
@@ -104,23 +115,26 @@ def _lead_scores(rows, thresholds):
     return metrics
 
 
-def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=()):
+def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False):
     """host: the block (a float64 array of HEADER + T * (4*nthr + 3) values; with `pools` (size, stride) pairs then the forecast's pooled
     table (T, npool, 4*nthr), with `persistence` then the baseline's (T, len(baseline_pools(pools)), 4*nthr): include/adnm_hip.h) -> the
     dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's (Shanghai_metrics.py:218-290) as GpuEvaluator.done()
     states them, from per-frame-index sums; "pooled", "persistence" and "per_lead" apply the same formulas to the pooled tables, the
     baseline's tables and the single rows.  With `fss` (odd scales) the forecast's FSS table (T, nscale, 3*nthr) follows, with
     `persistence` then the baseline's: "fss" {n: {thr: 2C / (A + F)}}, "fss_useful" {thr: 0.5 + f_o / 2} with f_o the observed event
-    fraction of the main table (the line above which a scale is called useful), and "fss" under "persistence" and "per_lead"."""
+    fraction of the main table (the line above which a scale is called useful), and "fss" under "persistence" and "per_lead".  With
+    `advection` two more tables close the block, the advected field's pooled table (T, len(baseline_pools(pools)), 4*nthr) and, with
+    `fss`, its FSS table: "advection" and "per_lead"/"advection", built like "persistence"."""
     nthr, T = len(thresholds), seq_len
     pools, fss = tuple(pools), tuple(fss)
     base = baseline_pools(pools) if persistence else ()
     n0, n1, n2 = block_doubles(T, nthr, pools, persistence)
     n3, n4 = fss_doubles(T, nthr, fss, persistence)
+    n5, n6 = advection_doubles(T, nthr, pools, fss, advection)
     blk = np.asarray(block, dtype=np.float64)
-    if blk.shape != (n0 + n1 + n2 + n3 + n4,):
-        raise ValueError(f"aggregate: a block of {n0 + n1 + n2 + n3 + n4} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
-                         f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + f"; got {blk.shape}")
+    if blk.shape != (n0 + n1 + n2 + n3 + n4 + n5 + n6,):
+        raise ValueError(f"aggregate: a block of {n0 + n1 + n2 + n3 + n4 + n5 + n6} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
+                         f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + (", advection" if advection else "") + f"; got {blk.shape}")
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
     tab = blk[HEADER:n0].reshape(T, 4 * nthr + 3)
     metrics, all_far = contingency_metrics(tab[:, :4 * nthr].sum(axis=0), thresholds)
@@ -136,7 +150,11 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     ftab = blk[n0:n0 + n1].reshape(T, len(pools), 4 * nthr)
     btab = blk[n0 + n1:n0 + n1 + n2].reshape(T, len(base), 4 * nthr)
     fss_f = blk[n0 + n1 + n2:n0 + n1 + n2 + n3].reshape(T, len(fss), 3 * nthr)
-    fss_b = blk[n0 + n1 + n2 + n3:].reshape(T, len(fss) if persistence else 0, 3 * nthr)
+    at = n0 + n1 + n2 + n3 + n4
+    fss_b = blk[n0 + n1 + n2 + n3:at].reshape(T, len(fss) if persistence else 0, 3 * nthr)
+    apools = baseline_pools(pools) if advection else ()
+    atab = blk[at:at + n5].reshape(T, len(apools), 4 * nthr)
+    fss_a = blk[at + n5:].reshape(T, len(fss) if advection else 0, 3 * nthr)
     if pools:
         res["pooled"] = {p: _scores(ftab[:, i].sum(axis=0), thresholds) for i, p in enumerate(pools)}
     if persistence:
@@ -149,6 +167,11 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
             res["fss_useful"] = {_thr_key(thr): float(0.5 + (cells[4 * k] + cells[4 * k + 1]) / cells[4 * k:4 * k + 4].sum() / 2.0) for k, thr in enumerate(thresholds)}
         if persistence:
             res["persistence"]["fss"] = _fss_scores(fss_b, fss, thresholds)
+    if advection:
+        res["advection"] = dict(_scores(atab[:, 0].sum(axis=0), thresholds),
+                                pooled={p: _scores(atab[:, apools.index(p)].sum(axis=0), thresholds) for p in pools})
+        if fss:
+            res["advection"]["fss"] = _fss_scores(fss_a, fss, thresholds)
     if per_lead:
         with np.errstate(divide="ignore", invalid="ignore"):
             lead = {"RMSE": np.sqrt(mse_t), "MAE": tab[:, 4 * nthr] / (hw * samples),
@@ -163,13 +186,18 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
             lead["fss"] = _fss_lead(fss_f, fss, thresholds)
             if persistence:
                 lead["persistence"]["fss"] = _fss_lead(fss_b, fss, thresholds)
+        if advection:
+            lead["advection"] = {"threshold_metrics": _lead_scores(atab[:, 0], thresholds),
+                                 "pooled": {p: {"threshold_metrics": _lead_scores(atab[:, apools.index(p)], thresholds)} for p in pools}}
+            if fss:
+                lead["advection"]["fss"] = _fss_lead(fss_a, fss, thresholds)
         res["per_lead"] = lead
     return res
 
 
 class Validator(ForwardClient):
     def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False,
-                 fss=None):
+                 fss=None, advection=None):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -190,6 +218,12 @@ class Validator(ForwardClient):
         self.fss = ops.fss_scales(fss)   # distinct odd scales <= 33; ValueError on a bad entry
         # the FSS passes, the forecast's first: their tables follow the pooled ones in this order
         self._fss_passes = (["pred"] + (["last"] if self.persistence else [])) if self.fss else []
+        self.advection = ops.advection_spec(advection, self.thresholds)   # (block, radius, echo) or None; ValueError on a bad entry
+        if self.advection and len(baseline_pools(self.pools)) > ops.MAX_POOLS:
+            raise ValueError(f"Validator: the advection baseline is scored at (1, 1) and at every pool, which makes {len(self.pools) + 1} pools; "
+                             f"a pass takes {ops.MAX_POOLS} (give (1, 1) among the pools, or one pool fewer)")
+        if self.advection and not 0.0 < self.value_scale <= 255.0:
+            raise ValueError(f"Validator: advection matches blocks on quantised bytes, which needs 0 < value_scale <= 255, got {self.value_scale}")
         self._thr = (ctypes.c_float * len(self.thresholds))(*self.thresholds)
         self._fwd = GraphedForward(model, client=self, keep_quant=True)
         self._block = self._last = None    # the epoch's accumulator block and the last batch's fp32 loss: they outlive the graphs
@@ -201,7 +235,8 @@ class Validator(ForwardClient):
         if self._block is None:
             n = lib.query("adnm_valid_block_bytes", self.seq_len, len(self.thresholds))
             parts = (block_doubles(self.seq_len, len(self.thresholds), self.pools, self.persistence)
-                     + fss_doubles(self.seq_len, len(self.thresholds), self.fss, self.persistence))
+                     + fss_doubles(self.seq_len, len(self.thresholds), self.fss, self.persistence)
+                     + advection_doubles(self.seq_len, len(self.thresholds), self.pools, self.fss, self.advection))
             assert n == 8 * parts[0]
             self._block = torch.zeros(sum(parts), dtype=torch.float64, device=device)
             self._last = torch.zeros((), dtype=torch.float32, device=device)
@@ -234,6 +269,19 @@ class Validator(ForwardClient):
             lib.call("adnm_valid_fss_accum", src, strides[0], strides[1], ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
                      ops.fss_table(self.fss), len(self.fss), ent["ws_fss"].data_ptr(), ent["ws_fss"].numel(), B * T, T, H, W, stream)
             table += 8 * T * len(self.fss) * 3 * nthr
+        if self.advection:   # the advected field behind every pass that is there without it: its two tables close the block
+            block_px, radius, echo = self.advection
+            t_in, adv = sx.shape[1], ent["adv"]
+            lib.call("adnm_trec_motion", sx.data_ptr() + 4 * (t_in - 2) * H * W, sx.data_ptr() + 4 * (t_in - 1) * H * W, t_in * H * W, ent["motion"].data_ptr(),
+                     None, self.value_scale, block_px, radius, echo, ent["ws_trec"].data_ptr(), ent["ws_trec"].numel(), B, H, W, stream)
+            lib.call("adnm_advect", sx.data_ptr() + 4 * (t_in - 1) * H * W, t_in * H * W, ent["motion"].data_ptr(), adv.data_ptr(), block_px, B, T, H, W, stream)
+            pools = baseline_pools(self.pools)
+            lib.call("adnm_valid_pool_accum", adv.data_ptr(), T * H * W, H * W, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
+                     ops.pool_table(pools), len(pools), ent["ws_pool"].data_ptr(), ent["ws_pool"].numel(), B * T, T, H, W, stream)
+            table += 8 * T * len(pools) * 4 * nthr
+            if self.fss:
+                lib.call("adnm_valid_fss_accum", adv.data_ptr(), T * H * W, H * W, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
+                         ops.fss_table(self.fss), len(self.fss), ent["ws_fss"].data_ptr(), ent["ws_fss"].numel(), B * T, T, H, W, stream)
 
     # ---- ForwardClient: what GraphedForward calls with the entry of one input shape
     def open(self, ent, x):
@@ -248,8 +296,9 @@ class Validator(ForwardClient):
         if self.ssim and H > 10 and W > 10:   # 11 x 11 windows need a valid region; smaller frames: SSIM is None
             ws_ssim = torch.empty(max(int(lib.query("adnm_valid_ssim_accum_ws_bytes", B * T, T, H, W, nthr)), 16), dtype=torch.uint8, device=dev)
         ws_pool = None
-        if self._passes:
-            need = [lib.query("adnm_valid_pool_accum_ws_bytes", B * T, T, H, W, nthr, ops.pool_table(pools), len(pools)) for _, pools in self._passes]
+        passes = [pools for _, pools in self._passes] + ([baseline_pools(self.pools)] if self.advection else [])
+        if passes:
+            need = [lib.query("adnm_valid_pool_accum_ws_bytes", B * T, T, H, W, nthr, ops.pool_table(pools), len(pools)) for pools in passes]
             if min(need) < 0:
                 raise RuntimeError(f"Validator: pools {self.pools} on {B * T} frames of {H} x {W} are outside adnm_valid_pool_accum's limits "
                                    "(no window larger than the frame, H and W < 32768)")
@@ -260,14 +309,27 @@ class Validator(ForwardClient):
             if need < 0:
                 raise RuntimeError(f"Validator: fss on {B * T} frames of {H} x {W} is outside adnm_valid_fss_accum's limits (H and W < 32768)")
             ws_fss = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)   # the passes follow one another on one stream: one workspace
-        if self.persistence:
-            sx = ent["sx"]
+        if self.persistence or self.advection:
+            sx, what = ent["sx"], "persistence" if self.persistence else "advection"
             if (sx.dtype != torch.float32 or sx.dim() not in (4, 5) or (sx.dim() == 5 and sx.shape[2] != 1) or tuple(sx.shape[-2:]) != (H, W)
                     or sx.shape[1] < 1 or not sx.is_contiguous()):
-                raise RuntimeError(f"Validator: persistence needs the model's input as contiguous fp32 (B, T_in, 1, H, W) or (B, T_in, H, W) with the "
+                raise RuntimeError(f"Validator: {what} needs the model's input as contiguous fp32 (B, T_in, 1, H, W) or (B, T_in, H, W) with the "
                                    f"target's {H} x {W} frames, got {sx.dtype} {tuple(sx.shape)}")
+        adv = motion = ws_trec = None
+        if self.advection:
+            if ent["sx"].shape[1] < 2:
+                raise RuntimeError(f"Validator: advection estimates the motion from the last two input frames, the input has {ent['sx'].shape[1]}")
+            block_px, radius, _ = self.advection
+            need = lib.query("adnm_trec_ws_bytes", B, H, W, block_px, radius)
+            if need < 0:
+                raise RuntimeError(f"Validator: advection on {B} samples of {H} x {W} is outside adnm_trec_motion's limits (samples <= 65535, H and W < 32768, "
+                                   "H*W < 2^24)")
+            adv = torch.zeros(shape, dtype=torch.float32, device=dev)
+            motion = torch.zeros((B, -(-H // block_px), -(-W // block_px), 2), dtype=torch.int32, device=dev)
+            ws_trec = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=torch.empty(max(int(nb), 16), dtype=torch.uint8, device=dev),
-                   ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss, loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
+                   ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss, adv=adv, motion=motion, ws_trec=ws_trec,
+                   loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
         self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
 
@@ -324,6 +386,14 @@ class Validator(ForwardClient):
         feed.fetch_into(ent["sx"], ent["tgt"])
         return self._fwd.replay(ent, ent["sx"])["out"]
 
+    def advected(self, x):
+        """the advected forecast of the last batch of x's shape: the graph's static fp32 (B, T, H, W) tensor, valid until the next step
+        of that shape (Forecaster.render can colour it)"""
+        ent = self._fwd._graphs.get((tuple(x.shape), x.dtype, x.device))
+        if not self.advection or ent is None or ent.get("adv") is None:
+            raise RuntimeError("Validator.advected: needs advection= and a step() on an input of this shape, dtype and device first")
+        return ent["adv"]
+
     @property
     def last_loss(self):
         """the fp32 loss of the last batch: a 0-dim device tensor (reading it synchronises; the epoch's sum is in done())"""
@@ -338,7 +408,9 @@ class Validator(ForwardClient):
         scored on the same batches.  per_lead=True: plus "per_lead": length-T arrays "RMSE", "MAE", "SSIM" (or None) and
         "threshold_metrics"[thr][TP | FN | FP | TN | CSI | POD | FAR | HSS], and the same under "pooled" / "persistence" where those exist.
         fss: plus "fss": {n: {thr: FSS}} (NaN where neither field has an event), "fss_useful": {thr: 0.5 + f_o / 2}, and "fss" under
-        "persistence" and, as length-T arrays, under "per_lead" and "per_lead"/"persistence" where those exist."""
+        "persistence" and, as length-T arrays, under "per_lead" and "per_lead"/"persistence" where those exist.
+        advection: plus "advection" and "per_lead"/"advection", built like "persistence": the last input frame moved along its
+        block-matched motion, scored on the same batches."""
         if self._block is None or self._frame is None:
             raise RuntimeError("Validator.done: no batch since the last reset")
         blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
@@ -346,7 +418,7 @@ class Validator(ForwardClient):
         H, W = self._frame
         area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
         res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead,
-                        fss=self.fss)
+                        fss=self.fss, advection=bool(self.advection))
         if reset:
             self.reset()
         return res

@@ -43,10 +43,8 @@ struct Thr {
   int n;
 };
 
-// The quantisation of a field value, stated ONCE for every kernel that counts events (EvalAcc::add and pool_bits below):
-// q(v) = floorf(fminf(fmaxf(v, 0), 1) * value_scale) in fp32 (Shanghai_metrics.py:45-47).  NaN -> 0 (fmaxf), -Inf -> 0, +Inf -> floor(scale).
-__device__ __forceinline__ float eval_scaled(float v, float value_scale) { return fminf(fmaxf(v, 0.f), 1.f) * value_scale; }
-__device__ __forceinline__ float eval_trunc(float scaled) { return floorf(scaled); }   // .astype(np.uint16) of a non-negative float: truncation
+// The quantisation of a field value q(v): eval_scaled / eval_trunc of adnm_common.h, stated ONCE for every kernel that counts events
+// (EvalAcc::add and pool_bits below) or matches blocks (advect.hip).
 
 // One lane's share of a frame's contingency counts and error sums, and the workgroup's fold of it: the arithmetic of eval_counts, stated
 // ONCE for eval_counts_kernel and valid_accum_kernel (the validation epoch's accumulating pass) so that their counts cannot drift apart.

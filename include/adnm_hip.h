@@ -713,6 +713,43 @@ int adnm_valid_fss_accum(const float* pred, int64_t pred_sample_stride, int64_t 
                          const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* scales_host, int64_t nscale, void* ws,
                          int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
 
+/* The Lagrangian-persistence (advection) baseline: block-matched motion between the last two input frames (TREC, Rinehart & Garvey 1978)
+ * and the last frame moved along it.  The reference has none; the definitions are this project's.  Integer arithmetic and
+ * bit copies only: exact and bit-reproducible.
+ *   quantisation  q(v): adnm_eval_counts' device function, the one adnm_valid_pool_accum uses.  value_scale <= 255, so q fits a byte.
+ *   frames        prev, last: the last two input frames of a sample (x[:, T_in - 2], x[:, T_in - 1]), contiguous H x W fp32 each, given
+ *                 by two base addresses and ONE sample stride in elements (slices of a (B, T_in, H, W) input: stride T_in*H*W).
+ *   blocks        block in {8, 16, 32} tiles the frame from the top-left: nby = ceil(H / block), nbx = ceil(W / block); edge blocks are
+ *                 clipped to the frame.
+ *   cost          radius R in 1..8.  cost_b(dy, dx) = SUM |q(last)(y, x) - q(prev)(y - dy, x - dx)| for (dy, dx) in [-R, R]^2, over the
+ *                 pixels (y, x) of block b inside the frame; q(prev) is 0 outside the frame.  uint32, at most 32*32*255.
+ *   pick          the vector of a table: the (dy, dx) that minimises (cost, dy^2 + dx^2, dy, dx) lexicographically — an all-zero block and
+ *                 every tie fall towards (0, 0) in a fixed order.
+ *   global vector g = the pick of SUM_b cost_b (blocks tile the frame: the whole-frame SAD), summed in 64 bits.
+ *   valid blocks  a block is valid when at least `block` of its in-frame pixels have q(last) >= echo (1..255).  A valid block takes its
+ *                 own pick, an invalid one takes g (an echo could otherwise never be advected into an empty block).
+ *   motion        int32 (samples, nby, nbx, 2) holding (vy, vx); last(y, x) ~ prev(y - vy, x - vx): the echo moves by +v per frame interval.
+ *   advection     backward, semi-Lagrangian, piecewise constant: out[s, t, y, x] = last[s, y - (t+1) vy, x - (t+1) vx] with v of the block
+ *                 (y / block, x / block); +0.0f where the source lies outside the frame; otherwise the fp32 BIT PATTERN of last (NaN and Inf
+ *                 included, nothing is rounded).  Frame index t is lead t + 1 at the input's own frame spacing.
+ * adnm_trec_motion: two launches.  trec_cost, one workgroup per (block, sample), stages the block and the (block + 2R)^2 window once as
+ *   quantised bytes, four to a dword, and forms the (2R+1)^2 sums from packed dwords (v_alignbyte_b32, v_sad_u8); the tables and the echo
+ *   counts go to ws (adnm_trec_ws_bytes, every byte written).  trec_pick, one workgroup per sample, sums the tables in block order, picks
+ *   g and per block, applies validity and writes motion; cost_out (or NULL): uint32 (samples, nby, nbx, 2R+1, 2R+1), the tables, row dy + R,
+ *   column dx + R.  Aligned shapes (W and the stride multiples of 4, both bases 16-byte aligned) are read 16 bytes per access, all others
+ *   float by float: same result.
+ * adnm_advect: one launch; out contiguous fp32 (samples, T, H, W), stored 16 bytes per access when W % 4 == 0 and out is 16-byte aligned.
+ * All arguments are passed by value: the calls can be captured.
+ * Limits, refused before any launch (ADNM_EINVAL): a null pointer other than cost_out; prev / last / out / motion / cost_out not 4-byte
+ *   aligned; block outside {8, 16, 32}; radius outside 1..8; echo outside 1..255; value_scale not in (0, 255]; samples outside 1..65535;
+ *   T < 1; H or W outside [1, 32768); H*W >= 2^24; sample_stride < H*W.  adnm_trec_ws_bytes returns -1. */
+int64_t adnm_trec_ws_bytes(int64_t samples, int64_t H, int64_t W, int64_t block, int64_t radius);
+int adnm_trec_motion(const float* prev, const float* last, int64_t sample_stride, void* motion_i32, void* cost_out_u32_or_null, float value_scale,
+                     int64_t block, int64_t radius, int64_t echo, void* ws, int64_t ws_bytes, int64_t samples, int64_t H, int64_t W,
+                     adnm_stream_t stream);
+int adnm_advect(const float* last, int64_t sample_stride, const void* motion_i32, float* out, int64_t block, int64_t samples, int64_t T, int64_t H,
+                int64_t W, adnm_stream_t stream);
+
 /* The output side (pic_results.py:104-184 of the reference): a forecast as the bytes a consumer keeps, in ONE launch.
  * adnm_forecast_render: pred contiguous fp32 (B, T, H, W), 4-byte aligned.  fields: (B, T, H, W) uint8 or NULL.  strip: (B, H, Ws, 4) uint8
  *   (RGBA, 4-byte aligned) or NULL, Ws = n*W + (n-1)*gap, holding the n = ceil((T - frame_start) / frame_step) frames frame_start,
