@@ -423,7 +423,7 @@ class FoldRegistry:
 
     def active(self, device, on=True):
         """with FOLDS.active(dev): ... — deferral is on for the kernels launched inside (from any thread: autograd runs backward on
-        its own), the queue is flushed on the way out.  Scoped in time, so plain autograd users of the device are never deferred."""
+        its own), the queue is flushed on the way out (dropped, see abort(), when the body raises).  Scoped in time, so plain autograd users of the device are never deferred."""
         return _Active(self, device, on)
 
     def deferring(self, device):
@@ -491,7 +491,12 @@ class _Active:
 
     def __exit__(self, *exc):
         if self.on:
-            self.reg.enable(self.device, False)   # flushes
+            if exc[0] is not None:
+                # the body raised between push and flush: what is queued (whole leaf launches, not only folds) is dropped, not launched —
+                # the pass that wanted the results is gone, and a flush into a failed capture would hide the body's own error
+                self.reg.abort(self.device)
+            else:
+                self.reg.enable(self.device, False)   # flushes
         return False
 
 
@@ -2520,7 +2525,8 @@ class Conv3Fn(torch.autograd.Function):
         nb = lib.query("adnm_conv3_wgrad_ws_bytes", B, H, W, K, N)
         wsb = _ws(nb, dev)
         prec = 1 if MFMA_PREC[0] == 2 or QUANT.calibrating else MFMA_PREC[0]   # fp8 configuration: bf16 operands here
-        with FOLDS.defer(dev, wsb):
+        # (the operands stay referenced until the flush: under the leaf queue the launch itself is deferred, not just its fold)
+        with FOLDS.defer(dev, wsb, dy2, x2):
             lib.call("adnm_conv3_wgrad", dy2.data_ptr(), dy2.stride(0), x2.data_ptr(), x2.stride(0), g.data_ptr(), _p(db), wsb.data_ptr(), nb,
                      B, H, W, K, N, prec, _stream())
         return dx, g, db, None, None, None

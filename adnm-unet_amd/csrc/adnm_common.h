@@ -52,11 +52,21 @@ struct AdnmLeaf {
   double bytes;
   alignas(16) unsigned char args[200];
 };
-enum { ADNM_LEAF_SKGEMM_TN = 0, ADNM_LEAF_DWCONV_WGRAD_K3 = 1, ADNM_LEAF_DWCONV_WGRAD_K5 = 2, ADNM_LEAF_TSGEMM_TN = 3, ADNM_LEAF_KINDS = 4 };
+enum {
+  ADNM_LEAF_SKGEMM_TN = 0, ADNM_LEAF_DWCONV_WGRAD_K3 = 1, ADNM_LEAF_DWCONV_WGRAD_K5 = 2, ADNM_LEAF_TSGEMM_TN = 3,
+  ADNM_LEAF_DWCONV_WALK3 = 4,   // the 3x3 column walker (dwconv.hip: maps of 128 x 128 pixels and more)
+  ADNM_LEAF_CONV3_WGRAD = 5,    // the dense 3x3 conv's weight gradient (conv3.hip); prec = its MFMA precision, one launch per (NB, PREC)
+  ADNM_LEAF_COLSUM = 6,         // the tall column sum's first stage (core.hip: colsum_partial_kernel)
+  ADNM_LEAF_KINDS = 7
+};
 bool adnm_leafq_active();                                                    // would a push be queued?
-bool adnm_leafq_push(const AdnmLeaf& leaf);                                  // false: no queue bound on this thread (launch now)
+// false: launch now — no queue bound on this thread, or the kind is sent back inline by the measurement aid ADNM_LEAF_INLINE (a bit mask
+// over the kinds above, read at every push: 112 = the walker, conv3 and colsum).  Meant for the kinds whose plan ignores the queue (4 .. 6).
+bool adnm_leafq_push(const AdnmLeaf& leaf);
 int adnm_skgemm_tn_launch_multi(const AdnmLeaf* const* items, int n, hipStream_t st);   // skgemm.hip
 int adnm_dwconv_wgrad_launch_multi(const AdnmLeaf* const* items, int n, int K, hipStream_t st);   // dwconv.hip
+int adnm_dwconv_walk3_launch_multi(const AdnmLeaf* const* items, int n, hipStream_t st);   // dwconv.hip
+int adnm_conv3_wgrad_launch_multi(const AdnmLeaf* const* items, int n, hipStream_t st);   // conv3.hip
 int adnm_tsgemm_tn_launch_multi(const AdnmLeaf* const* items, int n, hipStream_t st);   // tsgemm.hip
 
 // Launch GROUP (core.hip, include/adnm_hip.h: adnm_group_*).  Between adnm_group_begin and adnm_group_launch the calling thread makes

@@ -20,6 +20,7 @@
 //   * wgrad: each WAVE owns a quarter of the tile's pixels and all 9 taps x up to 64 output channels x 16 input channels as
 //     register accumulators; per-wave partial rows + the shared deterministic fold (batchable: a parameter gradient).
 #include "adnm_common.h"
+#include <vector>
 
 namespace {
 
@@ -354,15 +355,16 @@ struct WgArgs {
   int vec_in, vec_do;
 };
 
+// (bx, by, bz): the workgroup's index inside its problem (row band, input-channel chunk, output-channel group); gdx: that problem's band count
 template <int NB, int PREC>   // PREC: fp32 or bf16 (the fp8 configuration keeps bf16 operands for the weight gradient)
-__global__ __launch_bounds__(kBlock) void conv3_wgrad_kernel(WgArgs a) {
+__device__ __forceinline__ void conv3_wgrad_body(const WgArgs& a, const int bx, const int by, const int bz, const int gdx) {
   constexpr int DP = NB * 16 + 16;   // pitch of a dpre pixel row: (DP mod 32) == 16 -> conflict-free A-operand reads
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int TWp = a.TW + 2;
   float* sIn = smem;
   float* sD = smem + (a.TH + 2) * TWp * CKP;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, kk = lane >> 4;
-  const int c0 = blockIdx.y * CK, n0 = blockIdx.z * NB * 16;
+  const int c0 = by * CK, n0 = bz * NB * 16;
   f32x4 acc[9][NB];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
@@ -414,12 +416,12 @@ __global__ __launch_bounds__(kBlock) void conv3_wgrad_kernel(WgArgs a) {
       *reinterpret_cast<float4*>(sD + pxl * DP + 4 * q) = make_float4(rd[u][0], rd[u][1], rd[u][2], rd[u][3]);
     }
   };
-  if ((int)blockIdx.x < a.ntiles) load_tile(blockIdx.x);
-  for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+  if (bx < a.ntiles) load_tile(bx);
+  for (int tile = bx; tile < a.ntiles; tile += gdx) {
     __syncthreads();   // every wave has finished reading the previous tile's LDS images
     store_tile();
     __syncthreads();
-    if (tile + (int)gridDim.x < a.ntiles) load_tile(tile + gridDim.x);   // in flight under this tile's MFMAs
+    if (tile + gdx < a.ntiles) load_tile(tile + gdx);   // in flight under this tile's MFMAs
     // reduction = the pixels of the wave's MB = 2 pixel blocks: lane (., kk) takes pixels 4 kk .. 4 kk + 3 of each (step e) — 8 per lane =
     // one 32-step MFMA group
     static_assert(MB == 2, "the weight-gradient step pairs the wave's two pixel blocks");
@@ -448,7 +450,7 @@ __global__ __launch_bounds__(kBlock) void conv3_wgrad_kernel(WgArgs a) {
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) acc[tap][nb] = adnm_mma<PREC, false, false>(fa[nb], fb, acc[tap][nb]);
     }
-    if (a.want_bias && blockIdx.y == 0 && lane < NB * 16) {
+    if (a.want_bias && by == 0 && lane < NB * 16) {
 #pragma unroll 8
       for (int p = 0; p < MB * 16; ++p) bsum += sD[(wave * MB * 16 + p) * DP + lane];
     }
@@ -466,18 +468,50 @@ __global__ __launch_bounds__(kBlock) void conv3_wgrad_kernel(WgArgs a) {
       for (int r = 0; r < 4; ++r) red[(wave * (kPer + 1) + (tap * NB + nb) * 4 + r) * 64 + lane] = acc[tap][nb][r];
   red[(wave * (kPer + 1) + kPer) * 64 + lane] = bsum;
   __syncthreads();
-  float* dst = a.part + (int64_t)blockIdx.x * a.rowlen;
+  float* dst = a.part + (int64_t)bx * a.rowlen;
   for (int e = threadIdx.x; e < (kPer + 1) * 64; e += kBlock) {
     const float v = (red[e] + red[(kPer + 1) * 64 + e]) + (red[2 * (kPer + 1) * 64 + e] + red[3 * (kPer + 1) * 64 + e]);
     const int slot = e >> 6, ln = e & 63;
     if (slot == kPer) {
-      if (a.want_bias && blockIdx.y == 0 && ln < NB * 16 && n0 + ln < a.N) dst[(int64_t)a.N * 9 * a.K + n0 + ln] = v;
+      if (a.want_bias && by == 0 && ln < NB * 16 && n0 + ln < a.N) dst[(int64_t)a.N * 9 * a.K + n0 + ln] = v;
       continue;
     }
     const int r = slot & 3, nb = (slot >> 2) % NB, tap = slot / (4 * NB);
     const int n = n0 + nb * 16 + (ln >> 4) * 4 + r, k = c0 + (ln & 15);
     if (n < a.N && k < a.K) dst[((int64_t)n * 9 + tap) * a.K + k] = v;
   }
+}
+
+template <int NB, int PREC>
+__global__ __launch_bounds__(kBlock) void conv3_wgrad_kernel(WgArgs a) {
+  conv3_wgrad_body<NB, PREC>(a, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x);
+}
+
+// grouped form: the queued problems of one (NB, PREC) instantiation, kMaxWgLeaf per launch, descriptors in the kernel argument segment.
+// A problem keeps the grid of its single launch (gx row bands x gy input chunks x gz output groups), linearised x fastest.
+constexpr int kMaxWgLeaf = 16;
+struct Conv3WgLeaf {
+  WgArgs a;
+  int gx, gy, gz, smem;
+};
+struct MultiConv3Wg {
+  int blk_end[kMaxWgLeaf];   // inclusive prefix of the problems' workgroup counts (unused entries repeat the total)
+  Conv3WgLeaf p[kMaxWgLeaf];
+};
+static_assert(sizeof(MultiConv3Wg) <= 4096, "the descriptor table must fit the kernel argument segment");
+template <int NB, int PREC>
+__global__ __launch_bounds__(kBlock) void conv3_wgrad_multi_kernel(MultiConv3Wg by_value) {
+  (void)by_value;
+  const auto& m = *(const __attribute__((address_space(4))) MultiConv3Wg*)__builtin_amdgcn_kernarg_segment_ptr();
+  int k = 0;
+#pragma unroll
+  for (int i = 0; i < kMaxWgLeaf - 1; ++i) k += (int)blockIdx.x >= m.blk_end[i] ? 1 : 0;
+  const int lin = (int)blockIdx.x - (k ? m.blk_end[k - 1] : 0);
+  const auto& q = m.p[k].a;   // workgroup-uniform: scalar loads
+  const WgArgs a{q.dout, q.lddo, q.in, q.ldin, q.part, q.rowlen, q.want_bias, q.B, q.H, q.W, q.K, q.N, q.ntiles,
+                 q.TW, q.RB, q.TH, q.VR, q.tiles_x, q.vec_in, q.vec_do};
+  const int gx = m.p[k].gx, gy = m.p[k].gy;
+  conv3_wgrad_body<NB, PREC>(a, lin % gx, (lin / gx) % gy, lin / (gx * gy), gx);
 }
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -681,21 +715,60 @@ extern "C" int adnm_conv3_wgrad(const float* dout, int64_t lddo, const float* in
   size_t smem = sizeof(float) * ((size_t)(g.TH + 2) * (g.TW + 2) * CKP + (size_t)kTilePix * (p.nb * 16 + 16));
   const size_t red = sizeof(float) * (size_t)kWaves * (9 * p.nb * 4 + 1) * 64;   // the cross-wave sum reuses the same LDS
   if (smem < red) smem = red;
-  const dim3 grid((unsigned)p.rows, (unsigned)p.cichunks, (unsigned)p.cogroups);
-  {
-    ADNM_PROF("conv3_wgrad", st, 4.0 * ((double)B * H * W * (K + N) + 9.0 * K * N));
-#define WG(NBV, PRECV)                                                                        \
-  do {                                                                                        \
-    ADNM_ALLOW_LDS((conv3_wgrad_kernel<NBV, PRECV>), smem, "conv3_wgrad");                    \
-    conv3_wgrad_kernel<NBV, PRECV><<<grid, kBlock, smem, st>>>(a);                            \
-  } while (0)
-    if (p.nb == 2) { if (prec == ADNM_MFMA_BF16) WG(2, ADNM_MFMA_BF16); else WG(2, ADNM_MFMA_F32); }
-    else { if (prec == ADNM_MFMA_BF16) WG(1, ADNM_MFMA_BF16); else WG(1, ADNM_MFMA_F32); }
-#undef WG
+  // a leaf of the backward pass: under a bound leaf queue the launch waits for the grouped one, with the row bands (and so the partial
+  // rows) it has alone — plan_wgrad does not look at the queue; the caller keeps both operands and ws until the flush
+  static_assert(sizeof(Conv3WgLeaf) <= sizeof(AdnmLeaf::args), "Conv3WgLeaf must fit a leaf record");
+  const Conv3WgLeaf cl{a, p.rows, p.cichunks, p.cogroups, (int)smem};
+  AdnmLeaf leaf;
+  leaf.kind = ADNM_LEAF_CONV3_WGRAD, leaf.grid = p.rows * p.cichunks * p.cogroups, leaf.prec = p.nb * 16 + prec;   // the instantiation key
+  leaf.prof = "conv3_wgrad", leaf.bytes = 4.0 * ((double)B * H * W * (K + N) + 9.0 * K * N);
+  memcpy(leaf.args, &cl, sizeof(cl));
+  if (!adnm_leafq_push(leaf)) {
+    const AdnmLeaf* one = &leaf;
+    if (int rc = adnm_conv3_wgrad_launch_multi(&one, 1, st)) return rc;
   }
   ADNM_CHECK_LAUNCH("conv3_wgrad");
   adnm_launch_fold("conv3_wgrad_fold", (const float*)ws, p.rows, (int)p.rowlen, {dw, (int)(N * 9 * K)}, {dbias, dbias ? (int)N : 0}, {nullptr, 0},
                    {nullptr, 0}, st);
   ADNM_CHECK_LAUNCH("conv3_wgrad_fold");
+  return ADNM_OK;
+}
+
+// the queued dense-conv weight gradients: one launch per (NB, PREC) instantiation present (kMaxWgLeaf problems each at most), in the order
+// of first appearance; a group of one is the plain single-problem launch
+int adnm_conv3_wgrad_launch_multi(const AdnmLeaf* const* items, int n, hipStream_t st) {
+  std::vector<char> done((size_t)n, 0);
+  for (int i = 0; i < n; ++i) {
+    if (done[i]) continue;
+    const int key = items[i]->prec, nb = key / 16, prec = key % 16;
+    MultiConv3Wg m;
+    int count = 0, blocks = 0, smem = 0;
+    double bytes = 0;
+    for (int j = i; j < n && count < kMaxWgLeaf; ++j) {
+      if (done[j] || items[j]->prec != key) continue;
+      memcpy(&m.p[count], items[j]->args, sizeof(Conv3WgLeaf));
+      smem = m.p[count].smem > smem ? m.p[count].smem : smem;   // dynamic LDS: the largest any of the problems asks for
+      blocks += items[j]->grid;
+      m.blk_end[count++] = blocks;
+      bytes += items[j]->bytes;
+      done[j] = 1;
+    }
+    for (int k = count; k < kMaxWgLeaf; ++k) m.blk_end[k] = blocks, m.p[k] = m.p[0];
+    ADNM_PROF("conv3_wgrad", st, bytes);
+#define WG(NBV, PRECV)                                                                                                   \
+  do {                                                                                                                   \
+    if (count == 1) {                                                                                                    \
+      ADNM_ALLOW_LDS((conv3_wgrad_kernel<NBV, PRECV>), (size_t)smem, "conv3_wgrad");                                     \
+      conv3_wgrad_kernel<NBV, PRECV><<<dim3(m.p[0].gx, m.p[0].gy, m.p[0].gz), kBlock, (size_t)smem, st>>>(m.p[0].a);     \
+    } else {                                                                                                             \
+      ADNM_ALLOW_LDS((conv3_wgrad_multi_kernel<NBV, PRECV>), (size_t)smem, "conv3_wgrad");                               \
+      conv3_wgrad_multi_kernel<NBV, PRECV><<<(unsigned)blocks, kBlock, (size_t)smem, st>>>(m);                           \
+    }                                                                                                                    \
+  } while (0)
+    if (nb == 2) { if (prec == ADNM_MFMA_BF16) WG(2, ADNM_MFMA_BF16); else WG(2, ADNM_MFMA_F32); }
+    else { if (prec == ADNM_MFMA_BF16) WG(1, ADNM_MFMA_BF16); else WG(1, ADNM_MFMA_F32); }
+#undef WG
+  }
+  ADNM_CHECK_LAUNCH("conv3_wgrad");
   return ADNM_OK;
 }

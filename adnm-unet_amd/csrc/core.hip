@@ -490,6 +490,9 @@ thread_local LeafQueue* tls_leafq = nullptr;
 bool adnm_leafq_active() { return tls_leafq && tls_foldq; }
 bool adnm_leafq_push(const AdnmLeaf& leaf) {
   if (!tls_leafq || !tls_foldq) return false;   // (a leaf's partials are folded by a QUEUED fold: without the fold queue the order would break)
+  // measurement aid: ADNM_LEAF_INLINE = bit mask of kinds that launch where they are produced (read per push: an A/B on one build and process)
+  const char* e = getenv("ADNM_LEAF_INLINE");
+  if (e && ((atoi(e) >> leaf.kind) & 1)) return false;
   tls_leafq->items.push_back(leaf);
   return true;
 }
@@ -509,6 +512,7 @@ extern "C" int adnm_leafq_clear(void* q) {
   ((LeafQueue*)q)->items.clear();
   return ADNM_OK;
 }
+static int colsum_launch_multi(const AdnmLeaf* const* items, int n, hipStream_t st);   // below, beside its kernel
 extern "C" int adnm_leafq_flush(void* q, adnm_stream_t stream) {
   ADNM_REQUIRE(q, "leafq_flush: null queue");
   ADNM_REQUIRE(!tls_group.open, "leafq_flush: a launch group is open on this thread (its recorded launches may produce what the leaves read)");
@@ -522,6 +526,9 @@ extern "C" int adnm_leafq_flush(void* q, adnm_stream_t stream) {
     if (sel.empty()) continue;
     if (kind == ADNM_LEAF_SKGEMM_TN) rc = adnm_skgemm_tn_launch_multi(sel.data(), (int)sel.size(), (hipStream_t)stream);
     else if (kind == ADNM_LEAF_TSGEMM_TN) rc = adnm_tsgemm_tn_launch_multi(sel.data(), (int)sel.size(), (hipStream_t)stream);
+    else if (kind == ADNM_LEAF_DWCONV_WALK3) rc = adnm_dwconv_walk3_launch_multi(sel.data(), (int)sel.size(), (hipStream_t)stream);
+    else if (kind == ADNM_LEAF_CONV3_WGRAD) rc = adnm_conv3_wgrad_launch_multi(sel.data(), (int)sel.size(), (hipStream_t)stream);
+    else if (kind == ADNM_LEAF_COLSUM) rc = colsum_launch_multi(sel.data(), (int)sel.size(), (hipStream_t)stream);
     else rc = adnm_dwconv_wgrad_launch_multi(sel.data(), (int)sel.size(), kind == ADNM_LEAF_DWCONV_WGRAD_K3 ? 3 : 5, (hipStream_t)stream);
   }
   lq->items.clear();
@@ -533,12 +540,12 @@ extern "C" int adnm_leafq_flush(void* q, adnm_stream_t stream) {
 // contiguous band of rows (lanes along the columns, 256 / ncol row lanes, LDS tree), then the shared fold adds the bands.
 namespace {
 constexpr int kColsumThreads = 256, kColsumMinRows = 2048;
-__global__ __launch_bounds__(kColsumThreads) void colsum_partial_kernel(const float* __restrict__ x, float* __restrict__ part, int rows, int n, int band) {
+__device__ __forceinline__ void colsum_partial_body(const float* __restrict__ x, float* __restrict__ part, int rows, int n, int band, const int bx) {
   __shared__ float sm[kColsumThreads];
   int ncol = 1;
   while (ncol < n && ncol < kColsumThreads) ncol <<= 1;   // columns a workgroup pass covers (power of two >= n, or 256)
   const int lanes = kColsumThreads / ncol, cl = threadIdx.x & (ncol - 1), rl = threadIdx.x / ncol;
-  const int r0 = blockIdx.x * band, r1 = r0 + band < rows ? r0 + band : rows;
+  const int r0 = bx * band, r1 = r0 + band < rows ? r0 + band : rows;
   for (int c0 = 0; c0 < n; c0 += ncol) {
     const int c = c0 + cl;
     float a0 = 0.f, a1 = 0.f;
@@ -557,9 +564,32 @@ __global__ __launch_bounds__(kColsumThreads) void colsum_partial_kernel(const fl
       if (rl < h) sm[threadIdx.x] += sm[threadIdx.x + h * ncol];
       __syncthreads();
     }
-    if (rl == 0 && c < n) part[(int64_t)blockIdx.x * n + c] = sm[threadIdx.x];
+    if (rl == 0 && c < n) part[(int64_t)bx * n + c] = sm[threadIdx.x];
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(kColsumThreads) void colsum_partial_kernel(const float* __restrict__ x, float* __restrict__ part, int rows, int n, int band) {
+  colsum_partial_body(x, part, rows, n, band, (int)blockIdx.x);
+}
+// grouped form: the queued problems of a flush, kMaxColsum per launch, descriptors in the kernel argument segment; every problem keeps
+// the row bands (and so the partial rows) of its single launch
+constexpr int kMaxColsum = 16;
+struct ColsumLeaf {
+  const float* x;
+  float* part;
+  int rows, n, band;
+};
+struct MultiColsum {
+  int blk_end[kMaxColsum];   // inclusive prefix of the problems' workgroup counts (unused entries repeat the total)
+  ColsumLeaf p[kMaxColsum];
+};
+__global__ __launch_bounds__(kColsumThreads) void colsum_partial_multi_kernel(MultiColsum by_value) {
+  (void)by_value;
+  const auto& m = *(const __attribute__((address_space(4))) MultiColsum*)__builtin_amdgcn_kernarg_segment_ptr();
+  int k = 0;
+#pragma unroll
+  for (int i = 0; i < kMaxColsum - 1; ++i) k += (int)blockIdx.x >= m.blk_end[i] ? 1 : 0;
+  colsum_partial_body(m.p[k].x, m.p[k].part, m.p[k].rows, m.p[k].n, m.p[k].band, (int)blockIdx.x - (k ? m.blk_end[k - 1] : 0));
 }
 int colsum_bands(int64_t rows) { return rows < kColsumMinRows ? 0 : (int)(rows / 256 < 256 ? rows / 256 : 256); }
 }  // namespace
@@ -582,16 +612,41 @@ extern "C" int adnm_colsum(const float* x, float* out, int64_t rows, int64_t n, 
     adnm_set_error("colsum: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)adnm_colsum_ws_bytes(rows, n));
     return ADNM_EWORKSPACE;
   }
-  {
+  // a leaf of the backward pass (a bias gradient): under a bound leaf queue the first stage waits for the grouped launch, with the bands
+  // it has alone; the caller keeps x and ws until the flush
+  static_assert(sizeof(ColsumLeaf) <= sizeof(AdnmLeaf::args), "ColsumLeaf must fit a leaf record");
+  const ColsumLeaf cl{x, (float*)ws, (int)rows, (int)n, (int)adnm_cdiv(rows, bands)};
+  AdnmLeaf leaf;
+  leaf.kind = ADNM_LEAF_COLSUM, leaf.grid = bands, leaf.prec = 0, leaf.prof = "colsum_partial", leaf.bytes = 4.0 * (double)rows * n;
+  memcpy(leaf.args, &cl, sizeof(cl));
+  if (!adnm_leafq_push(leaf)) {
     ADNM_PROF("colsum_partial", st, 4.0 * (double)rows * n);
-    colsum_partial_kernel<<<bands, kColsumThreads, 0, st>>>(x, (float*)ws, (int)rows, (int)n, (int)adnm_cdiv(rows, bands));
+    colsum_partial_kernel<<<bands, kColsumThreads, 0, st>>>(x, (float*)ws, (int)rows, (int)n, cl.band);
   }
   ADNM_CHECK_LAUNCH("colsum_partial");
   adnm_launch_fold("colsum", (const float*)ws, bands, (int)n, {out, (int)n}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}, st);
   ADNM_CHECK_LAUNCH("colsum");
   return ADNM_OK;
 }
-
+static int colsum_launch_multi(const AdnmLeaf* const* items, int n, hipStream_t st) {
+  for (int i = 0; i < n;) {
+    MultiColsum m;
+    int count = 0, blocks = 0;
+    double bytes = 0;
+    for (; i < n && count < kMaxColsum; ++i) {
+      memcpy(&m.p[count], items[i]->args, sizeof(ColsumLeaf));
+      blocks += items[i]->grid;
+      m.blk_end[count++] = blocks;
+      bytes += items[i]->bytes;
+    }
+    for (int k = count; k < kMaxColsum; ++k) m.blk_end[k] = blocks, m.p[k] = m.p[0];
+    ADNM_PROF("colsum_partial", st, bytes);
+    if (count == 1) colsum_partial_kernel<<<(unsigned)blocks, kColsumThreads, 0, st>>>(m.p[0].x, m.p[0].part, m.p[0].rows, m.p[0].n, m.p[0].band);
+    else colsum_partial_multi_kernel<<<(unsigned)blocks, kColsumThreads, 0, st>>>(m);
+  }
+  ADNM_CHECK_LAUNCH("colsum_partial (grouped)");
+  return ADNM_OK;
+}
 
 // ---- delayed per-tensor scaling of the fp8 configuration (include/adnm_hip.h: adnm_quant_update).  One workgroup: a model has a
 // few hundred GEMM call sites, and a single workgroup can advance the step counter behind its own barrier.

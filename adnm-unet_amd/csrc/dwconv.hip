@@ -391,17 +391,17 @@ __global__ __launch_bounds__(64 * K * kWgSlices) void dwconv_wgrad_multi_kernel(
 // than the tap-row version above, which stays for 5x5 (its 25 accumulators + 5-row window do not fit in registers).
 // block = cgb channel quads x (256 / cgb) strips; part[blockIdx.y, tap, c] as above.
 template <typename T>
-__global__ __launch_bounds__(kBlock) void dwconv_wgrad3_roll_kernel(const T* __restrict__ dpre, int64_t ldd, const T* __restrict__ x, int64_t ldx,
-                                                                    float* __restrict__ part, int B, int H, int W, int C, int cgb, int SEG,
-                                                                    int nseg, int wcm) {
+__device__ __forceinline__ void dwconv_wgrad3_roll_body(const T* __restrict__ dpre, int64_t ldd, const T* __restrict__ x, int64_t ldx,
+                                                        float* __restrict__ part, int B, int H, int W, int C, int cgb, int SEG, int nseg, int wcm,
+                                                        const int bx, const int by) {
   constexpr int K = 3, NT = 9, N = CVec<T>::N;
   using V = CVec<T>;
   __shared__ __attribute__((aligned(16))) float red[kBlock / 64 - 1][NT + 1][64][N];
   const int C4 = C / N;   // channel vectors per pixel
   const int WT = (W + TW - 1) / TW;
   const int cgl = threadIdx.x & (cgb - 1), sp = threadIdx.x / cgb, spb = kBlock / cgb;
-  const int cg = blockIdx.x * cgb + cgl;
-  const int64_t S = (int64_t)B * nseg * WT, sidx = (int64_t)blockIdx.y * spb + sp;
+  const int cg = bx * cgb + cgl;
+  const int64_t S = (int64_t)B * nseg * WT, sidx = (int64_t)by * spb + sp;
   const bool cv = cg < C4, live = cv && sidx < S;
   const int c = cv ? cg * N : 0;
   V aw[NT], ab = cv_zero<T>();
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(kBlock) void dwconv_wgrad3_roll_kernel(const T* __r
   if (wave == 0 && lane < cgb) {
     // lanes 0..cgb-1 of wave 0 hold channel vectors cgl = lane; lane l of every other wave holds the same vector iff (l & (cgb-1)) == lane,
     // and after wave_sum_from all lanes of a vector hold the wave's total, so reading lane `lane` of each wave is enough
-    float* dst = part + (int64_t)blockIdx.y * (NT + 1) * C;
+    float* dst = part + (int64_t)by * (NT + 1) * C;
 #pragma unroll
     for (int k = 0; k <= NT; ++k) {
       V v = k < NT ? aw[k] : ab;
@@ -490,6 +490,13 @@ __global__ __launch_bounds__(kBlock) void dwconv_wgrad3_roll_kernel(const T* __r
       }
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void dwconv_wgrad3_roll_kernel(const T* __restrict__ dpre, int64_t ldd, const T* __restrict__ x, int64_t ldx,
+                                                                    float* __restrict__ part, int B, int H, int W, int C, int cgb, int SEG,
+                                                                    int nseg, int wcm) {
+  dwconv_wgrad3_roll_body<T>(dpre, ldd, x, ldx, part, B, H, W, C, cgb, SEG, nseg, wcm, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // (c'') 5x5 weight / bias gradients, the same column walker (fp32 tokens).  The tap-row kernel above moves 7.5x its algorithmic bytes
@@ -616,6 +623,19 @@ __global__ __launch_bounds__(kBlock) void dwconv_wgrad5_walk_multi_kernel(MultiW
                                      m.p[k].seg, m.p[k].nseg, m.p[k].wcm, lin % gx, lin / gx);
 }
 
+// grouped form of the 3x3 walker (fp32 tokens): the same record; the problem is found through the prefix of workgroup counts
+__global__ __launch_bounds__(kBlock) void dwconv_wgrad3_roll_multi_kernel(MultiWalk by_value) {
+  (void)by_value;
+  const auto& m = *(const __attribute__((address_space(4))) MultiWalk*)__builtin_amdgcn_kernarg_segment_ptr();
+  int k = 0;
+#pragma unroll
+  for (int i = 0; i < kMaxWg - 1; ++i) k += (int)blockIdx.x >= m.blk_end[i] ? 1 : 0;   // (unused entries repeat the total)
+  const int lin = (int)blockIdx.x - (k ? m.blk_end[k - 1] : 0);
+  const int gx = m.p[k].gx;
+  dwconv_wgrad3_roll_body<float>(m.p[k].dpre, m.p[k].ldd, m.p[k].x, m.p[k].ldx, m.p[k].part, m.p[k].B, m.p[k].H, m.p[k].W, m.p[k].C, m.p[k].cgb,
+                                 m.p[k].seg, m.p[k].nseg, m.p[k].wcm, lin % gx, lin / gx);
+}
+
 struct WGeo {
   int cgb, gx, npb, rows;
   int seg, nseg;   // 3x3 column walker: rows per strip, strips per image column (0 = tap-row kernel)
@@ -737,9 +757,18 @@ void launch_wgrad(const void* dpre, int64_t ldd, const void* x, int64_t ldx, flo
   }
   const WGeo g = wgeo(B, H, W, C, K, CVec<T>::N);
   const dim3 grid(g.gx, g.npb);
-  if (K == 3 && g.seg > 0)
-    { ADNM_PROF("dwconv_wgrad_k3", st, (double)sizeof(T) * B * H * W * C * 2); dwconv_wgrad3_roll_kernel<T><<<grid, kBlock, 0, st>>>((const T*)dpre, ldd, (const T*)x, ldx, part, (int)B, (int)H, (int)W, (int)C, g.cgb, g.seg, g.nseg, wcm); }
-  else {
+  if (K == 3 && g.seg > 0) {
+    bool queued = false;
+    if (sizeof(T) == 4) {   // a leaf like the others (fp32 tokens); wgeo's walker plan does not look at the queue, so the partial rows are the inline ones
+      WalkLeaf w{(const float*)dpre, ldd, (const float*)x, ldx, part, (int)B, (int)H, (int)W, (int)C, g.cgb, wcm, g.gx, g.npb, g.seg, g.nseg};
+      AdnmLeaf leaf;
+      leaf.kind = ADNM_LEAF_DWCONV_WALK3, leaf.grid = g.gx * g.npb, leaf.prec = 0, leaf.prof = "dwconv_wgrad_k3", leaf.bytes = 4.0 * B * H * W * C * 2;
+      memcpy(leaf.args, &w, sizeof(w));
+      queued = adnm_leafq_push(leaf);
+    }
+    if (!queued)
+      { ADNM_PROF("dwconv_wgrad_k3", st, (double)sizeof(T) * B * H * W * C * 2); dwconv_wgrad3_roll_kernel<T><<<grid, kBlock, 0, st>>>((const T*)dpre, ldd, (const T*)x, ldx, part, (int)B, (int)H, (int)W, (int)C, g.cgb, g.seg, g.nseg, wcm); }
+  } else {
     bool queued = false;
     if (sizeof(T) == 4) {   // a leaf of the backward pass: may wait for the grouped launch (fp32 tokens)
       static_assert(sizeof(WgLeaf) <= sizeof(AdnmLeaf::args), "WgLeaf must fit a leaf record");
@@ -892,5 +921,31 @@ int adnm_dwconv_wgrad_launch_multi(const AdnmLeaf* const* items, int n, int K, h
     dwconv_wgrad_multi_kernel<3><<<(unsigned)blocks, 64 * 3 * kWgSlices, 0, st>>>(m);
   }
   ADNM_CHECK_LAUNCH("dwconv_wgrad (grouped)");
+  return ADNM_OK;
+}
+
+// the queued 3x3 column-walker problems, kMaxWg per launch
+int adnm_dwconv_walk3_launch_multi(const AdnmLeaf* const* items, int n, hipStream_t st) {
+  for (int i = 0; i < n;) {
+    MultiWalk m;
+    m.count = 0;
+    int blocks = 0;
+    double bytes = 0;
+    for (; i < n && m.count < kMaxWg; ++i) {
+      memcpy(&m.p[m.count], items[i]->args, sizeof(WalkLeaf));
+      blocks += items[i]->grid;
+      m.blk_end[m.count++] = blocks;
+      bytes += items[i]->bytes;
+    }
+    for (int k = m.count; k < kMaxWg; ++k) m.blk_end[k] = blocks, m.p[k] = m.p[0];
+    ADNM_PROF("dwconv_wgrad_k3", st, bytes);
+    if (m.count == 1) {
+      const WalkLeaf& w = m.p[0];
+      dwconv_wgrad3_roll_kernel<float><<<dim3(w.gx, w.npb), kBlock, 0, st>>>(w.dpre, w.ldd, w.x, w.ldx, w.part, w.B, w.H, w.W, w.C, w.cgb, w.seg, w.nseg, w.wcm);
+    } else {
+      dwconv_wgrad3_roll_multi_kernel<<<(unsigned)blocks, kBlock, 0, st>>>(m);
+    }
+  }
+  ADNM_CHECK_LAUNCH("dwconv_wgrad_k3 (grouped walker)");
   return ADNM_OK;
 }

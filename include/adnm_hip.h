@@ -108,7 +108,11 @@ int adnm_foldq_accumulate_next(int mask);
  * clip_grad_norm_ / the optimiser (train.py:140-144) — and individually small (70 launches of ~10 us at config 2).  While the calling
  * thread has bound BOTH a leaf queue and a fold queue, adnm_skgemm(TN) stores its prepared launch instead of making it (operands,
  * workspace and destination must stay alive); adnm_leafq_flush launches the stored problems grouped, 16 per launch, and must be called
- * BEFORE adnm_foldq_flush (the folds of split problems read the partials those launches write).  Results are bitwise the same either way. */
+ * BEFORE adnm_foldq_flush (the folds of split problems read the partials those launches write).  Results are bitwise the same either way.
+ * The same holds for adnm_tsgemm_tn, the weight gradients of adnm_dwconv_bwd / adnm_dwconv_wgrad (fp32 tokens), adnm_conv3_wgrad and the
+ * two-stage path of adnm_colsum; the last three kinds — the 3x3 column walker of maps of 128 x 128 pixels and more, conv3, colsum — keep
+ * the plan of their single launch, so their results do not depend on the queue at all.  ADNM_LEAF_INLINE (environment, a bit mask over
+ * the kinds of csrc/adnm_common.h, read at every push) sends kinds back inline: a measurement aid. */
 void* adnm_leafq_create(void);
 int adnm_leafq_destroy(void* q);
 int adnm_leafq_bind(void* q); /* NULL unbinds */
