@@ -3465,6 +3465,62 @@ def advect(last, motion, block, T):
     return out
 
 
+# ======================================================================================= radially averaged power spectra (csrc/spectrum.hip)
+MIN_SPECTRUM_SIZE, MAX_SPECTRUM_SIZE = 8, 512
+SPECTRUM_LIMITS = f"H and W powers of two in {MIN_SPECTRUM_SIZE}..{MAX_SPECTRUM_SIZE}"
+
+
+def _spectrum_size(H, W):
+    for n in (H, W):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not MIN_SPECTRUM_SIZE <= n <= MAX_SPECTRUM_SIZE or n & (n - 1):
+            raise ValueError(f"spectrum: frames of {H} x {W} are outside adnm_valid_spectrum_accum's limits ({SPECTRUM_LIMITS})")
+    return int(H), int(W)
+
+
+def spectrum_bins(H, W):
+    """-> (n_r, wavelength_px), numpy arrays of length R = max(H, W) / 2: the number of DFT coefficients of an H x W frame in radial bin r
+    (int64) and the bin's wavelength L / r in pixels, L = max(H, W), inf at r = 0.  The bin of (ky, kx), ky in [-H/2, H/2), kx in
+    [-W/2, W/2), is the r with r^2 - r < k2 <= r^2 + r for k2 = (ky L/H)^2 + (kx L/W)^2, i.e. round(sqrt(k2)), in integer arithmetic
+    (include/adnm_hip.h: adnm_valid_spectrum_accum); coefficients with r >= R are dropped.  ValueError outside the limits."""
+    H, W = _spectrum_size(H, W)
+    L = max(H, W)
+    R = L // 2
+    ky = np.arange(-H // 2, H // 2, dtype=np.int64) * (L // H)
+    kx = np.arange(-W // 2, W // 2, dtype=np.int64) * (L // W)
+    k2 = ky[:, None] ** 2 + kx[None, :] ** 2
+    r = np.arange(L + 1, dtype=np.int64)                       # k2 <= L^2 / 2 < (L + 1)^2 - (L + 1)
+    b = np.searchsorted(r * r + r, k2.reshape(-1), side="left")   # the first r with k2 <= r^2 + r; r^2 - r = (r-1)^2 + (r-1) < k2 follows
+    n_r = np.bincount(b, minlength=L + 1)[:R].astype(np.int64)
+    with np.errstate(divide="ignore"):
+        wavelength = L / np.arange(R, dtype=np.float64)
+    return n_r, wavelength
+
+
+def power_spectrum(truth, pred, value_scale):
+    """truth / pred: contiguous fp32 GPU tensors (frames, H, W) of one shape -> (frames, R, 3) float64 on the device, R = max(H, W) / 2:
+    per frame and radial bin r the SUMS P_o = sum |O|^2 / (H W), P_f = sum |F|^2 / (H W), C = sum Re(F conj O) / (H W) over the bin's DFT
+    coefficients, O / F the transforms of clip(truth, 0, 1) * value_scale / clip(pred, 0, 1) * value_scale (spectrum_bins gives the
+    counts to divide by).  The one-shot use of adnm_valid_spectrum_accum (T = frames)."""
+    if not (torch.is_tensor(truth) and torch.is_tensor(pred)):
+        raise RuntimeError("power_spectrum: needs GPU tensors")
+    _need_gpu(truth)
+    _need_gpu(pred)
+    if (truth.dtype != torch.float32 or pred.dtype != torch.float32 or truth.shape != pred.shape or truth.dim() != 3 or truth.device != pred.device
+            or not truth.is_contiguous() or not pred.is_contiguous()):
+        _unsupported("power_spectrum", f"takes two contiguous fp32 tensors (frames, H, W) of one shape, got {truth.dtype} {tuple(truth.shape)} and "
+                                       f"{pred.dtype} {tuple(pred.shape)}")
+    frames, H, W = truth.shape
+    nb = lib.query("adnm_valid_spectrum_accum_ws_bytes", frames, frames, H, W)
+    if nb < 0:
+        raise RuntimeError(f"power_spectrum: {frames} frames of {H} x {W} are outside adnm_valid_spectrum_accum's limits (1 <= frames <= 65535, "
+                           f"{SPECTRUM_LIMITS})")
+    out = torch.zeros((frames, max(H, W) // 2, 3), dtype=torch.float64, device=truth.device)
+    ws = _ws(nb, truth.device)
+    lib.call("adnm_valid_spectrum_accum", pred.data_ptr(), H * W, H * W, truth.data_ptr(), out.data_ptr(), float(value_scale), ws.data_ptr(), int(nb),
+             frames, frames, H, W, _stream())
+    return out
+
+
 # ======================================================================================= the output side (csrc/dataio.hip: forecast_render)
 def edges_up_f32(edges):
     """double edges -> float32, each rounded UP to the smallest float >= it: the kernel compares an fp32 value with fp32 edges where

@@ -26,6 +26,11 @@ Validator(..., advection=True) adds the Lagrangian-persistence baseline (DESIGN.
 motion vector per block from the last two input frames, advect moves the last frame along it for every frame index, and that field is
 scored as a second baseline by the same pooled and FSS passes, into two tables APPENDED to the block (pooled, then FSS).
 
+Validator(..., spectrum=True) adds radially averaged power spectra (DESIGN.md §4k): csrc/spectrum.hip::valid_spectrum_accum transforms the
+clipped, scaled target and forecast (power-of-two frames of 8..512 pixels a side) and adds the power of each and their co-spectrum per
+radial wavenumber and frame index into a table APPENDED last to the block; done() reports the mean power per coefficient, the forecast's
+share of the observed power, the spectral coherence and the scale down to which the forecast keeps half the observed power.
+
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
@@ -76,6 +81,26 @@ def advection_doubles(seq_len, nthr, pools=(), fss=(), advection=False):
     return seq_len * 4 * nthr * len(baseline_pools(pools)), seq_len * len(fss) * 3 * nthr
 
 
+def spectrum_doubles(seq_len, frame=None):
+    """-> doubles of the spectrum table (T, max(H, W) / 2, 3), the LAST part of the ONE allocation; frame: (H, W), or None / False for none"""
+    return seq_len * (max(frame) // 2) * 3 if frame else 0
+
+
+def _spectrum_entries(sums, cells, wavelength):
+    """(..., R, 3) sums P_o, P_f, C and the (..., R)-broadcastable number of coefficients behind each -> the entries of "spectrum"; the
+    leading axes (none, or T) are kept"""
+    sums = np.asarray(sums, dtype=np.float64)
+    p_o, p_f, c = sums[..., 0], sums[..., 1], sums[..., 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = p_f / p_o
+        coherence = np.where((p_o == 0) | (p_f == 0), np.nan, c / np.sqrt(p_o * p_f))
+        target, forecast = p_o / cells, p_f / cells
+    keeps = np.cumprod(ratio[..., 1:] >= 0.5, axis=-1).sum(axis=-1)   # the largest r with ratio >= 0.5 at every bin 1 .. r (0: bin 1 fails)
+    eff = np.where(keeps > 0, wavelength[keeps], np.inf)
+    return {"wavenumber": np.arange(sums.shape[-2]), "wavelength_px": wavelength, "target": target, "forecast": forecast, "ratio": ratio,
+            "coherence": coherence, "effective_resolution_px": float(eff) if eff.ndim == 0 else eff}
+
+
 def _fss(sums):
     """(..., 3 * nthr) sums A, F, C -> (..., nthr) FSS = 2C / (A + F); NaN where A + F = 0 (no event in either field)"""
     sums = np.asarray(sums, dtype=np.float64)
@@ -115,7 +140,7 @@ def _lead_scores(rows, thresholds):
     return metrics
 
 
-def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False):
+def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False, spectrum=None):
     """host: the block (a float64 array of HEADER + T * (4*nthr + 3) values; with `pools` (size, stride) pairs then the forecast's pooled
     table (T, npool, 4*nthr), with `persistence` then the baseline's (T, len(baseline_pools(pools)), 4*nthr): include/adnm_hip.h) -> the
     dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's (Shanghai_metrics.py:218-290) as GpuEvaluator.done()
@@ -124,17 +149,26 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     `persistence` then the baseline's: "fss" {n: {thr: 2C / (A + F)}}, "fss_useful" {thr: 0.5 + f_o / 2} with f_o the observed event
     fraction of the main table (the line above which a scale is called useful), and "fss" under "persistence" and "per_lead".  With
     `advection` two more tables close the block, the advected field's pooled table (T, len(baseline_pools(pools)), 4*nthr) and, with
-    `fss`, its FSS table: "advection" and "per_lead"/"advection", built like "persistence"."""
+    `fss`, its FSS table: "advection" and "per_lead"/"advection", built like "persistence".  With `spectrum` = (H, W), the frame size, the
+    spectrum table (T, max(H, W) / 2, 3) of sums P_o, P_f, C is the last part: "spectrum" {"wavenumber", "wavelength_px", "target" and
+    "forecast" (mean power per coefficient: sum / (n_r * samples * T)), "ratio" (forecast / target), "coherence" (C / sqrt(P_o P_f) of the
+    sums over the horizon, NaN where a power is 0), "effective_resolution_px" (the wavelength of the largest r >= 1 with ratio >= 0.5 at
+    every bin 1 .. r; inf when bin 1 fails)}, and under "per_lead" the same as (T, R) arrays from the single rows."""
     nthr, T = len(thresholds), seq_len
     pools, fss = tuple(pools), tuple(fss)
     base = baseline_pools(pools) if persistence else ()
     n0, n1, n2 = block_doubles(T, nthr, pools, persistence)
     n3, n4 = fss_doubles(T, nthr, fss, persistence)
     n5, n6 = advection_doubles(T, nthr, pools, fss, advection)
+    spectrum = tuple(int(v) for v in spectrum) if spectrum else None
+    n7 = spectrum_doubles(T, spectrum)
+    if spectrum:
+        n_r, wavelength = ops.spectrum_bins(*spectrum)   # ValueError outside the limits
     blk = np.asarray(block, dtype=np.float64)
-    if blk.shape != (n0 + n1 + n2 + n3 + n4 + n5 + n6,):
-        raise ValueError(f"aggregate: a block of {n0 + n1 + n2 + n3 + n4 + n5 + n6} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
-                         f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + (", advection" if advection else "") + f"; got {blk.shape}")
+    if blk.shape != (n0 + n1 + n2 + n3 + n4 + n5 + n6 + n7,):
+        raise ValueError(f"aggregate: a block of {n0 + n1 + n2 + n3 + n4 + n5 + n6 + n7} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
+                         f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + (", advection" if advection else "")
+                         + (f", spectrum of {spectrum[0]} x {spectrum[1]} frames" if spectrum else "") + f"; got {blk.shape}")
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
     tab = blk[HEADER:n0].reshape(T, 4 * nthr + 3)
     metrics, all_far = contingency_metrics(tab[:, :4 * nthr].sum(axis=0), thresholds)
@@ -154,7 +188,7 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     fss_b = blk[n0 + n1 + n2 + n3:at].reshape(T, len(fss) if persistence else 0, 3 * nthr)
     apools = baseline_pools(pools) if advection else ()
     atab = blk[at:at + n5].reshape(T, len(apools), 4 * nthr)
-    fss_a = blk[at + n5:].reshape(T, len(fss) if advection else 0, 3 * nthr)
+    fss_a = blk[at + n5:at + n5 + n6].reshape(T, len(fss) if advection else 0, 3 * nthr)
     if pools:
         res["pooled"] = {p: _scores(ftab[:, i].sum(axis=0), thresholds) for i, p in enumerate(pools)}
     if persistence:
@@ -172,6 +206,9 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
                                 pooled={p: _scores(atab[:, apools.index(p)].sum(axis=0), thresholds) for p in pools})
         if fss:
             res["advection"]["fss"] = _fss_scores(fss_a, fss, thresholds)
+    if spectrum:
+        stab = blk[at + n5 + n6:].reshape(T, -1, 3)
+        res["spectrum"] = _spectrum_entries(stab.sum(axis=0), n_r * (samples * T), wavelength)
     if per_lead:
         with np.errstate(divide="ignore", invalid="ignore"):
             lead = {"RMSE": np.sqrt(mse_t), "MAE": tab[:, 4 * nthr] / (hw * samples),
@@ -191,13 +228,15 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
                                  "pooled": {p: {"threshold_metrics": _lead_scores(atab[:, apools.index(p)], thresholds)} for p in pools}}
             if fss:
                 lead["advection"]["fss"] = _fss_lead(fss_a, fss, thresholds)
+        if spectrum:
+            lead["spectrum"] = _spectrum_entries(stab, n_r * samples, wavelength)
         res["per_lead"] = lead
     return res
 
 
 class Validator(ForwardClient):
     def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False,
-                 fss=None, advection=None):
+                 fss=None, advection=None, spectrum=False):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -224,10 +263,12 @@ class Validator(ForwardClient):
                              f"a pass takes {ops.MAX_POOLS} (give (1, 1) among the pools, or one pool fewer)")
         if self.advection and not 0.0 < self.value_scale <= 255.0:
             raise ValueError(f"Validator: advection matches blocks on quantised bytes, which needs 0 < value_scale <= 255, got {self.value_scale}")
+        self.spectrum = bool(spectrum)   # the spectrum table is the last part of the block; its size follows the epoch's frames
         self._thr = (ctypes.c_float * len(self.thresholds))(*self.thresholds)
         self._fwd = GraphedForward(model, client=self, keep_quant=True)
         self._block = self._last = None    # the epoch's accumulator block and the last batch's fp32 loss: they outlive the graphs
         self._frame = None                  # (H, W) of the epoch
+        self._spectrum_frame = None         # (H, W) the block's spectrum table was sized for
 
     # ---- device state
     def _block_for(self, device):
@@ -236,12 +277,17 @@ class Validator(ForwardClient):
             n = lib.query("adnm_valid_block_bytes", self.seq_len, len(self.thresholds))
             parts = (block_doubles(self.seq_len, len(self.thresholds), self.pools, self.persistence)
                      + fss_doubles(self.seq_len, len(self.thresholds), self.fss, self.persistence)
-                     + advection_doubles(self.seq_len, len(self.thresholds), self.pools, self.fss, self.advection))
+                     + advection_doubles(self.seq_len, len(self.thresholds), self.pools, self.fss, self.advection)
+                     + (spectrum_doubles(self.seq_len, self._frame if self.spectrum else None),))
             assert n == 8 * parts[0]
             self._block = torch.zeros(sum(parts), dtype=torch.float64, device=device)
             self._last = torch.zeros((), dtype=torch.float32, device=device)
+            self._spectrum_frame = self._frame
         elif self._block.device != device:
             raise RuntimeError(f"Validator: one device per Validator (the block is on {self._block.device}, the batch on {device})")
+        elif self.spectrum and self._spectrum_frame != self._frame:
+            raise RuntimeError(f"Validator: spectrum=True keeps one frame size per Validator (the table in the block is for frames of "
+                               f"{self._spectrum_frame[0]} x {self._spectrum_frame[1]}, the batch has {self._frame[0]} x {self._frame[1]})")
         return self._block
 
     def _launch(self, ent, sx, pred, block, loss_out):
@@ -282,6 +328,10 @@ class Validator(ForwardClient):
             if self.fss:
                 lib.call("adnm_valid_fss_accum", adv.data_ptr(), T * H * W, H * W, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
                          ops.fss_table(self.fss), len(self.fss), ent["ws_fss"].data_ptr(), ent["ws_fss"].numel(), B * T, T, H, W, stream)
+        if self.spectrum:   # the last table of the block
+            table = block.data_ptr() + 8 * (block.numel() - spectrum_doubles(T, (H, W)))
+            lib.call("adnm_valid_spectrum_accum", pred.data_ptr(), T * H * W, H * W, ent["tgt"].data_ptr(), table, self.value_scale, ent["ws_spectrum"].data_ptr(),
+                     ent["ws_spectrum"].numel(), B * T, T, H, W, stream)
 
     # ---- ForwardClient: what GraphedForward calls with the entry of one input shape
     def open(self, ent, x):
@@ -327,8 +377,15 @@ class Validator(ForwardClient):
             adv = torch.zeros(shape, dtype=torch.float32, device=dev)
             motion = torch.zeros((B, -(-H // block_px), -(-W // block_px), 2), dtype=torch.int32, device=dev)
             ws_trec = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
+        ws_spectrum = None
+        if self.spectrum:
+            need = lib.query("adnm_valid_spectrum_accum_ws_bytes", B * T, T, H, W)
+            if need < 0:
+                raise RuntimeError(f"Validator: spectrum on {B * T} frames of {H} x {W} is outside adnm_valid_spectrum_accum's limits (frames <= 65535, "
+                                   f"{ops.SPECTRUM_LIMITS})")
+            ws_spectrum = torch.empty(int(need), dtype=torch.uint8, device=dev)
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=torch.empty(max(int(nb), 16), dtype=torch.uint8, device=dev),
-                   ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss, adv=adv, motion=motion, ws_trec=ws_trec,
+                   ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss, ws_spectrum=ws_spectrum, adv=adv, motion=motion, ws_trec=ws_trec,
                    loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
         self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
@@ -410,7 +467,9 @@ class Validator(ForwardClient):
         fss: plus "fss": {n: {thr: FSS}} (NaN where neither field has an event), "fss_useful": {thr: 0.5 + f_o / 2}, and "fss" under
         "persistence" and, as length-T arrays, under "per_lead" and "per_lead"/"persistence" where those exist.
         advection: plus "advection" and "per_lead"/"advection", built like "persistence": the last input frame moved along its
-        block-matched motion, scored on the same batches."""
+        block-matched motion, scored on the same batches.
+        spectrum: plus "spectrum" {"wavenumber", "wavelength_px", "target", "forecast", "ratio", "coherence", "effective_resolution_px"}
+        (aggregate) and, as (T, R) arrays with a length-T "effective_resolution_px", "per_lead"/"spectrum"."""
         if self._block is None or self._frame is None:
             raise RuntimeError("Validator.done: no batch since the last reset")
         blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
@@ -418,7 +477,7 @@ class Validator(ForwardClient):
         H, W = self._frame
         area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
         res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead,
-                        fss=self.fss, advection=bool(self.advection))
+                        fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None)
         if reset:
             self.reset()
         return res

@@ -754,6 +754,46 @@ int adnm_trec_motion(const float* prev, const float* last, int64_t sample_stride
 int adnm_advect(const float* last, int64_t sample_stride, const void* motion_i32, float* out, int64_t block, int64_t samples, int64_t T, int64_t H,
                 int64_t W, adnm_stream_t stream);
 
+/* Radially averaged power spectra (RAPSD) of observation and forecast and their co-spectrum, per wavenumber and frame index, as SUMS.
+ * The reference has no spectrum; the definitions are this project's, follow pysteps' rapsd convention, and the yardstick
+ * is numpy.fft.fft2 in float64.
+ *   fields        o = clip(target, 0, 1) * value_scale, f = clip(forecast, 0, 1) * value_scale in fp32: the fields whose differences
+ *                 adnm_valid_accum sums for RMSE, except that a NaN stays a NaN (numpy's clip) instead of becoming 0.
+ *   frame sizes   H and W powers of two, 8 <= H, W <= 512.  L = max(H, W).
+ *   transform     O = DFT2(o), F = DFT2(f), unnormalised; signed frequencies ky in [-H/2, H/2), kx in [-W/2, W/2).  Per coefficient
+ *                 p_o = |O|^2 / (H W), p_f = |F|^2 / (H W), c = Re(F conj O) / (H W).
+ *   radial bin    the wavenumber in cycles per L pixels is (ky L/H, kx L/W), both integers; r = round(sqrt(k2)), k2 = (ky L/H)^2 +
+ *                 (kx L/W)^2, formed in integers as the r with r^2 - r < k2 <= r^2 + r (sqrt of an integer is never m + 1/2).  Bins
+ *                 r = 0 .. R - 1, R = L/2, are kept; coefficients with r >= R (the corners) are dropped, as in pysteps.  n_r, the number of
+ *                 coefficients of bin r, depends on (H, W) only: the host's business (ops.spectrum_bins).
+ *   sums          P_o[r] = SUM p_o, P_f[r] = SUM p_f, C[r] = SUM c over the coefficients of bin r.  The device keeps SUMS; the caller
+ *                 divides by n_r * samples for pysteps' mean.
+ * table: adnm_valid_spectrum_block_bytes(T, H, W) = 8 * T * R * 3 bytes, 8-byte aligned, zeroed by the caller, all double, shape (T, R, 3):
+ *   [t][r] = P_o, P_f, C for frame index t (frame f of a batch belongs to row f mod T), summed over every sample so far.  No header.
+ * adnm_valid_spectrum_accum ADDS a batch.  target, pred and the two strides: adnm_valid_pool_accum's meaning (a contiguous forecast is
+ *   (T*H*W, H*W), a held frame (T_in*H*W, 0)).  With T = frames on a zeroed table it is the one-shot per-frame form.  Every argument is
+ *   passed by value, nothing is allocated and no device memory is read on the host: the call can be captured.  Three launches.  Rows: rows
+ *   2p and 2p + 1 of ONE field are the real and imaginary part of one complex row, transformed along x in LDS and separated again; the
+ *   fields are real, so only kx = 0 .. W/2 is kept and goes, transposed, to ws.  Columns: one workgroup per (kx, frame) transforms o's and
+ *   f's column along y, forms p_o, p_f, c with one expression, doubles them for 0 < kx < W/2 (the column stands for -kx as well) and
+ *   adds each bin's run of |ky| in ascending order in fp32; fold: per (t, r) the partials are added in DOUBLE, samples ascending, then kx
+ *   ascending, and the table is updated.  o and f go through the SAME instructions and are never packed into one transform: pred == target
+ *   gives P_f == P_o == C bit for bit, pred == 0 gives P_f = C = 0 exactly.  Each pixel is read from HBM once, 16 bytes per access when
+ *   both bases are 16-byte aligned and both strides multiples of 4, float by float otherwise: same result.
+ *   precision     radix-2 decimation in time in fp32; twiddles exp(-2 pi i j / N) from sincospi in double, rounded once to fp32.  A bin
+ *                 sum has at most 2 + log2(H W) roundings per coefficient in front of it, then a handful of fp32 additions within one
+ *                 column, then double.  No atomics: the same calls on the same table give the same bits, whatever ws held.
+ *   ws            adnm_valid_spectrum_accum_ws_bytes: frames * (W/2 + 1) * (2 * H * 8 + R * 3 * 4) bytes, the transposed row transforms
+ *                 and the per-workgroup partials, every byte written before it is read.
+ * Limits, refused before any launch (ADNM_EINVAL): a null pointer; pred / target not 4-byte or table / ws not 8-byte aligned; H or W not a
+ *   power of two or outside 8..512; T < 1 or not dividing frames; frames > 65535; pred_frame_stride neither 0 nor >= H*W;
+ *   pred_sample_stride < 0; ws_bytes below the query.  The *_bytes queries return -1. */
+int64_t adnm_valid_spectrum_block_bytes(int64_t T, int64_t H, int64_t W);
+int64_t adnm_valid_spectrum_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W);
+int adnm_valid_spectrum_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                              float value_scale, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W,
+                              adnm_stream_t stream);
+
 /* The output side (pic_results.py:104-184 of the reference): a forecast as the bytes a consumer keeps, in ONE launch.
  * adnm_forecast_render: pred contiguous fp32 (B, T, H, W), 4-byte aligned.  fields: (B, T, H, W) uint8 or NULL.  strip: (B, H, Ws, 4) uint8
  *   (RGBA, 4-byte aligned) or NULL, Ws = n*W + (n-1)*gap, holding the n = ceil((T - frame_start) / frame_step) frames frame_start,
