@@ -3521,6 +3521,50 @@ def power_spectrum(truth, pred, value_scale):
     return out
 
 
+# ======================================================================================= joint intensity histogram (csrc/joint.hip)
+MIN_JOINT_LEVELS, MAX_JOINT_LEVELS = 2, 128
+JOINT_LIMITS = f"value_scale finite with {MIN_JOINT_LEVELS} <= floor(value_scale) + 1 <= {MAX_JOINT_LEVELS}"
+
+
+def joint_levels(value_scale):
+    """-> L = floor(value_scale) + 1, the number of quantised levels 0 .. L - 1 of eval's q(v) = floor(clip(v, 0, 1) * value_scale), as the
+    device forms it from the fp32 value_scale (include/adnm_hip.h: adnm_valid_joint_levels).  ValueError outside the limits."""
+    try:
+        scale = float(value_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"joint: value_scale is a number, got {value_scale!r} ({JOINT_LIMITS})") from None
+    L = lib.query("adnm_valid_joint_levels", scale)
+    if L < 0:
+        raise ValueError(f"joint: value_scale {value_scale!r} is outside adnm_valid_joint_accum's limits ({JOINT_LIMITS})")
+    return int(L)
+
+
+def joint_histogram(truth, pred, value_scale):
+    """truth / pred: contiguous fp32 GPU tensors (frames, H, W) or (B, T, H, W) of one shape -> (frames, L, L) int64 on the device,
+    L = joint_levels(value_scale): [f][q_o][q_f] = the number of pixels of frame f whose quantised truth is q_o and whose quantised forecast
+    is q_f.  Exact.  The one-shot use of adnm_valid_joint_accum (T = frames); validate.joint_entries / joint_counts_at read it."""
+    if not (torch.is_tensor(truth) and torch.is_tensor(pred)):
+        raise RuntimeError("joint_histogram: needs GPU tensors")
+    _need_gpu(truth)
+    _need_gpu(pred)
+    if (truth.dtype != torch.float32 or pred.dtype != torch.float32 or truth.shape != pred.shape or truth.dim() not in (3, 4) or truth.device != pred.device
+            or not truth.is_contiguous() or not pred.is_contiguous()):
+        _unsupported("joint_histogram", f"takes two contiguous fp32 tensors (frames, H, W) or (B, T, H, W) of one shape, got {truth.dtype} {tuple(truth.shape)} "
+                                        f"and {pred.dtype} {tuple(pred.shape)}")
+    L = joint_levels(value_scale)
+    H, W = truth.shape[-2:]
+    frames = truth.numel() // (H * W) if H * W else 0
+    nb = lib.query("adnm_valid_joint_accum_ws_bytes", frames, frames, H * W, float(value_scale))
+    if nb < 0:
+        raise RuntimeError(f"joint_histogram: {frames} frames of {H} x {W} are outside adnm_valid_joint_accum's limits (1 <= frames <= 65535, "
+                           "1 <= H*W < 2^24)")
+    out = torch.zeros((frames, L, L), dtype=torch.float64, device=truth.device)
+    ws = _ws(nb, truth.device) if nb else None
+    lib.call("adnm_valid_joint_accum", pred.data_ptr(), H * W, H * W, truth.data_ptr(), out.data_ptr(), float(value_scale), None if ws is None else ws.data_ptr(),
+             int(nb), frames, frames, H * W, _stream())
+    return out.to(torch.int64)   # integers below 2^53 in doubles: exact
+
+
 # ======================================================================================= the output side (csrc/dataio.hip: forecast_render)
 def edges_up_f32(edges):
     """double edges -> float32, each rounded UP to the smallest float >= it: the kernel compares an fp32 value with fp32 edges where

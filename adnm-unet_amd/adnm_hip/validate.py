@@ -31,6 +31,11 @@ clipped, scaled target and forecast (power-of-two frames of 8..512 pixels a side
 radial wavenumber and frame index into a table APPENDED last to the block; done() reports the mean power per coefficient, the forecast's
 share of the observed power, the spectral coherence and the scale down to which the forecast keeps half the observed power.
 
+Validator(..., joint=True) adds the joint intensity histogram (DESIGN.md §4l): csrc/joint.hip::valid_joint_accum counts, per frame index, the
+pixels at every pair (quantised target, quantised forecast) into a (T, L, L) table APPENDED behind the spectrum table, L = floor(value_scale)
++ 1; done() derives the contingency table and the scores at EVERY integer threshold, the frequency bias, the conditional mean, a
+quantile-mapping table and the correlation from it (joint_entries), and joint_counts_at gives the counts at any threshold.
+
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
@@ -82,8 +87,101 @@ def advection_doubles(seq_len, nthr, pools=(), fss=(), advection=False):
 
 
 def spectrum_doubles(seq_len, frame=None):
-    """-> doubles of the spectrum table (T, max(H, W) / 2, 3), the LAST part of the ONE allocation; frame: (H, W), or None / False for none"""
+    """-> doubles of the spectrum table (T, max(H, W) / 2, 3), which follows advection_doubles' two parts in the ONE allocation; frame: (H, W),
+    or None / False for none"""
     return seq_len * (max(frame) // 2) * 3 if frame else 0
+
+
+def joint_doubles(seq_len, value_scale=None):
+    """-> doubles of the joint histogram (T, L, L), L = ops.joint_levels(value_scale), the LAST part of the ONE allocation; value_scale None /
+    False for none"""
+    if value_scale is None or value_scale is False:
+        return 0
+    L = ops.joint_levels(value_scale)
+    return seq_len * L * L
+
+
+def _counts(hist):
+    """a histogram as numpy int64 (..., L, L): a torch tensor (ops.joint_histogram's, on any device) or anything numpy takes; doubles holding
+    integers (the Validator's table) are converted exactly"""
+    if torch.is_tensor(hist):
+        hist = hist.detach().cpu().numpy()
+    h = np.asarray(hist)
+    if h.ndim < 2 or h.shape[-1] != h.shape[-2] or h.shape[-1] < 1:
+        raise ValueError(f"joint: a histogram is (..., L, L), got {h.shape}")
+    if h.dtype.kind == "f":
+        if not (np.isfinite(h).all() and (h == np.rint(h)).all()):
+            raise ValueError("joint: a histogram holds integer counts")
+    elif h.dtype.kind not in "iu":
+        raise ValueError(f"joint: a histogram holds integer counts, got {h.dtype}")
+    h = h.astype(np.int64)
+    if (h < 0).any():
+        raise ValueError("joint: a histogram holds counts >= 0")
+    return h
+
+
+def _tail_sums(a, axis):
+    """s[v] = sum of a[u] over u >= v along `axis`"""
+    return np.flip(np.cumsum(np.flip(a, axis), axis=axis), axis)
+
+
+def _scalar(a):
+    return a.item() if a.ndim == 0 else a
+
+
+def joint_counts_at(hist, thr):
+    """hist: (..., L, L) counts [q_o][q_f] (ops.joint_histogram's tensor, done()["joint"]["histogram"], ...) -> (TP, FN, FP, TN) at the float
+    threshold thr, int64 with the leading axes kept (Python ints when there are none): an event is q >= thr, which for an integer q is
+    q >= ceil(thr); a threshold above L - 1 gives no events, one <= 0 makes every pixel an event."""
+    h = _counts(hist)
+    L = h.shape[-1]
+    thr = float(thr)
+    if thr != thr:
+        raise ValueError("joint_counts_at: the threshold is NaN")
+    v = int(min(max(np.ceil(thr), 0), L))
+    tp = h[..., v:, v:].sum(axis=(-2, -1))
+    fn = h[..., v:, :v].sum(axis=(-2, -1))
+    fp = h[..., :v, v:].sum(axis=(-2, -1))
+    tn = h[..., :v, :v].sum(axis=(-2, -1))
+    return tuple(_scalar(a) for a in (tp, fn, fp, tn))
+
+
+def joint_entries(hist):
+    """hist: (..., L, L) counts, the target's level on the row and the forecast's on the column -> the entries of done()["joint"], the
+    leading axes (none, or T, or ops.joint_histogram's frames) kept in front of every array:
+      "levels" L; "histogram" (L, L) int64; "marginal_target", "marginal_forecast" (L,) int64;
+      "curves": per integer threshold v = 0 .. L - 1 the (L,) arrays TP, FN, FP, TN (int64, two-sided cumulative sums: TP[v] = sum of
+                h[o >= v, f >= v]), CSI, POD, FAR, HSS (evaluator.contingency_metrics' formulas) and bias = (TP + FP) / (TP + FN);
+      "conditional_mean" (L,): E[q_f | q_o = v], NaN where the target never took v;
+      "qq" (L,) int64: the smallest u with CDF_o(u) >= CDF_f(v), the table that maps the forecast's marginal onto the observation's;
+      "correlation": Pearson's r of (q_o, q_f) from the histogram's moments in float64, NaN when either variance is 0;
+      "mean_error": E[q_f - q_o]."""
+    h = _counts(hist)
+    L = h.shape[-1]
+    m_o, m_f = h.sum(axis=-1), h.sum(axis=-2)
+    n = m_o.sum(axis=-1)
+    tp = np.diagonal(_tail_sums(_tail_sums(h, -1), -2), axis1=-2, axis2=-1).copy()
+    fn, fp = _tail_sums(m_o, -1) - tp, _tail_sums(m_f, -1) - tp
+    tn = n[..., None] - tp - fn - fp
+    as_f = [a.astype(np.float64) for a in (tp, fn, fp, tn)]
+    metrics, all_far = contingency_metrics(as_f, (0,))
+    level = np.arange(L, dtype=np.float64)
+    nf = n.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        bias = (as_f[0] + as_f[2]) / (as_f[0] + as_f[1])
+        cond = (h * level).sum(axis=-1) / m_o
+        mean_o, mean_f = (m_o * level).sum(axis=-1) / nf, (m_f * level).sum(axis=-1) / nf
+        d_o, d_f = level - mean_o[..., None], level - mean_f[..., None]
+        var_o, var_f = (m_o * d_o * d_o).sum(axis=-1) / nf, (m_f * d_f * d_f).sum(axis=-1) / nf
+        cov = (h * d_o[..., :, None] * d_f[..., None, :]).sum(axis=(-2, -1)) / nf
+        corr = np.where((var_o > 0) & (var_f > 0), cov / np.sqrt(var_o * var_f), np.nan)
+        mean_error = mean_f - mean_o
+    cum_o, cum_f = np.cumsum(m_o, axis=-1), np.cumsum(m_f, axis=-1)
+    qq = (cum_o[..., None, :] >= cum_f[..., :, None]).argmax(axis=-1).astype(np.int64)   # cum_o[L - 1] = n >= every cum_f: a True exists
+    curves = {"TP": tp, "FN": fn, "FP": fp, "TN": tn, "CSI": metrics[0]["CSI"], "POD": metrics[0]["POD"], "FAR": all_far[0], "HSS": metrics[0]["HSS"],
+              "bias": bias}
+    return {"levels": L, "histogram": h, "marginal_target": m_o, "marginal_forecast": m_f, "curves": curves, "conditional_mean": cond, "qq": qq,
+            "correlation": _scalar(corr), "mean_error": _scalar(mean_error)}
 
 
 def _spectrum_entries(sums, cells, wavelength):
@@ -140,7 +238,7 @@ def _lead_scores(rows, thresholds):
     return metrics
 
 
-def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False, spectrum=None):
+def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False, spectrum=None, joint=None):
     """host: the block (a float64 array of HEADER + T * (4*nthr + 3) values; with `pools` (size, stride) pairs then the forecast's pooled
     table (T, npool, 4*nthr), with `persistence` then the baseline's (T, len(baseline_pools(pools)), 4*nthr): include/adnm_hip.h) -> the
     dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's (Shanghai_metrics.py:218-290) as GpuEvaluator.done()
@@ -153,7 +251,9 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     spectrum table (T, max(H, W) / 2, 3) of sums P_o, P_f, C is the last part: "spectrum" {"wavenumber", "wavelength_px", "target" and
     "forecast" (mean power per coefficient: sum / (n_r * samples * T)), "ratio" (forecast / target), "coherence" (C / sqrt(P_o P_f) of the
     sums over the horizon, NaN where a power is 0), "effective_resolution_px" (the wavelength of the largest r >= 1 with ratio >= 0.5 at
-    every bin 1 .. r; inf when bin 1 fails)}, and under "per_lead" the same as (T, R) arrays from the single rows."""
+    every bin 1 .. r; inf when bin 1 fails)}, and under "per_lead" the same as (T, R) arrays from the single rows.  With `joint` = L, the
+    number of levels, the joint histogram (T, L, L) is the last part: "joint" = joint_entries of its sum over the horizon, and under
+    "per_lead" joint_entries of the table, every array with a leading T axis."""
     nthr, T = len(thresholds), seq_len
     pools, fss = tuple(pools), tuple(fss)
     base = baseline_pools(pools) if persistence else ()
@@ -164,11 +264,16 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     n7 = spectrum_doubles(T, spectrum)
     if spectrum:
         n_r, wavelength = ops.spectrum_bins(*spectrum)   # ValueError outside the limits
+    joint = int(joint) if joint else None
+    if joint is not None and not ops.MIN_JOINT_LEVELS <= joint <= ops.MAX_JOINT_LEVELS:
+        raise ValueError(f"aggregate: joint is the number of levels, {ops.MIN_JOINT_LEVELS}..{ops.MAX_JOINT_LEVELS}, or None; got {joint}")
+    n8 = T * joint * joint if joint else 0
     blk = np.asarray(block, dtype=np.float64)
-    if blk.shape != (n0 + n1 + n2 + n3 + n4 + n5 + n6 + n7,):
-        raise ValueError(f"aggregate: a block of {n0 + n1 + n2 + n3 + n4 + n5 + n6 + n7} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
+    if blk.shape != (n0 + n1 + n2 + n3 + n4 + n5 + n6 + n7 + n8,):
+        raise ValueError(f"aggregate: a block of {n0 + n1 + n2 + n3 + n4 + n5 + n6 + n7 + n8} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
                          f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + (", advection" if advection else "")
-                         + (f", spectrum of {spectrum[0]} x {spectrum[1]} frames" if spectrum else "") + f"; got {blk.shape}")
+                         + (f", spectrum of {spectrum[0]} x {spectrum[1]} frames" if spectrum else "") + (f", a joint histogram of {joint} levels" if joint else "")
+                         + f"; got {blk.shape}")
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
     tab = blk[HEADER:n0].reshape(T, 4 * nthr + 3)
     metrics, all_far = contingency_metrics(tab[:, :4 * nthr].sum(axis=0), thresholds)
@@ -207,8 +312,11 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
         if fss:
             res["advection"]["fss"] = _fss_scores(fss_a, fss, thresholds)
     if spectrum:
-        stab = blk[at + n5 + n6:].reshape(T, -1, 3)
+        stab = blk[at + n5 + n6:at + n5 + n6 + n7].reshape(T, -1, 3)
         res["spectrum"] = _spectrum_entries(stab.sum(axis=0), n_r * (samples * T), wavelength)
+    if joint:
+        jtab = blk[at + n5 + n6 + n7:].reshape(T, joint, joint)
+        res["joint"] = joint_entries(jtab.sum(axis=0))
     if per_lead:
         with np.errstate(divide="ignore", invalid="ignore"):
             lead = {"RMSE": np.sqrt(mse_t), "MAE": tab[:, 4 * nthr] / (hw * samples),
@@ -230,13 +338,15 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
                 lead["advection"]["fss"] = _fss_lead(fss_a, fss, thresholds)
         if spectrum:
             lead["spectrum"] = _spectrum_entries(stab, n_r * samples, wavelength)
+        if joint:
+            lead["joint"] = joint_entries(jtab)
         res["per_lead"] = lead
     return res
 
 
 class Validator(ForwardClient):
     def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False,
-                 fss=None, advection=None, spectrum=False):
+                 fss=None, advection=None, spectrum=False, joint=False):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -263,7 +373,9 @@ class Validator(ForwardClient):
                              f"a pass takes {ops.MAX_POOLS} (give (1, 1) among the pools, or one pool fewer)")
         if self.advection and not 0.0 < self.value_scale <= 255.0:
             raise ValueError(f"Validator: advection matches blocks on quantised bytes, which needs 0 < value_scale <= 255, got {self.value_scale}")
-        self.spectrum = bool(spectrum)   # the spectrum table is the last part of the block; its size follows the epoch's frames
+        self.spectrum = bool(spectrum)   # the spectrum table follows every other pass's; its size follows the epoch's frames
+        self.joint = bool(joint)         # the joint histogram (T, L, L) is the last part of the block
+        self._levels = ops.joint_levels(self.value_scale) if self.joint else None   # ValueError outside the limits
         self._thr = (ctypes.c_float * len(self.thresholds))(*self.thresholds)
         self._fwd = GraphedForward(model, client=self, keep_quant=True)
         self._block = self._last = None    # the epoch's accumulator block and the last batch's fp32 loss: they outlive the graphs
@@ -278,7 +390,8 @@ class Validator(ForwardClient):
             parts = (block_doubles(self.seq_len, len(self.thresholds), self.pools, self.persistence)
                      + fss_doubles(self.seq_len, len(self.thresholds), self.fss, self.persistence)
                      + advection_doubles(self.seq_len, len(self.thresholds), self.pools, self.fss, self.advection)
-                     + (spectrum_doubles(self.seq_len, self._frame if self.spectrum else None),))
+                     + (spectrum_doubles(self.seq_len, self._frame if self.spectrum else None),)
+                     + (joint_doubles(self.seq_len, self.value_scale if self.joint else None),))
             assert n == 8 * parts[0]
             self._block = torch.zeros(sum(parts), dtype=torch.float64, device=device)
             self._last = torch.zeros((), dtype=torch.float32, device=device)
@@ -328,10 +441,15 @@ class Validator(ForwardClient):
             if self.fss:
                 lib.call("adnm_valid_fss_accum", adv.data_ptr(), T * H * W, H * W, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
                          ops.fss_table(self.fss), len(self.fss), ent["ws_fss"].data_ptr(), ent["ws_fss"].numel(), B * T, T, H, W, stream)
-        if self.spectrum:   # the last table of the block
-            table = block.data_ptr() + 8 * (block.numel() - spectrum_doubles(T, (H, W)))
+        tail = T * self._levels * self._levels if self.joint else 0   # the joint histogram closes the block
+        if self.spectrum:   # the last table in front of that tail
+            table = block.data_ptr() + 8 * (block.numel() - tail - spectrum_doubles(T, (H, W)))
             lib.call("adnm_valid_spectrum_accum", pred.data_ptr(), T * H * W, H * W, ent["tgt"].data_ptr(), table, self.value_scale, ent["ws_spectrum"].data_ptr(),
                      ent["ws_spectrum"].numel(), B * T, T, H, W, stream)
+        if self.joint:
+            ws = ent["ws_joint"]
+            lib.call("adnm_valid_joint_accum", pred.data_ptr(), T * H * W, H * W, ent["tgt"].data_ptr(), block.data_ptr() + 8 * (block.numel() - tail),
+                     self.value_scale, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), B * T, T, H * W, stream)
 
     # ---- ForwardClient: what GraphedForward calls with the entry of one input shape
     def open(self, ent, x):
@@ -384,8 +502,16 @@ class Validator(ForwardClient):
                 raise RuntimeError(f"Validator: spectrum on {B * T} frames of {H} x {W} is outside adnm_valid_spectrum_accum's limits (frames <= 65535, "
                                    f"{ops.SPECTRUM_LIMITS})")
             ws_spectrum = torch.empty(int(need), dtype=torch.uint8, device=dev)
+        ws_joint = None
+        if self.joint:
+            need = lib.query("adnm_valid_joint_accum_ws_bytes", B * T, T, H * W, self.value_scale)
+            if need < 0:
+                raise RuntimeError(f"Validator: joint on {B * T} frames of {H} x {W} is outside adnm_valid_joint_accum's limits (frames <= 65535, "
+                                   f"H*W < 2^24, {ops.JOINT_LIMITS})")
+            if need:
+                ws_joint = torch.empty(int(need), dtype=torch.uint8, device=dev)
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=torch.empty(max(int(nb), 16), dtype=torch.uint8, device=dev),
-                   ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss, ws_spectrum=ws_spectrum, adv=adv, motion=motion, ws_trec=ws_trec,
+                   ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss, ws_spectrum=ws_spectrum, ws_joint=ws_joint, adv=adv, motion=motion, ws_trec=ws_trec,
                    loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
         self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
@@ -469,7 +595,9 @@ class Validator(ForwardClient):
         advection: plus "advection" and "per_lead"/"advection", built like "persistence": the last input frame moved along its
         block-matched motion, scored on the same batches.
         spectrum: plus "spectrum" {"wavenumber", "wavelength_px", "target", "forecast", "ratio", "coherence", "effective_resolution_px"}
-        (aggregate) and, as (T, R) arrays with a length-T "effective_resolution_px", "per_lead"/"spectrum"."""
+        (aggregate) and, as (T, R) arrays with a length-T "effective_resolution_px", "per_lead"/"spectrum".
+        joint: plus "joint" {"levels", "histogram", "marginal_target", "marginal_forecast", "curves", "conditional_mean", "qq", "correlation",
+        "mean_error"} (joint_entries of the table summed over the horizon) and "per_lead"/"joint", the same with a leading T axis."""
         if self._block is None or self._frame is None:
             raise RuntimeError("Validator.done: no batch since the last reset")
         blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
@@ -477,7 +605,7 @@ class Validator(ForwardClient):
         H, W = self._frame
         area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
         res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead,
-                        fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None)
+                        fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None, joint=self._levels)
         if reset:
             self.reset()
         return res

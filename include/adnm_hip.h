@@ -794,6 +794,38 @@ int adnm_valid_spectrum_accum(const float* pred, int64_t pred_sample_stride, int
                               float value_scale, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W,
                               adnm_stream_t stream);
 
+/* The joint histogram of the quantised observation and the quantised forecast per frame index: the sufficient statistic of every
+ * contingency table at every integer threshold, of the frequency bias, the conditional bias and a quantile-mapping table.
+ * The reference has no histogram; the yardstick is numpy.histogram2d on the quantised fields (tests/joint_ref.py), integer for integer.
+ *   levels        L = (int)floorf(value_scale) + 1 (adnm_valid_joint_levels); value_scale finite with 2 <= L <= 128.
+ *   q(v)          eval_trunc(eval_scaled(v, value_scale)) = floor(clip(v, 0, 1) * value_scale) in fp32, the level adnm_valid_accum compares
+ *                 with its thresholds: a NaN, -Inf and negatives give 0, +Inf and values >= 1 give L - 1.
+ * table: adnm_valid_joint_block_bytes(T, value_scale) = 8 * T * L * L bytes, 8-byte aligned device memory, zeroed by the caller, all double,
+ *   shape (T, L, L): [t][q(target)][q(forecast)] = the number of pixels, over every sample so far, of the frames f with f mod T = t.  The
+ *   target is on the row, the forecast on the column.  No header.  Every entry is an integer held in a double.
+ * adnm_valid_joint_accum ADDS a batch.  target, pred and the two strides: adnm_valid_pool_accum's meaning (a contiguous forecast is
+ *   (T*hw, hw), a held frame (T_in*hw, 0)); hw = H * W pixels per frame.  With T = frames on a zeroed table it is the one-shot per-frame
+ *   form.  Every argument is passed by value, nothing is allocated and no device memory is read on the host: the call can be captured.  One
+ *   launch, grid (G, T): a row's frames are cut into items of 4096 pixels, a workgroup counts its items into one u32 histogram of L * L bins
+ *   in LDS (dynamic, 4 L^2 <= 64 KB: no function attribute) and adds the NON-ZERO bins to the table at the end.  Each pixel of each field is
+ *   read from HBM once, 16 bytes per access when both bases are 16-byte aligned and hw and both strides are multiples of 4, float by float
+ *   otherwise: same result.
+ *   the hot bin   a radar field is mostly zero.  The lanes of a wave whose bin is (0, 0) are counted with a ballot and a popcount into a
+ *                 per-wave scalar that reaches LDS once per workgroup; only the other lanes issue an LDS atomic.
+ *   exactness     the counts in LDS are u32 integer atomics, and G is chosen so that a workgroup counts at most 2^31 pixels.  The flush is
+ *                 a double atomic add per non-zero bin.  Every addend and every partial sum is an integer below 2^53 (frames * hw < 2^40
+ *                 per call), so every addition is exact and the sum does not depend on the order: the table is exact, and the same bits on
+ *                 every run, although the order of the atomics is not fixed.
+ *   ws            adnm_valid_joint_accum_ws_bytes is 0 for every accepted shape (the partial histograms live in LDS); ws may be NULL.
+ * Limits, refused before any launch (ADNM_EINVAL): a null pred, target or table; pred / target not 4-byte or table / ws not 8-byte aligned;
+ *   value_scale outside the range above; T < 1 or not dividing frames; frames > 65535; hw < 1 or >= 2^24; pred_frame_stride neither 0 nor
+ *   >= hw; pred_sample_stride < 0; ws_bytes below the query.  The queries return -1. */
+int64_t adnm_valid_joint_levels(float value_scale);
+int64_t adnm_valid_joint_block_bytes(int64_t T, float value_scale);
+int64_t adnm_valid_joint_accum_ws_bytes(int64_t frames, int64_t T, int64_t hw, float value_scale);
+int adnm_valid_joint_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                           float value_scale, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t hw, adnm_stream_t stream);
+
 /* The output side (pic_results.py:104-184 of the reference): a forecast as the bytes a consumer keeps, in ONE launch.
  * adnm_forecast_render: pred contiguous fp32 (B, T, H, W), 4-byte aligned.  fields: (B, T, H, W) uint8 or NULL.  strip: (B, H, Ws, 4) uint8
  *   (RGBA, 4-byte aligned) or NULL, Ws = n*W + (n-1)*gap, holding the n = ceil((T - frame_start) / frame_step) frames frame_start,
