@@ -3287,16 +3287,25 @@ def pool_table(pairs):
     return lib.i64_table([v for p in pairs for v in p])
 
 
+def _pair(op, truth, pred, ranks, shapes, contiguous=False):
+    """the check the one-shot scoring wrappers share: two fp32 GPU tensors of one shape and device, of a rank in `ranks` (None: >= 2), contiguous
+    where the wrapper passes them on as they are; `shapes` names the shapes in the message"""
+    if not (torch.is_tensor(truth) and torch.is_tensor(pred)):
+        raise RuntimeError(f"{op}: needs GPU tensors")
+    _need_gpu(truth)
+    _need_gpu(pred)
+    if (truth.dtype != torch.float32 or pred.dtype != torch.float32 or truth.shape != pred.shape or truth.device != pred.device
+            or (truth.dim() < 2 if ranks is None else truth.dim() not in ranks)
+            or (contiguous and not (truth.is_contiguous() and pred.is_contiguous()))):
+        _unsupported(op, f"takes two {'contiguous ' if contiguous else ''}fp32 tensors {shapes} of one shape, got {truth.dtype} {tuple(truth.shape)} and "
+                         f"{pred.dtype} {tuple(pred.shape)}")
+
+
 def pool_counts(truth, pred, thresholds, value_scale, pools):
     """truth / pred: fp32 GPU tensors (..., H, W) of the same shape -> (frames, npool, 4 * nthr) float64 on the device: per frame and
     pool (an int p = (p, p), or (size, stride): the windows of max_pool2d(kernel_size=size, stride=stride)) TP, FN, FP, TN per threshold,
     counted per window on the fields quantised as adnm_eval_counts quantises them.  The one-shot use of adnm_valid_pool_accum (T = frames)."""
-    if not (torch.is_tensor(truth) and torch.is_tensor(pred)):
-        raise RuntimeError("pool_counts: needs GPU tensors")
-    _need_gpu(truth)
-    _need_gpu(pred)
-    if truth.dtype != torch.float32 or pred.dtype != torch.float32 or truth.shape != pred.shape or truth.dim() < 2 or truth.device != pred.device:
-        _unsupported("pool_counts", f"takes two fp32 tensors (..., H, W) of one shape, got {truth.dtype} {tuple(truth.shape)} and {pred.dtype} {tuple(pred.shape)}")
+    _pair("pool_counts", truth, pred, None, "(..., H, W)")
     pairs = pool_pairs(pools)
     thr = [float(t) for t in thresholds]
     if not pairs or not 1 <= len(thr) <= 8:
@@ -3354,12 +3363,7 @@ def fss_sums(truth, pred, thresholds, value_scale, scales):
     scale n (odd, <= 33) A = sum c_o^2, F = sum c_f^2, C = sum c_o c_f per threshold, c the number of threshold pixels in the n x n window
     centred on each pixel (zero outside the frame), on the fields quantised as adnm_eval_counts quantises them.  FSS = 2C / (A + F).
     The one-shot use of adnm_valid_fss_accum (T = frames)."""
-    if not (torch.is_tensor(truth) and torch.is_tensor(pred)):
-        raise RuntimeError("fss_sums: needs GPU tensors")
-    _need_gpu(truth)
-    _need_gpu(pred)
-    if truth.dtype != torch.float32 or pred.dtype != torch.float32 or truth.shape != pred.shape or truth.dim() < 2 or truth.device != pred.device:
-        _unsupported("fss_sums", f"takes two fp32 tensors (..., H, W) of one shape, got {truth.dtype} {tuple(truth.shape)} and {pred.dtype} {tuple(pred.shape)}")
+    _pair("fss_sums", truth, pred, None, "(..., H, W)")
     ns = fss_scales(scales)
     thr = [float(t) for t in thresholds]
     if not ns or not 1 <= len(thr) <= 8:
@@ -3501,14 +3505,7 @@ def power_spectrum(truth, pred, value_scale):
     per frame and radial bin r the SUMS P_o = sum |O|^2 / (H W), P_f = sum |F|^2 / (H W), C = sum Re(F conj O) / (H W) over the bin's DFT
     coefficients, O / F the transforms of clip(truth, 0, 1) * value_scale / clip(pred, 0, 1) * value_scale (spectrum_bins gives the
     counts to divide by).  The one-shot use of adnm_valid_spectrum_accum (T = frames)."""
-    if not (torch.is_tensor(truth) and torch.is_tensor(pred)):
-        raise RuntimeError("power_spectrum: needs GPU tensors")
-    _need_gpu(truth)
-    _need_gpu(pred)
-    if (truth.dtype != torch.float32 or pred.dtype != torch.float32 or truth.shape != pred.shape or truth.dim() != 3 or truth.device != pred.device
-            or not truth.is_contiguous() or not pred.is_contiguous()):
-        _unsupported("power_spectrum", f"takes two contiguous fp32 tensors (frames, H, W) of one shape, got {truth.dtype} {tuple(truth.shape)} and "
-                                       f"{pred.dtype} {tuple(pred.shape)}")
+    _pair("power_spectrum", truth, pred, (3,), "(frames, H, W)", contiguous=True)
     frames, H, W = truth.shape
     nb = lib.query("adnm_valid_spectrum_accum_ws_bytes", frames, frames, H, W)
     if nb < 0:
@@ -3543,14 +3540,7 @@ def joint_histogram(truth, pred, value_scale):
     """truth / pred: contiguous fp32 GPU tensors (frames, H, W) or (B, T, H, W) of one shape -> (frames, L, L) int64 on the device,
     L = joint_levels(value_scale): [f][q_o][q_f] = the number of pixels of frame f whose quantised truth is q_o and whose quantised forecast
     is q_f.  Exact.  The one-shot use of adnm_valid_joint_accum (T = frames); validate.joint_entries / joint_counts_at read it."""
-    if not (torch.is_tensor(truth) and torch.is_tensor(pred)):
-        raise RuntimeError("joint_histogram: needs GPU tensors")
-    _need_gpu(truth)
-    _need_gpu(pred)
-    if (truth.dtype != torch.float32 or pred.dtype != torch.float32 or truth.shape != pred.shape or truth.dim() not in (3, 4) or truth.device != pred.device
-            or not truth.is_contiguous() or not pred.is_contiguous()):
-        _unsupported("joint_histogram", f"takes two contiguous fp32 tensors (frames, H, W) or (B, T, H, W) of one shape, got {truth.dtype} {tuple(truth.shape)} "
-                                        f"and {pred.dtype} {tuple(pred.shape)}")
+    _pair("joint_histogram", truth, pred, (3, 4), "(frames, H, W) or (B, T, H, W)", contiguous=True)
     L = joint_levels(value_scale)
     H, W = truth.shape[-2:]
     frames = truth.numel() // (H * W) if H * W else 0

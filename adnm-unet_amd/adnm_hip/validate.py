@@ -13,32 +13,37 @@ target) and valid_ssim_accum, both ADDING into one block of doubles that lives o
 include/adnm_hip.h, adnm_valid_accum).  done() reads that block — summed over the ranks of `process_group` with one all-reduce —
 and aggregates it exactly as GpuEvaluator.done() does.
 
+Every option below adds tables of its own behind that block, in the same allocation.  block_parts is the ONE statement of which tables
+there are and where each lies: the allocation, the launches (one per table, in the table's order) and aggregate all read it.  The defaults
+allocate and launch nothing new.
+
 Validator(..., pools=(4, 16, (16, 8)), persistence=True) adds neighbourhood scores and the persistence baseline:
 csrc/dataio.hip::valid_pool_accum counts TP / FN / FP / TN per window of a spatial max-pool, for the forecast and for the last input
-frame held over the horizon, into tables that follow the block in the same allocation; done(per_lead=True) adds every score per frame
-index, from the rows the block always kept.  The defaults allocate and launch nothing new.
+frame held over the horizon; done(per_lead=True) adds every score per frame index, from the rows the block always kept.
 
 Validator(..., fss=(1, 5, 17, 33)) adds the Fractions Skill Score per scale and threshold (DESIGN.md §4i): csrc/dataio.hip::valid_fss_accum
-adds the integer sums A = sum c_o^2, F = sum c_f^2, C = sum c_o c_f of the windowed event counts into tables that follow the pooled
-ones (the forecast's, then with persistence the baseline's), and done() reports FSS = 2C / (A + F) from the summed rows.
+adds the integer sums A = sum c_o^2, F = sum c_f^2, C = sum c_o c_f of the windowed event counts (for the forecast, and with persistence
+for the baseline), and done() reports FSS = 2C / (A + F) from the summed rows.
 
 Validator(..., advection=True) adds the Lagrangian-persistence baseline (DESIGN.md §4j): csrc/advect.hip::trec_cost / trec_pick estimate one
 motion vector per block from the last two input frames, advect moves the last frame along it for every frame index, and that field is
-scored as a second baseline by the same pooled and FSS passes, into two tables APPENDED to the block (pooled, then FSS).
+scored as a second baseline by the same pooled and FSS passes.
 
 Validator(..., spectrum=True) adds radially averaged power spectra (DESIGN.md §4k): csrc/spectrum.hip::valid_spectrum_accum transforms the
 clipped, scaled target and forecast (power-of-two frames of 8..512 pixels a side) and adds the power of each and their co-spectrum per
-radial wavenumber and frame index into a table APPENDED last to the block; done() reports the mean power per coefficient, the forecast's
-share of the observed power, the spectral coherence and the scale down to which the forecast keeps half the observed power.
+radial wavenumber and frame index; done() reports the mean power per coefficient, the forecast's share of the observed power, the
+spectral coherence and the scale down to which the forecast keeps half the observed power.
 
 Validator(..., joint=True) adds the joint intensity histogram (DESIGN.md §4l): csrc/joint.hip::valid_joint_accum counts, per frame index, the
-pixels at every pair (quantised target, quantised forecast) into a (T, L, L) table APPENDED behind the spectrum table, L = floor(value_scale)
-+ 1; done() derives the contingency table and the scores at EVERY integer threshold, the frequency bias, the conditional mean, a
-quantile-mapping table and the correlation from it (joint_entries), and joint_counts_at gives the counts at any threshold.
+pixels at every pair (quantised target, quantised forecast) into a (T, L, L) table, L = floor(value_scale) + 1; done() derives the
+contingency table and the scores at EVERY integer threshold, the frequency bias, the conditional mean, a quantile-mapping table and the
+correlation from it (joint_entries), and joint_counts_at gives the counts at any threshold.
 
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
+import math
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -67,38 +72,75 @@ def baseline_pools(pools):
     return ((1, 1),) + tuple(p for p in pools if p != (1, 1))
 
 
+class Part(NamedTuple):
+    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint, `field` the field it scores against the target
+    (pred: the forecast, last: the last input frame held, adv: that frame advected; None for main), `pools` the (size, stride) pairs of a
+    pool part's pass, `offset` its place in the block in doubles"""
+    name: str
+    kind: str
+    field: Optional[str]
+    pools: tuple
+    shape: tuple
+    offset: int
+
+    @property
+    def size(self):
+        return math.prod(self.shape)
+
+
+def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None):
+    """-> (the parts of the ONE allocation in their order, its doubles).  The order of the block, and of the launches that fill it, is stated
+    here and nowhere else.  pools: (size, stride) pairs; fss: scales; spectrum: (H, W) of the frames, or None; joint: the levels L, or None."""
+    pools, fss = tuple(pools), tuple(fss)
+    base = baseline_pools(pools)
+    pooled, scaled = (T, len(base), 4 * nthr), (T, len(fss), 3 * nthr)
+    rows = (("main", "main", None, (), (HEADER + T * (4 * nthr + 3),), True),
+            ("pooled", "pool", "pred", pools, (T, len(pools), 4 * nthr), pools),
+            ("persistence/pooled", "pool", "last", base, pooled, persistence),
+            ("fss", "fss", "pred", (), scaled, fss),
+            ("persistence/fss", "fss", "last", (), scaled, fss and persistence),
+            ("advection/pooled", "pool", "adv", base, pooled, advection),
+            ("advection/fss", "fss", "adv", (), scaled, fss and advection),
+            ("spectrum", "spectrum", "pred", (), (T, max(spectrum) // 2, 3) if spectrum else (), spectrum),
+            ("joint", "joint", "pred", (), (T, joint, joint), joint))
+    parts, at = [], 0
+    for *head, shape, present in rows:
+        if present:
+            parts.append(Part(*head, shape, at))
+            at += parts[-1].size
+    return parts, at
+
+
+def _doubles(names, *options, **more):
+    """the doubles of the named parts of block_parts(*options, **more), 0 for a part that is not there"""
+    size = {p.name: p.size for p in block_parts(*options, **more)[0]}
+    return tuple(size.get(n, 0) for n in names)
+
+
 def block_doubles(seq_len, nthr, pools=(), persistence=False):
-    """-> (doubles of the main block, of the forecast's pooled table, of the baseline's): the three parts of the ONE allocation, in order"""
-    cell = seq_len * 4 * nthr
-    return HEADER + seq_len * (4 * nthr + 3), cell * len(pools), cell * len(baseline_pools(pools)) if persistence else 0
+    """-> (doubles of the main block, of the forecast's pooled table, of the baseline's)"""
+    return _doubles(("main", "pooled", "persistence/pooled"), seq_len, nthr, pools, persistence)
 
 
 def fss_doubles(seq_len, nthr, fss=(), persistence=False):
-    """-> (doubles of the forecast's FSS table, of the baseline's): they follow block_doubles' three parts in the ONE allocation"""
-    cell = seq_len * len(fss) * 3 * nthr
-    return cell, cell if persistence else 0
+    """-> (doubles of the forecast's FSS table, of the baseline's)"""
+    return _doubles(("fss", "persistence/fss"), seq_len, nthr, (), persistence, fss)
 
 
 def advection_doubles(seq_len, nthr, pools=(), fss=(), advection=False):
-    """-> (doubles of the advection baseline's pooled table, of its FSS table): they follow fss_doubles' two parts in the ONE allocation"""
-    if not advection:
-        return 0, 0
-    return seq_len * 4 * nthr * len(baseline_pools(pools)), seq_len * len(fss) * 3 * nthr
+    """-> (doubles of the advection baseline's pooled table, of its FSS table)"""
+    return _doubles(("advection/pooled", "advection/fss"), seq_len, nthr, pools, fss=fss, advection=advection)
 
 
 def spectrum_doubles(seq_len, frame=None):
-    """-> doubles of the spectrum table (T, max(H, W) / 2, 3), which follows advection_doubles' two parts in the ONE allocation; frame: (H, W),
-    or None / False for none"""
-    return seq_len * (max(frame) // 2) * 3 if frame else 0
+    """-> doubles of the spectrum table (T, max(H, W) / 2, 3); frame: (H, W), or None / False for none"""
+    return _doubles(("spectrum",), seq_len, 1, spectrum=frame)[0]
 
 
 def joint_doubles(seq_len, value_scale=None):
-    """-> doubles of the joint histogram (T, L, L), L = ops.joint_levels(value_scale), the LAST part of the ONE allocation; value_scale None /
-    False for none"""
-    if value_scale is None or value_scale is False:
-        return 0
-    L = ops.joint_levels(value_scale)
-    return seq_len * L * L
+    """-> doubles of the joint histogram (T, L, L), L = ops.joint_levels(value_scale); value_scale None / False for none"""
+    none = value_scale is None or value_scale is False
+    return _doubles(("joint",), seq_len, 1, joint=None if none else ops.joint_levels(value_scale))[0]
 
 
 def _counts(hist):
@@ -239,44 +281,36 @@ def _lead_scores(rows, thresholds):
 
 
 def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False, spectrum=None, joint=None):
-    """host: the block (a float64 array of HEADER + T * (4*nthr + 3) values; with `pools` (size, stride) pairs then the forecast's pooled
-    table (T, npool, 4*nthr), with `persistence` then the baseline's (T, len(baseline_pools(pools)), 4*nthr): include/adnm_hip.h) -> the
-    dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's (Shanghai_metrics.py:218-290) as GpuEvaluator.done()
-    states them, from per-frame-index sums; "pooled", "persistence" and "per_lead" apply the same formulas to the pooled tables, the
-    baseline's tables and the single rows.  With `fss` (odd scales) the forecast's FSS table (T, nscale, 3*nthr) follows, with
-    `persistence` then the baseline's: "fss" {n: {thr: 2C / (A + F)}}, "fss_useful" {thr: 0.5 + f_o / 2} with f_o the observed event
-    fraction of the main table (the line above which a scale is called useful), and "fss" under "persistence" and "per_lead".  With
-    `advection` two more tables close the block, the advected field's pooled table (T, len(baseline_pools(pools)), 4*nthr) and, with
-    `fss`, its FSS table: "advection" and "per_lead"/"advection", built like "persistence".  With `spectrum` = (H, W), the frame size, the
-    spectrum table (T, max(H, W) / 2, 3) of sums P_o, P_f, C is the last part: "spectrum" {"wavenumber", "wavelength_px", "target" and
-    "forecast" (mean power per coefficient: sum / (n_r * samples * T)), "ratio" (forecast / target), "coherence" (C / sqrt(P_o P_f) of the
-    sums over the horizon, NaN where a power is 0), "effective_resolution_px" (the wavelength of the largest r >= 1 with ratio >= 0.5 at
-    every bin 1 .. r; inf when bin 1 fails)}, and under "per_lead" the same as (T, R) arrays from the single rows.  With `joint` = L, the
-    number of levels, the joint histogram (T, L, L) is the last part: "joint" = joint_entries of its sum over the horizon, and under
-    "per_lead" joint_entries of the table, every array with a leading T axis."""
+    """host: the block (a float64 array laid out as block_parts states for these options; `spectrum` = (H, W), the frame size, `joint` = L,
+    the number of levels: include/adnm_hip.h) -> the dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's
+    (Shanghai_metrics.py:218-290) as GpuEvaluator.done() states them, from per-frame-index sums; "pooled", "persistence", "advection" and
+    "per_lead" apply the same formulas to the pooled tables, the baselines' tables and the single rows.  `fss`: "fss" {n: {thr: 2C / (A + F)}},
+    also under each baseline and under "per_lead", and "fss_useful" {thr: 0.5 + f_o / 2} with f_o the observed event fraction of the main
+    table (the line above which a scale is called useful).  `spectrum`: "spectrum" {"wavenumber", "wavelength_px", "target" and "forecast"
+    (mean power per coefficient: sum / (n_r * samples * T)), "ratio" (forecast / target), "coherence" (C / sqrt(P_o P_f) of the sums over the
+    horizon, NaN where a power is 0), "effective_resolution_px" (the wavelength of the largest r >= 1 with ratio >= 0.5 at every bin 1 .. r;
+    inf when bin 1 fails)}, and under "per_lead" the same as (T, R) arrays from the single rows.  `joint`: "joint" = joint_entries of the
+    histogram's sum over the horizon, and under "per_lead" joint_entries of the table, every array with a leading T axis."""
     nthr, T = len(thresholds), seq_len
     pools, fss = tuple(pools), tuple(fss)
-    base = baseline_pools(pools) if persistence else ()
-    n0, n1, n2 = block_doubles(T, nthr, pools, persistence)
-    n3, n4 = fss_doubles(T, nthr, fss, persistence)
-    n5, n6 = advection_doubles(T, nthr, pools, fss, advection)
     spectrum = tuple(int(v) for v in spectrum) if spectrum else None
-    n7 = spectrum_doubles(T, spectrum)
     if spectrum:
         n_r, wavelength = ops.spectrum_bins(*spectrum)   # ValueError outside the limits
     joint = int(joint) if joint else None
     if joint is not None and not ops.MIN_JOINT_LEVELS <= joint <= ops.MAX_JOINT_LEVELS:
         raise ValueError(f"aggregate: joint is the number of levels, {ops.MIN_JOINT_LEVELS}..{ops.MAX_JOINT_LEVELS}, or None; got {joint}")
-    n8 = T * joint * joint if joint else 0
+    parts, total = block_parts(T, nthr, pools, persistence, fss, advection, spectrum, joint)
     blk = np.asarray(block, dtype=np.float64)
-    if blk.shape != (n0 + n1 + n2 + n3 + n4 + n5 + n6 + n7 + n8,):
-        raise ValueError(f"aggregate: a block of {n0 + n1 + n2 + n3 + n4 + n5 + n6 + n7 + n8} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
+    if blk.shape != (total,):
+        raise ValueError(f"aggregate: a block of {total} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
                          f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + (", advection" if advection else "")
                          + (f", spectrum of {spectrum[0]} x {spectrum[1]} frames" if spectrum else "") + (f", a joint histogram of {joint} levels" if joint else "")
                          + f"; got {blk.shape}")
+    tabs = {p.name: blk[p.offset:p.offset + p.size].reshape(p.shape) for p in parts}
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
-    tab = blk[HEADER:n0].reshape(T, 4 * nthr + 3)
-    metrics, all_far = contingency_metrics(tab[:, :4 * nthr].sum(axis=0), thresholds)
+    tab = tabs["main"][HEADER:].reshape(T, 4 * nthr + 3)
+    cells = tab[:, :4 * nthr].sum(axis=0)
+    metrics, all_far = contingency_metrics(cells, thresholds)
     with np.errstate(divide="ignore", invalid="ignore"):
         mse_t = tab[:, 4 * nthr + 1] / (hw * samples)            # per frame index: the mean over the samples of the frame's MSE
         rmse = float(np.mean(np.sqrt(mse_t)))
@@ -286,60 +320,45 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     res = {"threshold_metrics": metrics, "FAR": float(np.mean(all_far)), "RMSE": rmse, "MAE": mae, "MSE": float(mse_t.mean()), "SSIM": ssim,
            "LPIPS": None, "loss_sum": loss_sum, "loss_mean": loss_sum / finite if finite > 0 else float("nan"), "batches": int(batches),
            "samples": int(samples), "nonfinite": int(nonfinite)}
-    ftab = blk[n0:n0 + n1].reshape(T, len(pools), 4 * nthr)
-    btab = blk[n0 + n1:n0 + n1 + n2].reshape(T, len(base), 4 * nthr)
-    fss_f = blk[n0 + n1 + n2:n0 + n1 + n2 + n3].reshape(T, len(fss), 3 * nthr)
-    at = n0 + n1 + n2 + n3 + n4
-    fss_b = blk[n0 + n1 + n2 + n3:at].reshape(T, len(fss) if persistence else 0, 3 * nthr)
-    apools = baseline_pools(pools) if advection else ()
-    atab = blk[at:at + n5].reshape(T, len(apools), 4 * nthr)
-    fss_a = blk[at + n5:at + n5 + n6].reshape(T, len(fss) if advection else 0, 3 * nthr)
-    if pools:
-        res["pooled"] = {p: _scores(ftab[:, i].sum(axis=0), thresholds) for i, p in enumerate(pools)}
-    if persistence:
-        res["persistence"] = dict(_scores(btab[:, 0].sum(axis=0), thresholds),
-                                  pooled={p: _scores(btab[:, base.index(p)].sum(axis=0), thresholds) for p in pools})
-    if fss:
-        res["fss"] = _fss_scores(fss_f, fss, thresholds)
-        cells = tab[:, :4 * nthr].sum(axis=0)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            res["fss_useful"] = {_thr_key(thr): float(0.5 + (cells[4 * k] + cells[4 * k + 1]) / cells[4 * k:4 * k + 4].sum() / 2.0) for k, thr in enumerate(thresholds)}
-        if persistence:
-            res["persistence"]["fss"] = _fss_scores(fss_b, fss, thresholds)
-    if advection:
-        res["advection"] = dict(_scores(atab[:, 0].sum(axis=0), thresholds),
-                                pooled={p: _scores(atab[:, apools.index(p)].sum(axis=0), thresholds) for p in pools})
+
+    def counted(rows, lead):
+        """(T, 4 * nthr) counts of one field at one pool -> its entries over the horizon, or per frame index"""
+        return {"threshold_metrics": _lead_scores(rows, thresholds)} if lead else _scores(rows.sum(axis=0), thresholds)
+
+    def baseline(name, lead):
+        """the entries of a baseline field (persistence, advection) from its pooled table and, with fss, its FSS table"""
+        rows, order = tabs[name + "/pooled"], baseline_pools(pools)
+        ent = dict(counted(rows[:, 0], lead), pooled={p: counted(rows[:, order.index(p)], lead) for p in pools})
         if fss:
-            res["advection"]["fss"] = _fss_scores(fss_a, fss, thresholds)
-    if spectrum:
-        stab = blk[at + n5 + n6:at + n5 + n6 + n7].reshape(T, -1, 3)
-        res["spectrum"] = _spectrum_entries(stab.sum(axis=0), n_r * (samples * T), wavelength)
-    if joint:
-        jtab = blk[at + n5 + n6 + n7:].reshape(T, joint, joint)
-        res["joint"] = joint_entries(jtab.sum(axis=0))
+            ent["fss"] = (_fss_lead if lead else _fss_scores)(tabs[name + "/fss"], fss, thresholds)
+        return ent
+
+    def optional(lead):
+        """the entries the options add, in the dictionary's order: over the horizon, or (lead) per frame index"""
+        if pools:
+            yield "pooled", {p: counted(tabs["pooled"][:, i], lead) for i, p in enumerate(pools)}
+        if persistence:
+            yield "persistence", baseline("persistence", lead)
+        if fss:
+            yield "fss", (_fss_lead if lead else _fss_scores)(tabs["fss"], fss, thresholds)
+            if not lead:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    yield "fss_useful", {_thr_key(thr): float(0.5 + (cells[4 * k] + cells[4 * k + 1]) / cells[4 * k:4 * k + 4].sum() / 2.0)
+                                         for k, thr in enumerate(thresholds)}
+        if advection:
+            yield "advection", baseline("advection", lead)
+        if spectrum:
+            stab = tabs["spectrum"]
+            yield "spectrum", _spectrum_entries(stab if lead else stab.sum(axis=0), n_r * (samples if lead else samples * T), wavelength)
+        if joint:
+            yield "joint", joint_entries(tabs["joint"] if lead else tabs["joint"].sum(axis=0))
+    res.update(optional(False))
     if per_lead:
         with np.errstate(divide="ignore", invalid="ignore"):
             lead = {"RMSE": np.sqrt(mse_t), "MAE": tab[:, 4 * nthr] / (hw * samples),
                     "SSIM": None if ssim_area is None else tab[:, 4 * nthr + 2] / (ssim_area * samples),
                     "threshold_metrics": _lead_scores(tab[:, :4 * nthr], thresholds)}
-        if pools:
-            lead["pooled"] = {p: {"threshold_metrics": _lead_scores(ftab[:, i], thresholds)} for i, p in enumerate(pools)}
-        if persistence:
-            lead["persistence"] = {"threshold_metrics": _lead_scores(btab[:, 0], thresholds),
-                                   "pooled": {p: {"threshold_metrics": _lead_scores(btab[:, base.index(p)], thresholds)} for p in pools}}
-        if fss:
-            lead["fss"] = _fss_lead(fss_f, fss, thresholds)
-            if persistence:
-                lead["persistence"]["fss"] = _fss_lead(fss_b, fss, thresholds)
-        if advection:
-            lead["advection"] = {"threshold_metrics": _lead_scores(atab[:, 0], thresholds),
-                                 "pooled": {p: {"threshold_metrics": _lead_scores(atab[:, apools.index(p)], thresholds)} for p in pools}}
-            if fss:
-                lead["advection"]["fss"] = _fss_lead(fss_a, fss, thresholds)
-        if spectrum:
-            lead["spectrum"] = _spectrum_entries(stab, n_r * samples, wavelength)
-        if joint:
-            lead["joint"] = joint_entries(jtab)
+        lead.update(optional(True))
         res["per_lead"] = lead
     return res
 
@@ -359,23 +378,17 @@ class Validator(ForwardClient):
             raise ValueError("seq_len >= 1")
         self.ssim, self.process_group = bool(ssim), process_group
         self.pools, self.persistence = ops.pool_pairs(pools), bool(persistence)   # (size, stride) pairs; ValueError on a bad entry
-        # the pooled passes: (key of the input in _launch, its pools), the forecast's first — their tables follow the main block in this order
-        self._passes = ([("pred", self.pools)] if self.pools else []) + ([("last", baseline_pools(self.pools))] if self.persistence else [])
-        if self.persistence and len(baseline_pools(self.pools)) > ops.MAX_POOLS:
-            raise ValueError(f"Validator: the persistence baseline is scored at (1, 1) and at every pool, which makes {len(self.pools) + 1} pools; "
-                             f"a pass takes {ops.MAX_POOLS} (give (1, 1) among the pools, or one pool fewer)")
         self.fss = ops.fss_scales(fss)   # distinct odd scales <= 33; ValueError on a bad entry
-        # the FSS passes, the forecast's first: their tables follow the pooled ones in this order
-        self._fss_passes = (["pred"] + (["last"] if self.persistence else [])) if self.fss else []
         self.advection = ops.advection_spec(advection, self.thresholds)   # (block, radius, echo) or None; ValueError on a bad entry
-        if self.advection and len(baseline_pools(self.pools)) > ops.MAX_POOLS:
-            raise ValueError(f"Validator: the advection baseline is scored at (1, 1) and at every pool, which makes {len(self.pools) + 1} pools; "
-                             f"a pass takes {ops.MAX_POOLS} (give (1, 1) among the pools, or one pool fewer)")
         if self.advection and not 0.0 < self.value_scale <= 255.0:
             raise ValueError(f"Validator: advection matches blocks on quantised bytes, which needs 0 < value_scale <= 255, got {self.value_scale}")
-        self.spectrum = bool(spectrum)   # the spectrum table follows every other pass's; its size follows the epoch's frames
-        self.joint = bool(joint)         # the joint histogram (T, L, L) is the last part of the block
+        self.spectrum, self.joint = bool(spectrum), bool(joint)
         self._levels = ops.joint_levels(self.value_scale) if self.joint else None   # ValueError outside the limits
+        self._parts, _ = self._table(None)   # the spectrum part comes with the block: its size follows the epoch's frames
+        for part in self._parts:
+            if len(part.pools) > ops.MAX_POOLS:   # a baseline's pass; pool_pairs has bounded the forecast's
+                raise ValueError(f"Validator: the {part.name.split('/')[0]} baseline is scored at (1, 1) and at every pool, which makes {len(self.pools) + 1} pools; "
+                                 f"a pass takes {ops.MAX_POOLS} (give (1, 1) among the pools, or one pool fewer)")
         self._thr = (ctypes.c_float * len(self.thresholds))(*self.thresholds)
         self._fwd = GraphedForward(model, client=self, keep_quant=True)
         self._block = self._last = None    # the epoch's accumulator block and the last batch's fp32 loss: they outlive the graphs
@@ -383,17 +396,17 @@ class Validator(ForwardClient):
         self._spectrum_frame = None         # (H, W) the block's spectrum table was sized for
 
     # ---- device state
+    def _table(self, frame):
+        """block_parts for this Validator's options; frame: (H, W) of the epoch, which sizes the spectrum part (None: without that part)"""
+        return block_parts(self.seq_len, len(self.thresholds), self.pools, self.persistence, self.fss, bool(self.advection),
+                           frame if self.spectrum else None, self._levels)
+
     def _block_for(self, device):
-        """ONE allocation: adnm_valid_accum's block, then the pooled tables (none by default); done() reduces it with one all-reduce"""
+        """ONE allocation, the parts of block_parts; done() reduces it with one all-reduce"""
         if self._block is None:
-            n = lib.query("adnm_valid_block_bytes", self.seq_len, len(self.thresholds))
-            parts = (block_doubles(self.seq_len, len(self.thresholds), self.pools, self.persistence)
-                     + fss_doubles(self.seq_len, len(self.thresholds), self.fss, self.persistence)
-                     + advection_doubles(self.seq_len, len(self.thresholds), self.pools, self.fss, self.advection)
-                     + (spectrum_doubles(self.seq_len, self._frame if self.spectrum else None),)
-                     + (joint_doubles(self.seq_len, self.value_scale if self.joint else None),))
-            assert n == 8 * parts[0]
-            self._block = torch.zeros(sum(parts), dtype=torch.float64, device=device)
+            self._parts, total = self._table(self._frame)
+            assert lib.query("adnm_valid_block_bytes", self.seq_len, len(self.thresholds)) == 8 * self._parts[0].size
+            self._block = torch.zeros(total, dtype=torch.float64, device=device)
             self._last = torch.zeros((), dtype=torch.float32, device=device)
             self._spectrum_frame = self._frame
         elif self._block.device != device:
@@ -411,45 +424,36 @@ class Validator(ForwardClient):
         if ent["ws_ssim"] is not None:
             lib.call("adnm_valid_ssim_accum", pred.data_ptr(), ent["tgt"].data_ptr(), block.data_ptr(), nthr, self.value_scale, ent["ws_ssim"].data_ptr(),
                      ent["ws_ssim"].numel(), B * T, T, H, W, stream)
-        table = block.data_ptr() + 8 * block_doubles(T, nthr)[0]
 
-        def source(what):
-            if what == "pred":     # the forecast, contiguous
-                return pred.data_ptr(), (T * H * W, H * W)
-            t_in = sx.shape[1]     # persistence: the last input frame of the sample, for every frame index
-            return sx.data_ptr() + 4 * (t_in - 1) * H * W, (t_in * H * W, 0)
-        for what, pools in self._passes:
-            src, strides = source(what)
-            lib.call("adnm_valid_pool_accum", src, strides[0], strides[1], ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
-                     ops.pool_table(pools), len(pools), ent["ws_pool"].data_ptr(), ent["ws_pool"].numel(), B * T, T, H, W, stream)
-            table += 8 * T * len(pools) * 4 * nthr
-        for what in self._fss_passes:
-            src, strides = source(what)
-            lib.call("adnm_valid_fss_accum", src, strides[0], strides[1], ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
-                     ops.fss_table(self.fss), len(self.fss), ent["ws_fss"].data_ptr(), ent["ws_fss"].numel(), B * T, T, H, W, stream)
-            table += 8 * T * len(self.fss) * 3 * nthr
-        if self.advection:   # the advected field behind every pass that is there without it: its two tables close the block
-            block_px, radius, echo = self.advection
-            t_in, adv = sx.shape[1], ent["adv"]
-            lib.call("adnm_trec_motion", sx.data_ptr() + 4 * (t_in - 2) * H * W, sx.data_ptr() + 4 * (t_in - 1) * H * W, t_in * H * W, ent["motion"].data_ptr(),
-                     None, self.value_scale, block_px, radius, echo, ent["ws_trec"].data_ptr(), ent["ws_trec"].numel(), B, H, W, stream)
-            lib.call("adnm_advect", sx.data_ptr() + 4 * (t_in - 1) * H * W, t_in * H * W, ent["motion"].data_ptr(), adv.data_ptr(), block_px, B, T, H, W, stream)
-            pools = baseline_pools(self.pools)
-            lib.call("adnm_valid_pool_accum", adv.data_ptr(), T * H * W, H * W, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
-                     ops.pool_table(pools), len(pools), ent["ws_pool"].data_ptr(), ent["ws_pool"].numel(), B * T, T, H, W, stream)
-            table += 8 * T * len(pools) * 4 * nthr
-            if self.fss:
-                lib.call("adnm_valid_fss_accum", adv.data_ptr(), T * H * W, H * W, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale,
-                         ops.fss_table(self.fss), len(self.fss), ent["ws_fss"].data_ptr(), ent["ws_fss"].numel(), B * T, T, H, W, stream)
-        tail = T * self._levels * self._levels if self.joint else 0   # the joint histogram closes the block
-        if self.spectrum:   # the last table in front of that tail
-            table = block.data_ptr() + 8 * (block.numel() - tail - spectrum_doubles(T, (H, W)))
-            lib.call("adnm_valid_spectrum_accum", pred.data_ptr(), T * H * W, H * W, ent["tgt"].data_ptr(), table, self.value_scale, ent["ws_spectrum"].data_ptr(),
-                     ent["ws_spectrum"].numel(), B * T, T, H, W, stream)
-        if self.joint:
-            ws = ent["ws_joint"]
-            lib.call("adnm_valid_joint_accum", pred.data_ptr(), T * H * W, H * W, ent["tgt"].data_ptr(), block.data_ptr() + 8 * (block.numel() - tail),
-                     self.value_scale, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), B * T, T, H * W, stream)
+        def source(field):
+            """-> (pointer, sample stride, frame stride) of a scored field"""
+            if field == "last":    # persistence: the last input frame of the sample, for every frame index
+                t_in = sx.shape[1]
+                return sx.data_ptr() + 4 * (t_in - 1) * H * W, t_in * H * W, 0
+            return (pred if field == "pred" else ent["adv"]).data_ptr(), T * H * W, H * W   # contiguous (B, T, H, W)
+        moved = False
+        for part in self._parts[1:]:   # one launch per table, in the block's order
+            table = block.data_ptr() + 8 * part.offset
+            if part.field == "adv" and not moved:   # the advected field, in front of the first pass that scores it
+                block_px, radius, echo = self.advection
+                t_in, moved = sx.shape[1], True
+                lib.call("adnm_trec_motion", sx.data_ptr() + 4 * (t_in - 2) * H * W, sx.data_ptr() + 4 * (t_in - 1) * H * W, t_in * H * W, ent["motion"].data_ptr(),
+                         None, self.value_scale, block_px, radius, echo, ent["ws_trec"].data_ptr(), ent["ws_trec"].numel(), B, H, W, stream)
+                lib.call("adnm_advect", sx.data_ptr() + 4 * (t_in - 1) * H * W, t_in * H * W, ent["motion"].data_ptr(), ent["adv"].data_ptr(), block_px, B, T, H, W, stream)
+            src = source(part.field)
+            if part.kind == "pool":
+                lib.call("adnm_valid_pool_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, ops.pool_table(part.pools), len(part.pools),
+                         ent["ws_pool"].data_ptr(), ent["ws_pool"].numel(), B * T, T, H, W, stream)
+            elif part.kind == "fss":
+                lib.call("adnm_valid_fss_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, ops.fss_table(self.fss), len(self.fss),
+                         ent["ws_fss"].data_ptr(), ent["ws_fss"].numel(), B * T, T, H, W, stream)
+            elif part.kind == "spectrum":
+                lib.call("adnm_valid_spectrum_accum", *src, ent["tgt"].data_ptr(), table, self.value_scale, ent["ws_spectrum"].data_ptr(), ent["ws_spectrum"].numel(),
+                         B * T, T, H, W, stream)
+            else:   # joint
+                ws = ent["ws_joint"]
+                lib.call("adnm_valid_joint_accum", *src, ent["tgt"].data_ptr(), table, self.value_scale, None if ws is None else ws.data_ptr(),
+                         0 if ws is None else ws.numel(), B * T, T, H * W, stream)
 
     # ---- ForwardClient: what GraphedForward calls with the entry of one input shape
     def open(self, ent, x):
@@ -457,61 +461,53 @@ class Validator(ForwardClient):
         points on a scratch block (a kernel's first launch must not happen inside a capture)"""
         B, T, H, W = shape = (x.shape[0], self.seq_len) + self._frame
         dev, nthr = x.device, len(self.thresholds)
-        nb = lib.query("adnm_valid_accum_ws_bytes", B * T, T, H * W, nthr)
-        if nb < 0:
-            raise RuntimeError(f"Validator: a batch of {B * T} frames of {H} x {W} is outside adnm_valid_accum's limits (frames <= 65535, pixels per frame < 2^24)")
+
+        def workspace(entry, calls, limits, floor=16):
+            """query, raise with the limits, allocate: ONE workspace of the largest need among `calls` (the query's argument tuples), at least
+            `floor` bytes; None where nothing is needed"""
+            need = [int(lib.query(entry, *args)) for args in calls]
+            if min(need) < 0:
+                raise RuntimeError(f"Validator: {limits}")
+            size = max(need + [floor])
+            return torch.empty(size, dtype=torch.uint8, device=dev) if size else None
+        ws = workspace("adnm_valid_accum_ws_bytes", [(B * T, T, H * W, nthr)],
+                       f"a batch of {B * T} frames of {H} x {W} is outside adnm_valid_accum's limits (frames <= 65535, pixels per frame < 2^24)")
         ws_ssim = None
         if self.ssim and H > 10 and W > 10:   # 11 x 11 windows need a valid region; smaller frames: SSIM is None
             ws_ssim = torch.empty(max(int(lib.query("adnm_valid_ssim_accum_ws_bytes", B * T, T, H, W, nthr)), 16), dtype=torch.uint8, device=dev)
-        ws_pool = None
-        passes = [pools for _, pools in self._passes] + ([baseline_pools(self.pools)] if self.advection else [])
-        if passes:
-            need = [lib.query("adnm_valid_pool_accum_ws_bytes", B * T, T, H, W, nthr, ops.pool_table(pools), len(pools)) for pools in passes]
-            if min(need) < 0:
-                raise RuntimeError(f"Validator: pools {self.pools} on {B * T} frames of {H} x {W} are outside adnm_valid_pool_accum's limits "
-                                   "(no window larger than the frame, H and W < 32768)")
-            ws_pool = torch.empty(max(need), dtype=torch.uint8, device=dev)   # the passes follow one another on one stream: one workspace
-        ws_fss = None
-        if self.fss:
-            need = lib.query("adnm_valid_fss_accum_ws_bytes", B * T, T, H, W, nthr, ops.fss_table(self.fss), len(self.fss))
-            if need < 0:
-                raise RuntimeError(f"Validator: fss on {B * T} frames of {H} x {W} is outside adnm_valid_fss_accum's limits (H and W < 32768)")
-            ws_fss = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)   # the passes follow one another on one stream: one workspace
+        ws_pool = ws_fss = adv = motion = ws_trec = ws_spectrum = ws_joint = None
+        passes = [p.pools for p in self._parts if p.kind == "pool"]
+        if passes:   # the passes follow one another on one stream: one workspace
+            ws_pool = workspace("adnm_valid_pool_accum_ws_bytes", [(B * T, T, H, W, nthr, ops.pool_table(pools), len(pools)) for pools in passes],
+                                f"pools {self.pools} on {B * T} frames of {H} x {W} are outside adnm_valid_pool_accum's limits "
+                                "(no window larger than the frame, H and W < 32768)", floor=0)
+        if self.fss:   # likewise
+            ws_fss = workspace("adnm_valid_fss_accum_ws_bytes", [(B * T, T, H, W, nthr, ops.fss_table(self.fss), len(self.fss))],
+                               f"fss on {B * T} frames of {H} x {W} is outside adnm_valid_fss_accum's limits (H and W < 32768)")
         if self.persistence or self.advection:
             sx, what = ent["sx"], "persistence" if self.persistence else "advection"
             if (sx.dtype != torch.float32 or sx.dim() not in (4, 5) or (sx.dim() == 5 and sx.shape[2] != 1) or tuple(sx.shape[-2:]) != (H, W)
                     or sx.shape[1] < 1 or not sx.is_contiguous()):
                 raise RuntimeError(f"Validator: {what} needs the model's input as contiguous fp32 (B, T_in, 1, H, W) or (B, T_in, H, W) with the "
                                    f"target's {H} x {W} frames, got {sx.dtype} {tuple(sx.shape)}")
-        adv = motion = ws_trec = None
         if self.advection:
             if ent["sx"].shape[1] < 2:
                 raise RuntimeError(f"Validator: advection estimates the motion from the last two input frames, the input has {ent['sx'].shape[1]}")
             block_px, radius, _ = self.advection
-            need = lib.query("adnm_trec_ws_bytes", B, H, W, block_px, radius)
-            if need < 0:
-                raise RuntimeError(f"Validator: advection on {B} samples of {H} x {W} is outside adnm_trec_motion's limits (samples <= 65535, H and W < 32768, "
-                                   "H*W < 2^24)")
+            ws_trec = workspace("adnm_trec_ws_bytes", [(B, H, W, block_px, radius)],
+                                f"advection on {B} samples of {H} x {W} is outside adnm_trec_motion's limits (samples <= 65535, H and W < 32768, H*W < 2^24)")
             adv = torch.zeros(shape, dtype=torch.float32, device=dev)
             motion = torch.zeros((B, -(-H // block_px), -(-W // block_px), 2), dtype=torch.int32, device=dev)
-            ws_trec = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
-        ws_spectrum = None
         if self.spectrum:
-            need = lib.query("adnm_valid_spectrum_accum_ws_bytes", B * T, T, H, W)
-            if need < 0:
-                raise RuntimeError(f"Validator: spectrum on {B * T} frames of {H} x {W} is outside adnm_valid_spectrum_accum's limits (frames <= 65535, "
-                                   f"{ops.SPECTRUM_LIMITS})")
-            ws_spectrum = torch.empty(int(need), dtype=torch.uint8, device=dev)
-        ws_joint = None
+            ws_spectrum = workspace("adnm_valid_spectrum_accum_ws_bytes", [(B * T, T, H, W)],
+                                    f"spectrum on {B * T} frames of {H} x {W} is outside adnm_valid_spectrum_accum's limits (frames <= 65535, "
+                                    f"{ops.SPECTRUM_LIMITS})", floor=0)
         if self.joint:
-            need = lib.query("adnm_valid_joint_accum_ws_bytes", B * T, T, H * W, self.value_scale)
-            if need < 0:
-                raise RuntimeError(f"Validator: joint on {B * T} frames of {H} x {W} is outside adnm_valid_joint_accum's limits (frames <= 65535, "
-                                   f"H*W < 2^24, {ops.JOINT_LIMITS})")
-            if need:
-                ws_joint = torch.empty(int(need), dtype=torch.uint8, device=dev)
-        ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=torch.empty(max(int(nb), 16), dtype=torch.uint8, device=dev),
-                   ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss, ws_spectrum=ws_spectrum, ws_joint=ws_joint, adv=adv, motion=motion, ws_trec=ws_trec,
+            ws_joint = workspace("adnm_valid_joint_accum_ws_bytes", [(B * T, T, H * W, self.value_scale)],
+                                 f"joint on {B * T} frames of {H} x {W} is outside adnm_valid_joint_accum's limits (frames <= 65535, "
+                                 f"H*W < 2^24, {ops.JOINT_LIMITS})", floor=0)
+        ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=ws, ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss,
+                   ws_spectrum=ws_spectrum, ws_joint=ws_joint, adv=adv, motion=motion, ws_trec=ws_trec,
                    loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
         self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))

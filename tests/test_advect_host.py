@@ -176,11 +176,13 @@ def test_validator_arguments():
     assert inspect.signature(Validator.__init__).parameters["advection"].default is None
     model, crit = torch.nn.Identity(), enRainfallLoss()
     val = Validator(model, crit, 20, 255.0)
-    assert val.advection is None and val._passes == [] and val._fss_passes == []
+    pool = lambda v: [(p.field, p.pools) for p in v._parts if p.kind == "pool"]   # the pooled and the FSS passes, in the order of their tables and launches
+    fss = lambda v: [p.field for p in v._parts if p.kind == "fss"]
+    assert val.advection is None and pool(val) == [] and fss(val) == []
     val = Validator(model, crit, 20, 255.0, advection=True)
-    assert val.advection == (32, 4, 10) and val._passes == [] and val._fss_passes == []
+    assert val.advection == (32, 4, 10) and pool(val) == [("adv", ((1, 1),))] and fss(val) == []
     val = Validator(model, crit, 20, 90.0, [30, 40], advection=(16, 4), persistence=True, pools=(4,), fss=9)
-    assert val.advection == (16, 4, 15) and val._fss_passes == ["pred", "last"] and [p for _, p in val._passes] == [((4, 4),), ((1, 1), (4, 4))]
+    assert val.advection == (16, 4, 15) and fss(val) == ["pred", "last", "adv"] and pool(val) == [("pred", ((4, 4),)), ("last", ((1, 1), (4, 4))), ("adv", ((1, 1), (4, 4)))]
     for bad in ((12, 4), (16, 9), (16, 4, 0), "yes", 3):
         with pytest.raises(ValueError, match="advection"):
             Validator(model, crit, 20, 255.0, advection=bad)

@@ -285,11 +285,13 @@ def test_validator_arguments():
     assert inspect.signature(Validator.__init__).parameters["fss"].default is None
     model, crit = torch.nn.Identity(), enRainfallLoss()
     val = Validator(model, crit, 20, 255.0)
-    assert val.fss == () and val._fss_passes == [] and val._passes == []
+    pool = lambda v: [(p.field, p.pools) for p in v._parts if p.kind == "pool"]   # the pooled and the FSS passes, in the order of their tables and launches
+    fss = lambda v: [p.field for p in v._parts if p.kind == "fss"]
+    assert val.fss == () and fss(val) == [] and pool(val) == []
     val = Validator(model, crit, 20, 255.0, fss=(1, 5, 17, 33))
-    assert val.fss == (1, 5, 17, 33) and val._fss_passes == ["pred"] and val._passes == []
+    assert val.fss == (1, 5, 17, 33) and fss(val) == ["pred"] and pool(val) == []
     val = Validator(model, crit, 20, 255.0, fss=9, persistence=True, pools=(4,))
-    assert val.fss == (9,) and val._fss_passes == ["pred", "last"] and [p for _, p in val._passes] == [((4, 4),), ((1, 1), (4, 4))]
+    assert val.fss == (9,) and fss(val) == ["pred", "last"] and pool(val) == [("pred", ((4, 4),)), ("last", ((1, 1), (4, 4)))]
     for bad in ((2,), (35,), (5, 5), (1, 3, 5, 7, 9), (4.0,), "5"):
         with pytest.raises(ValueError):
             Validator(model, crit, 20, 255.0, fss=bad)

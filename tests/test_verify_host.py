@@ -215,11 +215,12 @@ def test_validator_arguments():
     assert list(inspect.signature(Validator.done).parameters)[:2] == ["self", "reset"]
     model, crit = torch.nn.Identity(), enRainfallLoss()
     val = Validator(model, crit, 20, 255.0)
-    assert val.pools == () and val.persistence is False and val._passes == []
+    passes = lambda v: [(p.field, p.pools) for p in v._parts if p.kind == "pool"]   # the pooled passes, in the order of their tables and launches
+    assert val.pools == () and val.persistence is False and passes(val) == [] and [p.name for p in val._parts] == ["main"]
     val = Validator(model, crit, 20, 255.0, pools=(4, 16, (16, 8)), persistence=True)
-    assert val.pools == ((4, 4), (16, 16), (16, 8)) and [p for _, p in val._passes] == [val.pools, ((1, 1),) + val.pools]
-    assert [p for _, p in Validator(model, crit, 20, 255.0, persistence=True)._passes] == [((1, 1),)]
-    assert [p for _, p in Validator(model, crit, 20, 255.0, pools=(4, 1), persistence=True)._passes] == [((4, 4), (1, 1)), ((1, 1), (4, 4))]
+    assert val.pools == ((4, 4), (16, 16), (16, 8)) and passes(val) == [("pred", val.pools), ("last", ((1, 1),) + val.pools)]
+    assert passes(Validator(model, crit, 20, 255.0, persistence=True)) == [("last", ((1, 1),))]
+    assert passes(Validator(model, crit, 20, 255.0, pools=(4, 1), persistence=True)) == [("pred", ((4, 4), (1, 1))), ("last", ((1, 1), (4, 4)))]
     for bad in ((0,), ((4, 5),), ((33, 1),), (2, 3, 4, 5, 6), (4.0,), ("4",), ((4, 2, 1),), (4, (4, 4))):
         with pytest.raises(ValueError):
             Validator(model, crit, 20, 255.0, pools=bad)
