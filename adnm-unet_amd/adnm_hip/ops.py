@@ -3555,6 +3555,72 @@ def joint_histogram(truth, pred, value_scale):
     return out.to(torch.int64)   # integers below 2^53 in doubles: exact
 
 
+# ======================================================================================= object-based scores (csrc/objects.hip)
+OBJ_COLS, OBJ_BINS, MAX_OBJECT_PIXELS = 23, 17, 65536
+OBJECTS_LIMITS = f"frames of 1 <= H * W <= {MAX_OBJECT_PIXELS} pixels"
+
+
+def objects_spec(objects):
+    """the Validator's `objects` argument -> min_area, or None for no object scores: None / False -> None, True -> 1, an int >= 1 ->
+    itself (objects of fewer pixels are ignored).  ValueError on anything else."""
+    if objects is None or objects is False:
+        return None
+    if objects is True:
+        return 1
+    if isinstance(objects, (int, np.integer)) and objects >= 1:
+        return int(objects)
+    raise ValueError(f"objects: None / False, True or an int min_area >= 1, got {objects!r}")
+
+
+def _min_area(op, min_area):
+    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or min_area < 1:
+        raise ValueError(f"{op}: min_area is an int >= 1, got {min_area!r}")
+    return int(min_area)
+
+
+def object_stats(truth, pred, thresholds, value_scale, min_area=1):
+    """truth / pred: contiguous fp32 GPU tensors (frames, H, W) or (B, T, H, W) of one shape -> (frames, 2, nthr, OBJ_COLS) int64 on the
+    device: per frame, field (0 = truth, 1 = pred) and threshold the number of 8-connected objects of the event mask q >= thr, their summed
+    area, summed squared area, the largest area, the number and the area of the objects that touch an event of the other field, and the
+    histogram of floor(log2(area)) (include/adnm_hip.h: adnm_valid_objects_accum).  Objects of fewer than min_area pixels are ignored.
+    Exact.  The one-shot use of adnm_valid_objects_accum (T = frames); validate.object_entries reads it."""
+    _pair("object_stats", truth, pred, (3, 4), "(frames, H, W) or (B, T, H, W)", contiguous=True)
+    thr = [float(t) for t in thresholds]
+    if not 1 <= len(thr) <= 8:
+        raise ValueError("object_stats: 1..8 thresholds")
+    min_area = _min_area("object_stats", min_area)
+    H, W = truth.shape[-2:]
+    frames = truth.numel() // (H * W) if H * W else 0
+    nb = lib.query("adnm_valid_objects_accum_ws_bytes", frames, frames, H, W, len(thr))
+    if nb < 0:
+        raise RuntimeError(f"object_stats: {frames} frames of {H} x {W} are outside adnm_valid_objects_accum's limits (1 <= frames <= 65535, "
+                           f"{OBJECTS_LIMITS})")
+    out = torch.zeros((frames, 2, len(thr), OBJ_COLS), dtype=torch.float64, device=truth.device)
+    ws = _ws(nb, truth.device) if nb else None
+    lib.call("adnm_valid_objects_accum", pred.data_ptr(), H * W, H * W, truth.data_ptr(), out.data_ptr(), (ctypes.c_float * len(thr))(*thr), len(thr),
+             float(value_scale), min_area, None if ws is None else ws.data_ptr(), int(nb), frames, frames, H, W, _stream())
+    return out.to(torch.int64)   # integers below 2^53 in doubles: exact
+
+
+def label_objects(field, thr, value_scale, min_area=1):
+    """field: a contiguous fp32 GPU tensor (..., H, W) -> int32 of the same shape: per frame the canonical labels of the 8-connected
+    objects of the event mask q >= thr, 1 + the row-major index of an object's first pixel, 0 for the background and for objects of fewer
+    than min_area pixels (include/adnm_hip.h: adnm_label_objects)."""
+    f = _frames("label_objects", field, "the field")
+    min_area = _min_area("label_objects", min_area)
+    H, W = f.shape[-2:]
+    frames = f.numel() // (H * W) if H * W else 0
+    nb = lib.query("adnm_label_objects_ws_bytes", frames, frames, H, W)
+    if nb < 0:
+        raise RuntimeError(f"label_objects: {frames} frames of {H} x {W} are outside adnm_label_objects' limits (1 <= frames <= 65535, "
+                           f"{OBJECTS_LIMITS})")
+    out = torch.empty(f.shape, dtype=torch.int32, device=f.device)
+    ws = _ws(nb, f.device) if nb else None
+    lib.call("adnm_label_objects", f.data_ptr(), H * W, H * W, out.data_ptr(), float(thr), float(value_scale), min_area,
+             None if ws is None else ws.data_ptr(), int(nb), frames, frames, H, W, _stream())
+    return out
+
+
 # ======================================================================================= the output side (csrc/dataio.hip: forecast_render)
 def edges_up_f32(edges):
     """double edges -> float32, each rounded UP to the smallest float >= it: the kernel compares an fp32 value with fp32 edges where

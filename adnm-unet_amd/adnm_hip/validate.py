@@ -39,6 +39,12 @@ pixels at every pair (quantised target, quantised forecast) into a (T, L, L) tab
 contingency table and the scores at EVERY integer threshold, the frequency bias, the conditional mean, a quantile-mapping table and the
 correlation from it (joint_entries), and joint_counts_at gives the counts at any threshold.
 
+Validator(..., objects=True) (or objects=min_area) adds object-based scores (DESIGN.md §4m): csrc/objects.hip::valid_objects_accum labels the
+8-connected components of the event mask of every frame, threshold and field (target, forecast) on the device and adds, per frame index, the
+number of objects, their areas, squared areas, the largest one, the objects the other field touches and a size histogram into a
+(T, 2, nthr, 23) table; done() reports counts, mean and area-weighted sizes, count and size bias and the object POD / FAR / CSI
+(object_entries).
+
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
@@ -73,7 +79,7 @@ def baseline_pools(pools):
 
 
 class Part(NamedTuple):
-    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint, `field` the field it scores against the target
+    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint / objects, `field` the field it scores against the target
     (pred: the forecast, last: the last input frame held, adv: that frame advected; None for main), `pools` the (size, stride) pairs of a
     pool part's pass, `offset` its place in the block in doubles"""
     name: str
@@ -88,9 +94,10 @@ class Part(NamedTuple):
         return math.prod(self.shape)
 
 
-def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None):
+def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, objects=None):
     """-> (the parts of the ONE allocation in their order, its doubles).  The order of the block, and of the launches that fill it, is stated
-    here and nowhere else.  pools: (size, stride) pairs; fss: scales; spectrum: (H, W) of the frames, or None; joint: the levels L, or None."""
+    here and nowhere else.  pools: (size, stride) pairs; fss: scales; spectrum: (H, W) of the frames, or None; joint: the levels L, or None;
+    objects: min_area, or None."""
     pools, fss = tuple(pools), tuple(fss)
     base = baseline_pools(pools)
     pooled, scaled = (T, len(base), 4 * nthr), (T, len(fss), 3 * nthr)
@@ -102,7 +109,8 @@ def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, s
             ("advection/pooled", "pool", "adv", base, pooled, advection),
             ("advection/fss", "fss", "adv", (), scaled, fss and advection),
             ("spectrum", "spectrum", "pred", (), (T, max(spectrum) // 2, 3) if spectrum else (), spectrum),
-            ("joint", "joint", "pred", (), (T, joint, joint), joint))
+            ("joint", "joint", "pred", (), (T, joint, joint), joint),
+            ("objects", "objects", "pred", (), (T, 2, nthr, ops.OBJ_COLS), objects))
     parts, at = [], 0
     for *head, shape, present in rows:
         if present:
@@ -141,6 +149,11 @@ def joint_doubles(seq_len, value_scale=None):
     """-> doubles of the joint histogram (T, L, L), L = ops.joint_levels(value_scale); value_scale None / False for none"""
     none = value_scale is None or value_scale is False
     return _doubles(("joint",), seq_len, 1, joint=None if none else ops.joint_levels(value_scale))[0]
+
+
+def objects_doubles(seq_len, nthr, objects=None):
+    """-> doubles of the objects table (T, 2, nthr, ops.OBJ_COLS); objects: what ops.objects_spec takes (None / False for none)"""
+    return _doubles(("objects",), seq_len, nthr, objects=ops.objects_spec(objects))[0]
 
 
 def _counts(hist):
@@ -226,6 +239,53 @@ def joint_entries(hist):
             "correlation": _scalar(corr), "mean_error": _scalar(mean_error)}
 
 
+def object_entries(rows, frames, thresholds, min_area=1):
+    """rows: (..., 2, nthr, ops.OBJ_COLS) integer sums (ops.object_stats' tensor, the Validator's table or its sum over the horizon; field 0 =
+    target, 1 = forecast) and `frames`, the number of frames behind every row (samples for a row of the table, samples * T for the sum over
+    the horizon) -> the entries of done()["objects"], the leading axes (none, or T) kept in front of every array:
+      "min_area"; then per threshold key
+        "target", "forecast": "count" N, "per_frame" N / frames, "area" sum a, "mean_area" sum a / N, "weighted_area" sum a^2 / sum a (the
+            size of the object a random event pixel lies in), "mean_largest" (the largest object's area, a frame without objects counting
+            0), "matched" (objects with a pixel that is an event of the other field), "matched_area", "size_histogram" (17 int64: objects
+            with floor(log2(area)) = k);
+        "count_bias" N_f / N_o, "size_bias" weighted_area_f / weighted_area_o, "object_POD" matched_o / N_o, "object_FAR"
+            1 - matched_f / N_f, "object_CSI" matched_o / (N_o + N_f - matched_f), "size_bin_edges" 2^k.
+    A division by zero gives NaN."""
+    if torch.is_tensor(rows):
+        rows = rows.detach().cpu().numpy()
+    r = np.asarray(rows)
+    nthr = len(thresholds)
+    if r.ndim < 3 or r.shape[-3:] != (2, nthr, ops.OBJ_COLS):
+        raise ValueError(f"objects: rows are (..., 2, {nthr}, {ops.OBJ_COLS}) for {nthr} thresholds, got {r.shape}")
+    if r.dtype.kind == "f":
+        if not (np.isfinite(r).all() and (r == np.rint(r)).all()):
+            raise ValueError("objects: the rows hold integer sums")
+    elif r.dtype.kind not in "iu":
+        raise ValueError(f"objects: the rows hold integer sums, got {r.dtype}")
+    r = r.astype(np.int64)
+    frames = np.asarray(frames, dtype=np.float64)
+
+    def ratio(a, b):
+        """a / b in float64, NaN where b is 0"""
+        a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return _scalar(np.where(b == 0, np.nan, a / b))
+
+    def field(c):
+        n, a, a2, big, m, ma = (c[..., i] for i in range(6))
+        return {"count": _scalar(n), "per_frame": ratio(n, frames), "area": _scalar(a), "mean_area": ratio(a, n), "weighted_area": ratio(a2, a),
+                "mean_largest": ratio(big, frames), "matched": _scalar(m), "matched_area": _scalar(ma), "size_histogram": c[..., 6:].copy()}
+    res = {"min_area": int(min_area)}
+    for k, thr in enumerate(thresholds):
+        o, f = field(r[..., 0, k, :]), field(r[..., 1, k, :])
+        res[_thr_key(thr)] = {"target": o, "forecast": f, "count_bias": ratio(f["count"], o["count"]),
+                              "size_bias": ratio(f["weighted_area"], o["weighted_area"]), "object_POD": ratio(o["matched"], o["count"]),
+                              "object_FAR": 1.0 - ratio(f["matched"], f["count"]),
+                              "object_CSI": ratio(o["matched"], np.asarray(o["count"]) + f["count"] - f["matched"]),
+                              "size_bin_edges": 2 ** np.arange(ops.OBJ_BINS, dtype=np.int64)}
+    return res
+
+
 def _spectrum_entries(sums, cells, wavelength):
     """(..., R, 3) sums P_o, P_f, C and the (..., R)-broadcastable number of coefficients behind each -> the entries of "spectrum"; the
     leading axes (none, or T) are kept"""
@@ -280,7 +340,8 @@ def _lead_scores(rows, thresholds):
     return metrics
 
 
-def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False, spectrum=None, joint=None):
+def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False, spectrum=None,
+              objects=None, joint=None):
     """host: the block (a float64 array laid out as block_parts states for these options; `spectrum` = (H, W), the frame size, `joint` = L,
     the number of levels: include/adnm_hip.h) -> the dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's
     (Shanghai_metrics.py:218-290) as GpuEvaluator.done() states them, from per-frame-index sums; "pooled", "persistence", "advection" and
@@ -290,7 +351,8 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     (mean power per coefficient: sum / (n_r * samples * T)), "ratio" (forecast / target), "coherence" (C / sqrt(P_o P_f) of the sums over the
     horizon, NaN where a power is 0), "effective_resolution_px" (the wavelength of the largest r >= 1 with ratio >= 0.5 at every bin 1 .. r;
     inf when bin 1 fails)}, and under "per_lead" the same as (T, R) arrays from the single rows.  `joint`: "joint" = joint_entries of the
-    histogram's sum over the horizon, and under "per_lead" joint_entries of the table, every array with a leading T axis."""
+    histogram's sum over the horizon, and under "per_lead" joint_entries of the table, every array with a leading T axis.  `objects` (what
+    ops.objects_spec takes): "objects" = object_entries of the table's sum over the horizon, and under "per_lead" object_entries of the table."""
     nthr, T = len(thresholds), seq_len
     pools, fss = tuple(pools), tuple(fss)
     spectrum = tuple(int(v) for v in spectrum) if spectrum else None
@@ -299,12 +361,14 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     joint = int(joint) if joint else None
     if joint is not None and not ops.MIN_JOINT_LEVELS <= joint <= ops.MAX_JOINT_LEVELS:
         raise ValueError(f"aggregate: joint is the number of levels, {ops.MIN_JOINT_LEVELS}..{ops.MAX_JOINT_LEVELS}, or None; got {joint}")
-    parts, total = block_parts(T, nthr, pools, persistence, fss, advection, spectrum, joint)
+    objects = ops.objects_spec(objects)
+    parts, total = block_parts(T, nthr, pools, persistence, fss, advection, spectrum, joint, objects)
     blk = np.asarray(block, dtype=np.float64)
     if blk.shape != (total,):
         raise ValueError(f"aggregate: a block of {total} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
                          f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + (", advection" if advection else "")
                          + (f", spectrum of {spectrum[0]} x {spectrum[1]} frames" if spectrum else "") + (f", a joint histogram of {joint} levels" if joint else "")
+                         + (", objects" if objects else "")
                          + f"; got {blk.shape}")
     tabs = {p.name: blk[p.offset:p.offset + p.size].reshape(p.shape) for p in parts}
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
@@ -352,6 +416,9 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
             yield "spectrum", _spectrum_entries(stab if lead else stab.sum(axis=0), n_r * (samples if lead else samples * T), wavelength)
         if joint:
             yield "joint", joint_entries(tabs["joint"] if lead else tabs["joint"].sum(axis=0))
+        if objects:
+            otab = tabs["objects"]
+            yield "objects", object_entries(otab if lead else otab.sum(axis=0), samples if lead else samples * T, thresholds, objects)
     res.update(optional(False))
     if per_lead:
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -365,7 +432,7 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
 
 class Validator(ForwardClient):
     def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False,
-                 fss=None, advection=None, spectrum=False, joint=False):
+                 fss=None, advection=None, spectrum=False, objects=None, joint=False):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -384,6 +451,7 @@ class Validator(ForwardClient):
             raise ValueError(f"Validator: advection matches blocks on quantised bytes, which needs 0 < value_scale <= 255, got {self.value_scale}")
         self.spectrum, self.joint = bool(spectrum), bool(joint)
         self._levels = ops.joint_levels(self.value_scale) if self.joint else None   # ValueError outside the limits
+        self.objects = ops.objects_spec(objects)   # min_area, or None; ValueError on a bad entry
         self._parts, _ = self._table(None)   # the spectrum part comes with the block: its size follows the epoch's frames
         for part in self._parts:
             if len(part.pools) > ops.MAX_POOLS:   # a baseline's pass; pool_pairs has bounded the forecast's
@@ -399,7 +467,7 @@ class Validator(ForwardClient):
     def _table(self, frame):
         """block_parts for this Validator's options; frame: (H, W) of the epoch, which sizes the spectrum part (None: without that part)"""
         return block_parts(self.seq_len, len(self.thresholds), self.pools, self.persistence, self.fss, bool(self.advection),
-                           frame if self.spectrum else None, self._levels)
+                           frame if self.spectrum else None, self._levels, self.objects)
 
     def _block_for(self, device):
         """ONE allocation, the parts of block_parts; done() reduces it with one all-reduce"""
@@ -450,10 +518,14 @@ class Validator(ForwardClient):
             elif part.kind == "spectrum":
                 lib.call("adnm_valid_spectrum_accum", *src, ent["tgt"].data_ptr(), table, self.value_scale, ent["ws_spectrum"].data_ptr(), ent["ws_spectrum"].numel(),
                          B * T, T, H, W, stream)
-            else:   # joint
+            elif part.kind == "joint":
                 ws = ent["ws_joint"]
                 lib.call("adnm_valid_joint_accum", *src, ent["tgt"].data_ptr(), table, self.value_scale, None if ws is None else ws.data_ptr(),
                          0 if ws is None else ws.numel(), B * T, T, H * W, stream)
+            else:   # objects
+                ws = ent["ws_objects"]
+                lib.call("adnm_valid_objects_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, self.objects,
+                         None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), B * T, T, H, W, stream)
 
     # ---- ForwardClient: what GraphedForward calls with the entry of one input shape
     def open(self, ent, x):
@@ -475,7 +547,7 @@ class Validator(ForwardClient):
         ws_ssim = None
         if self.ssim and H > 10 and W > 10:   # 11 x 11 windows need a valid region; smaller frames: SSIM is None
             ws_ssim = torch.empty(max(int(lib.query("adnm_valid_ssim_accum_ws_bytes", B * T, T, H, W, nthr)), 16), dtype=torch.uint8, device=dev)
-        ws_pool = ws_fss = adv = motion = ws_trec = ws_spectrum = ws_joint = None
+        ws_pool = ws_fss = adv = motion = ws_trec = ws_spectrum = ws_joint = ws_objects = None
         passes = [p.pools for p in self._parts if p.kind == "pool"]
         if passes:   # the passes follow one another on one stream: one workspace
             ws_pool = workspace("adnm_valid_pool_accum_ws_bytes", [(B * T, T, H, W, nthr, ops.pool_table(pools), len(pools)) for pools in passes],
@@ -506,8 +578,12 @@ class Validator(ForwardClient):
             ws_joint = workspace("adnm_valid_joint_accum_ws_bytes", [(B * T, T, H * W, self.value_scale)],
                                  f"joint on {B * T} frames of {H} x {W} is outside adnm_valid_joint_accum's limits (frames <= 65535, "
                                  f"H*W < 2^24, {ops.JOINT_LIMITS})", floor=0)
+        if self.objects:
+            ws_objects = workspace("adnm_valid_objects_accum_ws_bytes", [(B * T, T, H, W, nthr)],
+                                   f"objects on {B * T} frames of {H} x {W} are outside adnm_valid_objects_accum's limits (frames <= 65535, "
+                                   f"{ops.OBJECTS_LIMITS})", floor=0)
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=ws, ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss,
-                   ws_spectrum=ws_spectrum, ws_joint=ws_joint, adv=adv, motion=motion, ws_trec=ws_trec,
+                   ws_spectrum=ws_spectrum, ws_joint=ws_joint, ws_objects=ws_objects, adv=adv, motion=motion, ws_trec=ws_trec,
                    loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
         self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
@@ -593,7 +669,9 @@ class Validator(ForwardClient):
         spectrum: plus "spectrum" {"wavenumber", "wavelength_px", "target", "forecast", "ratio", "coherence", "effective_resolution_px"}
         (aggregate) and, as (T, R) arrays with a length-T "effective_resolution_px", "per_lead"/"spectrum".
         joint: plus "joint" {"levels", "histogram", "marginal_target", "marginal_forecast", "curves", "conditional_mean", "qq", "correlation",
-        "mean_error"} (joint_entries of the table summed over the horizon) and "per_lead"/"joint", the same with a leading T axis."""
+        "mean_error"} (joint_entries of the table summed over the horizon) and "per_lead"/"joint", the same with a leading T axis.
+        objects: plus "objects" {"min_area", thr: {"target", "forecast", "count_bias", "size_bias", "object_POD", "object_FAR", "object_CSI",
+        "size_bin_edges"}} (object_entries of the table summed over the horizon) and "per_lead"/"objects", the same with a leading T axis."""
         if self._block is None or self._frame is None:
             raise RuntimeError("Validator.done: no batch since the last reset")
         blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
@@ -601,7 +679,7 @@ class Validator(ForwardClient):
         H, W = self._frame
         area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
         res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead,
-                        fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None, joint=self._levels)
+                        fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None, joint=self._levels, objects=self.objects)
         if reset:
             self.reset()
         return res

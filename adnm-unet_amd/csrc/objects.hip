@@ -1,0 +1,344 @@
+// Connected-component labelling of the event masks and the object scores that follow from it (include/adnm_hip.h: adnm_valid_objects_accum,
+// adnm_label_objects).  An event is q(v) >= thr with q = eval_trunc(eval_scaled(v, value_scale)) of adnm_common.h; an object is
+// an 8-connected component of one frame's event mask; its label is 1 + the row-major index of its first pixel.
+//
+//   one workgroup   per (frame, threshold) in objects_kernel — it labels the target, then the forecast, because matching needs both masks —
+//                   and per frame in label_kernel.  No workgroup waits for another one: every barrier below is a workgroup barrier.
+//   the bits        each field is read from HBM once per workgroup and kept as one event bit per pixel in LDS (a ballot per 64 pixels).
+//                   Everything after that reads bits, never floats.
+//   the words       one u32 per pixel, in LDS where the frame fits beside the bits (H * W <= about 38 000) and in the workgroup's slice of
+//                   the workspace otherwise.  While labelling, an event pixel's word is its parent: the index of a pixel of the same
+//                   object that is not larger than its own.  A word only ever decreases.
+//   runs            a pixel starts with the first pixel of its horizontal run of events as parent (bit scans, no memory traffic), so
+//                   the left neighbour needs no union.
+//   unions          label equivalence: union-find with atomicMin links and pointer jumping (Komura 2015; Playne & Hawick 2018).  A pixel
+//                   unites with the row above only where no neighbour makes the same union: with N unless W and NW are events; else with
+//                   NW unless W is an event and with NE unless E is.  A union finds both roots, links the larger to the smaller with an
+//                   atomicMin and, where another lane was faster, goes on from the value it displaced.  ONE sweep of unions is complete
+//                   whatever the shape (a serpentine included); a find is bounded by H * W steps (parents decrease strictly), a union by
+//                   H * W retries, and a union that ran out raises a flag that repeats the sweep, itself at most H * W times.
+//   areas           after a flattening pass every event pixel points at its root, the smallest index of the object.  Roots then become
+//                   counters (kRoot | area, kMatched in the top bit): the first pixel of each run adds the run's length and ors the flag
+//                   in when the OTHER field has an event inside the run.
+//   the row         every root of at least min_area pixels adds its entries to 23 u64 counters in LDS; the non-zero ones go to the table
+//                   as double atomics.  Every addend and every sum is an integer below 2^53, so the table is exact and the same bits on
+//                   every run although the order of the atomics is not fixed.
+#include "adnm_common.h"
+
+namespace {
+constexpr int kBlock = 1024;
+constexpr int kMaxThr = 8;
+constexpr int kCols = 23, kBins = 17;          // count, area, area^2, largest, matched, matched area, 17 bins of floor(log2(area))
+static_assert(kCols == 6 + kBins, "six sums, then the size histogram");
+constexpr int64_t kMaxPixels = 65536;          // an area fits 17 bits (bin 16 is the last); area^2 <= 2^32
+constexpr int kMaxGroups = 512;                // workgroups of a launch whose words live in the workspace
+constexpr size_t kLdsLimit = 160 * 1024;
+constexpr unsigned kRoot = 1u << 30, kMatched = 1u << 31, kAreaMask = (1u << 20) - 1u;
+constexpr size_t kHead = 8 * 24 + 16;          // 23 u64 counters (24 for alignment), then the sweep flag
+
+struct ObjThr {
+  float t[kMaxThr];
+};
+
+__device__ __forceinline__ unsigned ld(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ bool bit(const unsigned* bits, int p) { return (bits[p >> 5] >> (p & 31)) & 1u; }
+
+// words of one field's bits: whole ballots of 64 pixels
+__host__ __device__ __forceinline__ int bit_words(int hw) { return 2 * ((hw + 63) / 64); }
+
+// one event bit per pixel; every word of bits[0 .. bit_words(hw)) is written, pixels past hw as 0
+__device__ __forceinline__ void stage_bits(unsigned* bits, const float* __restrict__ src, int hw, float thr, float value_scale) {
+  const int lane = threadIdx.x & 63, span = bit_words(hw) * 32;
+  for (int base = (threadIdx.x >> 6) * 64; base < span; base += kBlock) {
+    const int p = base + lane;
+    const bool ev = p < hw && eval_trunc(eval_scaled(src[p], value_scale)) >= thr;
+    const unsigned long long m = __ballot(ev);
+    if (lane == 0) bits[base >> 5] = (unsigned)m, bits[(base >> 5) + 1] = (unsigned)(m >> 32);
+  }
+}
+
+// the first pixel of the run of events that holds p (bit p is set), not left of row0.  At most W / 32 + 1 words are looked at.
+__device__ __forceinline__ int run_start(const unsigned* bits, int p, int row0) {
+  int w = p >> 5;
+  unsigned zeros = ~bits[w] & ((2u << (p & 31)) - 1u);   // the non-events at or below p in its word
+  while (zeros == 0u) {
+    if ((w << 5) <= row0) return row0;
+    zeros = ~bits[--w];
+  }
+  const int s = (w << 5) + 32 - __clz((int)zeros);
+  return s > row0 ? s : row0;
+}
+// one past the last pixel of that run, not right of row1 = the row's end.  Bits past H * W are 0, so no word past the array is read.
+__device__ __forceinline__ int run_end(const unsigned* bits, int p, int row1) {
+  int w = p >> 5;
+  unsigned zeros = ~bits[w] & ~((2u << (p & 31)) - 1u);  // the non-events above p in its word
+  while (zeros == 0u) {
+    if (((++w) << 5) >= row1) return row1;
+    zeros = ~bits[w];
+  }
+  const int e = (w << 5) + __ffs((int)zeros) - 1;
+  return e < row1 ? e : row1;
+}
+// does bits hold an event in [s, e)?  s < e
+__device__ __forceinline__ bool any_bit(const unsigned* bits, int s, int e) {
+  const int w0 = s >> 5, w1 = (e - 1) >> 5;
+  for (int w = w0; w <= w1; ++w) {
+    unsigned m = bits[w];
+    if (w == w0) m &= ~0u << (s & 31);
+    if (w == w1) m &= ~0u >> (31 - ((e - 1) & 31));
+    if (m) return true;
+  }
+  return false;
+}
+
+// the root above x as far as `bound` steps reach (parents decrease strictly: hw steps reach every root); x's word jumps to it
+__device__ __forceinline__ unsigned find_root(unsigned* word, unsigned x, int bound) {
+  const unsigned first = ld(word + x);
+  unsigned r = x, p = first;
+  for (int i = 0; p != r && i < bound; ++i) r = p, p = ld(word + r);
+  if (r != first) atomicMin(word + x, r);
+  return r;
+}
+// a and b are pixels of one object: afterwards they have one root.  false: gave up after `bound` lost races (the sweep is then repeated)
+__device__ __forceinline__ bool unite(unsigned* word, unsigned a, unsigned b, int bound) {
+  for (int i = 0; i < bound; ++i) {
+    a = find_root(word, a, bound), b = find_root(word, b, bound);
+    if (a == b) return true;
+    if (a < b) {
+      const unsigned t = a;
+      a = b, b = t;
+    }
+    const unsigned old = atomicMin(word + a, b);   // a > b: hang a below b
+    if (old == a) return true;
+    a = old;   // another lane had linked a already, and that link may be gone now: go on with what it pointed at
+  }
+  return false;
+}
+
+// bits -> word[p] = kRoot | area (| kMatched) for the first pixel p of every object, the index of that pixel for the object's other pixels,
+// 0 for non-events.  other: the other field's bits, or nullptr.  Every lane of the workgroup calls it.
+__device__ __forceinline__ void label_field(unsigned* word, const unsigned* bits, const unsigned* other, unsigned* flag, int hw, int W) {
+  const int tid = threadIdx.x;
+  for (int p = tid; p < hw; p += kBlock) st(word + p, bit(bits, p) ? (unsigned)run_start(bits, p, p - p % W) : 0u);
+  for (int sweep = 0; sweep < hw; ++sweep) {   // one sweep unless a union gave up
+    __syncthreads();
+    if (tid == 0) *flag = 0u;
+    __syncthreads();
+    bool ok = true;
+    for (int p = tid + W; p < hw; p += kBlock) {
+      if (!bit(bits, p)) continue;
+      const int x = p % W, up = p - W;
+      const bool l = x > 0, r = x + 1 < W;
+      const bool n = bit(bits, up), w = l && bit(bits, p - 1), e = r && bit(bits, p + 1), nw = l && bit(bits, up - 1), ne = r && bit(bits, up + 1);
+      if (n) {
+        if (!(w && nw)) ok &= unite(word, p, up, hw);
+      } else {
+        if (nw && !w) ok &= unite(word, p, up - 1, hw);
+        if (ne && !e) ok &= unite(word, p, up + 1, hw);
+      }
+    }
+    if (!ok) *flag = 1u;
+    __syncthreads();
+    if (*flag == 0u) break;
+  }
+  for (int p = tid; p < hw; p += kBlock)
+    if (bit(bits, p)) find_root(word, p, hw);   // the forest is final: every event's word becomes its root
+  __syncthreads();
+  for (int p = tid; p < hw; p += kBlock)
+    if (bit(bits, p) && ld(word + p) == (unsigned)p) st(word + p, kRoot);
+  __syncthreads();
+  for (int p = tid; p < hw; p += kBlock) {
+    const int row0 = p - p % W;
+    if (!bit(bits, p) || (p > row0 && bit(bits, p - 1))) continue;   // the first pixel of a run speaks for the run
+    const int e = run_end(bits, p, row0 + W);
+    const unsigned wd = ld(word + p), root = (wd & kRoot) ? (unsigned)p : wd;
+    atomicAdd(word + root, (unsigned)(e - p));
+    if (other && any_bit(other, p, e)) atomicOr(word + root, kMatched);
+  }
+  __syncthreads();
+}
+
+struct Smem {
+  unsigned long long* acc;
+  unsigned *flag, *bits_o, *bits_f, *word;
+};
+// dynamic LDS: counters, flag, the two bit fields, then (LDSW) the words
+template <bool LDSW>
+__device__ __forceinline__ Smem carve(unsigned char* smem, unsigned* ws, int hw) {
+  Smem s;
+  s.acc = (unsigned long long*)smem;
+  s.flag = (unsigned*)(smem + 8 * 24);
+  s.bits_o = (unsigned*)(smem + kHead);
+  s.bits_f = s.bits_o + bit_words(hw);
+  if constexpr (LDSW) s.word = s.bits_f + bit_words(hw);
+  else s.word = ws + (int64_t)blockIdx.x * hw;
+  return s;
+}
+
+// grid (G): item = frame * nthr + k; frame f = b * T + t of the forecast starts at pred + b * sstride + t * fstride
+template <bool LDSW>
+__global__ __launch_bounds__(kBlock) void objects_kernel(const float* __restrict__ pred, int64_t sstride, int64_t fstride, const float* __restrict__ tgt,
+                                                         double* __restrict__ table, ObjThr thr, int nthr, float value_scale, unsigned min_area,
+                                                         unsigned* __restrict__ ws, int items, int T, int H, int W) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int hw = H * W, tid = threadIdx.x;
+  const Smem s = carve<LDSW>(smem, ws, hw);
+  for (int item = blockIdx.x; item < items; item += gridDim.x) {
+    const int f = item / nthr, k = item % nthr, b = f / T, t = f % T;
+    __syncthreads();   // the item before is done with the bits
+    stage_bits(s.bits_o, tgt + (int64_t)f * hw, hw, thr.t[k], value_scale);
+    stage_bits(s.bits_f, pred + (int64_t)b * sstride + (int64_t)t * fstride, hw, thr.t[k], value_scale);
+    for (int field = 0; field < 2; ++field) {
+      const unsigned* bits = field ? s.bits_f : s.bits_o;
+      if (tid < 24) s.acc[tid] = 0ull;
+      __syncthreads();   // the bits and the zeroed counters
+      label_field(s.word, bits, field ? s.bits_o : s.bits_f, s.flag, hw, W);
+      unsigned n = 0, area = 0, largest = 0, matched = 0, matched_area = 0;
+      unsigned long long squares = 0;
+      for (int p = tid; p < hw; p += kBlock) {
+        if (!bit(bits, p)) continue;
+        const unsigned wd = ld(s.word + p), a = wd & kAreaMask;
+        if (!(wd & kRoot) || a < min_area) continue;
+        n += 1, area += a, squares += (unsigned long long)a * a, largest = a > largest ? a : largest;
+        if (wd & kMatched) matched += 1, matched_area += a;
+        atomicAdd(&s.acc[6 + 31 - __clz((int)a)], 1ull);   // a <= 65536: bin <= 16
+      }
+      if (n) {
+        atomicAdd(&s.acc[0], (unsigned long long)n), atomicAdd(&s.acc[1], (unsigned long long)area), atomicAdd(&s.acc[2], squares);
+        atomicMax(&s.acc[3], (unsigned long long)largest);
+        if (matched) atomicAdd(&s.acc[4], (unsigned long long)matched), atomicAdd(&s.acc[5], (unsigned long long)matched_area);
+      }
+      __syncthreads();
+      if (tid < kCols && s.acc[tid]) unsafeAtomicAdd(&table[(((int64_t)t * 2 + field) * nthr + k) * kCols + tid], (double)s.acc[tid]);
+      __syncthreads();   // the counters are read before the next field zeroes them
+    }
+  }
+}
+
+// grid (G): one frame of one field per item; frame f = b * T + t starts at src + b * sstride + t * fstride
+template <bool LDSW>
+__global__ __launch_bounds__(kBlock) void label_kernel(const float* __restrict__ src, int64_t sstride, int64_t fstride, int* __restrict__ labels, float thr,
+                                                       float value_scale, unsigned min_area, unsigned* __restrict__ ws, int frames, int T, int H, int W) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int hw = H * W, tid = threadIdx.x;
+  const Smem s = carve<LDSW>(smem, ws, hw);
+  for (int f = blockIdx.x; f < frames; f += gridDim.x) {
+    __syncthreads();
+    stage_bits(s.bits_o, src + (int64_t)(f / T) * sstride + (int64_t)(f % T) * fstride, hw, thr, value_scale);
+    __syncthreads();
+    label_field(s.word, s.bits_o, nullptr, s.flag, hw, W);
+    int* out = labels + (int64_t)f * hw;
+    for (int p = tid; p < hw; p += kBlock) {
+      int lab = 0;
+      if (bit(s.bits_o, p)) {
+        const unsigned wd = ld(s.word + p), root = (wd & kRoot) ? (unsigned)p : wd;
+        if ((ld(s.word + root) & kAreaMask) >= min_area) lab = (int)root + 1;
+      }
+      out[p] = lab;
+    }
+  }
+}
+
+inline size_t lds_bytes(int64_t hw, bool words) { return kHead + 2 * sizeof(unsigned) * (size_t)bit_words((int)hw) + (words ? sizeof(unsigned) * (size_t)hw : 0); }
+inline bool words_in_lds(int64_t hw) { return lds_bytes(hw, true) <= kLdsLimit; }
+const char* frame_why(int64_t frames, int64_t T, int64_t H, int64_t W) {
+  if (T < 1 || frames < 1 || frames % T != 0) return "T >= 1 must divide frames";
+  if (frames > 65535) return "frames <= 65535";
+  if (H < 1 || W < 1 || H > kMaxPixels || W > kMaxPixels || H * W > kMaxPixels) return "1 <= H * W <= 65536";
+  return nullptr;
+}
+inline int64_t groups_of(int64_t items, int64_t hw) { return words_in_lds(hw) || items < kMaxGroups ? items : kMaxGroups; }
+inline int64_t ws_need(int64_t items, int64_t hw) { return words_in_lds(hw) ? 0 : (int64_t)sizeof(unsigned) * groups_of(items, hw) * hw; }
+}  // namespace
+
+extern "C" int64_t adnm_valid_objects_block_bytes(int64_t T, int64_t nthr) {
+  if (T < 1 || T > 65535 || nthr < 1 || nthr > kMaxThr) return -1;
+  return (int64_t)sizeof(double) * T * 2 * nthr * kCols;
+}
+
+extern "C" int64_t adnm_valid_objects_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr) {
+  if (frame_why(frames, T, H, W) || nthr < 1 || nthr > kMaxThr) return -1;
+  return ws_need(frames * nthr, H * W);
+}
+
+extern "C" int64_t adnm_label_objects_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W) {
+  if (frame_why(frames, T, H, W)) return -1;
+  return ws_need(frames, H * W);
+}
+
+extern "C" int adnm_valid_objects_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                                        const float* thresholds_host, int64_t nthr, float value_scale, int64_t min_area, void* ws, int64_t ws_bytes,
+                                        int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream) {
+  ADNM_REQUIRE(pred && target && table && thresholds_host, "valid_objects_accum: null pointer");
+  ADNM_REQUIRE(((uintptr_t)pred | (uintptr_t)target) % 4 == 0, "valid_objects_accum: pred and target must be 4-byte aligned");
+  ADNM_REQUIRE((uintptr_t)table % 8 == 0, "valid_objects_accum: the table must be 8-byte aligned");
+  ADNM_REQUIRE((uintptr_t)ws % 8 == 0, "valid_objects_accum: the workspace must be 8-byte aligned");
+  ADNM_REQUIRE(nthr >= 1 && nthr <= kMaxThr, "valid_objects_accum: 1..%d thresholds, got %lld", kMaxThr, (long long)nthr);
+  ADNM_REQUIRE(min_area >= 1, "valid_objects_accum: min_area >= 1, got %lld", (long long)min_area);
+  const char* why = frame_why(frames, T, H, W);
+  if (why) {
+    adnm_set_error("valid_objects_accum: %s (got frames %lld T %lld H %lld W %lld)", why, (long long)frames, (long long)T, (long long)H, (long long)W);
+    return ADNM_EINVAL;
+  }
+  const int64_t hw = H * W;
+  ADNM_REQUIRE(pred_frame_stride == 0 || pred_frame_stride >= hw, "valid_objects_accum: pred_frame_stride must be 0 or >= H*W, got %lld",
+               (long long)pred_frame_stride);
+  ADNM_REQUIRE(pred_sample_stride >= 0, "valid_objects_accum: pred_sample_stride must be >= 0, got %lld", (long long)pred_sample_stride);
+  const int64_t items = frames * nthr, need = ws_need(items, hw);
+  ADNM_REQUIRE(ws_bytes >= need && (ws || !need), "valid_objects_accum: workspace %lld < %lld bytes", (long long)(ws ? ws_bytes : 0), (long long)need);
+  ObjThr thr;
+  for (int k = 0; k < kMaxThr; ++k) thr.t[k] = k < nthr ? thresholds_host[k] : 0.f;
+  const unsigned small = (unsigned)(min_area > kMaxPixels + 1 ? kMaxPixels + 1 : min_area);   // no object is larger than a frame
+  const bool in_lds = words_in_lds(hw);
+  const size_t lds = lds_bytes(hw, in_lds);
+  const unsigned grid = (unsigned)groups_of(items, hw);
+  hipStream_t st = (hipStream_t)stream;
+  if (in_lds) {
+    ADNM_ALLOW_LDS(objects_kernel<true>, lds, "valid_objects");
+    ADNM_PROF("valid_objects", st, 8.0 * items * hw);
+    objects_kernel<true><<<grid, kBlock, lds, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (double*)table, thr, (int)nthr, value_scale, small,
+                                                    nullptr, (int)items, (int)T, (int)H, (int)W);
+  } else {
+    ADNM_PROF("valid_objects", st, 8.0 * items * hw);
+    objects_kernel<false><<<grid, kBlock, lds, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (double*)table, thr, (int)nthr, value_scale, small,
+                                                     (unsigned*)ws, (int)items, (int)T, (int)H, (int)W);
+  }
+  ADNM_CHECK_LAUNCH("valid_objects");
+  return ADNM_OK;
+}
+
+extern "C" int adnm_label_objects(const float* src, int64_t sample_stride, int64_t frame_stride, void* labels_i32, float thr, float value_scale,
+                                  int64_t min_area, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream) {
+  ADNM_REQUIRE(src && labels_i32, "label_objects: null pointer");
+  ADNM_REQUIRE(((uintptr_t)src | (uintptr_t)labels_i32) % 4 == 0, "label_objects: src and labels must be 4-byte aligned");
+  ADNM_REQUIRE((uintptr_t)ws % 8 == 0, "label_objects: the workspace must be 8-byte aligned");
+  ADNM_REQUIRE(min_area >= 1, "label_objects: min_area >= 1, got %lld", (long long)min_area);
+  const char* why = frame_why(frames, T, H, W);
+  if (why) {
+    adnm_set_error("label_objects: %s (got frames %lld T %lld H %lld W %lld)", why, (long long)frames, (long long)T, (long long)H, (long long)W);
+    return ADNM_EINVAL;
+  }
+  const int64_t hw = H * W;
+  ADNM_REQUIRE(frame_stride == 0 || frame_stride >= hw, "label_objects: frame_stride must be 0 or >= H*W, got %lld", (long long)frame_stride);
+  ADNM_REQUIRE(sample_stride >= 0, "label_objects: sample_stride must be >= 0, got %lld", (long long)sample_stride);
+  const int64_t need = ws_need(frames, hw);
+  ADNM_REQUIRE(ws_bytes >= need && (ws || !need), "label_objects: workspace %lld < %lld bytes", (long long)(ws ? ws_bytes : 0), (long long)need);
+  const unsigned small = (unsigned)(min_area > kMaxPixels + 1 ? kMaxPixels + 1 : min_area);
+  const bool in_lds = words_in_lds(hw);
+  const size_t lds = lds_bytes(hw, in_lds);
+  const unsigned grid = (unsigned)groups_of(frames, hw);
+  hipStream_t st = (hipStream_t)stream;
+  if (in_lds) {
+    ADNM_ALLOW_LDS(label_kernel<true>, lds, "label_objects");
+    ADNM_PROF("label_objects", st, 8.0 * frames * hw);
+    label_kernel<true><<<grid, kBlock, lds, st>>>(src, sample_stride, frame_stride, (int*)labels_i32, thr, value_scale, small, nullptr, (int)frames, (int)T,
+                                                  (int)H, (int)W);
+  } else {
+    ADNM_PROF("label_objects", st, 8.0 * frames * hw);
+    label_kernel<false><<<grid, kBlock, lds, st>>>(src, sample_stride, frame_stride, (int*)labels_i32, thr, value_scale, small, (unsigned*)ws, (int)frames,
+                                                   (int)T, (int)H, (int)W);
+  }
+  ADNM_CHECK_LAUNCH("label_objects");
+  return ADNM_OK;
+}

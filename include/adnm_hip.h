@@ -826,6 +826,52 @@ int64_t adnm_valid_joint_accum_ws_bytes(int64_t frames, int64_t T, int64_t hw, f
 int adnm_valid_joint_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
                            float value_scale, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t hw, adnm_stream_t stream);
 
+/* Object-based scores from connected-component labelling of the event masks: how many rain cells a field has, how large
+ * they are, and how many of them the other field touches.  The reference has no object score; the yardstick is scipy.ndimage.label on the
+ * CPU (tests/objects_ref.py), integer for integer and pixel for pixel.
+ *   field         q(v) = eval_trunc(eval_scaled(v, value_scale)), adnm_valid_joint_accum's: a NaN, -Inf and negatives give 0, +Inf and
+ *                 values >= 1 give floor(value_scale).
+ *   event         q >= thr, adnm_valid_accum's comparison.
+ *   object        an 8-connected component of the event mask of ONE frame of ONE field; frames do not wrap and do not connect.
+ *   label         1 + the row-major index of the object's first pixel; the background is 0.
+ *   min_area      an object of fewer than min_area (>= 1) pixels is ignored in every column and labelled 0.
+ * table: adnm_valid_objects_block_bytes(T, nthr) = 8 * T * 2 * nthr * 23 bytes, 8-byte aligned device memory, zeroed by the caller, all
+ *   double, shape (T, 2, nthr, 23): [t][field][k], field 0 = target, 1 = forecast, threshold k, summed over every sample so far of the
+ *   frames f with f mod T = t.  No header.  Columns:
+ *     [0] objects   [1] SUM area (the frame's event count when min_area = 1)   [2] SUM area^2   [3] SUM over frames of the largest object's
+ *     area (a frame without objects adds 0)   [4] matched objects: at least one pixel is an event of the OTHER field at the same threshold
+ *     [5] SUM area of the matched objects   [6 + b] objects with floor(log2(area)) = b, b = 0 .. 16.
+ *   Every addend is an integer.  A frame has at most 65 536 pixels, so it adds at most 2^32 to SUM area^2 (one object that fills it): the
+ *   sums over 2^20 frames per frame index stay below 2^53 and every entry is exact.
+ * adnm_valid_objects_accum ADDS a batch.  target, pred and the two strides: adnm_valid_pool_accum's meaning (a contiguous forecast is
+ *   (T*H*W, H*W), a held frame (T_in*H*W, 0)).  thresholds_host (nthr floats) is read on the host at call time and passed by value: the call
+ *   can be captured.  With T = frames on a zeroed table it is the one-shot per-frame form.  One launch, one workgroup of 1024 lanes per
+ *   (frame, threshold), which labels BOTH fields (matching needs both masks).  The event bits of both fields are staged once in LDS, one
+ *   ballot per 64 pixels, floats read 4 bytes per lane (any 4-byte aligned address takes the same route).  Labels are resolved by label
+ *   equivalence: a pixel starts at the first pixel of its horizontal run, and a union-find with atomicMin links and pointer jumping unites the
+ *   runs with the row above in ONE sweep, whatever the shape.  One u32 word per pixel holds the parent, then, for a root, its area in the
+ *   low bits and the matched flag in the top bit.  The words live in LDS where the frame fits beside the bits (H * W <= about 38 000; up to
+ *   160 KB of dynamic LDS) and in ws otherwise.  The roots' entries are reduced in u64 LDS counters and added to the table as double
+ *   atomics: integers below 2^53, so the table is exact and the same bits on every run although the order of the atomics is not fixed.
+ *   termination   no workgroup waits for another one.  A parent only decreases, so a find takes at most H * W steps; a union retries at
+ *                 most H * W times, and one that gave up repeats the sweep, at most H * W times.
+ *   ws            adnm_valid_objects_accum_ws_bytes: 0 where the words are in LDS, else 4 * H * W * min(frames * nthr, 512) bytes; what it
+ *                 held does not matter; ws may be NULL when the query is 0.
+ * adnm_label_objects writes the int32 label image (frames, H, W) of ONE field at ONE threshold with the same device code (one workgroup per
+ *   frame); frame f = b*T + t starts at src + b*sample_stride + t*frame_stride.  adnm_label_objects_ws_bytes likewise, with frames for
+ *   frames * nthr.
+ * Limits, refused before any launch (ADNM_EINVAL): a null pointer other than ws; pred / target / src / labels not 4-byte or table / ws not
+ *   8-byte aligned; nthr outside 1..8; min_area < 1; T < 1 or not dividing frames; frames > 65535; H or W < 1; H * W > 65 536; a frame
+ *   stride neither 0 nor >= H*W; a sample stride < 0; ws_bytes below the query.  The queries return -1. */
+int64_t adnm_valid_objects_block_bytes(int64_t T, int64_t nthr);
+int64_t adnm_valid_objects_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr);
+int adnm_valid_objects_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                             const float* thresholds_host, int64_t nthr, float value_scale, int64_t min_area, void* ws, int64_t ws_bytes,
+                             int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
+int64_t adnm_label_objects_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W);
+int adnm_label_objects(const float* src, int64_t sample_stride, int64_t frame_stride, void* labels_i32, float thr, float value_scale,
+                       int64_t min_area, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
+
 /* The output side (pic_results.py:104-184 of the reference): a forecast as the bytes a consumer keeps, in ONE launch.
  * adnm_forecast_render: pred contiguous fp32 (B, T, H, W), 4-byte aligned.  fields: (B, T, H, W) uint8 or NULL.  strip: (B, H, Ws, 4) uint8
  *   (RGBA, 4-byte aligned) or NULL, Ws = n*W + (n-1)*gap, holding the n = ceil((T - frame_start) / frame_step) frames frame_start,
