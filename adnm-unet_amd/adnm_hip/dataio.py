@@ -158,6 +158,109 @@ class EpochOrder:
         self.perm = None if perm is None else perm.to("cpu").clone()
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Augmentation in the fetch.  The reference has none (its only transform is the resize, datasets/Shanghai.py:40-59).
+# One int32 word per POSITION of the epoch tells csrc/dataio.hip::batch_fetch_aug which window of the stored frame to serve and under
+# which of the square's eight symmetries.  pack_word / unpack_word are the one statement of the layout on the host
+# (include/adnm_hip.h: adnm_batch_fetch_aug is the one on the device side).
+FLIP_H, FLIP_V, TRANSPOSE = 1, 2, 4      # bit 0: flip left-right, bit 1: flip up-down, bit 2: transpose
+OFFSET_LIMIT = 1 << 14                   # oy (bits 3-16) and ox (bits 17-30) are 14-bit fields; bit 31 stays 0
+
+
+def pack_word(code, oy, ox):
+    """(code in 0..7, oy, ox in 0..16383) -> the word; Python ints give an int, tensors an int32 tensor"""
+    if torch.is_tensor(code) or torch.is_tensor(oy) or torch.is_tensor(ox):
+        code, oy, ox = (torch.as_tensor(v).to(torch.int64) for v in (code, oy, ox))
+        if bool(((code < 0) | (code > 7) | (oy < 0) | (oy >= OFFSET_LIMIT) | (ox < 0) | (ox >= OFFSET_LIMIT)).any()):
+            raise ValueError("pack_word: a code outside 0..7 or an offset outside 0..16383")
+        return (code | (oy << 3) | (ox << 17)).to(torch.int32)
+    code, oy, ox = int(code), int(oy), int(ox)
+    if not (0 <= code <= 7 and 0 <= oy < OFFSET_LIMIT and 0 <= ox < OFFSET_LIMIT):
+        raise ValueError(f"pack_word: code {code} (0..7), oy {oy}, ox {ox} (0..16383)")
+    return code | (oy << 3) | (ox << 17)
+
+
+def unpack_word(word):
+    """-> (code, oy, ox), ints for an int and int64 tensors for a tensor"""
+    w = word.to(torch.int64) if torch.is_tensor(word) else int(word)
+    return w & 7, (w >> 3) & (OFFSET_LIMIT - 1), (w >> 17) & (OFFSET_LIMIT - 1)
+
+
+class Augment:
+    """Which augmentations a feed draws, and the generator it draws them from.
+
+    The generator is PRIVATE and seeded with `seed`: nothing is ever drawn from the default generator or from the EpochOrder's, so the
+    order stays the DataLoader's, batch for batch.  draw() always makes its draws in this order: randint(0, 8, (n,)) & mask, then
+    randint(0, span_y + 1, (n,)), then randint(0, span_x + 1, (n,)); with shift=False both offsets are the centre (span // 2) and
+    nothing is drawn for them.  That fixed sequence is what makes a run reproducible from `seed` alone."""
+
+    def __init__(self, flip_h=True, flip_v=True, transpose=True, shift=True, seed=0):
+        self.flip_h, self.flip_v, self.transpose, self.shift, self.seed = bool(flip_h), bool(flip_v), bool(transpose), bool(shift), int(seed)
+        self.mask = (FLIP_H if self.flip_h else 0) | (FLIP_V if self.flip_v else 0) | (TRANSPOSE if self.transpose else 0)
+        self.generator = torch.Generator()
+        self.generator.manual_seed(self.seed)
+
+    def spec(self):
+        return {"flip_h": self.flip_h, "flip_v": self.flip_v, "transpose": self.transpose, "shift": self.shift, "seed": self.seed}
+
+    def draw(self, n, span_y, span_x):
+        """-> (n,) int32 words with offsets in [0, span_y] x [0, span_x] (span = stored side - served side)"""
+        n, span_y, span_x = int(n), int(span_y), int(span_x)
+        if not (0 <= span_y < OFFSET_LIMIT and 0 <= span_x < OFFSET_LIMIT):
+            raise ValueError(f"Augment.draw: spans {span_y}, {span_x} outside 0..16383")
+        code = torch.randint(0, 8, (n,), generator=self.generator) & self.mask
+        if self.shift:
+            oy = torch.randint(0, span_y + 1, (n,), generator=self.generator)
+            ox = torch.randint(0, span_x + 1, (n,), generator=self.generator)
+        else:
+            oy, ox = torch.full((n,), span_y // 2), torch.full((n,), span_x // 2)
+        return pack_word(code, oy, ox)
+
+
+class EpochWords:
+    """The words of an epoch beside an EpochOrder, on the host (no GPU needed): next_epoch() draws all n of them (every rank draws the
+    same n from its identically seeded generator and reads its own positions, as it does for the order).  augment=None: the centre
+    window, untransformed, every epoch (the validation feed of a cropped store); nothing is drawn and nothing is saved."""
+
+    def __init__(self, n, span_y, span_x, augment=None):
+        self.n, self.span_y, self.span_x, self.augment = int(n), int(span_y), int(span_x), augment
+        if not (0 <= self.span_y < OFFSET_LIMIT and 0 <= self.span_x < OFFSET_LIMIT):
+            raise ValueError(f"EpochWords: spans {span_y}, {span_x} outside 0..16383")
+        self.words = None if augment is not None else torch.full((self.n,), pack_word(0, self.span_y // 2, self.span_x // 2), dtype=torch.int32)
+
+    def next_epoch(self):
+        if self.augment is not None:
+            self.words = self.augment.draw(self.n, self.span_y, self.span_x)
+        return self.words
+
+    def _spec(self):
+        return dict(self.augment.spec(), n=self.n, span_y=self.span_y, span_x=self.span_x)
+
+    def state_into(self, sd):
+        """adds the key "augment" (spec, the epoch's words, the generator's state) to a feed's state; without an Augment: nothing"""
+        if self.augment is not None:
+            sd["augment"] = {"spec": self._spec(), "words": None if self.words is None else self.words.clone(),
+                             "generator": self.augment.generator.get_state().clone()}
+        return sd
+
+    def load_from(self, sd):
+        if self.augment is None:
+            if "augment" in sd:
+                raise ValueError("ResidentDataset.load_state_dict: the state was saved by an augmenting feed, this feed has no Augment")
+            return
+        if "augment" not in sd:
+            raise ValueError('ResidentDataset.load_state_dict: the state has no "augment" key (it was saved by a feed without augmentation), '
+                             "this feed augments: its words and generator cannot be restored")
+        st = sd["augment"]
+        if st["spec"] != self._spec():
+            raise ValueError(f"ResidentDataset.load_state_dict: saved with augmentation {st['spec']}, this feed has {self._spec()}")
+        words = st["words"]
+        if words is not None and (words.dtype != torch.int32 or tuple(words.shape) != (self.n,)):
+            raise ValueError(f"ResidentDataset.load_state_dict: the words are {words.dtype} {tuple(words.shape)}, expected int32 ({self.n},)")
+        self.augment.generator.set_state(st["generator"].to("cpu", torch.uint8))
+        self.words = None if words is None else words.to("cpu").clone()
+
+
 class ResidentDataset:
     """A whole split on the device and its batches by kernel.
 
@@ -168,20 +271,47 @@ class ResidentDataset:
                 loss = trainer.step_from(feed)  # one launch in front of the graph replay, into the graph's static buffers
 
     store: (N, T, S, S) fp32; order: (N,) int32 on the device.  The position is a kernel ARGUMENT, kept on the host; the fetch runs on
-    the current stream.  state_dict() is the order's: the store is not saved."""
+    the current stream.  state_dict() is the order's: the store is not saved.
 
-    def __init__(self, store, in_frames, batch, shuffle=True, generator=None, rank=0, world=1):
+    crop=(H, W) serves H x W windows of a larger stored frame, augment=Augment(...) flips, transposes and shifts them, in the fetch
+    itself (adnm_batch_fetch_aug): begin_epoch() draws one word per position after the order and uploads both.
+    from_bytes(size=160, crop=(128, 128)) keeps 160 x 160 and feeds 128 x 128: 1.56 times the store of size=128.  crop without augment
+    (or with shift=False) is the centre window ((Hs - H) // 2, (Ws - W) // 2): the validation feed of a cropped store.  With neither
+    argument nothing is allocated, adnm_batch_fetch is launched and state_dict() is the order's, as before; with an Augment it gains
+    the key "augment" (the spec, the epoch's words, the generator's state)."""
+
+    def __init__(self, store, in_frames, batch, shuffle=True, generator=None, rank=0, world=1, crop=None, augment=None):
         if not (torch.is_tensor(store) and store.is_cuda and store.dtype == torch.float32 and store.dim() == 4 and store.is_contiguous()):
             raise RuntimeError("ResidentDataset: the store is a contiguous fp32 (N, T, H, W) GPU tensor (from_bytes / from_frames build it)")
         N, T, H, W = store.shape
         if not 1 <= int(in_frames) < T:
             raise ValueError(f"ResidentDataset: in_frames {in_frames} of {T} frames per sample")
+        self.served = self._served(H, W, crop, augment)
         self.store, self.in_frames, self.batch, self.device = store, int(in_frames), int(batch), store.device
         self.order = EpochOrder(N, batch, shuffle=shuffle, generator=generator, rank=rank, world=world)
         self._order_dev = torch.empty(N, dtype=torch.int32, device=store.device)
         self._order_pin = torch.empty(N, dtype=torch.int32).pin_memory()   # the upload is asynchronous: the host never waits for the stream
         self._order_sent = None      # the event behind the last upload (the pinned image may be rewritten once it has passed)
         self._uploaded = None        # the epoch whose order _order_dev holds
+        self.augment, self.words = augment, None
+        if crop is not None or augment is not None:
+            self.words = EpochWords(N, H - self.served[0], W - self.served[1], augment)
+            self._words_dev = torch.empty(N, dtype=torch.int32, device=store.device)
+            self._words_pin = torch.empty(N, dtype=torch.int32).pin_memory()
+
+    @staticmethod
+    def _served(Hs, Ws, crop, augment):
+        """-> the served frame (H, W); refuses what adnm_batch_fetch_aug would refuse or answer with NaNs"""
+        if augment is not None and not isinstance(augment, Augment):
+            raise TypeError("ResidentDataset: augment is an adnm_hip.dataio.Augment or None")
+        H, W = (Hs, Ws) if crop is None else (int(crop[0]), int(crop[1]))
+        if not (1 <= H <= Hs and 1 <= W <= Ws):
+            raise ValueError(f"ResidentDataset: crop {(H, W)} of a stored frame of {(Hs, Ws)}")
+        if (crop is not None or augment is not None) and not (Hs < OFFSET_LIMIT and Ws < OFFSET_LIMIT):
+            raise ValueError(f"ResidentDataset: crop / augment need stored sides below {OFFSET_LIMIT}, the store has {(Hs, Ws)}")
+        if augment is not None and augment.transpose and H != W:
+            raise ValueError(f"ResidentDataset: transpose=True needs a square served frame, got {(H, W)}")
+        return (H, W)
 
     @staticmethod
     def _alloc_store(shape, device):
@@ -194,14 +324,16 @@ class ResidentDataset:
             raise RuntimeError(f"ResidentDataset: the store {tuple(shape)} fp32 needs {need} bytes of device memory, which did not fit ({e})") from None
 
     @classmethod
-    def from_bytes(cls, frames_u8, size, in_frames, batch, device, shuffle=True, generator=None, rank=0, world=1, chunk=64):
+    def from_bytes(cls, frames_u8, size, in_frames, batch, device, shuffle=True, generator=None, rank=0, world=1, chunk=64, crop=None, augment=None):
         """frames_u8: (N, T, H0, W0) uint8, numpy or CPU tensor.  Moved in chunks of `chunk` samples through two pinned staging buffers
-        and ingested with adnm_radar_ingest (/255 and the resize on the device): store[i] is bit for bit dataio.ingest(sample i, size)."""
+        and ingested with adnm_radar_ingest (/255 and the resize on the device): store[i] is bit for bit dataio.ingest(sample i, size).
+        crop, augment: as in the constructor (the store is size x size, the feed serves crop)."""
         src = torch.from_numpy(frames_u8) if isinstance(frames_u8, np.ndarray) else frames_u8
         if not torch.is_tensor(src) or src.is_cuda or src.dtype != torch.uint8 or src.dim() != 4:
             raise RuntimeError("ResidentDataset.from_bytes: expected (N, T, H0, W0) uint8 in host memory")
         device, chunk = torch.device(device), max(1, min(int(chunk), src.shape[0]))
         N, T, H0, W0 = src.shape
+        cls._served(size, size, crop, augment)             # a bad crop is refused before the split is moved
         store = cls._alloc_store((N, T, size, size), device)
         pinned = [torch.empty((chunk, T, H0, W0), dtype=torch.uint8).pin_memory() for _ in range(2)]
         dev = [torch.empty((chunk, T, H0, W0), dtype=torch.uint8, device=device) for _ in range(2)]
@@ -219,29 +351,30 @@ class ResidentDataset:
                 lib.call("adnm_radar_ingest", dev[s].data_ptr(), store[lo:lo + n].data_ptr(), n * T, H0, W0, size, 1.0 / 255.0, cur.cuda_stream)
             cur.synchronize()
         del pinned, dev                                    # staging is given back; the store stays
-        return cls(store, in_frames, batch, shuffle=shuffle, generator=generator, rank=rank, world=world)
+        return cls(store, in_frames, batch, shuffle=shuffle, generator=generator, rank=rank, world=world, crop=crop, augment=augment)
 
     @classmethod
-    def from_frames(cls, frames_f32, in_frames, batch, device, shuffle=True, generator=None, rank=0, world=1):
+    def from_frames(cls, frames_f32, in_frames, batch, device, shuffle=True, generator=None, rank=0, world=1, crop=None, augment=None):
         """frames_f32: (N, T, H, W) or (N, T, 1, H, W) float32 that is final (the LAPS fields): kept bit for bit, no resize."""
         src = torch.from_numpy(frames_f32) if isinstance(frames_f32, np.ndarray) else frames_f32
         if torch.is_tensor(src) and src.dim() == 5 and src.shape[2] == 1:
             src = src[:, :, 0]
         if not torch.is_tensor(src) or src.dtype != torch.float32 or src.dim() != 4:
             raise RuntimeError("ResidentDataset.from_frames: expected (N, T, H, W) float32")
+        cls._served(src.shape[2], src.shape[3], crop, augment)
         store = cls._alloc_store(tuple(src.shape), torch.device(device))
         store.copy_(src)
-        return cls(store, in_frames, batch, shuffle=shuffle, generator=generator, rank=rank, world=world)
+        return cls(store, in_frames, batch, shuffle=shuffle, generator=generator, rank=rank, world=world, crop=crop, augment=augment)
 
     # ---- shapes
     @property
     def x_shape(self):
-        N, T, H, W = self.store.shape
+        H, W = self.served
         return (self.batch, self.in_frames, 1, H, W)
 
     @property
     def tgt_shape(self):
-        N, T, H, W = self.store.shape
+        T, (H, W) = self.store.shape[1], self.served
         return (self.batch, T - self.in_frames, 1, H, W)
 
     def __len__(self):
@@ -253,23 +386,31 @@ class ResidentDataset:
 
     # ---- per epoch, per step
     def _upload(self):
-        """the epoch's order to the device, on the current stream (behind the last fetch of the epoch before, which read the old one)"""
+        """the epoch's order (and words) to the device, on the current stream (behind the last fetch of the epoch before, which read the
+        old ones)"""
         if self._order_sent is not None:
             self._order_sent.synchronize()
         self._order_pin.copy_(self.order.perm)
         self._order_dev.copy_(self._order_pin, non_blocking=True)
+        if self.words is not None:
+            if self.words.words is None:
+                raise RuntimeError("ResidentDataset: the restored state holds an order but no words")
+            self._words_pin.copy_(self.words.words)
+            self._words_dev.copy_(self._words_pin, non_blocking=True)
         self._order_sent = torch.cuda.Event()
         self._order_sent.record(torch.cuda.current_stream(self.device))
         self._uploaded = self.order.epoch
 
     def begin_epoch(self):
         self.order.next_epoch()
+        if self.words is not None:
+            self.words.next_epoch()          # after the order, from the Augment's own generator: the order's draws are untouched
         self._upload()
 
     def _check(self, t, shape, what):
         if not (torch.is_tensor(t) and t.device == self.device and t.dtype == torch.float32 and t.is_contiguous()):
             raise RuntimeError(f"ResidentDataset.fetch_into: {what} must be a contiguous fp32 tensor on {self.device}")
-        N, T, H, W = self.store.shape
+        H, W = self.served
         if t.numel() != shape[0] * shape[1] * H * W or t.shape[0] != shape[0] or t.shape[1] != shape[1] or tuple(t.shape[-2:]) != (H, W):
             raise RuntimeError(f"ResidentDataset.fetch_into: {what} is {tuple(t.shape)}, the feed gives {shape} (or the same without the channel axis)")
 
@@ -289,8 +430,13 @@ class ResidentDataset:
         if self._uploaded != order.epoch:           # a restored order: its permutation goes to the device before the first fetch
             self._upload()
         N, T, H, W = self.store.shape
-        lib.call("adnm_batch_fetch", self.store.data_ptr(), N, T, H * W, self._order_dev.data_ptr(), N, order.offset(), x.data_ptr(), tgt.data_ptr(),
-                 self.batch, self.in_frames, torch.cuda.current_stream(self.device).cuda_stream)
+        if self.words is None:
+            lib.call("adnm_batch_fetch", self.store.data_ptr(), N, T, H * W, self._order_dev.data_ptr(), N, order.offset(), x.data_ptr(), tgt.data_ptr(),
+                     self.batch, self.in_frames, torch.cuda.current_stream(self.device).cuda_stream)
+        else:
+            lib.call("adnm_batch_fetch_aug", self.store.data_ptr(), N, T, H, W, self._order_dev.data_ptr(), self._words_dev.data_ptr(), N, order.offset(),
+                     x.data_ptr(), tgt.data_ptr(), self.batch, self.in_frames, self.served[0], self.served[1],
+                     torch.cuda.current_stream(self.device).cuda_stream)
         order.pos += 1
 
     def fetch(self):
@@ -300,8 +446,10 @@ class ResidentDataset:
         return x, tgt
 
     def state_dict(self):
-        return self.order.state_dict()
+        sd = self.order.state_dict()
+        return sd if self.words is None else self.words.state_into(sd)
 
     def load_state_dict(self, sd):
+        (self.words or EpochWords(self.order.n, 0, 0)).load_from(sd)   # refuses before anything is changed
         self.order.load_state_dict(sd)
         self._uploaded = None

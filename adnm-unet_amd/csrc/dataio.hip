@@ -340,6 +340,162 @@ extern "C" int adnm_batch_fetch(const float* store, int64_t n_samples, int64_t T
   return ADNM_OK;
 }
 
+// ---- the resident split, augmented: a window of the stored frame under one of the square's symmetries (adnm_batch_fetch_aug) ----
+namespace {
+constexpr int kAugTile = 32;             // the transposing path's LDS tile: kAugTile x (kAugTile + 1) floats
+constexpr int64_t kAugMaxSide = 16384;   // oy and ox are 14-bit fields of the word
+
+struct AugGeom {
+  int T, T_in, H, W, Hs, Ws;
+};
+
+__device__ __forceinline__ float aug_reversed(float v) { return v; }
+__device__ __forceinline__ float4 aug_reversed(float4 v) { return make_float4(v.w, v.z, v.y, v.x); }
+
+// Without the transpose bit an output row is a row of the window, possibly read from its far end.  V = float4: W, Ws and the window's
+// ox are multiples of 4, so that every row piece is a 16-byte access on both sides (a reversed row takes its pieces from the far end
+// and swaps the components inside each).  The output of a sample is contiguous, so piece i goes where batch_fetch_kernel puts it; only
+// the source address needs (t, y, c).  win: the window's origin in frame 0 of the sample.  All indices fit 32 bits (the host refuses
+// T*Hs*Ws >= 2^31).
+template <typename V>
+__device__ __forceinline__ void aug_rows(const float* __restrict__ win, float* __restrict__ dx, float* __restrict__ dt, const AugGeom& g, bool flip_lr,
+                                         bool flip_ud) {
+  constexpr uint32_t E = sizeof(V) / sizeof(float);
+  const uint32_t wv = (uint32_t)g.W / E, H = (uint32_t)g.H, units = (uint32_t)g.T * H * wv, split = (uint32_t)g.T_in * H * wv;
+  const uint32_t stride = gridDim.x * kBlock, fs = (uint32_t)g.Hs * (uint32_t)g.Ws;
+  V* ox_ = (V*)dx;
+  V* ot_ = (V*)dt;   // dt is `split` pieces before the sample's target rows: piece i >= split -> ot_[i]
+  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  // (t, y, c) of piece i: two divisions per lane here, none per piece.  A step of `stride` pieces is (dt, dy, dc) with carries, and
+  // the step's own split is uniform.  The three always belong to i, and nothing is loaded for an i >= units.
+  const uint32_t dr = stride / wv, dc = stride - dr * wv, dt_ = dr / H, dy = dr - dt_ * H;
+  uint32_t row = i / wv, c = i - row * wv, t = row / H, y = row - t * H;
+  auto load_and_step = [&]() {
+    const uint32_t sy = flip_ud ? H - 1 - y : y, sc = flip_lr ? wv - 1 - c : c;
+    const V v = *(const V*)(win + (t * fs + sy * (uint32_t)g.Ws + sc * E));
+    c += dc;
+    const bool cc = c >= wv;      // c < 2 wv
+    c -= cc ? wv : 0u;
+    y += dy + (cc ? 1u : 0u);
+    const bool cy = y >= H;       // y <= (H - 1) + (H - 1) + 1 < 2 H
+    y -= cy ? H : 0u;
+    t += dt_ + (cy ? 1u : 0u);
+    return flip_lr ? aug_reversed(v) : v;
+  };
+  for (; (uint64_t)i + (uint64_t)(kFetchUnroll - 1) * stride < units; i += kFetchUnroll * stride) {
+    V v[kFetchUnroll];
+#pragma unroll
+    for (int k = 0; k < kFetchUnroll; ++k) v[k] = load_and_step();
+#pragma unroll
+    for (int k = 0; k < kFetchUnroll; ++k) (i + k * stride < split ? ox_ : ot_)[i + k * stride] = v[k];
+  }
+  for (; i < units; i += stride) (i < split ? ox_ : ot_)[i] = load_and_step();
+}
+
+// With the transpose bit (H == W = n) output rows are source columns:  out[t][r][c] = window[t][fy(c)][fx(r)],  fy / fx the flips.  A
+// workgroup takes 32 x 32 output tiles.  Loading, lane lx runs along the SOURCE row (consecutive or, flipped, descending addresses: one
+// 128-byte line per 32 lanes) and writes tile[ly][lx]; storing, lane lx runs along the OUTPUT row and reads tile[lx][ly].  Rows are 33
+// dwords apart, so both the row writes (banks lx + const) and the column reads (banks 33 lx + const = lx + const mod 32) of a 32-lane
+// half touch 32 different banks.  Ragged tiles at the right and bottom edges skip what lies outside.
+__device__ __forceinline__ void aug_transposed(const float* __restrict__ win, float* __restrict__ dx, float* __restrict__ dt, const AugGeom& g, bool flip_lr,
+                                               bool flip_ud, float (*tile)[kAugTile + 1]) {
+  constexpr int kRows = kBlock / kAugTile;   // tile rows a pass of the workgroup covers
+  const int n = g.H, side = (n + kAugTile - 1) / kAugTile, tiles = g.T * side * side;
+  const int lx = threadIdx.x % kAugTile, ly = threadIdx.x / kAugTile;
+  const int64_t fs = (int64_t)g.Hs * g.Ws, split = (int64_t)g.T_in * n * n;
+  for (int u = blockIdx.x; u < tiles; u += gridDim.x) {   // the same trips for every lane: the barriers below see the whole workgroup
+    const int t = u / (side * side), q = u - t * side * side, r0 = (q / side) * kAugTile, c0 = (q % side) * kAugTile;
+    const float* sp = win + t * fs;
+    const int sr = r0 + lx;   // the output ROW this lane loads for: its source column is fx(sr)
+    float v[kAugTile / kRows];
+#pragma unroll
+    for (int k = 0; k < kAugTile / kRows; ++k) {
+      const int sc = c0 + ly + k * kRows;   // the output COLUMN: its source row is fy(sc)
+      v[k] = 0.f;
+      if (sr < n && sc < n) v[k] = sp[(int64_t)(flip_ud ? n - 1 - sc : sc) * g.Ws + (flip_lr ? n - 1 - sr : sr)];
+    }
+#pragma unroll
+    for (int k = 0; k < kAugTile / kRows; ++k) tile[ly + k * kRows][lx] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kAugTile / kRows; ++k) {
+      const int r = r0 + ly + k * kRows, c = c0 + lx;
+      if (r < n && c < n) {
+        const int64_t e = ((int64_t)t * n + r) * n + c;
+        (e < split ? dx : dt)[e] = tile[lx][ly + k * kRows];
+      }
+    }
+    __syncthreads();   // the next tile rewrites what this one still reads
+  }
+}
+
+// gridDim.y = the batch, as batch_fetch_kernel: index s = order[pos + b] and word a = aug[pos + b] are two uniform loads, and every
+// branch below is taken by a whole workgroup.  A sample that must not be served (see include/adnm_hip.h) is filled with quiet NaNs
+// before anything of it is turned into an address.  can_vec: what the 16-byte path needs of the LAUNCH (W and Ws multiples of 4, the
+// three bases aligned); the sample adds ox % 4 == 0.
+__global__ __launch_bounds__(kBlock) void batch_fetch_aug_kernel(const float* __restrict__ store, const int32_t* __restrict__ order,
+                                                                 const int32_t* __restrict__ aug, int64_t pos, int n_samples, AugGeom g, int can_vec,
+                                                                 float* __restrict__ x, float* __restrict__ tgt) {
+  __shared__ float tile[kAugTile][kAugTile + 1];
+  const int64_t b = blockIdx.y;
+  const int s = order[pos + b];
+  const uint32_t a = (uint32_t)aug[pos + b];
+  const bool flip_lr = a & 1u, flip_ud = a & 2u, transpose = a & 4u;
+  const int oy = (int)((a >> 3) & 0x3fffu), ox = (int)((a >> 17) & 0x3fffu);
+  const int64_t hw = (int64_t)g.H * g.W, per = g.T * hw, split = g.T_in * hw;
+  float* dx = x + b * split;
+  float* dt = tgt + b * (per - split) - split;   // element i >= split of the sample -> dt[i]
+  if (s < 0 || s >= n_samples || (a >> 31) || oy + g.H > g.Hs || ox + g.W > g.Ws || (transpose && g.H != g.W)) {
+    float nan;
+    fetch_nan(nan);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < per; i += (int64_t)gridDim.x * kBlock) (i < split ? dx : dt)[i] = nan;
+    return;
+  }
+  const float* win = store + (int64_t)s * g.T * g.Hs * g.Ws + (int64_t)oy * g.Ws + ox;
+  if (transpose) aug_transposed(win, dx, dt, g, flip_lr, flip_ud, tile);
+  else if (can_vec && ox % 4 == 0) aug_rows<float4>(win, dx, dt, g, flip_lr, flip_ud);
+  else aug_rows<float>(win, dx, dt, g, flip_lr, flip_ud);
+}
+}  // namespace
+
+extern "C" int adnm_batch_fetch_aug(const float* store, int64_t n_samples, int64_t T, int64_t Hs, int64_t Ws, const int32_t* order, const int32_t* aug,
+                                    int64_t order_len, int64_t pos, float* x, float* tgt, int64_t B, int64_t T_in, int64_t H, int64_t W,
+                                    adnm_stream_t stream) {
+  ADNM_REQUIRE(store && order && aug && x && tgt, "batch_fetch_aug: null pointer");
+  ADNM_REQUIRE(((uintptr_t)store | (uintptr_t)order | (uintptr_t)aug | (uintptr_t)x | (uintptr_t)tgt) % 4 == 0,
+               "batch_fetch_aug: store, order, aug, x and tgt must be 4-byte aligned");
+  ADNM_REQUIRE(B >= 1 && B <= kFetchMaxBatch, "batch_fetch_aug: the batch must be in [1, %lld] (one grid row per sample), got %lld", (long long)kFetchMaxBatch,
+               (long long)B);
+  ADNM_REQUIRE(H >= 1 && H < kAugMaxSide && W >= 1 && W < kAugMaxSide && Hs >= 1 && Hs < kAugMaxSide && Ws >= 1 && Ws < kAugMaxSide,
+               "batch_fetch_aug: H, W, Hs and Ws must be in [1, 16384) (the word's offsets are 14-bit fields), got %lld x %lld of %lld x %lld", (long long)H,
+               (long long)W, (long long)Hs, (long long)Ws);
+  ADNM_REQUIRE(H <= Hs && W <= Ws, "batch_fetch_aug: the served frame %lld x %lld is larger than the stored one, %lld x %lld", (long long)H, (long long)W,
+               (long long)Hs, (long long)Ws);
+  ADNM_REQUIRE(T >= 1 && T < (1ll << 31) && T * Hs * Ws < (1ll << 31),"batch_fetch_aug: a stored sample must hold fewer than 2^31 floats, got T %lld of %lld x %lld",
+               (long long)T, (long long)Hs, (long long)Ws);
+  ADNM_REQUIRE(T_in >= 1 && T_in < T, "batch_fetch_aug: T_in must be in [1, T), got T_in %lld of T %lld", (long long)T_in, (long long)T);
+  ADNM_REQUIRE(n_samples >= 1 && n_samples < (1ll << 31) && order_len >= 1 && order_len < (1ll << 31),
+               "batch_fetch_aug: n_samples and order_len must be in [1, 2^31), got %lld and %lld", (long long)n_samples, (long long)order_len);
+  ADNM_REQUIRE(pos >= 0 && pos <= order_len - B, "batch_fetch_aug: %lld positions from %lld on lie outside an order of %lld", (long long)B, (long long)pos,
+               (long long)order_len);
+  const int64_t per = T * H * W;
+  // what the 16-byte path needs of the launch: every row start on both sides (W, Ws multiples of 4, hence the frame strides, the sample
+  // strides and the x / tgt split as well) and the three bases; a sample adds ox % 4 == 0 in the kernel
+  const bool can_vec = W % 4 == 0 && Ws % 4 == 0 && adnm_quad_aligned(ADNM_F32, {store, x, tgt});
+  const int64_t units = can_vec ? per / 4 : per;
+  int64_t gx = adnm_cdiv(units, (int64_t)kBlock * kFetchUnroll), cap = kFetchMaxBlocks / B;
+  cap = cap < 1 ? 1 : cap;
+  gx = gx > cap ? cap : gx;
+  const AugGeom g = {(int)T, (int)T_in, (int)H, (int)W, (int)Hs, (int)Ws};
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ADNM_PROF("batch_fetch_aug", st, 8.0 * B * per);
+    batch_fetch_aug_kernel<<<dim3((unsigned)gx, (unsigned)B), kBlock, 0, st>>>(store, order, aug, pos, (int)n_samples, g, can_vec ? 1 : 0, x, tgt);
+  }
+  ADNM_CHECK_LAUNCH("batch_fetch_aug");
+  return ADNM_OK;
+}
+
 extern "C" int64_t adnm_eval_counts_ws_bytes(int64_t frames, int64_t hw, int64_t nthr) {
   if (frames <= 0 || hw <= 0 || nthr <= 0 || nthr > kMaxThr) return 0;
   return (int64_t)eval_blocks(hw) * frames * (4 * nthr + 2) * (int64_t)sizeof(float);

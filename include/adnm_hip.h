@@ -626,6 +626,27 @@ int adnm_radar_ingest(const void* src_u8, float* dst, int64_t frames, int64_t H0
  *   moves floats one by one with the SAME result: such a call is served, not refused. */
 int adnm_batch_fetch(const float* store, int64_t n_samples, int64_t T, int64_t hw, const int32_t* order, int64_t order_len, int64_t pos,
                      float* x, float* tgt, int64_t B, int64_t T_in, adnm_stream_t stream);
+/* adnm_batch_fetch_aug: adnm_batch_fetch with the label-preserving augmentations of gridded fields done in the copy.  The reference has
+ *   none: its only transform is the resize (datasets/Shanghai.py:40-59), so this entry point adds to what train.py can do and a feed
+ *   without augmentation keeps launching adnm_batch_fetch.  store: (n_samples, T, Hs, Ws) fp32 contiguous; order, aug: order_len int32
+ *   each, DEVICE memory, indexed by the position in the epoch (a word belongs to a position, not to a sample); x: (B, T_in, H, W),
+ *   tgt: (B, T - T_in, H, W), contiguous.  The word a = aug[pos + b]:
+ *     bit 0 flip left-right | bit 1 flip up-down | bit 2 transpose | bits 3-16 oy | bits 17-30 ox | bit 31 must be 0
+ *   With s = order[pos + b], on every frame of the sample and as bit patterns (NaN payloads and -0.0 are copied, never recomputed):
+ *     w = store[s, :, oy:oy+H, ox:ox+W];  bit 1: w = w.flip(-2);  bit 0: w = w.flip(-1);  bit 2: w = w.transpose(-1, -2)
+ *     x[b], tgt[b] = w[:T_in], w[T_in:]
+ *   input and target of a sample are therefore transformed identically.  One launch, gridDim.y = B, no workspace.
+ *   NOT served, per sample: an index outside [0, n_samples); a word with bit 31 set; oy + H > Hs or ox + W > Ws; the transpose bit with
+ *   H != W.  None of these is turned into an address: the sample's x and tgt rows are filled with quiet NaNs (adnm_batch_fetch's rule).
+ *   Refused before any launch (ADNM_EINVAL): a null pointer or one that is not 4-byte aligned; B outside [1, 65535]; T_in outside
+ *   [1, T); H, W, Hs or Ws outside [1, 16384); H > Hs or W > Ws; T*Hs*Ws >= 2^31; pos < 0 or pos + B > order_len; n_samples or
+ *   order_len outside [1, 2^31).  Access width is the entry point's business and is chosen PER SAMPLE: without the transpose bit rows
+ *   move as 16-byte pieces when W and Ws are multiples of 4, store, x and tgt are 16-byte aligned and the sample's ox is a multiple of
+ *   4 (a reversed row swaps the components of each piece), else float by float; with it, through a 32 x 33 LDS tile, float by float
+ *   and coalesced on both sides.  The result is the same on every path. */
+int adnm_batch_fetch_aug(const float* store, int64_t n_samples, int64_t T, int64_t Hs, int64_t Ws, const int32_t* order, const int32_t* aug,
+                         int64_t order_len, int64_t pos, float* x, float* tgt, int64_t B, int64_t T_in, int64_t H, int64_t W,
+                         adnm_stream_t stream);
 int64_t adnm_eval_counts_ws_bytes(int64_t frames, int64_t hw, int64_t nthr);
 int adnm_eval_counts(const float* truth, const float* pred, float* out, const float* thresholds_host, int64_t nthr, float value_scale,
                      void* ws, int64_t ws_bytes, int64_t frames, int64_t hw, adnm_stream_t stream);
