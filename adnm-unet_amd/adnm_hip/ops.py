@@ -3250,7 +3250,7 @@ def attn4(qkv, heads, scale):
     return Attn4Fn.apply(qkv, heads, scale)
 
 
-# ======================================================================================= pooled contingency counts (csrc/dataio.hip: valid_pool_accum)
+# ======================================================================================= pooled contingency counts (csrc/neighbour.hip: valid_pool_accum)
 MAX_POOLS, MAX_POOL_WINDOW = 4, 32
 
 
@@ -3301,6 +3301,21 @@ def _pair(op, truth, pred, ranks, shapes, contiguous=False):
                          f"{pred.dtype} {tuple(pred.shape)}")
 
 
+def _score_once(entry, truth, pred, frames, *, dims, query_tail, limits, table_shape, args):
+    """the one-shot use (T = frames) the scoring wrappers share of an entry point of csrc/scored_pair.h's contract: ask `entry`_ws_bytes
+    (frames, frames, *dims, *query_tail), raise RuntimeError(limits) on -1, then call `entry` on a zeroed float64 table of `table_shape`
+    with the contiguous forecast's strides, `args` between the table and the workspace (none where zero bytes are needed).  -> the table"""
+    H, W = truth.shape[-2:]
+    nb = lib.query(entry + "_ws_bytes", frames, frames, *dims, *query_tail)
+    if nb < 0:
+        raise RuntimeError(limits)
+    out = torch.zeros(table_shape, dtype=torch.float64, device=truth.device)
+    ws = _ws(nb, truth.device) if nb else None
+    lib.call(entry, pred.data_ptr(), H * W, H * W, truth.data_ptr(), out.data_ptr(), *args, None if ws is None else ws.data_ptr(), int(nb), frames, frames, *dims,
+             _stream())
+    return out
+
+
 def pool_counts(truth, pred, thresholds, value_scale, pools):
     """truth / pred: fp32 GPU tensors (..., H, W) of the same shape -> (frames, npool, 4 * nthr) float64 on the device: per frame and
     pool (an int p = (p, p), or (size, stride): the windows of max_pool2d(kernel_size=size, stride=stride)) TP, FN, FP, TN per threshold,
@@ -3314,18 +3329,13 @@ def pool_counts(truth, pred, thresholds, value_scale, pools):
     t, p = truth.contiguous(), pred.contiguous()
     frames = t.numel() // (H * W) if H * W else 0
     tab = pool_table(pairs)
-    nb = lib.query("adnm_valid_pool_accum_ws_bytes", frames, frames, H, W, len(thr), tab, len(pairs))
-    if nb < 0:
-        raise RuntimeError(f"pool_counts: {frames} frames of {H} x {W} with pools {pairs} are outside adnm_valid_pool_accum's limits "
-                           "(1 <= frames <= 65535, H*W < 2^24, no window larger than the frame)")
-    out = torch.zeros((frames, len(pairs), 4 * len(thr)), dtype=torch.float64, device=t.device)
-    ws = _ws(nb, t.device)
-    lib.call("adnm_valid_pool_accum", p.data_ptr(), H * W, H * W, t.data_ptr(), out.data_ptr(), (ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale),
-             tab, len(pairs), ws.data_ptr(), int(nb), frames, frames, H, W, _stream())
-    return out
+    return _score_once("adnm_valid_pool_accum", t, p, frames, dims=(H, W), query_tail=(len(thr), tab, len(pairs)),
+                       limits=f"pool_counts: {frames} frames of {H} x {W} with pools {pairs} are outside adnm_valid_pool_accum's limits "
+                       "(1 <= frames <= 65535, H*W < 2^24, no window larger than the frame)",
+                       table_shape=(frames, len(pairs), 4 * len(thr)), args=((ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale), tab, len(pairs)))
 
 
-# ======================================================================================= Fractions Skill Score sums (csrc/dataio.hip: valid_fss_accum)
+# ======================================================================================= Fractions Skill Score sums (csrc/neighbour.hip: valid_fss_accum)
 MAX_FSS_SCALES, MAX_FSS_SCALE = 4, 33
 
 
@@ -3372,15 +3382,10 @@ def fss_sums(truth, pred, thresholds, value_scale, scales):
     t, p = truth.contiguous(), pred.contiguous()
     frames = t.numel() // (H * W) if H * W else 0
     tab = fss_table(ns)
-    nb = lib.query("adnm_valid_fss_accum_ws_bytes", frames, frames, H, W, len(thr), tab, len(ns))
-    if nb < 0:
-        raise RuntimeError(f"fss_sums: {frames} frames of {H} x {W} are outside adnm_valid_fss_accum's limits (1 <= frames <= 65535, H and W < 32768, "
-                           "H*W < 2^24)")
-    out = torch.zeros((frames, len(ns), 3 * len(thr)), dtype=torch.float64, device=t.device)
-    ws = _ws(nb, t.device)
-    lib.call("adnm_valid_fss_accum", p.data_ptr(), H * W, H * W, t.data_ptr(), out.data_ptr(), (ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale),
-             tab, len(ns), ws.data_ptr(), int(nb), frames, frames, H, W, _stream())
-    return out
+    return _score_once("adnm_valid_fss_accum", t, p, frames, dims=(H, W), query_tail=(len(thr), tab, len(ns)),
+                       limits=f"fss_sums: {frames} frames of {H} x {W} are outside adnm_valid_fss_accum's limits (1 <= frames <= 65535, H and W < 32768, "
+                       "H*W < 2^24)",
+                       table_shape=(frames, len(ns), 3 * len(thr)), args=((ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale), tab, len(ns)))
 
 
 # ======================================================================================= block-matched motion and advection (csrc/advect.hip)
@@ -3507,15 +3512,10 @@ def power_spectrum(truth, pred, value_scale):
     counts to divide by).  The one-shot use of adnm_valid_spectrum_accum (T = frames)."""
     _pair("power_spectrum", truth, pred, (3,), "(frames, H, W)", contiguous=True)
     frames, H, W = truth.shape
-    nb = lib.query("adnm_valid_spectrum_accum_ws_bytes", frames, frames, H, W)
-    if nb < 0:
-        raise RuntimeError(f"power_spectrum: {frames} frames of {H} x {W} are outside adnm_valid_spectrum_accum's limits (1 <= frames <= 65535, "
-                           f"{SPECTRUM_LIMITS})")
-    out = torch.zeros((frames, max(H, W) // 2, 3), dtype=torch.float64, device=truth.device)
-    ws = _ws(nb, truth.device)
-    lib.call("adnm_valid_spectrum_accum", pred.data_ptr(), H * W, H * W, truth.data_ptr(), out.data_ptr(), float(value_scale), ws.data_ptr(), int(nb),
-             frames, frames, H, W, _stream())
-    return out
+    return _score_once("adnm_valid_spectrum_accum", truth, pred, frames, dims=(H, W), query_tail=(),
+                       limits=f"power_spectrum: {frames} frames of {H} x {W} are outside adnm_valid_spectrum_accum's limits (1 <= frames <= 65535, "
+                       f"{SPECTRUM_LIMITS})",
+                       table_shape=(frames, max(H, W) // 2, 3), args=(float(value_scale),))
 
 
 # ======================================================================================= joint intensity histogram (csrc/joint.hip)
@@ -3544,14 +3544,10 @@ def joint_histogram(truth, pred, value_scale):
     L = joint_levels(value_scale)
     H, W = truth.shape[-2:]
     frames = truth.numel() // (H * W) if H * W else 0
-    nb = lib.query("adnm_valid_joint_accum_ws_bytes", frames, frames, H * W, float(value_scale))
-    if nb < 0:
-        raise RuntimeError(f"joint_histogram: {frames} frames of {H} x {W} are outside adnm_valid_joint_accum's limits (1 <= frames <= 65535, "
-                           "1 <= H*W < 2^24)")
-    out = torch.zeros((frames, L, L), dtype=torch.float64, device=truth.device)
-    ws = _ws(nb, truth.device) if nb else None
-    lib.call("adnm_valid_joint_accum", pred.data_ptr(), H * W, H * W, truth.data_ptr(), out.data_ptr(), float(value_scale), None if ws is None else ws.data_ptr(),
-             int(nb), frames, frames, H * W, _stream())
+    out = _score_once("adnm_valid_joint_accum", truth, pred, frames, dims=(H * W,), query_tail=(float(value_scale),),
+                      limits=f"joint_histogram: {frames} frames of {H} x {W} are outside adnm_valid_joint_accum's limits (1 <= frames <= 65535, "
+                      "1 <= H*W < 2^24)",
+                      table_shape=(frames, L, L), args=(float(value_scale),))
     return out.to(torch.int64)   # integers below 2^53 in doubles: exact
 
 
@@ -3591,14 +3587,10 @@ def object_stats(truth, pred, thresholds, value_scale, min_area=1):
     min_area = _min_area("object_stats", min_area)
     H, W = truth.shape[-2:]
     frames = truth.numel() // (H * W) if H * W else 0
-    nb = lib.query("adnm_valid_objects_accum_ws_bytes", frames, frames, H, W, len(thr))
-    if nb < 0:
-        raise RuntimeError(f"object_stats: {frames} frames of {H} x {W} are outside adnm_valid_objects_accum's limits (1 <= frames <= 65535, "
-                           f"{OBJECTS_LIMITS})")
-    out = torch.zeros((frames, 2, len(thr), OBJ_COLS), dtype=torch.float64, device=truth.device)
-    ws = _ws(nb, truth.device) if nb else None
-    lib.call("adnm_valid_objects_accum", pred.data_ptr(), H * W, H * W, truth.data_ptr(), out.data_ptr(), (ctypes.c_float * len(thr))(*thr), len(thr),
-             float(value_scale), min_area, None if ws is None else ws.data_ptr(), int(nb), frames, frames, H, W, _stream())
+    out = _score_once("adnm_valid_objects_accum", truth, pred, frames, dims=(H, W), query_tail=(len(thr),),
+                      limits=f"object_stats: {frames} frames of {H} x {W} are outside adnm_valid_objects_accum's limits (1 <= frames <= 65535, "
+                      f"{OBJECTS_LIMITS})",
+                      table_shape=(frames, 2, len(thr), OBJ_COLS), args=((ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale), min_area))
     return out.to(torch.int64)   # integers below 2^53 in doubles: exact
 
 

@@ -425,8 +425,8 @@ __device__ __forceinline__ float adnm_rainloss_term(float p, float t, float omeg
   return e;
 }
 
-// The quantisation of a field value, stated ONCE for every kernel that counts events (dataio.hip: eval_counts, valid_accum, valid_pool_accum,
-// valid_fss_accum) or matches blocks (advect.hip: trec_cost):
+// The quantisation of a field value, stated ONCE for every kernel that counts events (dataio.hip: eval_counts, valid_accum; scored_pair.h:
+// pair_bits) or matches blocks (advect.hip: trec_cost):
 // q(v) = floorf(fminf(fmaxf(v, 0), 1) * value_scale) in fp32 (Shanghai_metrics.py:45-47).  NaN -> 0 (fmaxf), -Inf -> 0, +Inf -> floor(scale).
 __device__ __forceinline__ float eval_scaled(float v, float value_scale) { return fminf(fmaxf(v, 0.f), 1.f) * value_scale; }
 __device__ __forceinline__ float eval_trunc(float scaled) { return floorf(scaled); }   // .astype(np.uint16) of a non-negative float: truncation

@@ -1,4 +1,7 @@
-// The data formats on either side of the hot path.
+// The data formats on either side of the hot path: data in (radar_ingest, batch_fetch and its augmented
+// form), the point-wise evaluator (eval_counts, eval_ssim), the validation epoch's accumulators of a CONTIGUOUS prediction (valid_accum,
+// valid_ssim_accum) and data out (forecast_render).  The scores of a strided forecast against a target live in files of their own
+// (scored_pair.h names them).
 //
 //   radar_ingest  — the input pipeline of datasets/Shanghai.py:52-59,121: uint8 radar frames (25, H0, W0) in 0..70 -> float / 255 ->
 //                   transforms.Resize((S, S)) (bilinear, align_corners=False, no antialias: what torchvision's tensor Resize hands to
@@ -12,12 +15,11 @@
 //   forecast_render — the output side, pic_results.py:104-184: the forecast quantised to a byte per pixel ((seq * pixel_scale).astype(uint8)),
 //                   the frame selection seq[1::2], BoundaryNorm + ListedColormap as a table lookup and the frames laid side by side with a
 //                   gap of opaque white, as RGBA bytes: what a consumer stores, instead of a float copy and numpy / matplotlib per frame.
-#include "adnm_common.h"
+#include "scored_pair.h"
 #include <math.h>
 
 namespace {
 constexpr int kBlock = 256;
-constexpr int kMaxThr = 8;
 
 __global__ __launch_bounds__(kBlock) void radar_ingest_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, int64_t frames, int H0, int W0,
                                                               int S, float scale_y, float scale_x, float mul) {
@@ -38,13 +40,8 @@ __global__ __launch_bounds__(kBlock) void radar_ingest_kernel(const uint8_t* __r
   dst[i] = hy * (hx * (v00 * mul) + lx * (v01 * mul)) + ly * (hx * (v10 * mul) + lx * (v11 * mul));
 }
 
-struct Thr {
-  float t[kMaxThr];
-  int n;
-};
-
 // The quantisation of a field value q(v): eval_scaled / eval_trunc of adnm_common.h, stated ONCE for every kernel that counts events
-// (EvalAcc::add and pool_bits below) or matches blocks (advect.hip).
+// (EvalAcc::add here, pair_bits of scored_pair.h) or matches blocks (advect.hip).  Thr, the thresholds as a kernel argument: scored_pair.h.
 
 // One lane's share of a frame's contingency counts and error sums, and the workgroup's fold of it: the arithmetic of eval_counts, stated
 // ONCE for eval_counts_kernel and valid_accum_kernel (the validation epoch's accumulating pass) so that their counts cannot drift apart.
@@ -511,9 +508,7 @@ extern "C" int adnm_eval_counts(const float* truth, const float* pred, float* ou
     adnm_set_error("eval_counts: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)adnm_eval_counts_ws_bytes(frames, hw, nthr));
     return ADNM_EWORKSPACE;
   }
-  Thr thr;
-  thr.n = (int)nthr;
-  for (int k = 0; k < kMaxThr; ++k) thr.t[k] = k < nthr ? thresholds_host[k] : 0.f;
+  const Thr thr = thr_fill(thresholds_host, nthr);
   hipStream_t st = (hipStream_t)stream;
   const int nb = eval_blocks(hw), nout = 4 * (int)nthr + 2;
   {
@@ -586,9 +581,7 @@ extern "C" int adnm_valid_accum(const float* pred, const float* target, void* bl
     adnm_set_error("valid_accum: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)adnm_valid_accum_ws_bytes(frames, T, hw, nthr));
     return ADNM_EWORKSPACE;
   }
-  Thr thr;
-  thr.n = (int)nthr;
-  for (int k = 0; k < kMaxThr; ++k) thr.t[k] = k < nthr ? thresholds_host[k] : 0.f;
+  const Thr thr = thr_fill(thresholds_host, nthr);
   hipStream_t st = (hipStream_t)stream;
   const int nb = eval_blocks(hw);
   {
@@ -636,458 +629,6 @@ extern "C" int adnm_valid_ssim_accum(const float* pred, const float* target, voi
     valid_ssim_fold_kernel<<<1, kFoldBlock, 0, st>>>((const float*)ws, tx * ty, (int)frames, (int)T, (int)nthr, (double*)block);
   }
   ADNM_CHECK_LAUNCH("valid_ssim_fold");
-  return ADNM_OK;
-}
-
-// ---- neighbourhood (pooled) contingency counts (include/adnm_hip.h: adnm_valid_pool_accum) ----
-// A window of a pool (s, d) is an event at threshold k iff ANY pixel of it has q >= thr_k (thresholding commutes with the max), so a
-// pixel's whole state is one byte per field (bit k = q >= thr_k) and max-pooling is a windowed OR.  A workgroup owns the windows whose
-// top-left pixel lies in its 32 x 32 tile of one frame.  It stages the tile and the halo its windows reach into ONCE, as 2 bytes per
-// pixel in LDS (low byte target, high byte forecast), and serves every pool and every threshold from that image: OR along rows, then
-// along columns, then per bit the number of windows with the target bit, the forecast bit and both.  Those are wave ballots summed in
-// scalar registers: integers throughout.  part[frame][tile][pool][3*nthr] uint32; the fold turns (obs, sim, both) into TP, FN, FP, TN.
-namespace {
-constexpr int kPoolMax = 4, kPoolWin = 32, kPoolTile = 32;
-constexpr int kPoolSide = kPoolTile + kPoolWin;   // staged rows / columns at most: a window reaches at most s - 1 <= 31 past the tile
-constexpr int kPoolPitch = kPoolSide + 4;         // uint16 per staged row: 136 bytes, so that a row start stays 8-byte aligned
-struct Pools {
-  int s[kPoolMax], d[kPoolMax], n;
-};
-
-__device__ __forceinline__ uint32_t pool_bits(float tv, float pv, float value_scale, const Thr& thr) {
-  const float ti = eval_trunc(eval_scaled(tv, value_scale)), pi = eval_trunc(eval_scaled(pv, value_scale));
-  uint32_t m = 0;
-#pragma unroll
-  for (int k = 0; k < kMaxThr; ++k)
-    if (k < thr.n) m |= (ti >= thr.t[k] ? 1u << k : 0u) | (pi >= thr.t[k] ? 0x100u << k : 0u);
-  return m;
-}
-
-// grid (tiles, frames).  Frame f of the forecast starts at pred + (f / T) * sstride + (f % T) * fstride.  ext: how far past the tile the
-// staged image goes (host: the largest s - gcd(d, 32) of the pools; VEC: rounded up to 4).  VEC: W, both strides and both bases are
-// multiples of 4 floats, so every staged row piece is a 16-byte load.
-template <bool VEC>
-__global__ __launch_bounds__(kBlock) void pool_counts_kernel(const float* __restrict__ pred, int64_t sstride, int64_t fstride, const float* __restrict__ tgt,
-                                                             uint32_t* __restrict__ part, int T, int H, int W, int tiles_x, int ext, float value_scale,
-                                                             Thr thr, Pools pools) {
-  __shared__ __attribute__((aligned(8))) uint16_t img[kPoolSide][kPoolPitch];
-  __shared__ uint16_t rowor[kPoolSide][kPoolTile + 1];
-  __shared__ uint32_t red[kBlock / 64][3 * kMaxThr];
-  const int f = blockIdx.y, tile = blockIdx.x, oy = (tile / tiles_x) * kPoolTile, ox = (tile % tiles_x) * kPoolTile;
-  const int rh = min(kPoolTile + ext, H - oy), rw = min(kPoolTile + ext, W - ox);
-  const float* tp = tgt + (int64_t)f * H * W + (int64_t)oy * W + ox;
-  const float* pp = pred + (int64_t)(f / T) * sstride + (int64_t)(f % T) * fstride + (int64_t)oy * W + ox;
-  if (VEC) {
-    const int q = rw >> 2;   // rw is a multiple of 4: W, ox and 32 + ext are
-    for (int i = threadIdx.x; i < rh * q; i += kBlock) {
-      const int r = i / q, c = (i % q) * 4;
-      const float4 a = *(const float4*)(tp + (int64_t)r * W + c), b = *(const float4*)(pp + (int64_t)r * W + c);
-      const uint32_t m0 = pool_bits(a.x, b.x, value_scale, thr), m1 = pool_bits(a.y, b.y, value_scale, thr);
-      const uint32_t m2 = pool_bits(a.z, b.z, value_scale, thr), m3 = pool_bits(a.w, b.w, value_scale, thr);
-      *(uint2*)&img[r][c] = make_uint2(m0 | (m1 << 16), m2 | (m3 << 16));
-    }
-  } else {
-    for (int i = threadIdx.x; i < rh * rw; i += kBlock) {
-      const int r = i / rw, c = i % rw;
-      img[r][c] = (uint16_t)pool_bits(tp[(int64_t)r * W + c], pp[(int64_t)r * W + c], value_scale, thr);
-    }
-  }
-  __syncthreads();
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nout = 3 * thr.n;
-  for (int p = 0; p < pools.n; ++p) {
-    const int s = pools.s[p], d = pools.d[p];
-    // the windows anchored in this tile: indices [j0, j0 + na) along each axis, the first one at offset c0 from the tile's origin
-    const int jx0 = (ox + d - 1) / d, jy0 = (oy + d - 1) / d;
-    const int nax = max(0, min((W - s) / d + 1, (ox + kPoolTile + d - 1) / d) - jx0), nay = max(0, min((H - s) / d + 1, (oy + kPoolTile + d - 1) / d) - jy0);
-    const int cx0 = jx0 * d - ox, cy0 = jy0 * d - oy;
-    for (int i = threadIdx.x; i < rh * nax; i += kBlock) {
-      const int r = i / nax, j = i % nax;
-      const uint16_t* src = &img[r][cx0 + j * d];   // cx0 + j*d + s <= min(W - ox, 32 + ext) = rw
-      uint32_t m = 0;
-      for (int u = 0; u < s; ++u) m |= src[u];
-      rowor[r][j] = (uint16_t)m;
-    }
-    __syncthreads();
-    uint32_t cnt[3 * kMaxThr];   // wave-uniform: windows with the target bit k, the forecast bit k, both
-#pragma unroll
-    for (int k = 0; k < 3 * kMaxThr; ++k) cnt[k] = 0;
-    const int na = nax * nay;
-    for (int i0 = 0; i0 < na; i0 += kBlock) {   // the same trips for every lane: the ballots below see whole waves
-      const int i = i0 + threadIdx.x;
-      uint32_t m = 0;
-      if (i < na) {
-        const int r0 = cy0 + (i / nax) * d, j = i % nax;   // r0 + s <= rh
-        for (int u = 0; u < s; ++u) m |= rowor[r0 + u][j];
-      }
-      const uint32_t o = m & 0xffu, sim = m >> 8, v = o | (sim << 8) | ((o & sim) << 16);
-#pragma unroll
-      for (int k = 0; k < kMaxThr; ++k)
-        if (k < thr.n) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) cnt[3 * k + c] += (uint32_t)__popcll(__ballot((v >> (8 * c + k)) & 1u));
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 3 * kMaxThr; ++k)
-        if (k < nout) red[wave][k] = cnt[k];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < nout)
-      part[(((int64_t)f * gridDim.x + tile) * pools.n + p) * nout + threadIdx.x] =
-          (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    __syncthreads();   // rowor and red are rewritten by the next pool
-  }
-}
-
-// One thread per (t, pool, threshold), a fixed order (samples ascending, tiles ascending: valid_fold_kernel's), double arithmetic on
-// integers: table[t][pool][4k .. 4k+3] += TP, FN, FP, TN of the batch, TN from the number of windows of the pool.
-__global__ __launch_bounds__(kFoldBlock) void pool_fold_kernel(const uint32_t* __restrict__ part, int tiles, int frames, int T, int nthr, int H, int W,
-                                                               Pools pools, double* __restrict__ table) {
-  const int np = pools.n, B = frames / T, i = blockIdx.x * kFoldBlock + threadIdx.x;
-  if (i >= T * np * nthr) return;
-  const int k = i % nthr, p = (i / nthr) % np, t = i / (nthr * np);
-  double obs = 0.0, sim = 0.0, both = 0.0;
-  for (int b = 0; b < B; ++b)
-    for (int tile = 0; tile < tiles; ++tile) {
-      const uint32_t* q = part + ((((int64_t)b * T + t) * tiles + tile) * np + p) * (3 * nthr) + 3 * k;
-      obs += (double)q[0], sim += (double)q[1], both += (double)q[2];
-    }
-  const double windows = (double)B * (double)((H - pools.s[p]) / pools.d[p] + 1) * (double)((W - pools.s[p]) / pools.d[p] + 1);
-  double* out = table + ((int64_t)t * np + p) * (4 * nthr) + 4 * k;
-  out[0] += both;
-  out[1] += obs - both;
-  out[2] += sim - both;
-  out[3] += windows - obs - sim + both;
-}
-
-int pool_gcd(int a, int b) { return b == 0 ? a : pool_gcd(b, a % b); }
-
-// the shape limits of the pooled pass; on refusal `why` names the limit
-bool pool_shape_ok(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* pools_host, int64_t npool, const char** why) {
-  const char* w = nullptr;
-  if (!pools_host) w = "null pointer";
-  else if (npool < 1 || npool > kPoolMax) w = "1..4 pools";
-  else if (nthr < 1 || nthr > kMaxThr) w = "1..8 thresholds";
-  else if (T < 1 || frames < 1 || frames % T != 0) w = "T >= 1 must divide frames";
-  else if (frames > 65535) w = "frames <= 65535";
-  else if (H < 1 || W < 1 || H >= 32768 || W >= 32768) w = "H and W must be in [1, 32768)";
-  else if (H * W >= (1ll << 24)) w = "pixels per frame < 2^24";
-  else
-    for (int64_t p = 0; p < npool && !w; ++p) {
-      const int64_t s = pools_host[2 * p], d = pools_host[2 * p + 1];
-      if (!(1 <= d && d <= s && s <= kPoolWin)) w = "a pool needs 1 <= stride <= size <= 32";
-      else if (s > (H < W ? H : W)) w = "a pool window is larger than the frame";
-    }
-  if (why) *why = w;
-  return w == nullptr;
-}
-inline int64_t pool_tiles(int64_t H, int64_t W) { return adnm_cdiv(H, kPoolTile) * adnm_cdiv(W, kPoolTile); }
-}  // namespace
-
-extern "C" int64_t adnm_valid_pool_block_bytes(int64_t T, int64_t nthr, int64_t npool) {
-  if (T < 1 || T > 65535 || nthr < 1 || nthr > kMaxThr || npool < 1 || npool > kPoolMax) return -1;
-  return (int64_t)sizeof(double) * T * npool * 4 * nthr;
-}
-
-extern "C" int64_t adnm_valid_pool_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* pools_host, int64_t npool) {
-  if (!pool_shape_ok(frames, T, H, W, nthr, pools_host, npool, nullptr)) return -1;
-  return frames * pool_tiles(H, W) * npool * 3 * nthr * (int64_t)sizeof(uint32_t);
-}
-
-extern "C" int adnm_valid_pool_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
-                                     const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* pools_host, int64_t npool, void* ws,
-                                     int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream) {
-  ADNM_REQUIRE(pred && target && table && thresholds_host && pools_host, "valid_pool_accum: null pointer");
-  ADNM_REQUIRE(((uintptr_t)pred | (uintptr_t)target) % 4 == 0, "valid_pool_accum: pred and target must be 4-byte aligned");
-  ADNM_REQUIRE((uintptr_t)table % 8 == 0, "valid_pool_accum: the table must be 8-byte aligned");
-  const char* why = nullptr;
-  if (!pool_shape_ok(frames, T, H, W, nthr, pools_host, npool, &why)) {
-    adnm_set_error("valid_pool_accum: %s (got frames %lld T %lld %lld x %lld nthr %lld npool %lld)", why, (long long)frames, (long long)T, (long long)H,
-                   (long long)W, (long long)nthr, (long long)npool);
-    return ADNM_EINVAL;
-  }
-  ADNM_REQUIRE(pred_frame_stride == 0 || pred_frame_stride >= H * W, "valid_pool_accum: pred_frame_stride must be 0 or >= H*W, got %lld",
-               (long long)pred_frame_stride);
-  ADNM_REQUIRE(pred_sample_stride >= 0, "valid_pool_accum: pred_sample_stride must be >= 0, got %lld", (long long)pred_sample_stride);
-  const int64_t need = adnm_valid_pool_accum_ws_bytes(frames, T, H, W, nthr, pools_host, npool);
-  if (!ws || ws_bytes < need) {
-    adnm_set_error("valid_pool_accum: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
-    return ADNM_EWORKSPACE;
-  }
-  Thr thr;
-  thr.n = (int)nthr;
-  for (int k = 0; k < kMaxThr; ++k) thr.t[k] = k < nthr ? thresholds_host[k] : 0.f;
-  Pools pools;
-  pools.n = (int)npool;
-  int ext = 0;
-  for (int p = 0; p < kPoolMax; ++p) {
-    pools.s[p] = p < npool ? (int)pools_host[2 * p] : 1;
-    pools.d[p] = p < npool ? (int)pools_host[2 * p + 1] : 1;
-    // windows start at multiples of d and tiles at multiples of 32: the last start in a tile is at most 32 - gcd(d, 32) into it
-    const int e = pools.s[p] - pool_gcd(pools.d[p], kPoolTile);
-    ext = e > ext ? e : ext;
-  }
-  // 16-byte loads need every frame and row start of both fields aligned; anything else (an odd W, a 4-byte aligned slice) takes the
-  // scalar path: same result
-  const bool vec = W % 4 == 0 && pred_sample_stride % 4 == 0 && pred_frame_stride % 4 == 0 && adnm_quad_aligned(ADNM_F32, {pred, target});
-  if (vec) ext = (int)adnm_align(ext, 4);
-  const int tiles_x = (int)adnm_cdiv(W, kPoolTile), tiles = (int)pool_tiles(H, W);
-  hipStream_t st = (hipStream_t)stream;
-  {
-    ADNM_PROF("valid_pool", st, 8.0 * frames * H * W);
-    const dim3 grid((unsigned)tiles, (unsigned)frames);
-    if (vec)
-      pool_counts_kernel<true><<<grid, kBlock, 0, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (uint32_t*)ws, (int)T, (int)H, (int)W, tiles_x, ext,
-                                                        value_scale, thr, pools);
-    else
-      pool_counts_kernel<false><<<grid, kBlock, 0, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (uint32_t*)ws, (int)T, (int)H, (int)W, tiles_x, ext,
-                                                         value_scale, thr, pools);
-  }
-  ADNM_CHECK_LAUNCH("valid_pool_accum");
-  {
-    ADNM_PROF("valid_pool_fold", st, 4.0 * frames * tiles * npool * 3 * nthr);
-    pool_fold_kernel<<<(unsigned)adnm_cdiv(T * npool * nthr, kFoldBlock), kFoldBlock, 0, st>>>((const uint32_t*)ws, tiles, (int)frames, (int)T, (int)nthr, (int)H,
-                                                                                             (int)W, pools, (double*)table);
-  }
-  ADNM_CHECK_LAUNCH("valid_pool_fold");
-  return ADNM_OK;
-}
-
-// ---- Fractions Skill Score: windowed fraction sums (include/adnm_hip.h: adnm_valid_fss_accum) ----
-// c_o(y, x) / c_f(y, x): the number of threshold-k pixels of the target / the forecast in the n x n window CENTRED on (y, x), zero outside
-// the frame.  A workgroup owns the 32 x 32 window centres of a tile of one frame.  It stages the tile and a halo of hs >= max(n) / 2
-// pixels on all four sides ONCE, as pool_bits' 2 bytes per pixel (0 outside the frame), and serves every scale and threshold from that
-// image, separably and with running sums:
-//   rows     wave q takes nibble q of the pixel (0, 1: target thresholds 0-3, 4-7; 2, 3: forecast), lane R the staged row R.  A nibble
-//            is spread to one count per BYTE (bit j -> byte j), and a running sum along the row (add the pixel entering the window,
-//            take the one leaving) gives the four thresholds' row counts (<= 33 each: bytes never carry) for the 32 centres' columns.
-//   columns  a thread owns 4 consecutive centres of one column; the row counts are summed down the window in 16-bit lanes (even bytes
-//            in one dword, odd bytes in another; <= 1089 each), again running: n adds for the first centre, one add and one
-//            subtraction for each of the next three.
-// c_o^2, c_f^2, c_o c_f per lane in uint32 (a tile's sum is at most 1024 * 1089^2 < 2^32), integer adds across the wave and the four
-// waves: part[frame][tile][scale][3*nthr] uint32.  LDS: image rows 33 dwords and row-count rows 33 dwords apart, so the lanes of the row
-// pass (one row each) and of the column pass (consecutive columns) hit distinct banks.
-namespace {
-constexpr int kFssMax = 4, kFssWin = 33, kFssTile = 32;
-constexpr int kFssSide = kFssTile + 2 * (kFssWin / 2);   // 64 staged rows / columns at most
-constexpr int kFssPitch = kFssSide + 2;                  // uint16 per staged row: 33 dwords
-struct Scales {
-  int n[kFssMax], cnt;
-};
-
-// bit j of a nibble -> byte j of a dword (0 or 1): x * (1 + 2^7 + 2^14 + 2^21) puts bit j at 8j among 16 distinct positions (no carries)
-__device__ __forceinline__ uint32_t fss_spread(uint32_t nibble) { return (nibble * 0x00204081u) & 0x01010101u; }
-
-__device__ __forceinline__ uint32_t fss_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-  return v;
-}
-
-// grid (tiles, frames).  Frame f of the forecast starts at pred + (f / T) * sstride + (f % T) * fstride.  hs: the staged halo (host: the
-// largest n / 2; VEC: rounded up to 4).  VEC: W, both strides and both bases are multiples of 4 floats; the staged columns start at a
-// multiple of 4, so every group of four is a 16-byte load and lies inside or outside the frame as a whole.
-template <bool VEC>
-__global__ __launch_bounds__(kBlock) void fss_sums_kernel(const float* __restrict__ pred, int64_t sstride, int64_t fstride, const float* __restrict__ tgt,
-                                                          uint32_t* __restrict__ part, int T, int H, int W, int tiles_x, int hs, float value_scale, Thr thr,
-                                                          Scales scales) {
-  __shared__ __attribute__((aligned(4))) uint16_t img[kFssSide][kFssPitch];
-  __shared__ uint32_t rs[4][kFssSide][kFssTile + 1];   // [nibble][staged row][centre column]: four thresholds' row counts, one per byte
-  __shared__ uint32_t red[kBlock / 64][3 * kMaxThr];
-  const int f = blockIdx.y, tile = blockIdx.x, oy = (tile / tiles_x) * kFssTile, ox = (tile % tiles_x) * kFssTile;
-  const int side = kFssTile + 2 * hs;
-  const float* tp = tgt + (int64_t)f * H * W;
-  const float* pp = pred + (int64_t)(f / T) * sstride + (int64_t)(f % T) * fstride;
-  if (VEC) {
-    const int q = side >> 2;
-    for (int i = threadIdx.x; i < side * q; i += kBlock) {
-      const int r = i / q, c = (i % q) * 4, gy = oy - hs + r, gx = ox - hs + c;
-      uint32_t lo = 0, hi = 0;
-      if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-        const float4 a = *(const float4*)(tp + (int64_t)gy * W + gx), b = *(const float4*)(pp + (int64_t)gy * W + gx);
-        lo = pool_bits(a.x, b.x, value_scale, thr) | (pool_bits(a.y, b.y, value_scale, thr) << 16);
-        hi = pool_bits(a.z, b.z, value_scale, thr) | (pool_bits(a.w, b.w, value_scale, thr) << 16);
-      }
-      uint32_t* dst = (uint32_t*)&img[r][c];   // c is even and a row is 33 dwords: 4-byte aligned
-      dst[0] = lo;
-      dst[1] = hi;
-    }
-  } else {
-    for (int i = threadIdx.x; i < side * side; i += kBlock) {
-      const int r = i / side, c = i % side, gy = oy - hs + r, gx = ox - hs + c;
-      uint32_t m = 0;
-      if (gy >= 0 && gy < H && gx >= 0 && gx < W) m = pool_bits(tp[(int64_t)gy * W + gx], pp[(int64_t)gy * W + gx], value_scale, thr);
-      img[r][c] = (uint16_t)m;
-    }
-  }
-  __syncthreads();
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nout = 3 * thr.n;
-  const int cx = threadIdx.x & 31, cy0 = (threadIdx.x >> 5) * 4;   // the column pass: centres (cy0 .. cy0 + 3, cx) of the tile
-  const bool col_in = ox + cx < W;
-  for (int p = 0; p < scales.cnt; ++p) {
-    const int n = scales.n[p], r = n >> 1, c0 = hs - r;   // centre x's window: staged columns c0 + x .. c0 + x + n - 1 (<= 2*hs + 31 < side)
-    if (lane < side && (thr.n > 4 || !(wave & 1))) {      // (nibbles 1 and 3 hold thresholds 4-7)
-      const uint16_t* row = img[lane];
-      const int sh = 4 * wave;
-      uint32_t s = 0;
-      for (int u = 0; u < n - 1; ++u) s += fss_spread((row[c0 + u] >> sh) & 0xfu);
-      for (int x = 0; x < kFssTile; ++x) {
-        s += fss_spread((row[c0 + x + n - 1] >> sh) & 0xfu);
-        rs[wave][lane][x] = s;
-        s -= fss_spread((row[c0 + x] >> sh) & 0xfu);   // it was added: no byte borrows
-      }
-    }
-    __syncthreads();
-    // acc[q][e]: nibble q's bytes e and e + 2 as 16-bit lanes; centre y's window: staged rows c0 + y .. c0 + y + n - 1
-    uint32_t acc[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
-    uint32_t sum[3 * kMaxThr];
-#pragma unroll
-    for (int k = 0; k < 3 * kMaxThr; ++k) sum[k] = 0;
-    auto rows = [&](int R, bool add) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (thr.n > 4 || !(q & 1)) {
-          const uint32_t v = rs[q][R][cx], e = v & 0x00ff00ffu, o = (v >> 8) & 0x00ff00ffu;
-          acc[q][0] = add ? acc[q][0] + e : acc[q][0] - e;
-          acc[q][1] = add ? acc[q][1] + o : acc[q][1] - o;
-        }
-    };
-    for (int u = 0; u < n - 1; ++u) rows(c0 + cy0 + u, true);
-    for (int j = 0; j < 4; ++j) {
-      rows(c0 + cy0 + j + n - 1, true);   // <= 2*hs + 31 < side
-      if (col_in && oy + cy0 + j < H) {
-#pragma unroll
-        for (int k = 0; k < kMaxThr; ++k)
-          if (k < thr.n) {
-            const int sh = 16 * ((k & 3) >> 1);
-            const uint32_t co = (acc[k >> 2][k & 1] >> sh) & 0xffffu, cf = (acc[2 + (k >> 2)][k & 1] >> sh) & 0xffffu;
-            sum[3 * k + 0] += co * co;
-            sum[3 * k + 1] += cf * cf;
-            sum[3 * k + 2] += co * cf;
-          }
-      }
-      rows(c0 + cy0 + j, false);
-    }
-#pragma unroll
-    for (int k = 0; k < 3 * kMaxThr; ++k)
-      if (k < nout) {
-        const uint32_t v = fss_wave_sum(sum[k]);
-        if (lane == 0) red[wave][k] = v;
-      }
-    __syncthreads();
-    if ((int)threadIdx.x < nout)
-      part[(((int64_t)f * gridDim.x + tile) * scales.cnt + p) * nout + threadIdx.x] =
-          (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    __syncthreads();   // rs and red are rewritten by the next scale
-  }
-}
-
-// One thread per (t, scale, threshold), a fixed order (samples ascending, tiles ascending: valid_fold_kernel's), double arithmetic on
-// integers: table[t][scale][3k .. 3k+2] += A, F, C of the batch.
-__global__ __launch_bounds__(kFoldBlock) void fss_fold_kernel(const uint32_t* __restrict__ part, int tiles, int frames, int T, int nthr, int ns,
-                                                              double* __restrict__ table) {
-  const int B = frames / T, i = blockIdx.x * kFoldBlock + threadIdx.x;
-  if (i >= T * ns * nthr) return;
-  const int k = i % nthr, p = (i / nthr) % ns, t = i / (nthr * ns);
-  double a = 0.0, fc = 0.0, c = 0.0;
-  for (int b = 0; b < B; ++b)
-    for (int tile = 0; tile < tiles; ++tile) {
-      const uint32_t* q = part + ((((int64_t)b * T + t) * tiles + tile) * ns + p) * (3 * nthr) + 3 * k;
-      a += (double)q[0], fc += (double)q[1], c += (double)q[2];
-    }
-  double* out = table + ((int64_t)t * ns + p) * (3 * nthr) + 3 * k;
-  out[0] += a;
-  out[1] += fc;
-  out[2] += c;
-}
-
-// the shape limits of the FSS pass; on refusal `why` names the limit
-bool fss_shape_ok(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* scales_host, int64_t nscale, const char** why) {
-  const char* w = nullptr;
-  if (!scales_host) w = "null pointer";
-  else if (nscale < 1 || nscale > kFssMax) w = "1..4 scales";
-  else if (nthr < 1 || nthr > kMaxThr) w = "1..8 thresholds";
-  else if (T < 1 || frames < 1 || frames % T != 0) w = "T >= 1 must divide frames";
-  else if (frames > 65535) w = "frames <= 65535";
-  else if (H < 1 || W < 1 || H >= 32768 || W >= 32768) w = "H and W must be in [1, 32768)";
-  else if (H * W >= (1ll << 24)) w = "pixels per frame < 2^24";
-  else
-    for (int64_t p = 0; p < nscale && !w; ++p) {
-      const int64_t n = scales_host[p];
-      if (n < 1 || n > kFssWin || n % 2 == 0) w = "a scale must be odd and in 1..33";
-      for (int64_t o = 0; o < p && !w; ++o)
-        if (scales_host[o] == n) w = "a scale is given twice";
-    }
-  if (why) *why = w;
-  return w == nullptr;
-}
-inline int64_t fss_tiles(int64_t H, int64_t W) { return adnm_cdiv(H, kFssTile) * adnm_cdiv(W, kFssTile); }
-}  // namespace
-
-extern "C" int64_t adnm_valid_fss_block_bytes(int64_t T, int64_t nthr, int64_t nscale) {
-  if (T < 1 || T > 65535 || nthr < 1 || nthr > kMaxThr || nscale < 1 || nscale > kFssMax) return -1;
-  return (int64_t)sizeof(double) * T * nscale * 3 * nthr;
-}
-
-extern "C" int64_t adnm_valid_fss_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* scales_host, int64_t nscale) {
-  if (!fss_shape_ok(frames, T, H, W, nthr, scales_host, nscale, nullptr)) return -1;
-  return frames * fss_tiles(H, W) * nscale * 3 * nthr * (int64_t)sizeof(uint32_t);
-}
-
-extern "C" int adnm_valid_fss_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
-                                    const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* scales_host, int64_t nscale, void* ws,
-                                    int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream) {
-  ADNM_REQUIRE(pred && target && table && thresholds_host && scales_host, "valid_fss_accum: null pointer");
-  ADNM_REQUIRE(((uintptr_t)pred | (uintptr_t)target) % 4 == 0, "valid_fss_accum: pred and target must be 4-byte aligned");
-  ADNM_REQUIRE((uintptr_t)table % 8 == 0, "valid_fss_accum: the table must be 8-byte aligned");
-  const char* why = nullptr;
-  if (!fss_shape_ok(frames, T, H, W, nthr, scales_host, nscale, &why)) {
-    adnm_set_error("valid_fss_accum: %s (got frames %lld T %lld %lld x %lld nthr %lld nscale %lld)", why, (long long)frames, (long long)T, (long long)H,
-                   (long long)W, (long long)nthr, (long long)nscale);
-    return ADNM_EINVAL;
-  }
-  ADNM_REQUIRE(pred_frame_stride == 0 || pred_frame_stride >= H * W, "valid_fss_accum: pred_frame_stride must be 0 or >= H*W, got %lld",
-               (long long)pred_frame_stride);
-  ADNM_REQUIRE(pred_sample_stride >= 0, "valid_fss_accum: pred_sample_stride must be >= 0, got %lld", (long long)pred_sample_stride);
-  const int64_t need = adnm_valid_fss_accum_ws_bytes(frames, T, H, W, nthr, scales_host, nscale);
-  if (!ws || ws_bytes < need) {
-    adnm_set_error("valid_fss_accum: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
-    return ADNM_EWORKSPACE;
-  }
-  Thr thr;
-  thr.n = (int)nthr;
-  for (int k = 0; k < kMaxThr; ++k) thr.t[k] = k < nthr ? thresholds_host[k] : 0.f;
-  Scales scales;
-  scales.cnt = (int)nscale;
-  int hs = 0;
-  for (int p = 0; p < kFssMax; ++p) {
-    scales.n[p] = p < nscale ? (int)scales_host[p] : 1;
-    hs = scales.n[p] / 2 > hs ? scales.n[p] / 2 : hs;
-  }
-  // 16-byte loads need every frame and row start of both fields aligned, and the staged columns to start at a multiple of 4; anything
-  // else (an odd W, a 4-byte aligned slice) takes the scalar path: same result
-  const bool vec = W % 4 == 0 && pred_sample_stride % 4 == 0 && pred_frame_stride % 4 == 0 && adnm_quad_aligned(ADNM_F32, {pred, target});
-  if (vec) hs = (int)adnm_align(hs, 4);   // <= 16
-  const int tiles_x = (int)adnm_cdiv(W, kFssTile), tiles = (int)fss_tiles(H, W);
-  hipStream_t st = (hipStream_t)stream;
-  {
-    ADNM_PROF("valid_fss", st, 8.0 * frames * H * W);
-    const dim3 grid((unsigned)tiles, (unsigned)frames);
-    if (vec)
-      fss_sums_kernel<true><<<grid, kBlock, 0, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (uint32_t*)ws, (int)T, (int)H, (int)W, tiles_x, hs,
-                                                     value_scale, thr, scales);
-    else
-      fss_sums_kernel<false><<<grid, kBlock, 0, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (uint32_t*)ws, (int)T, (int)H, (int)W, tiles_x, hs,
-                                                      value_scale, thr, scales);
-  }
-  ADNM_CHECK_LAUNCH("valid_fss_accum");
-  {
-    ADNM_PROF("valid_fss_fold", st, 4.0 * frames * tiles * nscale * 3 * nthr);
-    fss_fold_kernel<<<(unsigned)adnm_cdiv(T * nscale * nthr, kFoldBlock), kFoldBlock, 0, st>>>((const uint32_t*)ws, tiles, (int)frames, (int)T, (int)nthr,
-                                                                                            (int)nscale, (double*)table);
-  }
-  ADNM_CHECK_LAUNCH("valid_fss_fold");
   return ADNM_OK;
 }
 

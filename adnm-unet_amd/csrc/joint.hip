@@ -14,7 +14,7 @@
 //                  diagonal).  Every addend and every partial sum is an integer below 2^53, so the additions are exact in any order: the
 //                  result is exact and the same bits on every run although the order of the atomics is not fixed.
 //   counters       u32.  G is chosen so that a workgroup counts at most 2^31 pixels; no narrower counter is used.
-#include "adnm_common.h"
+#include "scored_pair.h"
 
 namespace {
 constexpr int kBlock = 256;
@@ -32,21 +32,19 @@ __device__ __forceinline__ void joint_count(unsigned* hist, bool valid, int bin,
   if (valid && bin != 0) atomicAdd(&hist[bin], 1u);
 }
 
-// frame f = b * T + t of the forecast starts at pred + b * sstride + t * fstride.  VEC: hw, both strides and both bases are multiples of 4
-// floats.
+// VEC: pair_quads with hw as the row length.
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void joint_kernel(const float* __restrict__ pred, int64_t sstride, int64_t fstride, const float* __restrict__ tgt,
-                                                       double* __restrict__ table, float value_scale, int L, int T, int hw, int chunks, int items) {
+__global__ __launch_bounds__(kBlock) void joint_kernel(ScoredPair pair, double* __restrict__ table, float value_scale, int L, int chunks, int items) {
   extern __shared__ __attribute__((aligned(16))) unsigned hist[];   // L * L
-  const int t = blockIdx.y, bins = L * L;
+  const int t = blockIdx.y, bins = L * L, T = pair.T, hw = pair.hw;
   for (int i = threadIdx.x; i < bins; i += kBlock) hist[i] = 0u;
   __syncthreads();
   unsigned zeros = 0;   // wave-uniform: the pixels of this wave in bin (0, 0)
   constexpr int kIter = VEC ? kChunk / (4 * kBlock) : kChunk / kBlock;
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
     const int b = item / chunks, px0 = (item % chunks) * kChunk;
-    const float* o_src = tgt + ((int64_t)b * T + t) * hw + px0;
-    const float* f_src = pred + (int64_t)b * sstride + (int64_t)t * fstride + px0;
+    const float* o_src = pair.target(b * T + t) + px0;
+    const float* f_src = pair.forecast(b, t) + px0;
     const int left = hw - px0;   // pixels of the frame from px0 on (>= 1)
     if (VEC) {
       float4 o[kIter], f[kIter];
@@ -89,10 +87,9 @@ inline int64_t joint_levels(float value_scale) {
   if (!(value_scale >= 1.f && value_scale < 128.f)) return -1;   // a NaN fails both; 2 <= L <= 128
   return (int64_t)floorf(value_scale) + 1;
 }
-const char* joint_shape_why(int64_t frames, int64_t T, int64_t hw, float value_scale) {
+const char* joint_why(int64_t frames, int64_t T, int64_t hw, float value_scale) {
   if (joint_levels(value_scale) < 0) return "value_scale must be finite with 2 <= L = floor(value_scale) + 1 <= 128";
-  if (T < 1 || frames < 1 || frames % T != 0) return "T >= 1 must divide frames";
-  if (frames > 65535) return "frames <= 65535";
+  if (const char* w = pair_frames_why(frames, T)) return w;
   if (hw < 1 || hw >= (1 << 24)) return "1 <= hw < 2^24";
   return nullptr;
 }
@@ -107,43 +104,30 @@ extern "C" int64_t adnm_valid_joint_block_bytes(int64_t T, float value_scale) {
 }
 
 extern "C" int64_t adnm_valid_joint_accum_ws_bytes(int64_t frames, int64_t T, int64_t hw, float value_scale) {
-  return joint_shape_why(frames, T, hw, value_scale) ? -1 : 0;   // the partial histograms live in LDS
+  return joint_why(frames, T, hw, value_scale) ? -1 : 0;   // the partial histograms live in LDS
 }
 
 extern "C" int adnm_valid_joint_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
                                       float value_scale, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t hw, adnm_stream_t stream) {
-  ADNM_REQUIRE(pred && target && table, "valid_joint_accum: null pointer");
-  ADNM_REQUIRE(((uintptr_t)pred | (uintptr_t)target) % 4 == 0, "valid_joint_accum: pred and target must be 4-byte aligned");
-  ADNM_REQUIRE((uintptr_t)table % 8 == 0, "valid_joint_accum: the table must be 8-byte aligned");
-  ADNM_REQUIRE((uintptr_t)ws % 8 == 0, "valid_joint_accum: the workspace must be 8-byte aligned");
-  const char* why = joint_shape_why(frames, T, hw, value_scale);
-  if (why) {
-    adnm_set_error("valid_joint_accum: %s (got frames %lld T %lld hw %lld value_scale %g)", why, (long long)frames, (long long)T, (long long)hw,
-                   (double)value_scale);
-    return ADNM_EINVAL;
-  }
-  ADNM_REQUIRE(pred_frame_stride == 0 || pred_frame_stride >= hw, "valid_joint_accum: pred_frame_stride must be 0 or >= hw, got %lld",
-               (long long)pred_frame_stride);
-  ADNM_REQUIRE(pred_sample_stride >= 0, "valid_joint_accum: pred_sample_stride must be >= 0, got %lld", (long long)pred_sample_stride);
-  const int64_t need = adnm_valid_joint_accum_ws_bytes(frames, T, hw, value_scale);
-  ADNM_REQUIRE(ws_bytes >= need, "valid_joint_accum: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
+  const PairCall call = {"valid_joint_accum", pred, pred_sample_stride, pred_frame_stride, target, table, ws, ws_bytes, 1, hw,
+                         /*flat*/ true, /*ws_optional*/ true, /*ws_aligned*/ true, /*ws_rc*/ ADNM_EINVAL};
+  if (int rc = pair_check(call, true, joint_why(frames, T, hw, value_scale),
+                          adnm_valid_joint_accum_ws_bytes(frames, T, hw, value_scale),
+                          "frames %lld T %lld hw %lld value_scale %g", (long long)frames, (long long)T, (long long)hw, (double)value_scale))
+    return rc;
   const int64_t L = joint_levels(value_scale), chunks = adnm_cdiv(hw, kChunk), items = (frames / T) * chunks;   // items <= 65535 * 4096 = 2^28
   int64_t groups = kTargetGroups / T > 1 ? kTargetGroups / T : 1;
   if (groups > items) groups = items;
   if (groups < adnm_cdiv(items, kMaxItemsPerGroup)) groups = adnm_cdiv(items, kMaxItemsPerGroup);
-  // 16-byte loads need every frame start of both fields aligned; a 4-byte aligned slice takes the scalar path: same result
-  const bool vec = hw % 4 == 0 && pred_sample_stride % 4 == 0 && pred_frame_stride % 4 == 0 && adnm_quad_aligned(ADNM_F32, {pred, target});
+  const bool vec = pair_quads(hw, pred_sample_stride, pred_frame_stride, pred, target);
+  const ScoredPair pair = {pred, pred_sample_stride, pred_frame_stride, target, (int)T, (int)hw};
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)groups, (unsigned)T);
   const size_t lds = sizeof(unsigned) * (size_t)(L * L);   // <= 64 KB: no function attribute is needed
   {
     ADNM_PROF("valid_joint", st, 8.0 * frames * hw);
-    if (vec)
-      joint_kernel<true><<<grid, kBlock, lds, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (double*)table, value_scale, (int)L, (int)T, (int)hw,
-                                                    (int)chunks, (int)items);
-    else
-      joint_kernel<false><<<grid, kBlock, lds, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (double*)table, value_scale, (int)L, (int)T, (int)hw,
-                                                     (int)chunks, (int)items);
+    if (vec) joint_kernel<true><<<grid, kBlock, lds, st>>>(pair, (double*)table, value_scale, (int)L, (int)chunks, (int)items);
+    else joint_kernel<false><<<grid, kBlock, lds, st>>>(pair, (double*)table, value_scale, (int)L, (int)chunks, (int)items);
   }
   ADNM_CHECK_LAUNCH("valid_joint");
   return ADNM_OK;

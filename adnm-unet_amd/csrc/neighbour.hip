@@ -1,0 +1,400 @@
+// The two neighbourhood scores of a scored pair (scored_pair.h): pooled contingency counts (include/adnm_hip.h: adnm_valid_pool_accum;
+// DESIGN.md §4h) and the Fractions Skill Score's windowed sums (adnm_valid_fss_accum; §4i).  Both cut a frame into 32 x 32 tiles, one
+// workgroup per (tile, frame).  A workgroup stages its tile and the margin its windows reach into ONCE, as pair_bits' 2 bytes per pixel in
+// LDS (low byte target, high byte forecast), and serves every pool or scale and every threshold from that image in integers.  Each pass
+// leaves 3 * nthr uint32 per workgroup, part[frame][tile][pass][3 * nthr], and one fold adds them to the table in double, in a fixed
+// order.  What the two share is written once: the stager, the store of a pass's counts and the fold.
+#include "scored_pair.h"
+
+namespace {
+constexpr int kBlock = 256, kFoldBlock = 256, kTile = 32;
+
+// The event bits of the rectangle [y0, y0 + rows) x [x0, x0 + cols) of one frame (tp: the target's, pp: the forecast's first pixel)
+// -> img[r * PITCH + c], 0 where the rectangle leaves the frame (INSIDE: the caller has clipped it, nothing is tested).  VEC: W, x0
+// and cols are multiples of 4 and every row of both fields starts on 16 bytes (pair_quads), so four columns are one 16-byte load per
+// field and lie inside or outside the frame as a whole.  Their four results leave as one 8-byte store where PITCH keeps a row start
+// 8-byte aligned, as two 4-byte stores where it does not.
+template <bool VEC, int PITCH, bool INSIDE>
+__device__ __forceinline__ void stage_pair_bits(uint16_t* img, const float* __restrict__ tp, const float* __restrict__ pp, int H, int W, int y0, int x0,
+                                                int rows, int cols, float value_scale, const Thr& thr) {
+  if (VEC) {
+    const int q = cols >> 2;
+    for (int i = threadIdx.x; i < rows * q; i += kBlock) {
+      const int r = i / q, c = (i % q) * 4, gy = y0 + r, gx = x0 + c;
+      uint32_t lo = 0, hi = 0;
+      if (INSIDE || (gy >= 0 && gy < H && gx >= 0 && gx < W)) {
+        const float4 a = *(const float4*)(tp + (int64_t)gy * W + gx), b = *(const float4*)(pp + (int64_t)gy * W + gx);
+        lo = pair_bits(a.x, b.x, value_scale, thr) | (pair_bits(a.y, b.y, value_scale, thr) << 16);
+        hi = pair_bits(a.z, b.z, value_scale, thr) | (pair_bits(a.w, b.w, value_scale, thr) << 16);
+      }
+      if constexpr (PITCH % 4 == 0) {
+        *(uint2*)&img[r * PITCH + c] = make_uint2(lo, hi);
+      } else {
+        uint32_t* dst = (uint32_t*)&img[r * PITCH + c];   // c and PITCH are even: 4-byte aligned
+        dst[0] = lo;
+        dst[1] = hi;
+      }
+    }
+  } else {
+    for (int i = threadIdx.x; i < rows * cols; i += kBlock) {
+      const int r = i / cols, c = i % cols, gy = y0 + r, gx = x0 + c;
+      uint32_t m = 0;
+      if (INSIDE || (gy >= 0 && gy < H && gx >= 0 && gx < W)) m = pair_bits(tp[(int64_t)gy * W + gx], pp[(int64_t)gy * W + gx], value_scale, thr);
+      img[r * PITCH + c] = (uint16_t)m;
+    }
+  }
+}
+
+// A pass's counts leave the workgroup: v[k], k < nout, is this WAVE's count (the same in every lane) -> red -> the four waves added as
+// (0 + 1) + (2 + 3) -> part[frame][tile][pass p of npass][k].  Ends synchronised: the next pass may rewrite red and whatever it read.
+__device__ __forceinline__ void store_part(uint32_t* __restrict__ part, uint32_t (*red)[3 * kMaxThr], const uint32_t (&v)[3 * kMaxThr], int f, int tile,
+                                           int npass, int p, int nout) {
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 3 * kMaxThr; ++k)
+      if (k < nout) red[threadIdx.x >> 6][k] = v[k];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nout)
+    part[(((int64_t)f * gridDim.x + tile) * npass + p) * nout + threadIdx.x] =
+        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  __syncthreads();
+}
+
+// One thread per (t, pass, threshold): the three uint32 columns of part[frame b * T + t][tile][pass][3k .. 3k + 2] summed in a fixed
+// order (samples ascending, then tiles ascending: valid_fold_kernel's), in double arithmetic on integers, and handed to
+// fin(t, p, k, B, s0, s1, s2), which adds the batch to the table.
+template <typename FIN>
+__device__ __forceinline__ void tile_fold(const uint32_t* __restrict__ part, int tiles, int frames, int T, int nthr, int npass, const FIN& fin) {
+  const int B = frames / T, i = blockIdx.x * kFoldBlock + threadIdx.x;
+  if (i >= T * npass * nthr) return;
+  const int k = i % nthr, p = (i / nthr) % npass, t = i / (nthr * npass);
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (int b = 0; b < B; ++b)
+    for (int tile = 0; tile < tiles; ++tile) {
+      const uint32_t* q = part + ((((int64_t)b * T + t) * tiles + tile) * npass + p) * (3 * nthr) + 3 * k;
+      s0 += (double)q[0], s1 += (double)q[1], s2 += (double)q[2];
+    }
+  fin(t, p, k, B, s0, s1, s2);
+}
+inline int64_t tiles_of(int64_t H, int64_t W) { return adnm_cdiv(H, kTile) * adnm_cdiv(W, kTile); }
+
+// ---- neighbourhood (pooled) contingency counts ----
+// A window of a pool (s, d) is an event at threshold k iff ANY pixel of it has q >= thr_k (thresholding commutes with the max), so a
+// pixel's whole state is one byte per field (bit k = q >= thr_k) and max-pooling is a windowed OR.  A workgroup owns the windows whose
+// top-left pixel lies in its tile.  From the staged image it serves every pool and every threshold: OR along rows, then along columns,
+// then per bit the number of windows with the target bit, the forecast bit and both.  Those are wave ballots summed in scalar registers:
+// integers throughout.  The fold turns (obs, sim, both) into TP, FN, FP, TN.
+constexpr int kPoolMax = 4, kPoolWin = 32;
+constexpr int kPoolSide = kTile + kPoolWin;   // staged rows / columns at most: a window reaches at most s - 1 <= 31 past the tile
+constexpr int kPoolPitch = kPoolSide + 4;     // uint16 per staged row: 136 bytes, so that a row start stays 8-byte aligned
+struct Pools {
+  int s[kPoolMax], d[kPoolMax], n;
+};
+
+// grid (tiles, frames).  ext: how far past the tile the staged image goes (host: the largest s - gcd(d, 32) of the pools; VEC: rounded
+// up to 4).  The staged rectangle is clipped to the frame: no window reads past rh x rw.
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void pool_counts_kernel(ScoredPair pair, uint32_t* __restrict__ part, int H, int W, int tiles_x, int ext,
+                                                             float value_scale, Thr thr, Pools pools) {
+  __shared__ __attribute__((aligned(8))) uint16_t img[kPoolSide][kPoolPitch];
+  __shared__ uint16_t rowor[kPoolSide][kTile + 1];
+  __shared__ uint32_t red[kBlock / 64][3 * kMaxThr];
+  const int f = blockIdx.y, tile = blockIdx.x, oy = (tile / tiles_x) * kTile, ox = (tile % tiles_x) * kTile;
+  const int rh = min(kTile + ext, H - oy), rw = min(kTile + ext, W - ox);   // VEC: rw is a multiple of 4, as W, ox and 32 + ext are
+  stage_pair_bits<VEC, kPoolPitch, true>(&img[0][0], pair.target(f), pair.forecast(f), H, W, oy, ox, rh, rw, value_scale, thr);
+  __syncthreads();
+  const int nout = 3 * thr.n;
+  for (int p = 0; p < pools.n; ++p) {
+    const int s = pools.s[p], d = pools.d[p];
+    // the windows anchored in this tile: indices [j0, j0 + na) along each axis, the first one at offset c0 from the tile's origin
+    const int jx0 = (ox + d - 1) / d, jy0 = (oy + d - 1) / d;
+    const int nax = max(0, min((W - s) / d + 1, (ox + kTile + d - 1) / d) - jx0), nay = max(0, min((H - s) / d + 1, (oy + kTile + d - 1) / d) - jy0);
+    const int cx0 = jx0 * d - ox, cy0 = jy0 * d - oy;
+    for (int i = threadIdx.x; i < rh * nax; i += kBlock) {
+      const int r = i / nax, j = i % nax;
+      const uint16_t* src = &img[r][cx0 + j * d];   // cx0 + j*d + s <= min(W - ox, 32 + ext) = rw
+      uint32_t m = 0;
+      for (int u = 0; u < s; ++u) m |= src[u];
+      rowor[r][j] = (uint16_t)m;
+    }
+    __syncthreads();
+    uint32_t cnt[3 * kMaxThr];   // wave-uniform: windows with the target bit k, the forecast bit k, both
+#pragma unroll
+    for (int k = 0; k < 3 * kMaxThr; ++k) cnt[k] = 0;
+    const int na = nax * nay;
+    for (int i0 = 0; i0 < na; i0 += kBlock) {   // the same trips for every lane: the ballots below see whole waves
+      const int i = i0 + threadIdx.x;
+      uint32_t m = 0;
+      if (i < na) {
+        const int r0 = cy0 + (i / nax) * d, j = i % nax;   // r0 + s <= rh
+        for (int u = 0; u < s; ++u) m |= rowor[r0 + u][j];
+      }
+      const uint32_t o = m & 0xffu, sim = m >> 8, v = o | (sim << 8) | ((o & sim) << 16);
+#pragma unroll
+      for (int k = 0; k < kMaxThr; ++k)
+        if (k < thr.n) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) cnt[3 * k + c] += (uint32_t)__popcll(__ballot((v >> (8 * c + k)) & 1u));
+        }
+    }
+    store_part(part, red, cnt, f, tile, pools.n, p, nout);   // rowor too is rewritten by the next pool
+  }
+}
+
+// table[t][pool][4k .. 4k+3] += TP, FN, FP, TN of the batch, TN from the number of windows of the pool
+__global__ __launch_bounds__(kFoldBlock) void pool_fold_kernel(const uint32_t* __restrict__ part, int tiles, int frames, int T, int nthr, int H, int W,
+                                                               Pools pools, double* __restrict__ table) {
+  tile_fold(part, tiles, frames, T, nthr, pools.n, [&](int t, int p, int k, int B, double obs, double sim, double both) {
+    const double windows = (double)B * (double)((H - pools.s[p]) / pools.d[p] + 1) * (double)((W - pools.s[p]) / pools.d[p] + 1);
+    double* out = table + ((int64_t)t * pools.n + p) * (4 * nthr) + 4 * k;
+    out[0] += both;
+    out[1] += obs - both;
+    out[2] += sim - both;
+    out[3] += windows - obs - sim + both;
+  });
+}
+
+int pool_gcd(int a, int b) { return b == 0 ? a : pool_gcd(b, a % b); }
+
+// the pooled pass's own limits: nullptr, or the one that refuses
+const char* pool_why(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* pools_host, int64_t npool) {
+  if (!pools_host) return "null pointer";
+  if (npool < 1 || npool > kPoolMax) return "1..4 pools";
+  if (nthr < 1 || nthr > kMaxThr) return "1..8 thresholds";
+  if (const char* w = pair_frames_why(frames, T)) return w;
+  if (const char* w = pair_tiled_shape_why(H, W)) return w;
+  for (int64_t p = 0; p < npool; ++p) {
+    const int64_t s = pools_host[2 * p], d = pools_host[2 * p + 1];
+    if (!(1 <= d && d <= s && s <= kPoolWin)) return "a pool needs 1 <= stride <= size <= 32";
+    if (s > (H < W ? H : W)) return "a pool window is larger than the frame";
+  }
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int64_t adnm_valid_pool_block_bytes(int64_t T, int64_t nthr, int64_t npool) {
+  if (T < 1 || T > 65535 || nthr < 1 || nthr > kMaxThr || npool < 1 || npool > kPoolMax) return -1;
+  return (int64_t)sizeof(double) * T * npool * 4 * nthr;
+}
+
+extern "C" int64_t adnm_valid_pool_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* pools_host, int64_t npool) {
+  if (pool_why(frames, T, H, W, nthr, pools_host, npool)) return -1;
+  return frames * tiles_of(H, W) * npool * 3 * nthr * (int64_t)sizeof(uint32_t);
+}
+
+extern "C" int adnm_valid_pool_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                                     const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* pools_host, int64_t npool, void* ws,
+                                     int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream) {
+  const PairCall call = {"valid_pool_accum", pred, pred_sample_stride, pred_frame_stride, target, table, ws, ws_bytes, H, W,
+                         /*flat*/ false, /*ws_optional*/ false, /*ws_aligned*/ false, /*ws_rc*/ ADNM_EWORKSPACE};
+  if (int rc = pair_check(call, thresholds_host && pools_host, pool_why(frames, T, H, W, nthr, pools_host, npool),
+                          adnm_valid_pool_accum_ws_bytes(frames, T, H, W, nthr, pools_host, npool),
+                          "frames %lld T %lld %lld x %lld nthr %lld npool %lld", (long long)frames, (long long)T, (long long)H, (long long)W,
+                          (long long)nthr, (long long)npool))
+    return rc;
+  const Thr thr = thr_fill(thresholds_host, nthr);
+  Pools pools;
+  pools.n = (int)npool;
+  int ext = 0;
+  for (int p = 0; p < kPoolMax; ++p) {
+    pools.s[p] = p < npool ? (int)pools_host[2 * p] : 1;
+    pools.d[p] = p < npool ? (int)pools_host[2 * p + 1] : 1;
+    // windows start at multiples of d and tiles at multiples of 32: the last start in a tile is at most 32 - gcd(d, 32) into it
+    const int e = pools.s[p] - pool_gcd(pools.d[p], kTile);
+    ext = e > ext ? e : ext;
+  }
+  const bool vec = pair_quads(W, pred_sample_stride, pred_frame_stride, pred, target);
+  if (vec) ext = (int)adnm_align(ext, 4);
+  const ScoredPair pair = {pred, pred_sample_stride, pred_frame_stride, target, (int)T, (int)(H * W)};
+  const int tiles_x = (int)adnm_cdiv(W, kTile), tiles = (int)tiles_of(H, W);
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ADNM_PROF("valid_pool", st, 8.0 * frames * H * W);
+    const dim3 grid((unsigned)tiles, (unsigned)frames);
+    if (vec) pool_counts_kernel<true><<<grid, kBlock, 0, st>>>(pair, (uint32_t*)ws, (int)H, (int)W, tiles_x, ext, value_scale, thr, pools);
+    else pool_counts_kernel<false><<<grid, kBlock, 0, st>>>(pair, (uint32_t*)ws, (int)H, (int)W, tiles_x, ext, value_scale, thr, pools);
+  }
+  ADNM_CHECK_LAUNCH("valid_pool_accum");
+  {
+    ADNM_PROF("valid_pool_fold", st, 4.0 * frames * tiles * npool * 3 * nthr);
+    pool_fold_kernel<<<(unsigned)adnm_cdiv(T * npool * nthr, kFoldBlock), kFoldBlock, 0, st>>>((const uint32_t*)ws, tiles, (int)frames, (int)T, (int)nthr, (int)H,
+                                                                                             (int)W, pools, (double*)table);
+  }
+  ADNM_CHECK_LAUNCH("valid_pool_fold");
+  return ADNM_OK;
+}
+
+// ---- Fractions Skill Score: windowed fraction sums ----
+// c_o(y, x) / c_f(y, x): the number of threshold-k pixels of the target / the forecast in the n x n window CENTRED on (y, x), zero outside
+// the frame.  A workgroup owns the 32 x 32 window centres of its tile.  It stages the tile and a halo of hs >= max(n) / 2 pixels on all
+// four sides (0 outside the frame), and serves every scale and threshold from that image, separably and with running sums:
+//   rows     wave q takes nibble q of the pixel (0, 1: target thresholds 0-3, 4-7; 2, 3: forecast), lane R the staged row R.  A nibble
+//            is spread to one count per BYTE (bit j -> byte j), and a running sum along the row (add the pixel entering the window,
+//            take the one leaving) gives the four thresholds' row counts (<= 33 each: bytes never carry) for the 32 centres' columns.
+//   columns  a thread owns 4 consecutive centres of one column; the row counts are summed down the window in 16-bit lanes (even bytes
+//            in one dword, odd bytes in another; <= 1089 each), again running: n adds for the first centre, one add and one
+//            subtraction for each of the next three.
+// c_o^2, c_f^2, c_o c_f per lane in uint32 (a tile's sum is at most 1024 * 1089^2 < 2^32), integer adds across the wave and the four
+// waves.  LDS: image rows 33 dwords and row-count rows 33 dwords apart, so the lanes of the row pass (one row each) and of the column
+// pass (consecutive columns) hit distinct banks.  The pooled pass's pitch cannot serve here (34 dwords: an even row distance puts two
+// lanes of the row pass on one bank), nor this one there (132-byte rows are not 8-byte aligned): the stager takes the pitch as a parameter.
+namespace {
+constexpr int kFssMax = 4, kFssWin = 33;
+constexpr int kFssSide = kTile + 2 * (kFssWin / 2);   // 64 staged rows / columns at most
+constexpr int kFssPitch = kFssSide + 2;               // uint16 per staged row: 33 dwords
+struct Scales {
+  int n[kFssMax], cnt;
+};
+
+// bit j of a nibble -> byte j of a dword (0 or 1): x * (1 + 2^7 + 2^14 + 2^21) puts bit j at 8j among 16 distinct positions (no carries)
+__device__ __forceinline__ uint32_t fss_spread(uint32_t nibble) { return (nibble * 0x00204081u) & 0x01010101u; }
+
+__device__ __forceinline__ uint32_t fss_wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+  return v;
+}
+
+// grid (tiles, frames).  hs: the staged halo (host: the largest n / 2; VEC: rounded up to 4, so that the staged columns start at a
+// multiple of 4).
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void fss_sums_kernel(ScoredPair pair, uint32_t* __restrict__ part, int H, int W, int tiles_x, int hs,
+                                                          float value_scale, Thr thr, Scales scales) {
+  __shared__ __attribute__((aligned(4))) uint16_t img[kFssSide][kFssPitch];
+  __shared__ uint32_t rs[4][kFssSide][kTile + 1];   // [nibble][staged row][centre column]: four thresholds' row counts, one per byte
+  __shared__ uint32_t red[kBlock / 64][3 * kMaxThr];
+  const int f = blockIdx.y, tile = blockIdx.x, oy = (tile / tiles_x) * kTile, ox = (tile % tiles_x) * kTile;
+  const int side = kTile + 2 * hs;
+  stage_pair_bits<VEC, kFssPitch, false>(&img[0][0], pair.target(f), pair.forecast(f), H, W, oy - hs, ox - hs, side, side, value_scale, thr);
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nout = 3 * thr.n;
+  const int cx = threadIdx.x & 31, cy0 = (threadIdx.x >> 5) * 4;   // the column pass: centres (cy0 .. cy0 + 3, cx) of the tile
+  const bool col_in = ox + cx < W;
+  for (int p = 0; p < scales.cnt; ++p) {
+    const int n = scales.n[p], r = n >> 1, c0 = hs - r;   // centre x's window: staged columns c0 + x .. c0 + x + n - 1 (<= 2*hs + 31 < side)
+    if (lane < side && (thr.n > 4 || !(wave & 1))) {      // (nibbles 1 and 3 hold thresholds 4-7)
+      const uint16_t* row = img[lane];
+      const int sh = 4 * wave;
+      uint32_t s = 0;
+      for (int u = 0; u < n - 1; ++u) s += fss_spread((row[c0 + u] >> sh) & 0xfu);
+      for (int x = 0; x < kTile; ++x) {
+        s += fss_spread((row[c0 + x + n - 1] >> sh) & 0xfu);
+        rs[wave][lane][x] = s;
+        s -= fss_spread((row[c0 + x] >> sh) & 0xfu);   // it was added: no byte borrows
+      }
+    }
+    __syncthreads();
+    // acc[q][e]: nibble q's bytes e and e + 2 as 16-bit lanes; centre y's window: staged rows c0 + y .. c0 + y + n - 1
+    uint32_t acc[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+    uint32_t sum[3 * kMaxThr];
+#pragma unroll
+    for (int k = 0; k < 3 * kMaxThr; ++k) sum[k] = 0;
+    auto rows = [&](int R, bool add) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (thr.n > 4 || !(q & 1)) {
+          const uint32_t v = rs[q][R][cx], e = v & 0x00ff00ffu, o = (v >> 8) & 0x00ff00ffu;
+          acc[q][0] = add ? acc[q][0] + e : acc[q][0] - e;
+          acc[q][1] = add ? acc[q][1] + o : acc[q][1] - o;
+        }
+    };
+    for (int u = 0; u < n - 1; ++u) rows(c0 + cy0 + u, true);
+    for (int j = 0; j < 4; ++j) {
+      rows(c0 + cy0 + j + n - 1, true);   // <= 2*hs + 31 < side
+      if (col_in && oy + cy0 + j < H) {
+#pragma unroll
+        for (int k = 0; k < kMaxThr; ++k)
+          if (k < thr.n) {
+            const int sh = 16 * ((k & 3) >> 1);
+            const uint32_t co = (acc[k >> 2][k & 1] >> sh) & 0xffffu, cf = (acc[2 + (k >> 2)][k & 1] >> sh) & 0xffffu;
+            sum[3 * k + 0] += co * co;
+            sum[3 * k + 1] += cf * cf;
+            sum[3 * k + 2] += co * cf;
+          }
+      }
+      rows(c0 + cy0 + j, false);
+    }
+#pragma unroll
+    for (int k = 0; k < 3 * kMaxThr; ++k)
+      if (k < nout) sum[k] = fss_wave_sum(sum[k]);
+    store_part(part, red, sum, f, tile, scales.cnt, p, nout);   // rs too is rewritten by the next scale
+  }
+}
+
+// table[t][scale][3k .. 3k+2] += A, F, C of the batch
+__global__ __launch_bounds__(kFoldBlock) void fss_fold_kernel(const uint32_t* __restrict__ part, int tiles, int frames, int T, int nthr, int ns,
+                                                              double* __restrict__ table) {
+  tile_fold(part, tiles, frames, T, nthr, ns, [&](int t, int p, int k, int, double a, double fc, double c) {
+    double* out = table + ((int64_t)t * ns + p) * (3 * nthr) + 3 * k;
+    out[0] += a;
+    out[1] += fc;
+    out[2] += c;
+  });
+}
+
+// the FSS pass's own limits: nullptr, or the one that refuses
+const char* fss_why(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* scales_host, int64_t nscale) {
+  if (!scales_host) return "null pointer";
+  if (nscale < 1 || nscale > kFssMax) return "1..4 scales";
+  if (nthr < 1 || nthr > kMaxThr) return "1..8 thresholds";
+  if (const char* w = pair_frames_why(frames, T)) return w;
+  if (const char* w = pair_tiled_shape_why(H, W)) return w;
+  for (int64_t p = 0; p < nscale; ++p) {
+    const int64_t n = scales_host[p];
+    if (n < 1 || n > kFssWin || n % 2 == 0) return "a scale must be odd and in 1..33";
+    for (int64_t o = 0; o < p; ++o)
+      if (scales_host[o] == n) return "a scale is given twice";
+  }
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int64_t adnm_valid_fss_block_bytes(int64_t T, int64_t nthr, int64_t nscale) {
+  if (T < 1 || T > 65535 || nthr < 1 || nthr > kMaxThr || nscale < 1 || nscale > kFssMax) return -1;
+  return (int64_t)sizeof(double) * T * nscale * 3 * nthr;
+}
+
+extern "C" int64_t adnm_valid_fss_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* scales_host, int64_t nscale) {
+  if (fss_why(frames, T, H, W, nthr, scales_host, nscale)) return -1;
+  return frames * tiles_of(H, W) * nscale * 3 * nthr * (int64_t)sizeof(uint32_t);
+}
+
+extern "C" int adnm_valid_fss_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                                    const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* scales_host, int64_t nscale, void* ws,
+                                    int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream) {
+  const PairCall call = {"valid_fss_accum", pred, pred_sample_stride, pred_frame_stride, target, table, ws, ws_bytes, H, W,
+                         /*flat*/ false, /*ws_optional*/ false, /*ws_aligned*/ false, /*ws_rc*/ ADNM_EWORKSPACE};
+  if (int rc = pair_check(call, thresholds_host && scales_host, fss_why(frames, T, H, W, nthr, scales_host, nscale),
+                          adnm_valid_fss_accum_ws_bytes(frames, T, H, W, nthr, scales_host, nscale),
+                          "frames %lld T %lld %lld x %lld nthr %lld nscale %lld", (long long)frames, (long long)T, (long long)H, (long long)W,
+                          (long long)nthr, (long long)nscale))
+    return rc;
+  const Thr thr = thr_fill(thresholds_host, nthr);
+  Scales scales;
+  scales.cnt = (int)nscale;
+  int hs = 0;
+  for (int p = 0; p < kFssMax; ++p) {
+    scales.n[p] = p < nscale ? (int)scales_host[p] : 1;
+    hs = scales.n[p] / 2 > hs ? scales.n[p] / 2 : hs;
+  }
+  const bool vec = pair_quads(W, pred_sample_stride, pred_frame_stride, pred, target);
+  if (vec) hs = (int)adnm_align(hs, 4);   // <= 16
+  const ScoredPair pair = {pred, pred_sample_stride, pred_frame_stride, target, (int)T, (int)(H * W)};
+  const int tiles_x = (int)adnm_cdiv(W, kTile), tiles = (int)tiles_of(H, W);
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ADNM_PROF("valid_fss", st, 8.0 * frames * H * W);
+    const dim3 grid((unsigned)tiles, (unsigned)frames);
+    if (vec) fss_sums_kernel<true><<<grid, kBlock, 0, st>>>(pair, (uint32_t*)ws, (int)H, (int)W, tiles_x, hs, value_scale, thr, scales);
+    else fss_sums_kernel<false><<<grid, kBlock, 0, st>>>(pair, (uint32_t*)ws, (int)H, (int)W, tiles_x, hs, value_scale, thr, scales);
+  }
+  ADNM_CHECK_LAUNCH("valid_fss_accum");
+  {
+    ADNM_PROF("valid_fss_fold", st, 4.0 * frames * tiles * nscale * 3 * nthr);
+    fss_fold_kernel<<<(unsigned)adnm_cdiv(T * nscale * nthr, kFoldBlock), kFoldBlock, 0, st>>>((const uint32_t*)ws, tiles, (int)frames, (int)T, (int)nthr,
+                                                                                            (int)nscale, (double*)table);
+  }
+  ADNM_CHECK_LAUNCH("valid_fss_fold");
+  return ADNM_OK;
+}

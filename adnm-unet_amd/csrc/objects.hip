@@ -23,11 +23,10 @@
 //   the row         every root of at least min_area pixels adds its entries to 23 u64 counters in LDS; the non-zero ones go to the table
 //                   as double atomics.  Every addend and every sum is an integer below 2^53, so the table is exact and the same bits on
 //                   every run although the order of the atomics is not fixed.
-#include "adnm_common.h"
+#include "scored_pair.h"
 
 namespace {
 constexpr int kBlock = 1024;
-constexpr int kMaxThr = 8;
 constexpr int kCols = 23, kBins = 17;          // count, area, area^2, largest, matched, matched area, 17 bins of floor(log2(area))
 static_assert(kCols == 6 + kBins, "six sums, then the size histogram");
 constexpr int64_t kMaxPixels = 65536;          // an area fits 17 bits (bin 16 is the last); area^2 <= 2^32
@@ -35,10 +34,6 @@ constexpr int kMaxGroups = 512;                // workgroups of a launch whose w
 constexpr size_t kLdsLimit = 160 * 1024;
 constexpr unsigned kRoot = 1u << 30, kMatched = 1u << 31, kAreaMask = (1u << 20) - 1u;
 constexpr size_t kHead = 8 * 24 + 16;          // 23 u64 counters (24 for alignment), then the sweep flag
-
-struct ObjThr {
-  float t[kMaxThr];
-};
 
 __device__ __forceinline__ unsigned ld(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -176,19 +171,18 @@ __device__ __forceinline__ Smem carve(unsigned char* smem, unsigned* ws, int hw)
   return s;
 }
 
-// grid (G): item = frame * nthr + k; frame f = b * T + t of the forecast starts at pred + b * sstride + t * fstride
+// grid (G): item = frame * nthr + k
 template <bool LDSW>
-__global__ __launch_bounds__(kBlock) void objects_kernel(const float* __restrict__ pred, int64_t sstride, int64_t fstride, const float* __restrict__ tgt,
-                                                         double* __restrict__ table, ObjThr thr, int nthr, float value_scale, unsigned min_area,
-                                                         unsigned* __restrict__ ws, int items, int T, int H, int W) {
+__global__ __launch_bounds__(kBlock) void objects_kernel(ScoredPair pair, double* __restrict__ table, Thr thr, float value_scale, unsigned min_area,
+                                                         unsigned* __restrict__ ws, int items, int W) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int hw = H * W, tid = threadIdx.x;
+  const int hw = pair.hw, nthr = thr.n, tid = threadIdx.x;
   const Smem s = carve<LDSW>(smem, ws, hw);
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
-    const int f = item / nthr, k = item % nthr, b = f / T, t = f % T;
+    const int f = item / nthr, k = item % nthr, t = f % pair.T;
     __syncthreads();   // the item before is done with the bits
-    stage_bits(s.bits_o, tgt + (int64_t)f * hw, hw, thr.t[k], value_scale);
-    stage_bits(s.bits_f, pred + (int64_t)b * sstride + (int64_t)t * fstride, hw, thr.t[k], value_scale);
+    stage_bits(s.bits_o, pair.target(f), hw, thr.t[k], value_scale);
+    stage_bits(s.bits_f, pair.forecast(f), hw, thr.t[k], value_scale);
     for (int field = 0; field < 2; ++field) {
       const unsigned* bits = field ? s.bits_f : s.bits_o;
       if (tid < 24) s.acc[tid] = 0ull;
@@ -216,7 +210,7 @@ __global__ __launch_bounds__(kBlock) void objects_kernel(const float* __restrict
   }
 }
 
-// grid (G): one frame of one field per item; frame f = b * T + t starts at src + b * sstride + t * fstride
+// grid (G): one frame of one field per item; frame f = b * T + t of the field is pair_frame(src, sstride, fstride, b, t)
 template <bool LDSW>
 __global__ __launch_bounds__(kBlock) void label_kernel(const float* __restrict__ src, int64_t sstride, int64_t fstride, int* __restrict__ labels, float thr,
                                                        float value_scale, unsigned min_area, unsigned* __restrict__ ws, int frames, int T, int H, int W) {
@@ -225,7 +219,7 @@ __global__ __launch_bounds__(kBlock) void label_kernel(const float* __restrict__
   const Smem s = carve<LDSW>(smem, ws, hw);
   for (int f = blockIdx.x; f < frames; f += gridDim.x) {
     __syncthreads();
-    stage_bits(s.bits_o, src + (int64_t)(f / T) * sstride + (int64_t)(f % T) * fstride, hw, thr, value_scale);
+    stage_bits(s.bits_o, pair_frame(src, sstride, fstride, f / T, f % T), hw, thr, value_scale);
     __syncthreads();
     label_field(s.word, s.bits_o, nullptr, s.flag, hw, W);
     int* out = labels + (int64_t)f * hw;
@@ -242,11 +236,15 @@ __global__ __launch_bounds__(kBlock) void label_kernel(const float* __restrict__
 
 inline size_t lds_bytes(int64_t hw, bool words) { return kHead + 2 * sizeof(unsigned) * (size_t)bit_words((int)hw) + (words ? sizeof(unsigned) * (size_t)hw : 0); }
 inline bool words_in_lds(int64_t hw) { return lds_bytes(hw, true) <= kLdsLimit; }
-const char* frame_why(int64_t frames, int64_t T, int64_t H, int64_t W) {
-  if (T < 1 || frames < 1 || frames % T != 0) return "T >= 1 must divide frames";
-  if (frames > 65535) return "frames <= 65535";
-  if (H < 1 || W < 1 || H > kMaxPixels || W > kMaxPixels || H * W > kMaxPixels) return "1 <= H * W <= 65536";
-  return nullptr;
+const char* frame_why(int64_t H, int64_t W) {
+  return H < 1 || W < 1 || H > kMaxPixels || W > kMaxPixels || H * W > kMaxPixels ? "1 <= H * W <= 65536" : nullptr;
+}
+// the object scores' own limits: nullptr, or the one that refuses
+const char* objects_why(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, int64_t min_area) {
+  if (nthr < 1 || nthr > kMaxThr) return "1..8 thresholds";
+  if (min_area < 1) return "min_area >= 1";
+  if (const char* w = pair_frames_why(frames, T)) return w;
+  return frame_why(H, W);
 }
 inline int64_t groups_of(int64_t items, int64_t hw) { return words_in_lds(hw) || items < kMaxGroups ? items : kMaxGroups; }
 inline int64_t ws_need(int64_t items, int64_t hw) { return words_in_lds(hw) ? 0 : (int64_t)sizeof(unsigned) * groups_of(items, hw) * hw; }
@@ -258,37 +256,28 @@ extern "C" int64_t adnm_valid_objects_block_bytes(int64_t T, int64_t nthr) {
 }
 
 extern "C" int64_t adnm_valid_objects_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr) {
-  if (frame_why(frames, T, H, W) || nthr < 1 || nthr > kMaxThr) return -1;
+  if (objects_why(frames, T, H, W, nthr, 1)) return -1;
   return ws_need(frames * nthr, H * W);
 }
 
 extern "C" int64_t adnm_label_objects_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W) {
-  if (frame_why(frames, T, H, W)) return -1;
+  if (pair_frames_why(frames, T) || frame_why(H, W)) return -1;
   return ws_need(frames, H * W);
 }
 
 extern "C" int adnm_valid_objects_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
                                         const float* thresholds_host, int64_t nthr, float value_scale, int64_t min_area, void* ws, int64_t ws_bytes,
                                         int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream) {
-  ADNM_REQUIRE(pred && target && table && thresholds_host, "valid_objects_accum: null pointer");
-  ADNM_REQUIRE(((uintptr_t)pred | (uintptr_t)target) % 4 == 0, "valid_objects_accum: pred and target must be 4-byte aligned");
-  ADNM_REQUIRE((uintptr_t)table % 8 == 0, "valid_objects_accum: the table must be 8-byte aligned");
-  ADNM_REQUIRE((uintptr_t)ws % 8 == 0, "valid_objects_accum: the workspace must be 8-byte aligned");
-  ADNM_REQUIRE(nthr >= 1 && nthr <= kMaxThr, "valid_objects_accum: 1..%d thresholds, got %lld", kMaxThr, (long long)nthr);
-  ADNM_REQUIRE(min_area >= 1, "valid_objects_accum: min_area >= 1, got %lld", (long long)min_area);
-  const char* why = frame_why(frames, T, H, W);
-  if (why) {
-    adnm_set_error("valid_objects_accum: %s (got frames %lld T %lld H %lld W %lld)", why, (long long)frames, (long long)T, (long long)H, (long long)W);
-    return ADNM_EINVAL;
-  }
-  const int64_t hw = H * W;
-  ADNM_REQUIRE(pred_frame_stride == 0 || pred_frame_stride >= hw, "valid_objects_accum: pred_frame_stride must be 0 or >= H*W, got %lld",
-               (long long)pred_frame_stride);
-  ADNM_REQUIRE(pred_sample_stride >= 0, "valid_objects_accum: pred_sample_stride must be >= 0, got %lld", (long long)pred_sample_stride);
-  const int64_t items = frames * nthr, need = ws_need(items, hw);
-  ADNM_REQUIRE(ws_bytes >= need && (ws || !need), "valid_objects_accum: workspace %lld < %lld bytes", (long long)(ws ? ws_bytes : 0), (long long)need);
-  ObjThr thr;
-  for (int k = 0; k < kMaxThr; ++k) thr.t[k] = k < nthr ? thresholds_host[k] : 0.f;
+  const PairCall call = {"valid_objects_accum", pred, pred_sample_stride, pred_frame_stride, target, table, ws, ws_bytes, H, W,
+                         /*flat*/ false, /*ws_optional*/ true, /*ws_aligned*/ true, /*ws_rc*/ ADNM_EINVAL};
+  if (int rc = pair_check(call, thresholds_host != nullptr, objects_why(frames, T, H, W, nthr, min_area),
+                          adnm_valid_objects_accum_ws_bytes(frames, T, H, W, nthr),
+                          "frames %lld T %lld H %lld W %lld nthr %lld min_area %lld", (long long)frames, (long long)T, (long long)H, (long long)W,
+                          (long long)nthr, (long long)min_area))
+    return rc;
+  const int64_t hw = H * W, items = frames * nthr;
+  const Thr thr = thr_fill(thresholds_host, nthr);
+  const ScoredPair pair = {pred, pred_sample_stride, pred_frame_stride, target, (int)T, (int)hw};
   const unsigned small = (unsigned)(min_area > kMaxPixels + 1 ? kMaxPixels + 1 : min_area);   // no object is larger than a frame
   const bool in_lds = words_in_lds(hw);
   const size_t lds = lds_bytes(hw, in_lds);
@@ -297,12 +286,10 @@ extern "C" int adnm_valid_objects_accum(const float* pred, int64_t pred_sample_s
   if (in_lds) {
     ADNM_ALLOW_LDS(objects_kernel<true>, lds, "valid_objects");
     ADNM_PROF("valid_objects", st, 8.0 * items * hw);
-    objects_kernel<true><<<grid, kBlock, lds, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (double*)table, thr, (int)nthr, value_scale, small,
-                                                    nullptr, (int)items, (int)T, (int)H, (int)W);
+    objects_kernel<true><<<grid, kBlock, lds, st>>>(pair, (double*)table, thr, value_scale, small, nullptr, (int)items, (int)W);
   } else {
     ADNM_PROF("valid_objects", st, 8.0 * items * hw);
-    objects_kernel<false><<<grid, kBlock, lds, st>>>(pred, pred_sample_stride, pred_frame_stride, target, (double*)table, thr, (int)nthr, value_scale, small,
-                                                     (unsigned*)ws, (int)items, (int)T, (int)H, (int)W);
+    objects_kernel<false><<<grid, kBlock, lds, st>>>(pair, (double*)table, thr, value_scale, small, (unsigned*)ws, (int)items, (int)W);
   }
   ADNM_CHECK_LAUNCH("valid_objects");
   return ADNM_OK;
@@ -314,7 +301,8 @@ extern "C" int adnm_label_objects(const float* src, int64_t sample_stride, int64
   ADNM_REQUIRE(((uintptr_t)src | (uintptr_t)labels_i32) % 4 == 0, "label_objects: src and labels must be 4-byte aligned");
   ADNM_REQUIRE((uintptr_t)ws % 8 == 0, "label_objects: the workspace must be 8-byte aligned");
   ADNM_REQUIRE(min_area >= 1, "label_objects: min_area >= 1, got %lld", (long long)min_area);
-  const char* why = frame_why(frames, T, H, W);
+  const char* why = pair_frames_why(frames, T);
+  if (!why) why = frame_why(H, W);
   if (why) {
     adnm_set_error("label_objects: %s (got frames %lld T %lld H %lld W %lld)", why, (long long)frames, (long long)T, (long long)H, (long long)W);
     return ADNM_EINVAL;

@@ -20,7 +20,7 @@
 // Transform: radix-2 decimation in time, log2 N stages in place in LDS, input stored bit-reversed.  Twiddles exp(-2 pi i j / N), j < N/2:
 // sincospi in DOUBLE, rounded once to fp32, built per workgroup in LDS.  All other arithmetic is fp32.  No atomics, a fixed order
 // everywhere: the same calls on the same table give the same bits, whatever the workspace held.
-#include "adnm_common.h"
+#include "scored_pair.h"
 
 namespace {
 constexpr int kBlock = 256, kFoldBlock = 256;
@@ -60,17 +60,15 @@ __device__ __forceinline__ void spec_stages(float2* buf, const float2* tw, int n
 
 __device__ __forceinline__ int spec_brev(int x, int logN) { return (int)(__brev((unsigned)x) >> (32 - logN)); }
 
-// grid (H / 2 / RP, frames): RP row pairs of frame blockIdx.y from pair blockIdx.x * RP on.  Frame f of the forecast starts at
-// pred + (f / T) * sstride + (f % T) * fstride.  VEC: both strides and both bases are multiples of 4 floats (W always is).
+// grid (H / 2 / RP, frames): RP row pairs of frame blockIdx.y from pair blockIdx.x * RP on.  VEC: pair_quads (W always is a multiple of 4).
 template <bool VEC>
-__global__ __launch_bounds__(kBlock) void spec_rows_kernel(const float* __restrict__ pred, int64_t sstride, int64_t fstride, const float* __restrict__ tgt,
-                                                           float2* __restrict__ cols, int T, int H, int W, int logW, int RP, float value_scale) {
+__global__ __launch_bounds__(kBlock) void spec_rows_kernel(ScoredPair pair, float2* __restrict__ cols, int H, int W, int logW, int RP, float value_scale) {
   __shared__ float2 buf[kRowBuf];
   __shared__ float2 tw[kMaxN / 2];
   const int f = blockIdx.y, p0 = blockIdx.x * RP, pitch = W + 1;
   spec_twiddles(tw, W);
   // transform q = field * RP + pair: field 0 the target, 1 the forecast
-  const float* src[2] = {tgt + (int64_t)f * H * W + (int64_t)2 * p0 * W, pred + (int64_t)(f / T) * sstride + (int64_t)(f % T) * fstride + (int64_t)2 * p0 * W};
+  const float* src[2] = {pair.target(f) + (int64_t)2 * p0 * W, pair.forecast(f) + (int64_t)2 * p0 * W};
   if (VEC) {
     for (int i = threadIdx.x; i < RP * (W >> 2); i += kBlock) {
       const int pr = i / (W >> 2), x = (i % (W >> 2)) * 4;
@@ -178,13 +176,9 @@ inline int spec_log2(int64_t n) {
   while ((1ll << l) < n) ++l;
   return l;
 }
-bool spec_shape_ok(int64_t frames, int64_t T, int64_t H, int64_t W, const char** why) {
-  const char* w = nullptr;
-  if (!spec_size_ok(H) || !spec_size_ok(W)) w = "H and W must be powers of two in 8..512";
-  else if (T < 1 || frames < 1 || frames % T != 0) w = "T >= 1 must divide frames";
-  else if (frames > 65535) w = "frames <= 65535";
-  if (why) *why = w;
-  return w == nullptr;
+const char* spec_why(int64_t frames, int64_t T, int64_t H, int64_t W) {
+  if (!spec_size_ok(H) || !spec_size_ok(W)) return "H and W must be powers of two in 8..512";
+  return pair_frames_why(frames, T);
 }
 inline int64_t spec_cols_bytes(int64_t frames, int64_t H, int64_t W) { return frames * (W / 2 + 1) * 2 * H * (int64_t)sizeof(float2); }
 }  // namespace
@@ -195,44 +189,31 @@ extern "C" int64_t adnm_valid_spectrum_block_bytes(int64_t T, int64_t H, int64_t
 }
 
 extern "C" int64_t adnm_valid_spectrum_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W) {
-  if (!spec_shape_ok(frames, T, H, W, nullptr)) return -1;
+  if (spec_why(frames, T, H, W)) return -1;
   return spec_cols_bytes(frames, H, W) + frames * (W / 2 + 1) * ((H > W ? H : W) / 2) * 3 * (int64_t)sizeof(float);
 }
 
 extern "C" int adnm_valid_spectrum_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
                                          float value_scale, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W,
                                          adnm_stream_t stream) {
-  ADNM_REQUIRE(pred && target && table && ws, "valid_spectrum_accum: null pointer");
-  ADNM_REQUIRE(((uintptr_t)pred | (uintptr_t)target) % 4 == 0, "valid_spectrum_accum: pred and target must be 4-byte aligned");
-  ADNM_REQUIRE((uintptr_t)table % 8 == 0, "valid_spectrum_accum: the table must be 8-byte aligned");
-  const char* why = nullptr;
-  if (!spec_shape_ok(frames, T, H, W, &why)) {
-    adnm_set_error("valid_spectrum_accum: %s (got frames %lld T %lld %lld x %lld)", why, (long long)frames, (long long)T, (long long)H, (long long)W);
-    return ADNM_EINVAL;
-  }
-  ADNM_REQUIRE(pred_frame_stride == 0 || pred_frame_stride >= H * W, "valid_spectrum_accum: pred_frame_stride must be 0 or >= H*W, got %lld",
-               (long long)pred_frame_stride);
-  ADNM_REQUIRE(pred_sample_stride >= 0, "valid_spectrum_accum: pred_sample_stride must be >= 0, got %lld", (long long)pred_sample_stride);
-  const int64_t need = adnm_valid_spectrum_accum_ws_bytes(frames, T, H, W);
-  ADNM_REQUIRE(ws_bytes >= need, "valid_spectrum_accum: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
-  ADNM_REQUIRE((uintptr_t)ws % 8 == 0, "valid_spectrum_accum: the workspace must be 8-byte aligned");
+  const PairCall call = {"valid_spectrum_accum", pred, pred_sample_stride, pred_frame_stride, target, table, ws, ws_bytes, H, W,
+                         /*flat*/ false, /*ws_optional*/ false, /*ws_aligned*/ true, /*ws_rc*/ ADNM_EINVAL};
+  if (int rc = pair_check(call, ws != nullptr, spec_why(frames, T, H, W),
+                          adnm_valid_spectrum_accum_ws_bytes(frames, T, H, W),
+                          "frames %lld T %lld %lld x %lld", (long long)frames, (long long)T, (long long)H, (long long)W))
+    return rc;
   const int64_t L = H > W ? H : W, R = L / 2, nk = W / 2 + 1;
   const int64_t rp = (kRowElems / 2) / W < H / 2 ? (kRowElems / 2) / W : H / 2;   // row pairs per workgroup: a power of two that divides H / 2
   float2* cols = (float2*)ws;
   float* part = (float*)((char*)ws + spec_cols_bytes(frames, H, W));
-  // 16-byte loads need every frame and row start of both fields aligned (W is a multiple of 8); a 4-byte aligned slice takes the scalar
-  // path: same result
-  const bool vec = pred_sample_stride % 4 == 0 && pred_frame_stride % 4 == 0 && adnm_quad_aligned(ADNM_F32, {pred, target});
+  const bool vec = pair_quads(W, pred_sample_stride, pred_frame_stride, pred, target);
+  const ScoredPair pair = {pred, pred_sample_stride, pred_frame_stride, target, (int)T, (int)(H * W)};
   hipStream_t st = (hipStream_t)stream;
   {
     ADNM_PROF("valid_spectrum_rows", st, 8.0 * frames * H * W + 16.0 * frames * nk * H);
     const dim3 grid((unsigned)(H / 2 / rp), (unsigned)frames);
-    if (vec)
-      spec_rows_kernel<true><<<grid, kBlock, 0, st>>>(pred, pred_sample_stride, pred_frame_stride, target, cols, (int)T, (int)H, (int)W, spec_log2(W), (int)rp,
-                                                      value_scale);
-    else
-      spec_rows_kernel<false><<<grid, kBlock, 0, st>>>(pred, pred_sample_stride, pred_frame_stride, target, cols, (int)T, (int)H, (int)W, spec_log2(W), (int)rp,
-                                                       value_scale);
+    if (vec) spec_rows_kernel<true><<<grid, kBlock, 0, st>>>(pair, cols, (int)H, (int)W, spec_log2(W), (int)rp, value_scale);
+    else spec_rows_kernel<false><<<grid, kBlock, 0, st>>>(pair, cols, (int)H, (int)W, spec_log2(W), (int)rp, value_scale);
   }
   ADNM_CHECK_LAUNCH("valid_spectrum_rows");
   {

@@ -1,4 +1,4 @@
-"""The CPU yardstick of the Fractions Skill Score sums (csrc/dataio.hip: adnm_valid_fss_accum): the fields quantised the way
+"""The CPU yardstick of the Fractions Skill Score sums (csrc/neighbour.hip: adnm_valid_fss_accum): the fields quantised the way
 adnm_eval_counts quantises them (verify_ref.quant), thresholded, and counted per n x n window centred on every pixel with zero padding
 by conv2d of the float64 bit fields with an all-ones kernel (exact integers).  Per frame, scale and threshold A = sum c_o^2,
 F = sum c_f^2, C = sum c_o c_f; FSS = 2C / (A + F).  Sums are integers: every comparison against this reference is exact.  The reference

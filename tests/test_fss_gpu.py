@@ -1,4 +1,4 @@
-"""Fractions Skill Score sums on the GPU (csrc/dataio.hip: adnm_valid_fss_accum; ops.fss_sums; Validator(fss=)): exact, integer for
+"""Fractions Skill Score sums on the GPU (csrc/neighbour.hip: adnm_valid_fss_accum; ops.fss_sums; Validator(fss=)): exact, integer for
 integer, against conv2d with an all-ones kernel on the thresholded quantised fields on the CPU (fss_ref), against the point-wise kernel
 the Validator already runs, and end to end through the captured graph.  The floats derived from the sums use the same double expression
 on both sides and are compared to 1e-12 relative."""

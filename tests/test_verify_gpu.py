@@ -1,4 +1,4 @@
-"""Pooled contingency counts on the GPU (csrc/dataio.hip: adnm_valid_pool_accum; ops.pool_counts; Validator(pools=, persistence=)):
+"""Pooled contingency counts on the GPU (csrc/neighbour.hip: adnm_valid_pool_accum; ops.pool_counts; Validator(pools=, persistence=)):
 exact, integer for integer, against max_pool2d on the quantised fields on the CPU (verify_ref), against the point-wise kernel the
 Validator already runs, and end to end through the captured graph."""
 import ctypes

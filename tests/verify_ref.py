@@ -1,4 +1,4 @@
-"""The CPU yardstick of the pooled contingency counts (csrc/dataio.hip: adnm_valid_pool_accum): torch's max_pool2d applied to the fields
+"""The CPU yardstick of the pooled contingency counts (csrc/neighbour.hip: adnm_valid_pool_accum): torch's max_pool2d applied to the fields
 quantised the way adnm_eval_counts quantises them, and a generator of radar-like fields.  Counts are integers: every comparison against
 this reference is exact.  The reference project has no pooled score, so nothing here is recorded from it."""
 import numpy as np
