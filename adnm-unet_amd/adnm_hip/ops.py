@@ -3474,6 +3474,97 @@ def advect(last, motion, block, T):
     return out
 
 
+# ======================================================================================= sub-pixel flow and transport along it (csrc/flow.hip)
+MAX_FLOW_T = 4096
+_FLOW_LIMITS = "1 <= samples <= 65535, H and W < 32768, H*W < 2^24, block 8 / 16 / 32"
+
+
+def trec_flow(prev, last, value_scale, block, radius, echo, return_motion=False):
+    """prev / last: what trec_motion takes -> int32 (n, nby, nbx, 2) on the device: the block flow (uy, ux) in 1/16 px, trec_motion's pick
+    refined by a parabola through its neighbours on the block's own table, on the sample's sum table where the block has no echo
+    (include/adnm_hip.h: adnm_trec_flow).  return_motion: -> (flow, trec_motion's vectors), from the same call."""
+    p, l = _frames("trec_flow", prev, "prev"), _frames("trec_flow", last, "last")
+    if p.shape != l.shape or p.device != l.device:
+        _unsupported("trec_flow", f"takes two fp32 tensors (..., H, W) of one shape, got {tuple(prev.shape)} and {tuple(last.shape)}")
+    H, W = l.shape[-2:]
+    n = l.numel() // (H * W) if H * W else 0
+    block, radius, echo = int(block), int(radius), int(echo)
+    nb = lib.query("adnm_trec_flow_ws_bytes", n, H, W, block, radius)
+    if nb < 0:
+        raise RuntimeError(f"trec_flow: {n} samples of {H} x {W} with block {block} and radius {radius} are outside adnm_trec_flow's limits "
+                           f"({_FLOW_LIMITS}, radius 1..8)")
+    shape = (n, -(-H // block), -(-W // block), 2)
+    flow = torch.empty(shape, dtype=torch.int32, device=l.device)
+    motion = torch.empty(shape, dtype=torch.int32, device=l.device) if return_motion else None
+    ws = _ws(nb, l.device)
+    lib.call("adnm_trec_flow", p.data_ptr(), l.data_ptr(), H * W, flow.data_ptr(), None if motion is None else motion.data_ptr(), float(value_scale),
+             block, radius, echo, ws.data_ptr(), int(nb), n, H, W, _stream())
+    return (flow, motion) if return_motion else flow
+
+
+def _flow_arg(op, flow, block, H, W, n=None):
+    """the block flow of n samples (its own leading size when n is None) of H x W at `block`, contiguous"""
+    block = int(block)
+    if not torch.is_tensor(flow):
+        raise RuntimeError(f"{op}: needs GPU tensors")
+    _need_gpu(flow)
+    if block not in TREC_BLOCKS:
+        raise RuntimeError(f"{op}: block is one of {TREC_BLOCKS}, got {block}")
+    shape = ((flow.shape[0] if flow.dim() else 0) if n is None else n, -(-H // block), -(-W // block), 2)
+    if flow.dtype != torch.int32 or tuple(flow.shape) != shape:
+        _unsupported(op, f"takes the flow as an int32 tensor {shape} (trec_flow at block {block}), got {flow.dtype} {tuple(flow.shape)}")
+    return flow.contiguous()
+
+
+def flow_field(flow, block, H, W):
+    """flow: int32 (n, nby, nbx, 2) of trec_flow at the same `block` for H x W frames -> int32 (n, H, W, 2): the dense field (Vy, Vx) in
+    1/256 px, bilinear between the block centres with integer weights (include/adnm_hip.h: adnm_flow_field)."""
+    H, W = int(H), int(W)
+    u = _flow_arg("flow_field", flow, block, H, W)
+    n = u.shape[0]
+    if lib.query("adnm_trec_ws_bytes", n, H, W, int(block), 1) < 0:
+        raise RuntimeError(f"flow_field: {n} samples of {H} x {W} with block {block} are outside adnm_flow_field's limits ({_FLOW_LIMITS})")
+    out = torch.empty((n, H, W, 2), dtype=torch.int32, device=u.device)
+    lib.call("adnm_flow_field", u.data_ptr(), out.data_ptr(), int(block), n, H, W, _stream())
+    return out
+
+
+def advect_flow(last, flow, block, T):
+    """last: fp32 GPU tensor (..., H, W), n samples; flow: int32 (n, nby, nbx, 2) of trec_flow at the same `block` -> fp32 (n, T, H, W):
+    frame t is `last` carried backwards along the dense field t + 1 times, one step per frame, and read with four taps in fp32, every
+    rounding prescribed; +0.0 outside the frame (include/adnm_hip.h: adnm_advect_flow)."""
+    l = _frames("advect_flow", last, "last")
+    H, W = l.shape[-2:]
+    n = l.numel() // (H * W) if H * W else 0
+    block, T = int(block), int(T)
+    if lib.query("adnm_trec_ws_bytes", n, H, W, block, 1) < 0 or not 1 <= T <= MAX_FLOW_T:
+        raise RuntimeError(f"advect_flow: {n} samples of {H} x {W} with block {block} and T {T} are outside adnm_advect_flow's limits "
+                           f"({_FLOW_LIMITS}, 1 <= T <= {MAX_FLOW_T})")
+    u = _flow_arg("advect_flow", flow, block, H, W, n)
+    if u.device != l.device:
+        _unsupported("advect_flow", f"takes the flow on {l.device}, got {u.device}")
+    out = torch.empty((n, T, H, W), dtype=torch.float32, device=l.device)
+    lib.call("adnm_advect_flow", l.data_ptr(), H * W, u.data_ptr(), out.data_ptr(), block, n, T, H, W, _stream())
+    return out
+
+
+def extrapolate(x, T, value_scale, block=32, radius=4, echo=None):
+    """The extrapolation nowcast as a product of its own.  x: fp32 GPU tensor (n, T_in >= 2, H, W) (or (n, T_in, 1, H, W)), the observed
+    frames -> fp32 (n, T, H, W): the last frame carried along the flow estimated from the last two (trec_flow, advect_flow), frame t at lead
+    t + 1 of the input's frame spacing; Forecaster.render can colour it.  echo: the quantised level a block needs `block` pixels of to move
+    on its own (1..255); None: a tenth of value_scale, at least 1."""
+    if not torch.is_tensor(x):
+        raise RuntimeError("extrapolate: needs GPU tensors")
+    _need_gpu(x)
+    if x.dim() == 5 and x.shape[2] == 1:
+        x = x[:, :, 0]
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] < 2:
+        _unsupported("extrapolate", f"takes the observed frames as fp32 (n, T_in >= 2, H, W), got {x.dtype} {tuple(x.shape)}")
+    echo = max(1, int(float(value_scale) / 10.0)) if echo is None else int(echo)
+    flow = trec_flow(x[:, -2], x[:, -1], value_scale, block, radius, echo)
+    return advect_flow(x[:, -1], flow, block, T)
+
+
 # ======================================================================================= radially averaged power spectra (csrc/spectrum.hip)
 MIN_SPECTRUM_SIZE, MAX_SPECTRUM_SIZE = 8, 512
 SPECTRUM_LIMITS = f"H and W powers of two in {MIN_SPECTRUM_SIZE}..{MAX_SPECTRUM_SIZE}"

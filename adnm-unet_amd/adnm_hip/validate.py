@@ -27,7 +27,9 @@ for the baseline), and done() reports FSS = 2C / (A + F) from the summed rows.
 
 Validator(..., advection=True) adds the Lagrangian-persistence baseline (DESIGN.md §4j): csrc/advect.hip::trec_cost / trec_pick estimate one
 motion vector per block from the last two input frames, advect moves the last frame along it for every frame index, and that field is
-scored as a second baseline by the same pooled and FSS passes.
+scored as a second baseline by the same pooled and FSS passes.  With advection_flow=True the field comes from
+csrc/flow.hip instead: trec_flow refines each vector to 1/16 px on the same cost tables and advect_flow carries the last frame backwards
+along the dense field between the block centres, one step per frame, with four taps in fp32; tables, passes and keys stay where they were.
 
 Validator(..., spectrum=True) adds radially averaged power spectra (DESIGN.md §4k): csrc/spectrum.hip::valid_spectrum_accum transforms the
 clipped, scaled target and forecast (power-of-two frames of 8..512 pixels a side) and adds the power of each and their co-spectrum per
@@ -432,7 +434,7 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
 
 class Validator(ForwardClient):
     def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False,
-                 fss=None, advection=None, spectrum=False, objects=None, joint=False):
+                 fss=None, advection=None, spectrum=False, objects=None, advection_flow=False, joint=False):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -449,6 +451,11 @@ class Validator(ForwardClient):
         self.advection = ops.advection_spec(advection, self.thresholds)   # (block, radius, echo) or None; ValueError on a bad entry
         if self.advection and not 0.0 < self.value_scale <= 255.0:
             raise ValueError(f"Validator: advection matches blocks on quantised bytes, which needs 0 < value_scale <= 255, got {self.value_scale}")
+        self.advection_flow = bool(advection_flow)   # the advected field by sub-pixel flow and transport along it (csrc/flow.hip) instead of block copies
+        if self.advection_flow and not self.advection:
+            raise ValueError("Validator: advection_flow=True chooses how the advection baseline moves the frame; it needs advection= as well")
+        if self.advection_flow and self.seq_len > ops.MAX_FLOW_T:
+            raise ValueError(f"Validator: advection_flow follows a displacement in int32, which needs seq_len <= {ops.MAX_FLOW_T}, got {self.seq_len}")
         self.spectrum, self.joint = bool(spectrum), bool(joint)
         self._levels = ops.joint_levels(self.value_scale) if self.joint else None   # ValueError outside the limits
         self.objects = ops.objects_spec(objects)   # min_area, or None; ValueError on a bad entry
@@ -505,9 +512,10 @@ class Validator(ForwardClient):
             if part.field == "adv" and not moved:   # the advected field, in front of the first pass that scores it
                 block_px, radius, echo = self.advection
                 t_in, moved = sx.shape[1], True
-                lib.call("adnm_trec_motion", sx.data_ptr() + 4 * (t_in - 2) * H * W, sx.data_ptr() + 4 * (t_in - 1) * H * W, t_in * H * W, ent["motion"].data_ptr(),
+                estimate, move, vectors = ("adnm_trec_flow", "adnm_advect_flow", ent["flow"]) if self.advection_flow else ("adnm_trec_motion", "adnm_advect", ent["motion"])
+                lib.call(estimate, sx.data_ptr() + 4 * (t_in - 2) * H * W, sx.data_ptr() + 4 * (t_in - 1) * H * W, t_in * H * W, vectors.data_ptr(),
                          None, self.value_scale, block_px, radius, echo, ent["ws_trec"].data_ptr(), ent["ws_trec"].numel(), B, H, W, stream)
-                lib.call("adnm_advect", sx.data_ptr() + 4 * (t_in - 1) * H * W, t_in * H * W, ent["motion"].data_ptr(), ent["adv"].data_ptr(), block_px, B, T, H, W, stream)
+                lib.call(move, sx.data_ptr() + 4 * (t_in - 1) * H * W, t_in * H * W, vectors.data_ptr(), ent["adv"].data_ptr(), block_px, B, T, H, W, stream)
             src = source(part.field)
             if part.kind == "pool":
                 lib.call("adnm_valid_pool_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, ops.pool_table(part.pools), len(part.pools),
@@ -547,7 +555,7 @@ class Validator(ForwardClient):
         ws_ssim = None
         if self.ssim and H > 10 and W > 10:   # 11 x 11 windows need a valid region; smaller frames: SSIM is None
             ws_ssim = torch.empty(max(int(lib.query("adnm_valid_ssim_accum_ws_bytes", B * T, T, H, W, nthr)), 16), dtype=torch.uint8, device=dev)
-        ws_pool = ws_fss = adv = motion = ws_trec = ws_spectrum = ws_joint = ws_objects = None
+        ws_pool = ws_fss = adv = motion = flow = ws_trec = ws_spectrum = ws_joint = ws_objects = None
         passes = [p.pools for p in self._parts if p.kind == "pool"]
         if passes:   # the passes follow one another on one stream: one workspace
             ws_pool = workspace("adnm_valid_pool_accum_ws_bytes", [(B * T, T, H, W, nthr, ops.pool_table(pools), len(pools)) for pools in passes],
@@ -569,7 +577,8 @@ class Validator(ForwardClient):
             ws_trec = workspace("adnm_trec_ws_bytes", [(B, H, W, block_px, radius)],
                                 f"advection on {B} samples of {H} x {W} is outside adnm_trec_motion's limits (samples <= 65535, H and W < 32768, H*W < 2^24)")
             adv = torch.zeros(shape, dtype=torch.float32, device=dev)
-            motion = torch.zeros((B, -(-H // block_px), -(-W // block_px), 2), dtype=torch.int32, device=dev)
+            vectors = torch.zeros((B, -(-H // block_px), -(-W // block_px), 2), dtype=torch.int32, device=dev)
+            motion, flow = (None, vectors) if self.advection_flow else (vectors, None)   # (adnm_trec_flow_ws_bytes is adnm_trec_ws_bytes)
         if self.spectrum:
             ws_spectrum = workspace("adnm_valid_spectrum_accum_ws_bytes", [(B * T, T, H, W)],
                                     f"spectrum on {B * T} frames of {H} x {W} is outside adnm_valid_spectrum_accum's limits (frames <= 65535, "
@@ -583,7 +592,7 @@ class Validator(ForwardClient):
                                    f"objects on {B * T} frames of {H} x {W} are outside adnm_valid_objects_accum's limits (frames <= 65535, "
                                    f"{ops.OBJECTS_LIMITS})", floor=0)
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=ws, ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss,
-                   ws_spectrum=ws_spectrum, ws_joint=ws_joint, ws_objects=ws_objects, adv=adv, motion=motion, ws_trec=ws_trec,
+                   ws_spectrum=ws_spectrum, ws_joint=ws_joint, ws_objects=ws_objects, adv=adv, motion=motion, flow=flow, ws_trec=ws_trec,
                    loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
         self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
@@ -649,6 +658,14 @@ class Validator(ForwardClient):
             raise RuntimeError("Validator.advected: needs advection= and a step() on an input of this shape, dtype and device first")
         return ent["adv"]
 
+    def flow(self, x):
+        """advection_flow: the block flow of the last batch of x's shape: the graph's static int32 (B, nby, nbx, 2) tensor, (uy, ux) in 1/16 px
+        per frame, valid until the next step of that shape (ops.flow_field spreads it to the dense field)"""
+        ent = self._fwd._graphs.get((tuple(x.shape), x.dtype, x.device))
+        if not self.advection_flow or ent is None or ent.get("flow") is None:
+            raise RuntimeError("Validator.flow: needs advection_flow=True and a step() on an input of this shape, dtype and device first")
+        return ent["flow"]
+
     @property
     def last_loss(self):
         """the fp32 loss of the last batch: a 0-dim device tensor (reading it synchronises; the epoch's sum is in done())"""
@@ -665,7 +682,8 @@ class Validator(ForwardClient):
         fss: plus "fss": {n: {thr: FSS}} (NaN where neither field has an event), "fss_useful": {thr: 0.5 + f_o / 2}, and "fss" under
         "persistence" and, as length-T arrays, under "per_lead" and "per_lead"/"persistence" where those exist.
         advection: plus "advection" and "per_lead"/"advection", built like "persistence": the last input frame moved along its
-        block-matched motion, scored on the same batches.
+        block-matched motion, scored on the same batches.  advection_flow: the same entries from the frame carried along the sub-pixel flow
+        (DESIGN.md §4p), and "advection"/"scheme" = "flow".
         spectrum: plus "spectrum" {"wavenumber", "wavelength_px", "target", "forecast", "ratio", "coherence", "effective_resolution_px"}
         (aggregate) and, as (T, R) arrays with a length-T "effective_resolution_px", "per_lead"/"spectrum".
         joint: plus "joint" {"levels", "histogram", "marginal_target", "marginal_forecast", "curves", "conditional_mean", "qq", "correlation",
@@ -680,6 +698,8 @@ class Validator(ForwardClient):
         area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
         res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead,
                         fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None, joint=self._levels, objects=self.objects)
+        if self.advection_flow:
+            res["advection"]["scheme"] = "flow"
         if reset:
             self.reset()
         return res

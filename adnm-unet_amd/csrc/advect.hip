@@ -10,11 +10,11 @@
 //   advect      adv[s, t, y, x] = last[s, y - (t+1) vy, x - (t+1) vx] with v of the block of (y, x): a gather of bit patterns.
 //
 // Integer arithmetic and bit copies only, no atomics: exact, and the same bits whatever the workspace held.
-#include "adnm_common.h"
+#include "trec.h"
 
 namespace {
 constexpr int kBlock = 256;
-constexpr int kMaxBs = 32, kMaxR = 8;
+constexpr int kMaxBs = kTrecMaxBs, kMaxR = kTrecMaxR;
 constexpr int kCurPitch = kMaxBs / 4;                        // dwords per staged row of the block
 constexpr int kWinRows = kMaxBs + 2 * kMaxR;                 // 48
 constexpr int kWinPitch = (kMaxBs + 2 * kMaxR) / 4 + 1;      // 12 dwords of window and one that is only ever the unused high operand: 13
@@ -106,22 +106,6 @@ __global__ __launch_bounds__(kBlock) void trec_cost_kernel(const float* __restri
   if (threadIdx.x == 0) out[nd] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// (cost, dy^2 + dx^2, dy, dx) as one integer whose order is the lexicographic one: cost < 2^32 (a sample's whole-frame sum is below
-// 2^24 * 255), dy^2 + dx^2 <= 128 in 8 bits, dy + R and dx + R <= 16 in 5 bits each.
-__device__ __forceinline__ uint64_t trec_key(uint64_t cost, int d, int R) {
-  const int D = 2 * R + 1, dy = d / D - R, dx = d % D - R;
-  return (cost << 18) | ((uint64_t)(dy * dy + dx * dx) << 10) | ((uint64_t)(dy + R) << 5) | (uint64_t)(dx + R);
-}
-__device__ __forceinline__ uint64_t trec_wave_min(uint64_t k) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)k, o, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(k >> 32), o, 64);
-    const uint64_t other = ((uint64_t)hi << 32) | lo;
-    k = other < k ? other : k;
-  }
-  return k;
-}
-
 // grid (samples).  ws: trec_cost's tables.  motion[s][b] = (vy, vx); cost_out (or null): the tables without the echo counts.
 __global__ __launch_bounds__(kBlock) void trec_pick_kernel(const uint32_t* __restrict__ ws, int32_t* __restrict__ motion, uint32_t* __restrict__ cost_out,
                                                            int nblk, int bs, int R) {
@@ -192,16 +176,6 @@ __global__ __launch_bounds__(kBlock) void advect_kernel(const uint32_t* __restri
   }
 }
 
-// the limits the three entry points share; on refusal `why` names the limit
-bool trec_shape_ok(int64_t samples, int64_t H, int64_t W, int64_t block, const char** why) {
-  const char* w = nullptr;
-  if (block != 8 && block != 16 && block != 32) w = "block must be 8, 16 or 32";
-  else if (samples < 1 || samples > 65535) w = "samples must be in 1..65535";
-  else if (H < 1 || W < 1 || H >= 32768 || W >= 32768) w = "H and W must be in [1, 32768)";
-  else if (H * W >= (1ll << 24)) w = "pixels per frame < 2^24";
-  if (why) *why = w;
-  return w == nullptr;
-}
 }  // namespace
 
 extern "C" int64_t adnm_trec_ws_bytes(int64_t samples, int64_t H, int64_t W, int64_t block, int64_t radius) {
@@ -210,33 +184,30 @@ extern "C" int64_t adnm_trec_ws_bytes(int64_t samples, int64_t H, int64_t W, int
   return samples * adnm_cdiv(H, block) * adnm_cdiv(W, block) * (D * D + 1) * (int64_t)sizeof(uint32_t);
 }
 
-extern "C" int adnm_trec_motion(const float* prev, const float* last, int64_t sample_stride, void* motion_i32, void* cost_out_u32_or_null, float value_scale,
-                                int64_t block, int64_t radius, int64_t echo, void* ws, int64_t ws_bytes, int64_t samples, int64_t H, int64_t W,
-                                adnm_stream_t stream) {
-  ADNM_REQUIRE(prev && last && motion_i32, "trec_motion: null pointer");
-  ADNM_REQUIRE(((uintptr_t)prev | (uintptr_t)last) % 4 == 0, "trec_motion: prev and last must be 4-byte aligned");
-  ADNM_REQUIRE(((uintptr_t)motion_i32 | (uintptr_t)cost_out_u32_or_null) % 4 == 0, "trec_motion: motion and cost_out must be 4-byte aligned");
+int adnm_trec_cost_launch(const char* what, const float* prev, const float* last, int64_t sample_stride, float value_scale, int64_t block, int64_t radius,
+                          int64_t echo, void* ws, int64_t ws_bytes, int64_t samples, int64_t H, int64_t W, hipStream_t st) {
+  ADNM_REQUIRE(prev && last, "%s: null pointer", what);
+  ADNM_REQUIRE(((uintptr_t)prev | (uintptr_t)last) % 4 == 0, "%s: prev and last must be 4-byte aligned", what);
   const char* why = nullptr;
   if (!trec_shape_ok(samples, H, W, block, &why)) {
-    adnm_set_error("trec_motion: %s (got samples %lld %lld x %lld block %lld)", why, (long long)samples, (long long)H, (long long)W, (long long)block);
+    adnm_set_error("%s: %s (got samples %lld %lld x %lld block %lld)", what, why, (long long)samples, (long long)H, (long long)W, (long long)block);
     return ADNM_EINVAL;
   }
-  ADNM_REQUIRE(radius >= 1 && radius <= kMaxR, "trec_motion: radius must be in 1..8, got %lld", (long long)radius);
-  ADNM_REQUIRE(echo >= 1 && echo <= 255, "trec_motion: echo must be in 1..255, got %lld", (long long)echo);
-  ADNM_REQUIRE(value_scale > 0.f && value_scale <= 255.f, "trec_motion: value_scale must be in (0, 255] so that q fits a byte, got %g", (double)value_scale);
-  ADNM_REQUIRE(sample_stride >= H * W, "trec_motion: sample_stride must be >= H*W, got %lld", (long long)sample_stride);
+  ADNM_REQUIRE(radius >= 1 && radius <= kMaxR, "%s: radius must be in 1..8, got %lld", what, (long long)radius);
+  ADNM_REQUIRE(echo >= 1 && echo <= 255, "%s: echo must be in 1..255, got %lld", what, (long long)echo);
+  ADNM_REQUIRE(value_scale > 0.f && value_scale <= 255.f, "%s: value_scale must be in (0, 255] so that q fits a byte, got %g", what, (double)value_scale);
+  ADNM_REQUIRE(sample_stride >= H * W, "%s: sample_stride must be >= H*W, got %lld", what, (long long)sample_stride);
   const int64_t need = adnm_trec_ws_bytes(samples, H, W, block, radius);
   if (!ws || ws_bytes < need) {
-    adnm_set_error("trec_motion: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
+    adnm_set_error("%s: workspace %lld < %lld bytes", what, (long long)ws_bytes, (long long)need);
     return ADNM_EWORKSPACE;
   }
-  ADNM_REQUIRE((uintptr_t)ws % 4 == 0, "trec_motion: the workspace must be 4-byte aligned");
+  ADNM_REQUIRE((uintptr_t)ws % 4 == 0, "%s: the workspace must be 4-byte aligned", what);
   const int nby = (int)adnm_cdiv(H, block), nbx = (int)adnm_cdiv(W, block);
   // 16-byte loads need every frame and row start of both frames aligned; anything else (an odd W, a 4-byte aligned slice) is read float
   // by float: same result
   const bool vec = W % 4 == 0 && sample_stride % 4 == 0 && adnm_quad_aligned(ADNM_F32, {prev, last});
   const int hs = (int)adnm_align(radius, 4);
-  hipStream_t st = (hipStream_t)stream;
   {
     ADNM_PROF("trec_cost", st, 8.0 * samples * H * W);
     const dim3 grid((unsigned)(nby * nbx), (unsigned)samples);   // nby * nbx <= 2^24 / 64
@@ -248,6 +219,18 @@ extern "C" int adnm_trec_motion(const float* prev, const float* last, int64_t sa
                                                        value_scale);
   }
   ADNM_CHECK_LAUNCH("trec_cost");
+  return ADNM_OK;
+}
+
+extern "C" int adnm_trec_motion(const float* prev, const float* last, int64_t sample_stride, void* motion_i32, void* cost_out_u32_or_null, float value_scale,
+                                int64_t block, int64_t radius, int64_t echo, void* ws, int64_t ws_bytes, int64_t samples, int64_t H, int64_t W,
+                                adnm_stream_t stream) {
+  ADNM_REQUIRE(motion_i32, "trec_motion: null pointer");
+  ADNM_REQUIRE(((uintptr_t)motion_i32 | (uintptr_t)cost_out_u32_or_null) % 4 == 0, "trec_motion: motion and cost_out must be 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = adnm_trec_cost_launch("trec_motion", prev, last, sample_stride, value_scale, block, radius, echo, ws, ws_bytes, samples, H, W, st)) return rc;
+  const int nby = (int)adnm_cdiv(H, block), nbx = (int)adnm_cdiv(W, block);
+  const int64_t need = adnm_trec_ws_bytes(samples, H, W, block, radius);
   {
     ADNM_PROF("trec_pick", st, (double)need);
     trec_pick_kernel<<<(unsigned)samples, kBlock, 0, st>>>((const uint32_t*)ws, (int32_t*)motion_i32, (uint32_t*)cost_out_u32_or_null, nby * nbx, (int)block,

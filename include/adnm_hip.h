@@ -775,6 +775,50 @@ int adnm_trec_motion(const float* prev, const float* last, int64_t sample_stride
 int adnm_advect(const float* last, int64_t sample_stride, const void* motion_i32, float* out, int64_t block, int64_t samples, int64_t T, int64_t H,
                 int64_t W, adnm_stream_t stream);
 
+/* The flow advection: the same baseline with sub-pixel vectors, a dense field and semi-Lagrangian transport along it.  It
+ * stands beside the block scheme above and changes nothing of it.  The cost tables, the integer pick d = (dy, dx), the global pick g of the
+ * 64-bit sum table and the validity of a block (`block` in-frame pixels with q(last) >= echo) are adnm_trec_motion's, unchanged.  All the
+ * motion arithmetic is integer (fixed point); the final interpolation is fp32 with every rounding prescribed: exact and bit-reproducible.
+ *   1. refinement  -> the block flow u, int32 (samples, nby, nbx, 2) holding (uy, ux) in 1/16 px.  A valid block refines its own pick on
+ *                  its own table; an invalid block takes the global pick refined on the sum table (int64 arithmetic).  Each axis is refined
+ *                  independently, using the two neighbours along that axis at the picked other coordinate.  With c0 the cost at the pick and
+ *                  cm, cp the costs at d - 1, d + 1:  delta = 0 if |d| == radius, or if den = cm - 2 c0 + cp <= 0;  otherwise
+ *                  num = 8 (cm - cp) and delta = sgn(num) * floor((2 |num| + den) / (2 den)): round half away from zero; |delta| <= 8
+ *                  follows from c0 being minimal.  u = 16 d + delta.
+ *   2. dense field V, int32 (samples, H, W, 2) in 1/256 px, bilinear between block centres.  Block centres are at b block + block/2 - 1/2;
+ *                  the weights are integers and the vectors are clamped at the outermost centres.  Per axis of length N with nb blocks, at
+ *                  pixel y:  p = 2y + 1 - block;  b0 = clamp(floor(p / (2 block)), 0, nb - 1);  b1 = min(b0 + 1, nb - 1);
+ *                  w1 = p < 0 ? 0 : clamp(p - 2 block b0, 0, 2 block);  w0 = 2 block - w1.  Then S = SUM wy_i wx_j 16 u[b_i, b_j] over the
+ *                  four corners and V = floor((S + 2 block^2) / (4 block^2)): an arithmetic shift, block is a power of two.
+ *   3. transport   backward, semi-Lagrangian, along the field.  Per pixel p = (y, x) the displacement D is int32 in 1/256 px, D_0 = 0.  For
+ *                  frame index t = 0 .. T - 1, per axis:  r = clamp(floor((256 p - D_t + 128) / 256), 0, N - 1), the pixel nearest the
+ *                  departure point;  D_{t+1} = D_t + V[r];  the source is s = 256 p - D_{t+1} with i = floor(s / 256) and
+ *                  f = (s - 256 i) / 256, exact in fp32.  The four taps are a = last[iy, ix], b = last[iy, ix+1], c = last[iy+1, ix],
+ *                  d = last[iy+1, ix+1].  A tap outside the frame is +0.0f.  A tap whose weight is 0 is not read and contributes nothing:
+ *                  fx == 0 gives top = a, fy == 0 gives out = top, so a NaN or Inf beside an integer source position does not leak, and
+ *                  zero or whole-pixel motion remains a copy of the value.  Otherwise, in fp32: gx = 1 - fx, top = gx a + fx b,
+ *                  bot = gx c + fx d, gy = 1 - fy, out = gy top + fy bot; every product and every sum is rounded to fp32 on its own, there
+ *                  is no fused multiply-add.  Frame index t is lead t + 1 at the input's own frame spacing.
+ * adnm_trec_flow: two launches.  adnm_trec_motion's trec_cost into ws (adnm_trec_flow_ws_bytes = adnm_trec_ws_bytes, every byte written);
+ *   trec_flow, one workgroup per sample, sums the tables in block order in 64 bits (integers, no atomics), picks g and per block, applies
+ *   validity, refines and writes flow; motion (or NULL): adnm_trec_motion's int32 (samples, nby, nbx, 2), so that one call serves both
+ *   schemes.  prev, last, sample_stride and the 16-byte rule: adnm_trec_motion's.
+ * adnm_flow_field: one launch, field = V; for inspection and drawing.  The transport does not need it.
+ * adnm_advect_flow: one launch; out contiguous fp32 (samples, T, H, W).  A sample's block vectors are staged in LDS (up to 4096 blocks; beyond
+ *   that they are read from memory: same result) and V at any pixel is formed from them by the integer formula; each lane owns four pixels
+ *   of a row for all T frames (the chain over t is sequential).  Stored 16 bytes per access when W % 4 == 0 and out is 16-byte aligned, float
+ *   by float otherwise: same result.
+ * All arguments are passed by value: the calls can be captured.
+ * Limits, refused before any launch (ADNM_EINVAL): those of adnm_trec_motion and adnm_advect (flow and field 4-byte aligned and not null),
+ *   and T > 4096 (|V| <= 16 * 136, so |D| stays below 2^24 and 256 p - D inside int32).  adnm_trec_flow_ws_bytes returns -1. */
+int64_t adnm_trec_flow_ws_bytes(int64_t samples, int64_t H, int64_t W, int64_t block, int64_t radius);
+int adnm_trec_flow(const float* prev, const float* last, int64_t sample_stride, void* flow_i32, void* motion_i32_or_null, float value_scale,
+                   int64_t block, int64_t radius, int64_t echo, void* ws, int64_t ws_bytes, int64_t samples, int64_t H, int64_t W,
+                   adnm_stream_t stream);
+int adnm_flow_field(const void* flow_i32, void* field_i32, int64_t block, int64_t samples, int64_t H, int64_t W, adnm_stream_t stream);
+int adnm_advect_flow(const float* last, int64_t sample_stride, const void* flow_i32, float* out, int64_t block, int64_t samples, int64_t T, int64_t H,
+                     int64_t W, adnm_stream_t stream);
+
 /* Radially averaged power spectra (RAPSD) of observation and forecast and their co-spectrum, per wavenumber and frame index, as SUMS.
  * The reference has no spectrum; the definitions are this project's, follow pysteps' rapsd convention, and the yardstick
  * is numpy.fft.fft2 in float64.
