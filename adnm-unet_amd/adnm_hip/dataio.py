@@ -290,14 +290,14 @@ class ResidentDataset:
         self.store, self.in_frames, self.batch, self.device = store, int(in_frames), int(batch), store.device
         self.order = EpochOrder(N, batch, shuffle=shuffle, generator=generator, rank=rank, world=world)
         self._order_dev = torch.empty(N, dtype=torch.int32, device=store.device)
-        self._order_pin = torch.empty(N, dtype=torch.int32).pin_memory()   # the upload is asynchronous: the host never waits for the stream
+        self._order_pin = torch.empty(N, dtype=torch.int32, pin_memory=True)   # the upload is asynchronous: the host never waits for the stream
         self._order_sent = None      # the event behind the last upload (the pinned image may be rewritten once it has passed)
         self._uploaded = None        # the epoch whose order _order_dev holds
         self.augment, self.words = augment, None
         if crop is not None or augment is not None:
             self.words = EpochWords(N, H - self.served[0], W - self.served[1], augment)
             self._words_dev = torch.empty(N, dtype=torch.int32, device=store.device)
-            self._words_pin = torch.empty(N, dtype=torch.int32).pin_memory()
+            self._words_pin = torch.empty(N, dtype=torch.int32, pin_memory=True)
 
     @staticmethod
     def _served(Hs, Ws, crop, augment):

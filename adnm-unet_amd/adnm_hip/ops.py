@@ -368,7 +368,8 @@ class GradRegistry:
 
     def take(self, ptr, shape, device, dtype=torch.float32, strides=None):
         """strides: the memory layout the caller is going to WRITE (element strides of `shape`); a registered slice laid out
-        differently is refused WITHOUT being recorded as claimed, so the trainer's gather still copies that gradient."""
+        differently is refused WITHOUT being recorded as claimed, so the trainer's gather still copies that gradient.  Fresh memory comes
+        in that layout too where it is a dense permutation of `shape` (the channels-last weight gradients of conv3 / convt2x)."""
         second = False
         with self._lock:
             self._drain()
@@ -391,6 +392,11 @@ class GradRegistry:
         if second:   # autograd is about to ADD this contribution to the first one: both must be complete when it does
             FOLDS.flush(device)
             FOLDS.hold(device)   # ... so the producer of this one must not defer its fold either
+        if strides is not None and len(strides) == len(shape):
+            order = sorted(range(len(shape)), key=lambda i: -strides[i])
+            t = torch.empty(tuple(shape[i] for i in order), dtype=dtype, device=device).permute(*sorted(range(len(shape)), key=order.__getitem__))
+            if tuple(t.stride()) == tuple(strides):
+                return t
         return torch.empty(tuple(shape), dtype=dtype, device=device)
 
 
@@ -867,11 +873,11 @@ def k_rownorm_fwd(x2, w, b, scale, shift, eps, mean, out=None):
     _need_gpu(x2)
     M, d = x2.shape
     y = out if out is not None else torch.empty((M, d), dtype=x2.dtype, device=x2.device)
-    mu = torch.empty(M if mean else 1, dtype=torch.float32, device=x2.device)
+    mu = torch.empty(M, dtype=torch.float32, device=x2.device) if mean else None   # (without the mean no kernel reads or writes it)
     rstd = torch.empty(M, dtype=torch.float32, device=x2.device)
     px, ldx = _rows(x2)
     py, ldy = _rows(y)
-    lib.call("adnm_rownorm_fwd", px, ldx, _p(_f32(w)), _p(_f32(b)), _p(scale), _p(shift), py, ldy, mu.data_ptr(),
+    lib.call("adnm_rownorm_fwd", px, ldx, _p(_f32(w)), _p(_f32(b)), _p(scale), _p(shift), py, ldy, _p(mu),
              rstd.data_ptr(), M, d, float(eps), int(mean), _dt(x2), _stream())
     return y, mu, rstd
 
@@ -892,7 +898,7 @@ def k_rownorm_bwd(dy2, x2, w, b, scale, mu, rstd, mean, want_b, want_affine, dx_
     pdx, lddx = _rows(dx)
     pres, ldres = _rows(dres) if dres is not None else (None, 0)
     with FOLDS.defer(dev, ws) if defer else _NODEFER:
-        lib.call("adnm_rownorm_bwd", pdy, lddy, px, ldx, _p(w), _p(b), _p(scale), mu.data_ptr(), rstd.data_ptr(), pdx, lddx,
+        lib.call("adnm_rownorm_bwd", pdy, lddy, px, ldx, _p(w), _p(b), _p(scale), _p(mu), rstd.data_ptr(), pdx, lddx,
                  dw.data_ptr(), _p(db), _p(dsc), _p(dsh), pres, ldres, ws.data_ptr(), nb, M, d, int(mean), _dt(x2), _stream())
     return dx, dw, db, dsc, dsh
 

@@ -179,3 +179,122 @@ def guarded_workspaces(monkeypatch):
     with monkeypatch.context() as m:
         m.setattr(ops, "_ws", lambda nbytes, device: g.alloc(nbytes, device))
         yield g
+
+
+# ------------------------------------------------------------------------------------------- poisoned outputs
+# Outputs, saved statistics, intermediates and fresh gradient buffers come from torch.empty / torch.empty_like: a kernel whose grid, tail
+# or early exit skips an element returns whatever the caching allocator handed back — usually the same op's right numbers of a moment ago.
+# Under poisoned_outputs every such tensor arrives filled with a bit pattern.  Two patterns, because an integer or byte output may
+# legitimately hold either value: an element that shows pattern 0 in run 0 AND pattern 1 in run 1 at the same index was written by nobody.
+_OUT_NAN = {torch.float32: (torch.int32, (0x7FC5A5A5, 0x7FC3C3C3)), torch.bfloat16: (torch.int16, (0x7FE5, 0x7FD3)),
+            torch.float16: (torch.int16, (0x7E5A, 0x7EA5)), torch.float64: (torch.int64, (0x7FF8A5A5A5A5A5A5, 0x7FF8C3C3C3C3C3C3))}
+_OUT_INT = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+assert _OUT_NAN[torch.float32][1][0] == _POISON_BITS[torch.float32][1] and _OUT_NAN[torch.bfloat16][1][0] == _POISON_BITS[torch.bfloat16][1]
+WORKSPACE = "workspace"   # the role of an allocation made through ops._ws (tests/test_workspace_contract_gpu.py owns those)
+
+
+def output_pattern(dtype, pattern):
+    """-> (integer view dtype, the pattern as that signed integer): a payload NaN for floating types, 0x5A.. / 0xA5.. bytes for the rest"""
+    if dtype in _OUT_NAN:
+        view, pats = _OUT_NAN[dtype]
+        return view, pats[pattern]
+    size = torch.empty((), dtype=dtype).element_size()   # integers, bool, bytes, fp8
+    v = int.from_bytes(bytes([(0x5A, 0xA5)[pattern]]) * size, "little", signed=True)
+    return _OUT_INT[size], v
+
+
+def pattern_mask(t, pattern):
+    """bool tensor of t's shape: the elements that hold output pattern `pattern`, bit for bit"""
+    view, v = output_pattern(t.dtype, pattern)
+    return t.view(view) == v
+
+
+class PoisonedOutputs:
+    """stands in for the `torch` of a module: every attribute is torch's, except empty / empty_like, which fill what they return"""
+
+    def __init__(self, pattern):
+        assert pattern in (0, 1)
+        self.pattern = pattern
+        self.records = []   # (tensor, site, role, file:line)
+
+    def __getattr__(self, name):
+        return getattr(torch, name)
+
+    def _site(self):
+        """(site, role, where) of the caller outside this file, as GuardedWorkspaces._caller finds it; the role is the target the
+        source line assigns to (`mu` of `mu = torch.empty(...)`), WORKSPACE for ops._ws"""
+        import linecache
+        f = sys._getframe(1)
+        while f is not None and f.f_code.co_filename == __file__:
+            f = f.f_back
+        if f is None:
+            return "?", "", "?"
+        fn, base = f.f_code.co_name, os.path.basename(f.f_code.co_filename)
+        if fn == "_ws" and base == "ops.py":
+            site, _, where = self._outer(f.f_back)
+            return site, WORKSPACE, where
+        return self._outer(f, linecache)
+
+    @staticmethod
+    def _outer(f, linecache=None):
+        if f is None:
+            return "?", "", "?"
+        fn, base, self_ = f.f_code.co_name, os.path.basename(f.f_code.co_filename), f.f_locals.get("ctx", None)
+        cls = type(self_).__name__.replace("Backward", "") if self_ is not None and fn in ("forward", "backward") else ""
+        role = ""
+        if linecache is not None:
+            line = linecache.getline(f.f_code.co_filename, f.f_lineno)
+            head = line.split("torch.empty")[0]
+            role = head.rsplit("=", 1)[0].strip() if "=" in head else ""
+        return f"{base} {cls + '.' if cls else ''}{fn}", role, f"{base}:{f.f_lineno}"
+
+    def _fill(self, t):
+        if t.device.type == "meta":
+            return t
+        if t.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("poisoned_outputs: allocation under stream capture (the fill would become a graph node)")
+        view, v = output_pattern(t.dtype, self.pattern)
+        if t.numel():
+            t.view(view).fill_(v)
+        self.records.append((t,) + self._site())
+        return t
+
+    def empty(self, *args, **kwargs):
+        return self._fill(torch.empty(*args, **kwargs))
+
+    def empty_like(self, *args, **kwargs):
+        return self._fill(torch.empty_like(*args, **kwargs))
+
+
+POISONED_MODULES = ("adnm_hip.ops", "adnm_hip.validate", "adnm_hip.forecast", "adnm_hip.dataio", "adnm_hip.evaluator", "models.ADNssd", "models.Vssd")
+
+
+@contextlib.contextmanager
+def poisoned_outputs(monkeypatch, pattern):
+    """with poisoned_outputs(monkeypatch, 0) as p: torch.empty / torch.empty_like of the POISONED_MODULES return tensors filled with output
+    pattern 0 (or 1); p.records lists (tensor, site, role, file:line) per allocation.  Production code is not changed: the modules see a
+    proxy as their `torch` for the length of the context.  Works on CPU tensors too."""
+    import importlib
+    p = PoisonedOutputs(pattern)
+    with monkeypatch.context() as m:
+        for name in POISONED_MODULES:
+            m.setattr(importlib.import_module(name), "torch", p)
+        yield p
+
+
+def unwritten(rec0, rec1):
+    """{(site, role): (elements, file:line, first flat index)} over the allocation sites of two runs of the same code, one per pattern:
+    the elements that still hold pattern 0 in run 0 and pattern 1 in run 1 at the same index.  Workspaces are skipped."""
+    assert [(r[1], r[2], tuple(r[0].shape), r[0].dtype) for r in rec0] == [(r[1], r[2], tuple(r[0].shape), r[0].dtype) for r in rec1], \
+        "the two runs did not allocate the same tensors in the same order"
+    found = {}
+    for (t0, site, role, where), (t1, _, _, _) in zip(rec0, rec1):
+        if role == WORKSPACE or t0.numel() == 0:
+            continue
+        both = pattern_mask(t0, 0) & pattern_mask(t1, 1)
+        n = int(both.sum())
+        if n:
+            first = int(both.flatten().nonzero()[0])
+            old = found.get((site, role))
+            found[(site, role)] = (n + (old[0] if old else 0), old[1] if old else where, old[2] if old else first)
+    return found
