@@ -3710,6 +3710,100 @@ def label_objects(field, thr, value_scale, min_area=1):
     return out
 
 
+# ======================================================================================= SAL scores from per-object intensity moments (csrc/sal.hip)
+SAL_COLS = 12
+SAL_LIMITS = f"{OBJECTS_LIMITS}, value_scale finite with 1 <= floor(value_scale) <= 255"
+
+
+def sal_spec(sal):
+    """the Validator's `sal` argument -> (min_area, intensity), or None for no SAL scores: None / False -> None, True -> (1, None), an int
+    min_area >= 1 -> (min_area, None), a dict with the keys min_area and / or intensity -> both (intensity: a sequence of integer weights per
+    quantised level, kept as a tuple and checked against a value_scale by sal_weights at its first use; None: the identity).  ValueError on
+    anything else."""
+    if sal is None or sal is False:
+        return None
+    if sal is True:
+        return 1, None
+    if isinstance(sal, (int, np.integer)) and sal >= 1:
+        return int(sal), None
+    if isinstance(sal, dict) and set(sal) <= {"min_area", "intensity"}:
+        area, table = sal.get("min_area", 1), sal.get("intensity")
+        if not isinstance(area, bool) and isinstance(area, (int, np.integer)) and area >= 1:
+            if table is None:
+                return int(area), None
+            if not isinstance(table, (str, bytes, dict)):
+                try:
+                    return int(area), tuple(np.asarray(table).reshape(-1).tolist())
+                except (TypeError, ValueError):
+                    pass
+    raise ValueError(f"sal: None / False, True, an int min_area >= 1 or dict(min_area=, intensity=), got {sal!r}")
+
+
+def sal_levels(value_scale):
+    """-> L = floor(value_scale) + 1, the levels an intensity table covers, as the device forms them from the fp32 value_scale.  ValueError
+    unless value_scale is finite with 1 <= floor(value_scale) <= 255."""
+    try:
+        scale = float(np.float32(value_scale))
+    except (TypeError, ValueError):
+        scale = float("nan")
+    if not 1.0 <= scale < 256.0:
+        raise ValueError(f"sal: value_scale finite with 1 <= floor(value_scale) <= 255, got {value_scale!r}")
+    return int(math.floor(scale)) + 1
+
+
+def sal_weights(intensity, value_scale):
+    """intensity (None, or L integers in 0 .. 65535, L = sal_levels(value_scale)) -> the host uint16 array adnm_valid_sal_accum reads, or None
+    for the identity.  ValueError on a table of another length or with another kind of entry."""
+    L = sal_levels(value_scale)
+    if intensity is None:
+        return None
+    vals = list(intensity)
+    if len(vals) != L or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 65535 for v in vals):
+        raise ValueError(f"sal: intensity is a table of {L} integers in 0..65535 for value_scale {value_scale!r} (one per level 0..{L - 1})")
+    return (ctypes.c_uint16 * L)(*[int(v) for v in vals])
+
+
+def sal_table(truth, pred, thresholds, value_scale, min_area=1, intensity=None):
+    """truth / pred: contiguous fp32 GPU tensors (frames, H, W) or (B, T, H, W) of one shape -> (frames, nthr, SAL_COLS) float64 on the device:
+    per frame and threshold the row of include/adnm_hip.h: adnm_valid_sal_accum — A, L1, S, L2 and L of that one frame pair behind their
+    "defined" flags, and the two flags for objects in one field only.  Objects of fewer than min_area pixels are ignored; intensity: the
+    weight per quantised level (sal_weights), None for w = q.  The one-shot use of adnm_valid_sal_accum (T = frames); validate.sal_entries
+    reads its sums."""
+    _pair("sal_table", truth, pred, (3, 4), "(frames, H, W) or (B, T, H, W)", contiguous=True)
+    thr = [float(t) for t in thresholds]
+    if not 1 <= len(thr) <= 8:
+        raise ValueError("sal_table: 1..8 thresholds")
+    min_area = _min_area("sal_table", min_area)
+    table = sal_weights(intensity, value_scale)
+    H, W = truth.shape[-2:]
+    frames = truth.numel() // (H * W) if H * W else 0
+    return _score_once("adnm_valid_sal_accum", truth, pred, frames, dims=(H, W), query_tail=(len(thr),),
+                       limits=f"sal_table: {frames} frames of {H} x {W} are outside adnm_valid_sal_accum's limits (1 <= frames <= 65535, "
+                       f"{SAL_LIMITS})",
+                       table_shape=(frames, len(thr), SAL_COLS), args=((ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale), min_area, table))
+
+
+def object_moments(field, thr, value_scale, min_area=1, intensity=None):
+    """field: a contiguous fp32 GPU tensor (..., H, W) -> int64 (..., 4, H, W): at the first pixel of every 8-connected object of the event
+    mask q >= thr with at least min_area pixels R = sum w, Q = max w, X = sum w x and Y = sum w y over the object's pixels (x = column,
+    y = row, w = intensity[q], None for w = q), 0 everywhere else (include/adnm_hip.h: adnm_object_moments).  Exact.  (X / R, Y / R) is the
+    object's intensity-weighted centroid; its first pixel p is where label_objects gives p + 1."""
+    f = _frames("object_moments", field, "the field")
+    min_area = _min_area("object_moments", min_area)
+    table = sal_weights(intensity, value_scale)
+    H, W = f.shape[-2:]
+    frames = f.numel() // (H * W) if H * W else 0
+    nb = lib.query("adnm_object_moments_ws_bytes", frames, frames, H, W)
+    if nb < 0:
+        raise RuntimeError(f"object_moments: {frames} frames of {H} x {W} are outside adnm_object_moments' limits (1 <= frames <= 65535, "
+                           f"{SAL_LIMITS})")
+    out = torch.empty(f.shape[:-2] + (4, H, W), dtype=torch.int64, device=f.device)
+    ws = _ws(nb, f.device) if nb else None
+    lib.call("adnm_object_moments", f.data_ptr(), H * W, H * W, out.data_ptr(), float(thr), float(value_scale), min_area, table,
+             None if ws is None else ws.data_ptr(), int(nb), frames, frames, H, W, _stream())
+    return out
+
+
 # ======================================================================================= the output side (csrc/dataio.hip: forecast_render)
 def edges_up_f32(edges):
     """double edges -> float32, each rounded UP to the smallest float >= it: the kernel compares an fp32 value with fp32 edges where

@@ -47,6 +47,11 @@ number of objects, their areas, squared areas, the largest one, the objects the 
 (T, 2, nthr, 23) table; done() reports counts, mean and area-weighted sizes, count and size bias and the object POD / FAR / CSI
 (object_entries).
 
+Validator(..., sal=True) (or sal=min_area, or sal=dict(min_area=, intensity=)) adds the SAL scores (DESIGN.md §4q): csrc/sal.hip::valid_sal_accum
+labels the same objects, gives each the sum, the maximum and the first moments of an intensity weight, forms Structure, Amplitude and Location
+per frame pair and threshold and adds them, with the number of frames each is defined on, into a (T, nthr, 12) table; done() reports the
+means (sal_entries).
+
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
@@ -81,7 +86,7 @@ def baseline_pools(pools):
 
 
 class Part(NamedTuple):
-    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint / objects, `field` the field it scores against the target
+    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint / objects / sal, `field` the field it scores against the target
     (pred: the forecast, last: the last input frame held, adv: that frame advected; None for main), `pools` the (size, stride) pairs of a
     pool part's pass, `offset` its place in the block in doubles"""
     name: str
@@ -96,10 +101,11 @@ class Part(NamedTuple):
         return math.prod(self.shape)
 
 
-def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, objects=None):
+def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, objects=None):
     """-> (the parts of the ONE allocation in their order, its doubles).  The order of the block, and of the launches that fill it, is stated
     here and nowhere else.  pools: (size, stride) pairs; fss: scales; spectrum: (H, W) of the frames, or None; joint: the levels L, or None;
-    objects: min_area, or None."""
+    objects: min_area, or None; sal: what ops.sal_spec returns, or None.  `sal` is passed BY NAME: it stands in front of `objects`, which
+    stays the last parameter, and its position may move when a further table arrives."""
     pools, fss = tuple(pools), tuple(fss)
     base = baseline_pools(pools)
     pooled, scaled = (T, len(base), 4 * nthr), (T, len(fss), 3 * nthr)
@@ -112,7 +118,8 @@ def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, s
             ("advection/fss", "fss", "adv", (), scaled, fss and advection),
             ("spectrum", "spectrum", "pred", (), (T, max(spectrum) // 2, 3) if spectrum else (), spectrum),
             ("joint", "joint", "pred", (), (T, joint, joint), joint),
-            ("objects", "objects", "pred", (), (T, 2, nthr, ops.OBJ_COLS), objects))
+            ("objects", "objects", "pred", (), (T, 2, nthr, ops.OBJ_COLS), objects),
+            ("sal", "sal", "pred", (), (T, nthr, ops.SAL_COLS), sal))
     parts, at = [], 0
     for *head, shape, present in rows:
         if present:
@@ -156,6 +163,11 @@ def joint_doubles(seq_len, value_scale=None):
 def objects_doubles(seq_len, nthr, objects=None):
     """-> doubles of the objects table (T, 2, nthr, ops.OBJ_COLS); objects: what ops.objects_spec takes (None / False for none)"""
     return _doubles(("objects",), seq_len, nthr, objects=ops.objects_spec(objects))[0]
+
+
+def sal_doubles(seq_len, nthr, sal=None):
+    """-> doubles of the SAL table (T, nthr, ops.SAL_COLS); sal: what ops.sal_spec takes (None / False for none)"""
+    return _doubles(("sal",), seq_len, nthr, sal=ops.sal_spec(sal))[0]
 
 
 def _counts(hist):
@@ -288,6 +300,42 @@ def object_entries(rows, frames, thresholds, min_area=1):
     return res
 
 
+def sal_entries(rows, thresholds, spec=(1, None)):
+    """rows: (..., nthr, ops.SAL_COLS) sums (the Validator's table, its sum over the horizon, or a sum of ops.sal_table's rows) and spec =
+    (min_area, intensity) as ops.sal_spec returns it -> the entries of done()["sal"], the leading axes (none, or T) kept in front of every
+    array:
+      "min_area", "intensity" (the table as a tuple, None for the identity); then per threshold key
+        "A", "abs_A" (means over "frames_A", the frames where either field has mass), "S", "abs_S", "L2", "L" (means over "frames_S", the
+        frames where both fields have an object), "L1" (mean over "frames_L1", the frames where both fields have mass), and "frames_A",
+        "frames_L1", "frames_S", "missed_frames" (only the target has an object), "false_frames" (only the forecast has one).
+    A mean over no frame is NaN."""
+    if torch.is_tensor(rows):
+        rows = rows.detach().cpu().numpy()
+    r = np.asarray(rows, dtype=np.float64)
+    nthr = len(thresholds)
+    if r.ndim < 2 or r.shape[-2:] != (nthr, ops.SAL_COLS):
+        raise ValueError(f"sal: rows are (..., {nthr}, {ops.SAL_COLS}) for {nthr} thresholds, got {r.shape}")
+    counts = r[..., [0, 3, 5, 10, 11]]
+    if not (np.isfinite(counts).all() and (counts == np.rint(counts)).all() and (counts >= 0).all()):
+        raise ValueError("sal: columns 0, 3, 5, 10 and 11 of the rows hold frame counts")
+    min_area, intensity = spec
+
+    def mean(col, count):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return _scalar(np.where(count == 0, np.nan, col / count))
+
+    def count(col):
+        return _scalar(col.astype(np.int64))
+    res = {"min_area": int(min_area), "intensity": None if intensity is None else tuple(intensity)}
+    for k, thr in enumerate(thresholds):
+        c = r[..., k, :]
+        n_a, n_l1, n_s = c[..., 0], c[..., 3], c[..., 5]
+        res[_thr_key(thr)] = {"A": mean(c[..., 1], n_a), "abs_A": mean(c[..., 2], n_a), "S": mean(c[..., 6], n_s), "abs_S": mean(c[..., 7], n_s),
+                              "L1": mean(c[..., 4], n_l1), "L2": mean(c[..., 8], n_s), "L": mean(c[..., 9], n_s), "frames_A": count(n_a),
+                              "frames_L1": count(n_l1), "frames_S": count(n_s), "missed_frames": count(c[..., 10]), "false_frames": count(c[..., 11])}
+    return res
+
+
 def _spectrum_entries(sums, cells, wavelength):
     """(..., R, 3) sums P_o, P_f, C and the (..., R)-broadcastable number of coefficients behind each -> the entries of "spectrum"; the
     leading axes (none, or T) are kept"""
@@ -343,7 +391,7 @@ def _lead_scores(rows, thresholds):
 
 
 def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False, spectrum=None,
-              objects=None, joint=None):
+              sal=None, objects=None, joint=None):
     """host: the block (a float64 array laid out as block_parts states for these options; `spectrum` = (H, W), the frame size, `joint` = L,
     the number of levels: include/adnm_hip.h) -> the dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's
     (Shanghai_metrics.py:218-290) as GpuEvaluator.done() states them, from per-frame-index sums; "pooled", "persistence", "advection" and
@@ -354,7 +402,9 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     horizon, NaN where a power is 0), "effective_resolution_px" (the wavelength of the largest r >= 1 with ratio >= 0.5 at every bin 1 .. r;
     inf when bin 1 fails)}, and under "per_lead" the same as (T, R) arrays from the single rows.  `joint`: "joint" = joint_entries of the
     histogram's sum over the horizon, and under "per_lead" joint_entries of the table, every array with a leading T axis.  `objects` (what
-    ops.objects_spec takes): "objects" = object_entries of the table's sum over the horizon, and under "per_lead" object_entries of the table."""
+    ops.objects_spec takes): "objects" = object_entries of the table's sum over the horizon, and under "per_lead" object_entries of the table.
+    `sal` (what ops.sal_spec takes; passed BY NAME, its position in front of `objects` is not part of the interface): "sal" = sal_entries of the
+    table's sum over the horizon, and under "per_lead" sal_entries of the table."""
     nthr, T = len(thresholds), seq_len
     pools, fss = tuple(pools), tuple(fss)
     spectrum = tuple(int(v) for v in spectrum) if spectrum else None
@@ -363,14 +413,14 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     joint = int(joint) if joint else None
     if joint is not None and not ops.MIN_JOINT_LEVELS <= joint <= ops.MAX_JOINT_LEVELS:
         raise ValueError(f"aggregate: joint is the number of levels, {ops.MIN_JOINT_LEVELS}..{ops.MAX_JOINT_LEVELS}, or None; got {joint}")
-    objects = ops.objects_spec(objects)
-    parts, total = block_parts(T, nthr, pools, persistence, fss, advection, spectrum, joint, objects)
+    objects, sal = ops.objects_spec(objects), ops.sal_spec(sal)
+    parts, total = block_parts(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal, objects)
     blk = np.asarray(block, dtype=np.float64)
     if blk.shape != (total,):
         raise ValueError(f"aggregate: a block of {total} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
                          f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + (", advection" if advection else "")
                          + (f", spectrum of {spectrum[0]} x {spectrum[1]} frames" if spectrum else "") + (f", a joint histogram of {joint} levels" if joint else "")
-                         + (", objects" if objects else "")
+                         + (", objects" if objects else "") + (", sal" if sal else "")
                          + f"; got {blk.shape}")
     tabs = {p.name: blk[p.offset:p.offset + p.size].reshape(p.shape) for p in parts}
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
@@ -421,6 +471,8 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
         if objects:
             otab = tabs["objects"]
             yield "objects", object_entries(otab if lead else otab.sum(axis=0), samples if lead else samples * T, thresholds, objects)
+        if sal:
+            yield "sal", sal_entries(tabs["sal"] if lead else tabs["sal"].sum(axis=0), thresholds, sal)
     res.update(optional(False))
     if per_lead:
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -434,7 +486,7 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
 
 class Validator(ForwardClient):
     def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False,
-                 fss=None, advection=None, spectrum=False, objects=None, advection_flow=False, joint=False):
+                 fss=None, advection=None, spectrum=False, objects=None, advection_flow=False, sal=None, joint=False):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -459,6 +511,8 @@ class Validator(ForwardClient):
         self.spectrum, self.joint = bool(spectrum), bool(joint)
         self._levels = ops.joint_levels(self.value_scale) if self.joint else None   # ValueError outside the limits
         self.objects = ops.objects_spec(objects)   # min_area, or None; ValueError on a bad entry
+        self.sal = ops.sal_spec(sal)   # (min_area, intensity), or None; ValueError on a bad entry
+        self._weights = ops.sal_weights(self.sal[1], self.value_scale) if self.sal else None   # the table's first use: ValueError outside the limits
         self._parts, _ = self._table(None)   # the spectrum part comes with the block: its size follows the epoch's frames
         for part in self._parts:
             if len(part.pools) > ops.MAX_POOLS:   # a baseline's pass; pool_pairs has bounded the forecast's
@@ -474,7 +528,7 @@ class Validator(ForwardClient):
     def _table(self, frame):
         """block_parts for this Validator's options; frame: (H, W) of the epoch, which sizes the spectrum part (None: without that part)"""
         return block_parts(self.seq_len, len(self.thresholds), self.pools, self.persistence, self.fss, bool(self.advection),
-                           frame if self.spectrum else None, self._levels, self.objects)
+                           frame if self.spectrum else None, self._levels, self.sal, self.objects)
 
     def _block_for(self, device):
         """ONE allocation, the parts of block_parts; done() reduces it with one all-reduce"""
@@ -530,6 +584,9 @@ class Validator(ForwardClient):
                 ws = ent["ws_joint"]
                 lib.call("adnm_valid_joint_accum", *src, ent["tgt"].data_ptr(), table, self.value_scale, None if ws is None else ws.data_ptr(),
                          0 if ws is None else ws.numel(), B * T, T, H * W, stream)
+            elif part.kind == "sal":
+                lib.call("adnm_valid_sal_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, self.sal[0], self._weights,
+                         ent["ws_sal"].data_ptr(), ent["ws_sal"].numel(), B * T, T, H, W, stream)
             else:   # objects
                 ws = ent["ws_objects"]
                 lib.call("adnm_valid_objects_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, self.objects,
@@ -555,7 +612,7 @@ class Validator(ForwardClient):
         ws_ssim = None
         if self.ssim and H > 10 and W > 10:   # 11 x 11 windows need a valid region; smaller frames: SSIM is None
             ws_ssim = torch.empty(max(int(lib.query("adnm_valid_ssim_accum_ws_bytes", B * T, T, H, W, nthr)), 16), dtype=torch.uint8, device=dev)
-        ws_pool = ws_fss = adv = motion = flow = ws_trec = ws_spectrum = ws_joint = ws_objects = None
+        ws_pool = ws_fss = adv = motion = flow = ws_trec = ws_spectrum = ws_joint = ws_objects = ws_sal = None
         passes = [p.pools for p in self._parts if p.kind == "pool"]
         if passes:   # the passes follow one another on one stream: one workspace
             ws_pool = workspace("adnm_valid_pool_accum_ws_bytes", [(B * T, T, H, W, nthr, ops.pool_table(pools), len(pools)) for pools in passes],
@@ -591,8 +648,11 @@ class Validator(ForwardClient):
             ws_objects = workspace("adnm_valid_objects_accum_ws_bytes", [(B * T, T, H, W, nthr)],
                                    f"objects on {B * T} frames of {H} x {W} are outside adnm_valid_objects_accum's limits (frames <= 65535, "
                                    f"{ops.OBJECTS_LIMITS})", floor=0)
+        if self.sal:
+            ws_sal = workspace("adnm_valid_sal_accum_ws_bytes", [(B * T, T, H, W, nthr)],
+                               f"sal on {B * T} frames of {H} x {W} is outside adnm_valid_sal_accum's limits (frames <= 65535, {ops.SAL_LIMITS})")
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=ws, ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss,
-                   ws_spectrum=ws_spectrum, ws_joint=ws_joint, ws_objects=ws_objects, adv=adv, motion=motion, flow=flow, ws_trec=ws_trec,
+                   ws_spectrum=ws_spectrum, ws_joint=ws_joint, ws_objects=ws_objects, ws_sal=ws_sal, adv=adv, motion=motion, flow=flow, ws_trec=ws_trec,
                    loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
         self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
@@ -689,7 +749,9 @@ class Validator(ForwardClient):
         joint: plus "joint" {"levels", "histogram", "marginal_target", "marginal_forecast", "curves", "conditional_mean", "qq", "correlation",
         "mean_error"} (joint_entries of the table summed over the horizon) and "per_lead"/"joint", the same with a leading T axis.
         objects: plus "objects" {"min_area", thr: {"target", "forecast", "count_bias", "size_bias", "object_POD", "object_FAR", "object_CSI",
-        "size_bin_edges"}} (object_entries of the table summed over the horizon) and "per_lead"/"objects", the same with a leading T axis."""
+        "size_bin_edges"}} (object_entries of the table summed over the horizon) and "per_lead"/"objects", the same with a leading T axis.
+        sal: plus "sal" {"min_area", "intensity", thr: {"A", "abs_A", "S", "abs_S", "L1", "L2", "L", "frames_A", "frames_L1", "frames_S",
+        "missed_frames", "false_frames"}} (sal_entries of the table summed over the horizon) and "per_lead"/"sal", the same with a leading T axis."""
         if self._block is None or self._frame is None:
             raise RuntimeError("Validator.done: no batch since the last reset")
         blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
@@ -697,7 +759,8 @@ class Validator(ForwardClient):
         H, W = self._frame
         area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
         res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead,
-                        fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None, joint=self._levels, objects=self.objects)
+                        fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None, joint=self._levels, objects=self.objects,
+                        sal=dict(min_area=self.sal[0], intensity=self.sal[1]) if self.sal else None)
         if self.advection_flow:
             res["advection"]["scheme"] = "flow"
         if reset:

@@ -937,6 +937,55 @@ int64_t adnm_label_objects_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_
 int adnm_label_objects(const float* src, int64_t sample_stride, int64_t frame_stride, void* labels_i32, float thr, float value_scale,
                        int64_t min_area, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
 
+/* SAL scores (Structure, Amplitude, Location; Wernli et al. 2008) from per-object intensity moments.  The reference has no
+ * object score; the yardstick is scipy.ndimage on the CPU (tests/sal_ref.py).  Field, event, object, label and min_area are those of the
+ * object scores above.
+ *   weight        w = intensity[q], intensity_host a HOST table of floor(value_scale) + 1 entries of uint16_t, read at call time and passed by
+ *                 value (the call can be captured); NULL is the identity w = q.  This needs value_scale finite with 1 <= floor(value_scale)
+ *                 <= 255: a level fits a byte.
+ *   coordinates   x = column, y = row; the domain scale is d = sqrt(H^2 + W^2).
+ *   whole field   M = SUM w, Mx = SUM w x, My = SUM w y over the frame (whatever the threshold), the centre c = (Mx / M, My / M).
+ *   per object    R = SUM w, Q = max w, X = SUM w x, Y = SUM w y over the pixels of an object of at least min_area pixels; an object with
+ *                 R = 0 (only with a zero weight) contributes nothing and does not count as an object.  R < 2^32, X and Y < 2^40: all exact.
+ *   per frame pair and threshold, in double, o = target and f = forecast:
+ *     A  = (M_f - M_o) / (0.5 (M_f + M_o))                      defined when M_o + M_f > 0
+ *     L1 = |c_f - c_o| / d                                      defined when M_o > 0 and M_f > 0
+ *     V  = SUM_n R_n (R_n / Q_n) / SUM_n R_n                    per field, with at least one object
+ *     r  = SUM_n R_n |(X_n / R_n, Y_n / R_n) - c| / SUM_n R_n   per field, with at least one object
+ *     S  = (V_f - V_o) / (0.5 (V_f + V_o)),  L2 = 2 |r_f - r_o| / d,  L = L1 + L2     defined when both fields have an object
+ * table: adnm_valid_sal_block_bytes(T, nthr) = 8 * T * nthr * 12 bytes, 8-byte aligned device memory, zeroed by the caller, all double,
+ *   shape (T, nthr, 12): [t][k], summed over every sample so far of the frames f with f mod T = t.  No header.  Columns:
+ *     [0] frames with A defined   [1] SUM A   [2] SUM |A|   [3] frames with L1 defined   [4] SUM L1   [5] frames with S defined   [6] SUM S
+ *     [7] SUM |S|   [8] SUM L2   [9] SUM L over the frames of [5]   [10] frames where only the target has an object   [11] frames where only
+ *     the forecast has one.  A and L1 do not depend on the threshold and are repeated in every threshold's row.
+ * adnm_valid_sal_accum ADDS a batch; pred, target, the strides and thresholds_host as in adnm_valid_objects_accum.  Two launches.  The first
+ *   runs one workgroup of 1024 lanes per (frame, threshold): it stages the event bits of both fields and the level q as one byte per pixel
+ *   in LDS (floats are read once), labels one field at a time with the device code of adnm_label_objects, lets the first pixel of every run
+ *   add the run's SUM w, max w, SUM w x and SUM w y to its object's record with integer atomics (record (y / 2) * ceil(W / 2) + x / 2 of the
+ *   object's first pixel: two first pixels never share an aligned 2 x 2 cell), reduces the objects in double in a fixed order (a lane's
+ *   objects ascending, a shuffle tree over the lanes, the waves ascending) and writes the item's 12 entries to ws.  The second adds, per
+ *   (t, k, column), the batch's entries, samples ascending from 0.0, and adds that one sum to the table.  No floating-point atomics: the
+ *   same bits on every run; a forecast that IS the target gives exact zeros.  Records and words live in LDS where they fit (H * W up to
+ *   about 13 000), the records in ws up to about 26 000 pixels, both in ws above.
+ *   ws            adnm_valid_sal_accum_ws_bytes = 8 * frames * nthr * 12 for the item rows, plus, per workgroup that needs a slice (at most
+ *                 256), 24 bytes per record and 4 per pixel: at most 16 * H * W + 16 bytes.  Never NULL; what it held does not matter.
+ * adnm_object_moments writes int64 (frames, 4, H, W) of ONE field at ONE threshold with the same device code (one workgroup per frame): R, Q,
+ *   X, Y at the first pixel of every object of at least min_area pixels, 0 everywhere else; every element is written.  Frame f = b*T + t
+ *   starts at src + b*sample_stride + t*frame_stride.  adnm_object_moments_ws_bytes: the slices alone (0: ws may be NULL).
+ * Limits, refused before any launch (ADNM_EINVAL): a null pointer other than intensity_host (and, for adnm_object_moments, ws when the query
+ *   is 0); pred / target / src not 4-byte or table / moments / ws not 8-byte aligned; nthr outside 1..8; min_area < 1; value_scale outside
+ *   the range above; T < 1 or not dividing frames; frames > 65535; H or W < 1; H * W > 65 536; a frame stride neither 0 nor >= H*W; a sample
+ *   stride < 0; ws_bytes below the query.  The queries return -1. */
+int64_t adnm_valid_sal_block_bytes(int64_t T, int64_t nthr);
+int64_t adnm_valid_sal_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr);
+int adnm_valid_sal_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                         const float* thresholds_host, int64_t nthr, float value_scale, int64_t min_area, const uint16_t* intensity_host,
+                         void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
+int64_t adnm_object_moments_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W);
+int adnm_object_moments(const float* src, int64_t sample_stride, int64_t frame_stride, void* moments_i64, float thr, float value_scale,
+                        int64_t min_area, const uint16_t* intensity_host, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t H,
+                        int64_t W, adnm_stream_t stream);
+
 /* The output side (pic_results.py:104-184 of the reference): a forecast as the bytes a consumer keeps, in ONE launch.
  * adnm_forecast_render: pred contiguous fp32 (B, T, H, W), 4-byte aligned.  fields: (B, T, H, W) uint8 or NULL.  strip: (B, H, Ws, 4) uint8
  *   (RGBA, 4-byte aligned) or NULL, Ws = n*W + (n-1)*gap, holding the n = ceil((T - frame_start) / frame_step) frames frame_start,
