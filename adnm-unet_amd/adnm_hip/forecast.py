@@ -14,6 +14,7 @@ What leaves the device is 1 + 4 n / T bytes per pixel (n of T frames selected) i
 
 The value rule is stated in include/adnm_hip.h (adnm_forecast_render); inside the uint8 range it is pic_results.py's, byte for byte
 (tests/golden/forecast_render_*.npz are matplotlib's own output).  Figure layout beyond the strip and LPIPS are not reproduced."""
+import ctypes
 import json
 import os
 import struct
@@ -109,17 +110,20 @@ def save_png(path, rgba_u8):
 class Forecast:
     """What a Forecaster call returns: .pred (fp32, the model's output in the model's own shape: (B, T, 1, H, W) from create_ADNMUNet's
     models, (B, T, H, W) from a model that emits that; for render() the tensor it was given), .fields (uint8 (B, T, H, W)),
-    .strip (uint8 (B, H, Ws, 4))."""
-    __slots__ = ("pred", "fields", "strip")
+    .strip (uint8 (B, H, Ws, 4)), and .prob (fp32 (K, B, T, H, W), the neighbourhood probability per threshold of a Forecaster with
+    probability=; None otherwise)."""
+    __slots__ = ("pred", "fields", "strip", "prob")
 
-    def __init__(self, pred, fields, strip):
-        self.pred, self.fields, self.strip = pred, fields, strip
+    def __init__(self, pred, fields, strip, prob=None):
+        self.pred, self.fields, self.strip, self.prob = pred, fields, strip, prob
 
 
 class Forecaster(ForwardClient):
-    def __init__(self, model, palette, pixel_scale=90.0, size=None, in_frames=5, frame_start=0, frame_step=1, gap=10):
+    def __init__(self, model, palette, pixel_scale=90.0, size=None, in_frames=5, frame_start=0, frame_step=1, gap=10, probability=None):
         """pixel_scale: pic_results.py's PIXEL_SCALE; None or 0 bins the float itself (the LAPS form).  size: the model's input edge,
-        needed for raw uint8 input only.  frame_start / frame_step: the frames of the strip (even_index_only=True is 1, 2)."""
+        needed for raw uint8 input only.  frame_start / frame_step: the frames of the strip (even_index_only=True is 1, 2).
+        probability: dict(thresholds=(35, 40), scale=9) adds Forecast.prob, the fraction of the scale x scale window at or above each
+        threshold on the field quantised with pixel_scale: one adnm_neighbour_prob launch behind the render, in the graph."""
         if not isinstance(palette, Palette):
             raise RuntimeError(f"Forecaster: palette must be a forecast.Palette, got {type(palette).__name__}")
         self.model, self.palette = model, palette
@@ -128,6 +132,16 @@ class Forecaster(ForwardClient):
         self.frame_start, self.frame_step, self.gap = int(frame_start), int(frame_step), int(gap)
         if not (self.pixel_scale >= 0.0 and np.isfinite(self.pixel_scale)) or self.frame_start < 0 or self.frame_step < 1 or self.gap < 0:
             raise ValueError("Forecaster: pixel_scale >= 0, frame_start >= 0, frame_step >= 1, gap >= 0")
+        self.probability = None             # (thresholds as the entry point reads them, K, scale)
+        if probability is not None:
+            if not isinstance(probability, dict) or set(probability) != {"thresholds", "scale"}:
+                raise ValueError(f"Forecaster: probability is dict(thresholds=, scale=), got {probability!r}")
+            if not self.pixel_scale > 0.0:
+                raise ValueError("Forecaster: probability= compares the field quantised with pixel_scale, which must be > 0 (not None or 0)")
+            thr, scales = [float(t) for t in probability["thresholds"]], ops.fss_scales(probability["scale"])
+            if len(scales) != 1 or not 1 <= len(thr) <= 8:
+                raise ValueError("Forecaster: probability takes one scale and 1..8 thresholds")
+            self.probability = ((ctypes.c_float * len(thr))(*thr), len(thr), scales[0])
         self.out_frames = None              # T of the model's output, known after the first call
         self._fwd = GraphedForward(model, client=self, keep_quant=True)
         self._warm = set()                  # the devices the render kernel has run on
@@ -139,6 +153,10 @@ class Forecaster(ForwardClient):
         if x.device not in self._warm:
             for w in (4, 1):
                 ops.forecast_render_tables(torch.zeros((1, 1, 1, w), dtype=torch.float32, device=x.device), self.palette._c, self.pixel_scale, gap=0)
+                if self.probability:   # likewise the probability kernel, aligned and not
+                    ops.neighbour_prob_into(torch.zeros((1, 1, 1, w), dtype=torch.float32, device=x.device),
+                                            torch.empty((self.probability[1], 1, 1, 1, w), dtype=torch.float32, device=x.device), *self.probability[:2],
+                                            self.pixel_scale, self.probability[2])
             self._warm.add(x.device)
         raw = x.dtype == torch.uint8
         ent["xin"] = torch.empty((x.shape[0], x.shape[1], 1, self.size, self.size), dtype=torch.float32, device=x.device) if raw else None
@@ -159,18 +177,21 @@ class Forecaster(ForwardClient):
             raise RuntimeError(f"Forecaster: frame_start {self.frame_start} outside the model's {T} output frames")
         ent["fields"] = torch.empty((B, T, H, W), dtype=torch.uint8, device=out.device)
         ent["strip"] = torch.empty((B, H, ops.strip_width(T, W, self.frame_start, self.frame_step, self.gap), 4), dtype=torch.uint8, device=out.device)
+        ent["prob"] = torch.empty((self.probability[1], B, T, H, W), dtype=torch.float32, device=out.device) if self.probability else None
 
     def after(self, ent, sx, out):
         ent["keep"] = pred = (out.squeeze(2) if out.dim() == 5 else out).contiguous()   # (a copy made here belongs to the graph's pool and is kept with it)
         ops.forecast_render_into(pred, ent["fields"], ent["strip"], self.palette._c, self.pixel_scale, self.frame_start, self.frame_step, self.gap)
-        ent["res"] = Forecast(out, ent["fields"], ent["strip"])
+        if self.probability:
+            ops.neighbour_prob_into(pred, ent["prob"], *self.probability[:2], self.pixel_scale, self.probability[2])
+        ent["res"] = Forecast(out, ent["fields"], ent["strip"], ent["prob"])
         self.out_frames = out.shape[1]
 
     # ---- the public surface
     @torch.no_grad()
     def __call__(self, x):
         """x: fp32 (B, in_frames, 1, S, S), or raw uint8 (B, in_frames, H0, W0) radar frames (then / 255 and the bilinear resize to
-        `size` run inside the same graph), on the GPU.  -> Forecast(pred, fields, strip): STATIC buffers of the graph of this input
+        `size` run inside the same graph), on the GPU.  -> Forecast(pred, fields, strip, prob): STATIC buffers of the graph of this input
         shape, valid until the next call with that shape (copy what has to last)."""
         if not (torch.is_tensor(x) and x.is_cuda):
             raise RuntimeError("Forecaster runs on GPU tensors only (there is no CPU path here)")

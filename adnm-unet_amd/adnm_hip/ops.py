@@ -3394,6 +3394,66 @@ def fss_sums(truth, pred, thresholds, value_scale, scales):
                        table_shape=(frames, len(ns), 3 * len(thr)), args=((ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale), tab, len(ns)))
 
 
+# ======================================================================================= neighbourhood probability (csrc/neighbour.hip: valid_nprob_accum)
+def nprob_layout(scales):
+    """scales (what fss_scales takes) -> (((at_o0, at_o1), ...) per scale, S): a (t, k) row of adnm_valid_nprob_accum's table holds S doubles,
+    the scales in the order given, each as [o = 0: c = 0 .. n^2][o = 1: c = 0 .. n^2] (include/adnm_hip.h).  The layout is stated here and
+    nowhere else on the Python side."""
+    at, out = 0, []
+    for n in fss_scales(scales):
+        out.append((at, at + n * n + 1))
+        at += 2 * (n * n + 1)
+    return tuple(out), at
+
+
+def neighbour_hist(truth, pred, thresholds, value_scale, scales):
+    """truth / pred: fp32 GPU tensors (..., H, W) of the same shape -> int64 (frames, nthr, S) on the device, S and the place of each scale
+    from nprob_layout(scales): per frame, threshold and scale n (odd, <= 33) the number of pixels whose truth has the event bit o and whose
+    n x n window (centred, zeros outside the frame) holds c forecast events, on the fields quantised as adnm_eval_counts quantises them.
+    Exact.  The one-shot use of adnm_valid_nprob_accum (T = frames); validate.nprob_entries reads it."""
+    _pair("neighbour_hist", truth, pred, None, "(..., H, W)")
+    ns = fss_scales(scales)
+    thr = [float(t) for t in thresholds]
+    if not ns or not 1 <= len(thr) <= 8:
+        raise ValueError("neighbour_hist: 1..4 scales and 1..8 thresholds")
+    H, W = truth.shape[-2:]
+    t, p = truth.contiguous(), pred.contiguous()
+    frames = t.numel() // (H * W) if H * W else 0
+    tab, S = fss_table(ns), nprob_layout(ns)[1]
+    out = _score_once("adnm_valid_nprob_accum", t, p, frames, dims=(H, W), query_tail=(len(thr), tab, len(ns)),
+                      limits=f"neighbour_hist: {frames} frames of {H} x {W} are outside adnm_valid_nprob_accum's limits (1 <= frames <= 65535, "
+                      "H and W < 32768, H*W < 2^24)",
+                      table_shape=(frames, len(thr), S), args=((ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale), tab, len(ns)))
+    return out.to(torch.int64)   # integers in doubles: exact
+
+
+def neighbour_prob_into(field, out, thresholds_c, nthr, value_scale, scale):
+    """the launch alone, on tensors the caller owns (field: fp32 contiguous (..., H, W); out: fp32 contiguous, nthr times field's elements)
+    and on the thresholds as a host float array: what a captured graph's body calls"""
+    H, W = field.shape[-2:]
+    lib.call("adnm_neighbour_prob", field.data_ptr(), out.data_ptr(), thresholds_c, int(nthr), float(value_scale), int(scale),
+             field.numel() // (H * W), H, W, _stream())
+
+
+def neighbour_prob(field, thresholds, value_scale, scale):
+    """field: fp32 GPU tensor (B, T, H, W) or (B, T, 1, H, W) -> fp32 (K, B, T, H, W): per threshold the fraction of the scale x scale window
+    (odd, <= 33; centred, zeros outside the frame, the denominator always scale^2) at or above it on the quantised field, the neighbourhood
+    probability of the event.  out[k] is contiguous (ops.forecast_render with pixel_scale=None colours it).  adnm_neighbour_prob."""
+    if not torch.is_tensor(field):
+        raise RuntimeError("neighbour_prob: needs a GPU tensor")
+    _need_gpu(field)
+    if field.dtype != torch.float32 or field.dim() not in (4, 5) or (field.dim() == 5 and field.shape[2] != 1) or field.numel() == 0:
+        _unsupported("neighbour_prob", f"takes a non-empty fp32 (B, T, H, W) or (B, T, 1, H, W), got {field.dtype} {tuple(field.shape)}")
+    ns = fss_scales(scale)
+    thr = [float(t) for t in thresholds]
+    if len(ns) != 1 or not 1 <= len(thr) <= 8:
+        raise ValueError("neighbour_prob: one scale and 1..8 thresholds")
+    f = (field.squeeze(2) if field.dim() == 5 else field).contiguous()
+    out = torch.empty((len(thr),) + tuple(f.shape), dtype=torch.float32, device=f.device)
+    neighbour_prob_into(f, out, (ctypes.c_float * len(thr))(*thr), len(thr), value_scale, ns[0])
+    return out
+
+
 # ======================================================================================= block-matched motion and advection (csrc/advect.hip)
 TREC_BLOCKS, MAX_TREC_RADIUS = (8, 16, 32), 8
 

@@ -52,6 +52,11 @@ labels the same objects, gives each the sum, the maximum and the first moments o
 per frame pair and threshold and adds them, with the number of frames each is defined on, into a (T, nthr, 12) table; done() reports the
 means (sal_entries).
 
+Validator(..., nprob=(1, 5, 17, 33)) (or nprob=True for the fss scales) adds the neighbourhood exceedance probability's verification
+(DESIGN.md §4r): csrc/neighbour.hip::valid_nprob_accum counts, per frame index, threshold and scale, the pixels by (observed event bit,
+forecast events in the n x n window) into a (T, nthr, S) table of integers; done() reports the Brier score and its decomposition, the ROC
+curve and its area and the reliability diagram of p = count / n^2 (nprob_entries).
+
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
@@ -86,7 +91,7 @@ def baseline_pools(pools):
 
 
 class Part(NamedTuple):
-    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint / objects / sal, `field` the field it scores against the target
+    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint / objects / sal / nprob, `field` the field it scores against the target
     (pred: the forecast, last: the last input frame held, adv: that frame advected; None for main), `pools` the (size, stride) pairs of a
     pool part's pass, `offset` its place in the block in doubles"""
     name: str
@@ -101,12 +106,13 @@ class Part(NamedTuple):
         return math.prod(self.shape)
 
 
-def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, objects=None):
+def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, objects=None):
     """-> (the parts of the ONE allocation in their order, its doubles).  The order of the block, and of the launches that fill it, is stated
     here and nowhere else.  pools: (size, stride) pairs; fss: scales; spectrum: (H, W) of the frames, or None; joint: the levels L, or None;
     objects: min_area, or None; sal: what ops.sal_spec returns, or None.  `sal` is passed BY NAME: it stands in front of `objects`, which
-    stays the last parameter, and its position may move when a further table arrives."""
-    pools, fss = tuple(pools), tuple(fss)
+    stays the last parameter, and its position may move when a further table arrives.  nprob: the scales of the neighbourhood probability's
+    histogram, or None; passed BY NAME as well, for the same reason (its table is the last one whatever its place here)."""
+    pools, fss, nprob = tuple(pools), tuple(fss), tuple(nprob or ())
     base = baseline_pools(pools)
     pooled, scaled = (T, len(base), 4 * nthr), (T, len(fss), 3 * nthr)
     rows = (("main", "main", None, (), (HEADER + T * (4 * nthr + 3),), True),
@@ -119,7 +125,8 @@ def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, s
             ("spectrum", "spectrum", "pred", (), (T, max(spectrum) // 2, 3) if spectrum else (), spectrum),
             ("joint", "joint", "pred", (), (T, joint, joint), joint),
             ("objects", "objects", "pred", (), (T, 2, nthr, ops.OBJ_COLS), objects),
-            ("sal", "sal", "pred", (), (T, nthr, ops.SAL_COLS), sal))
+            ("sal", "sal", "pred", (), (T, nthr, ops.SAL_COLS), sal),
+            ("nprob", "nprob", "pred", (), (T, nthr, ops.nprob_layout(nprob)[1]), nprob))
     parts, at = [], 0
     for *head, shape, present in rows:
         if present:
@@ -168,6 +175,11 @@ def objects_doubles(seq_len, nthr, objects=None):
 def sal_doubles(seq_len, nthr, sal=None):
     """-> doubles of the SAL table (T, nthr, ops.SAL_COLS); sal: what ops.sal_spec takes (None / False for none)"""
     return _doubles(("sal",), seq_len, nthr, sal=ops.sal_spec(sal))[0]
+
+
+def nprob_doubles(seq_len, nthr, nprob=None):
+    """-> doubles of the neighbourhood probability's table (T, nthr, S), S = ops.nprob_layout(scales)[1]; nprob: the scales (None / () for none)"""
+    return _doubles(("nprob",), seq_len, nthr, nprob=ops.fss_scales(nprob))[0]
 
 
 def _counts(hist):
@@ -336,6 +348,66 @@ def sal_entries(rows, thresholds, spec=(1, None)):
     return res
 
 
+def nprob_entries(rows, scales, thresholds, bins=10):
+    """rows: (..., nthr, S) integer counts laid out as ops.nprob_layout(scales) states (ops.neighbour_hist's tensor summed over its frames, the
+    Validator's table or its sum over the horizon) -> the entries of done()["nprob"], {n: {thr: {...}}}, the leading axes (none, or T) kept
+    in front of every array.  The forecast is p = c / n^2, c = 0 .. n^2, the observation o the event bit at the pixel; N = the counts:
+      "histogram" int64 (2, n^2 + 1), [o][c]; "base_rate" SUM N[1] / SUM N;
+      "brier" SUM N (p - o)^2 / SUM N; "reliability", "resolution", "uncertainty": Murphy's decomposition over the n^2 + 1 distinct forecast
+        values (exact for this discrete forecast: brier = reliability - resolution + uncertainty); "brier_skill" 1 - brier / uncertainty;
+      "roc" {"pofd", "pod"}: the decision "warn when c >= c*" for c* = 0 .. n^2, then the point (0, 0): n^2 + 2 points from (1, 1) down;
+        "roc_area" the trapezoid under them;
+      "reliability_diagram" {"edges" (bins + 1), "count", "forecast_mean", "observed_frequency" (bins)}: equal-width bins of p, bin b holding
+        b / bins <= p < (b + 1) / bins (compared in integers), the last one closed on the right.
+    A division by zero gives NaN."""
+    if torch.is_tensor(rows):
+        rows = rows.detach().cpu().numpy()
+    r = np.asarray(rows)
+    scales, nthr, bins = ops.fss_scales(scales), len(thresholds), int(bins)
+    layout, S = ops.nprob_layout(scales)
+    if not scales or r.ndim < 2 or r.shape[-2:] != (nthr, S):
+        raise ValueError(f"nprob: rows are (..., {nthr}, {S}) for {nthr} thresholds and scales {scales}, got {r.shape}")
+    if bins < 1:
+        raise ValueError(f"nprob: bins >= 1, got {bins}")
+    if r.dtype.kind == "f":
+        if not (np.isfinite(r).all() and (r == np.rint(r)).all()):
+            raise ValueError("nprob: the rows hold integer counts")
+    elif r.dtype.kind not in "iu":
+        raise ValueError(f"nprob: the rows hold integer counts, got {r.dtype}")
+    r = r.astype(np.int64)
+
+    def ratio(a, b):
+        """a / b in float64, NaN where b is 0"""
+        a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return _scalar(np.where(b == 0, np.nan, a / b))
+
+    def entry(n0, n1, n):
+        """n0, n1: (..., n^2 + 1) counts of the pixels without / with the observed event per window count"""
+        c = np.arange(n * n + 1)
+        p = c / float(n * n)
+        both = (n0 + n1).astype(np.float64)
+        total, events, quiet = both.sum(axis=-1), n1.sum(axis=-1), n0.sum(axis=-1)
+        base = np.asarray(ratio(events, total))
+        freq = np.asarray(ratio(n1, both))   # the observed frequency given the forecast value; NaN where the value never occurs
+        rel = np.where(both == 0, 0.0, both * (p - freq) ** 2).sum(axis=-1)
+        res = np.where(both == 0, 0.0, both * (freq - base[..., None]) ** 2).sum(axis=-1)
+        brier, unc = np.asarray(ratio((n0 * p ** 2 + n1 * (p - 1.0) ** 2).sum(axis=-1), total)), base * (1.0 - base)
+        zero = np.zeros(n0.shape[:-1] + (1,))
+        pod = np.concatenate([np.asarray(ratio(_tail_sums(n1, -1), events[..., None])), zero], axis=-1)
+        pofd = np.concatenate([np.asarray(ratio(_tail_sums(n0, -1), quiet[..., None])), zero], axis=-1)
+        area = ((pofd[..., :-1] - pofd[..., 1:]) * (pod[..., :-1] + pod[..., 1:]) / 2.0).sum(axis=-1)
+        member = (np.minimum(c * bins // (n * n), bins - 1)[:, None] == np.arange(bins)).astype(np.float64)   # (n^2 + 1, bins), one bin per value
+        count = both @ member
+        return {"histogram": np.stack([n0, n1], axis=-2), "base_rate": _scalar(base), "brier": _scalar(brier),
+                "reliability": ratio(rel, total), "resolution": ratio(res, total), "uncertainty": _scalar(unc),
+                "brier_skill": _scalar(1.0 - np.asarray(ratio(brier, unc))), "roc": {"pofd": pofd, "pod": pod}, "roc_area": _scalar(area),
+                "reliability_diagram": {"edges": np.linspace(0.0, 1.0, bins + 1), "count": count.astype(np.int64),
+                                        "forecast_mean": ratio((both * p) @ member, count), "observed_frequency": ratio(n1.astype(np.float64) @ member, count)}}
+    return {n: {_thr_key(thr): entry(r[..., k, a0:a0 + n * n + 1], r[..., k, a1:a1 + n * n + 1], n) for k, thr in enumerate(thresholds)}
+            for n, (a0, a1) in zip(scales, layout)}
+
+
 def _spectrum_entries(sums, cells, wavelength):
     """(..., R, 3) sums P_o, P_f, C and the (..., R)-broadcastable number of coefficients behind each -> the entries of "spectrum"; the
     leading axes (none, or T) are kept"""
@@ -391,7 +463,7 @@ def _lead_scores(rows, thresholds):
 
 
 def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False, spectrum=None,
-              sal=None, objects=None, joint=None):
+              sal=None, nprob=None, objects=None, joint=None):
     """host: the block (a float64 array laid out as block_parts states for these options; `spectrum` = (H, W), the frame size, `joint` = L,
     the number of levels: include/adnm_hip.h) -> the dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's
     (Shanghai_metrics.py:218-290) as GpuEvaluator.done() states them, from per-frame-index sums; "pooled", "persistence", "advection" and
@@ -404,7 +476,8 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     histogram's sum over the horizon, and under "per_lead" joint_entries of the table, every array with a leading T axis.  `objects` (what
     ops.objects_spec takes): "objects" = object_entries of the table's sum over the horizon, and under "per_lead" object_entries of the table.
     `sal` (what ops.sal_spec takes; passed BY NAME, its position in front of `objects` is not part of the interface): "sal" = sal_entries of the
-    table's sum over the horizon, and under "per_lead" sal_entries of the table."""
+    table's sum over the horizon, and under "per_lead" sal_entries of the table.  `nprob` (the scales; BY NAME): "nprob" = nprob_entries of the
+    table's sum over the horizon, and under "per_lead" nprob_entries of the table."""
     nthr, T = len(thresholds), seq_len
     pools, fss = tuple(pools), tuple(fss)
     spectrum = tuple(int(v) for v in spectrum) if spectrum else None
@@ -413,14 +486,14 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     joint = int(joint) if joint else None
     if joint is not None and not ops.MIN_JOINT_LEVELS <= joint <= ops.MAX_JOINT_LEVELS:
         raise ValueError(f"aggregate: joint is the number of levels, {ops.MIN_JOINT_LEVELS}..{ops.MAX_JOINT_LEVELS}, or None; got {joint}")
-    objects, sal = ops.objects_spec(objects), ops.sal_spec(sal)
-    parts, total = block_parts(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal, objects)
+    objects, sal, nprob = ops.objects_spec(objects), ops.sal_spec(sal), ops.fss_scales(nprob)
+    parts, total = block_parts(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, objects=objects)
     blk = np.asarray(block, dtype=np.float64)
     if blk.shape != (total,):
         raise ValueError(f"aggregate: a block of {total} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
                          f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + (", advection" if advection else "")
                          + (f", spectrum of {spectrum[0]} x {spectrum[1]} frames" if spectrum else "") + (f", a joint histogram of {joint} levels" if joint else "")
-                         + (", objects" if objects else "") + (", sal" if sal else "")
+                         + (", objects" if objects else "") + (", sal" if sal else "") + (f", nprob {nprob}" if nprob else "")
                          + f"; got {blk.shape}")
     tabs = {p.name: blk[p.offset:p.offset + p.size].reshape(p.shape) for p in parts}
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
@@ -473,6 +546,8 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
             yield "objects", object_entries(otab if lead else otab.sum(axis=0), samples if lead else samples * T, thresholds, objects)
         if sal:
             yield "sal", sal_entries(tabs["sal"] if lead else tabs["sal"].sum(axis=0), thresholds, sal)
+        if nprob:
+            yield "nprob", nprob_entries(tabs["nprob"] if lead else tabs["nprob"].sum(axis=0), nprob, thresholds)
     res.update(optional(False))
     if per_lead:
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -486,7 +561,7 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
 
 class Validator(ForwardClient):
     def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False,
-                 fss=None, advection=None, spectrum=False, objects=None, advection_flow=False, sal=None, joint=False):
+                 fss=None, advection=None, spectrum=False, objects=None, advection_flow=False, sal=None, nprob=None, joint=False):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -513,6 +588,9 @@ class Validator(ForwardClient):
         self.objects = ops.objects_spec(objects)   # min_area, or None; ValueError on a bad entry
         self.sal = ops.sal_spec(sal)   # (min_area, intensity), or None; ValueError on a bad entry
         self._weights = ops.sal_weights(self.sal[1], self.value_scale) if self.sal else None   # the table's first use: ValueError outside the limits
+        if nprob is True and not self.fss:
+            raise ValueError("Validator: nprob=True takes the fss scales; give fss= as well, or the scales themselves")
+        self.nprob = self.fss if nprob is True else ops.fss_scales(None if nprob is False else nprob)   # the scales, () for none; ValueError on a bad entry
         self._parts, _ = self._table(None)   # the spectrum part comes with the block: its size follows the epoch's frames
         for part in self._parts:
             if len(part.pools) > ops.MAX_POOLS:   # a baseline's pass; pool_pairs has bounded the forecast's
@@ -528,7 +606,7 @@ class Validator(ForwardClient):
     def _table(self, frame):
         """block_parts for this Validator's options; frame: (H, W) of the epoch, which sizes the spectrum part (None: without that part)"""
         return block_parts(self.seq_len, len(self.thresholds), self.pools, self.persistence, self.fss, bool(self.advection),
-                           frame if self.spectrum else None, self._levels, self.sal, self.objects)
+                           frame if self.spectrum else None, self._levels, sal=self.sal, nprob=self.nprob, objects=self.objects)
 
     def _block_for(self, device):
         """ONE allocation, the parts of block_parts; done() reduces it with one all-reduce"""
@@ -587,6 +665,9 @@ class Validator(ForwardClient):
             elif part.kind == "sal":
                 lib.call("adnm_valid_sal_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, self.sal[0], self._weights,
                          ent["ws_sal"].data_ptr(), ent["ws_sal"].numel(), B * T, T, H, W, stream)
+            elif part.kind == "nprob":   # (no workspace: the query in open() answered 0)
+                lib.call("adnm_valid_nprob_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, ops.fss_table(self.nprob),
+                         len(self.nprob), None, 0, B * T, T, H, W, stream)
             else:   # objects
                 ws = ent["ws_objects"]
                 lib.call("adnm_valid_objects_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, self.objects,
@@ -651,6 +732,9 @@ class Validator(ForwardClient):
         if self.sal:
             ws_sal = workspace("adnm_valid_sal_accum_ws_bytes", [(B * T, T, H, W, nthr)],
                                f"sal on {B * T} frames of {H} x {W} is outside adnm_valid_sal_accum's limits (frames <= 65535, {ops.SAL_LIMITS})")
+        if self.nprob and int(lib.query("adnm_valid_nprob_accum_ws_bytes", B * T, T, H, W, nthr, ops.fss_table(self.nprob), len(self.nprob))) != 0:
+            raise RuntimeError(f"Validator: nprob on {B * T} frames of {H} x {W} is outside adnm_valid_nprob_accum's limits (frames <= 65535, H and W < 32768, "
+                               "H*W < 2^24)")
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=ws, ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss,
                    ws_spectrum=ws_spectrum, ws_joint=ws_joint, ws_objects=ws_objects, ws_sal=ws_sal, adv=adv, motion=motion, flow=flow, ws_trec=ws_trec,
                    loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
@@ -751,7 +835,9 @@ class Validator(ForwardClient):
         objects: plus "objects" {"min_area", thr: {"target", "forecast", "count_bias", "size_bias", "object_POD", "object_FAR", "object_CSI",
         "size_bin_edges"}} (object_entries of the table summed over the horizon) and "per_lead"/"objects", the same with a leading T axis.
         sal: plus "sal" {"min_area", "intensity", thr: {"A", "abs_A", "S", "abs_S", "L1", "L2", "L", "frames_A", "frames_L1", "frames_S",
-        "missed_frames", "false_frames"}} (sal_entries of the table summed over the horizon) and "per_lead"/"sal", the same with a leading T axis."""
+        "missed_frames", "false_frames"}} (sal_entries of the table summed over the horizon) and "per_lead"/"sal", the same with a leading T axis.
+        nprob: plus "nprob" {n: {thr: {"histogram", "base_rate", "brier", "reliability", "resolution", "uncertainty", "brier_skill", "roc",
+        "roc_area", "reliability_diagram"}}} (nprob_entries of the table summed over the horizon) and "per_lead"/"nprob", the same with a leading T axis."""
         if self._block is None or self._frame is None:
             raise RuntimeError("Validator.done: no batch since the last reset")
         blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
@@ -760,7 +846,7 @@ class Validator(ForwardClient):
         area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
         res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead,
                         fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None, joint=self._levels, objects=self.objects,
-                        sal=dict(min_area=self.sal[0], intensity=self.sal[1]) if self.sal else None)
+                        sal=dict(min_area=self.sal[0], intensity=self.sal[1]) if self.sal else None, nprob=self.nprob)
         if self.advection_flow:
             res["advection"]["scheme"] = "flow"
         if reset:

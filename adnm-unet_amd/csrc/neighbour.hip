@@ -3,7 +3,9 @@
 // workgroup per (tile, frame).  A workgroup stages its tile and the margin its windows reach into ONCE, as pair_bits' 2 bytes per pixel in
 // LDS (low byte target, high byte forecast), and serves every pool or scale and every threshold from that image in integers.  Each pass
 // leaves 3 * nthr uint32 per workgroup, part[frame][tile][pass][3 * nthr], and one fold adds them to the table in double, in a fixed
-// order.  What the two share is written once: the stager, the store of a pass's counts and the fold.
+// order.  What the two share is written once: the stager, the store of a pass's counts and the fold.  Behind them stand the neighbourhood
+// exceedance probability's histogram (adnm_valid_nprob_accum; §4r), which shares the FSS pass's staging and running sums and flushes an LDS
+// histogram instead of partials, and the probability field itself (adnm_neighbour_prob).
 #include "scored_pair.h"
 
 namespace {
@@ -396,5 +398,296 @@ extern "C" int adnm_valid_fss_accum(const float* pred, int64_t pred_sample_strid
                                                                                             (int)nscale, (double*)table);
   }
   ADNM_CHECK_LAUNCH("valid_fss_fold");
+  return ADNM_OK;
+}
+
+// ---- neighbourhood exceedance probability: the histogram of (window count, observed bit), and the probability field ----
+// p(y, x) = c_f(y, x) / n^2 with FSS's c_f above (zeros outside the frame, the denominator always n^2), read as the probability of the
+// event at the pixel; o(y, x) is the target's event bit at the pixel itself.  The statistic (include/adnm_hip.h: adnm_valid_nprob_accum;
+// DESIGN.md §4r) is N[t][k][scale][o][c]: how many pixels have the observed bit o and the window count c.  Brier score, its decomposition,
+// the reliability diagram and the ROC curve are host arithmetic on it (validate.nprob_entries).
+//   one launch    grid (tiles, frames), FSS's staging.  Only the FORECAST is counted in windows, so a scale and a nibble (four thresholds)
+//                 need one plane of row counts, rs[staged row][centre column]: wave q takes the centre columns 8q .. 8q + 7, lane R the
+//                 staged row R, running along the row as the FSS pass does.  The column pass is FSS's: a thread owns four consecutive
+//                 centres of a column and keeps the four thresholds' counts in 16-bit lanes.
+//   the histogram u32 in LDS, hist[threshold of the nibble][o][c], 4 * 2 * (n^2 + 1) <= 8720 bins (34.9 KB).  Thresholds are taken four at
+//                 a time, so img + rs + hist is 51.8 KB of static LDS: below 64 KB, no function attribute, three workgroups per CU.  All
+//                 eight at once would be 78 KB of histogram and one workgroup less per CU for a pass that the row and column sums bound.
+//   the hot bin   radar fields are mostly empty, so nearly every lane holds (o = 0, c = 0): those lanes are counted with a ballot and a
+//                 popcount into a per-wave scalar per threshold, added to LDS once per wave (joint.hip's trick); the others issue an atomic.
+//   the flush     after a scale's nibble only the non-zero bins go to the table, as no-return double atomics, and are cleared.  Every
+//                 addend is an integer and every sum stays below 2^53: exact and the same bits on every run whatever the order.
+// No workgroup waits for another; every loop has a bound known at launch; no floating-point sum anywhere.
+namespace {
+constexpr int kNprobBins = 2 * (kFssWin * kFssWin + 1);   // of one threshold at the largest scale: 2180
+
+// The row pass of one nibble of one plane of staged bits: lane `R` of wave `q` takes staged row R and the centre columns 8q .. 8q + 7.
+// row: the staged row; sh: where the nibble stands in a pixel; c0: the staged column of centre 0's window.  rs[R][x] = the four
+// thresholds' counts over the staged columns c0 + x .. c0 + x + n - 1, one per byte (<= 33: bytes never carry).
+template <typename PX>
+__device__ __forceinline__ void nprob_row_pass(uint32_t (*rs)[kTile + 1], const PX* row, int R, int q, int sh, int c0, int n) {
+  const int x0 = 8 * q;
+  uint32_t s = 0;
+  for (int u = 0; u < n - 1; ++u) s += fss_spread((row[c0 + x0 + u] >> sh) & 0xfu);
+  for (int x = x0; x < x0 + 8; ++x) {
+    s += fss_spread((row[c0 + x + n - 1] >> sh) & 0xfu);   // c0 + x + n - 1 <= hs + n / 2 + 31 < side
+    rs[R][x] = s;
+    s -= fss_spread((row[c0 + x] >> sh) & 0xfu);           // it was added: no byte borrows
+  }
+}
+
+// The column pass: acc[e] holds bytes e and e + 2 of the row counts of column cx summed over a window of staged rows, as 16-bit lanes
+// (<= 1089 each).  Threshold kk of the nibble: nprob_count(acc, kk).
+__device__ __forceinline__ void nprob_rows(uint32_t (&acc)[2], const uint32_t (*rs)[kTile + 1], int R, int cx, bool add) {
+  const uint32_t v = rs[R][cx], e = v & 0x00ff00ffu, o = (v >> 8) & 0x00ff00ffu;
+  acc[0] = add ? acc[0] + e : acc[0] - e;
+  acc[1] = add ? acc[1] + o : acc[1] - o;
+}
+__device__ __forceinline__ uint32_t nprob_count(const uint32_t (&acc)[2], int kk) { return (acc[kk & 1] >> (16 * (kk >> 1))) & 0xffffu; }
+
+// grid (tiles, frames).  hs: as for fss_sums_kernel.  off[p]: where scale p's two runs start in a (t, k) row of S doubles.
+struct NprobOff {
+  int at[kFssMax], S;
+};
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void nprob_hist_kernel(ScoredPair pair, double* __restrict__ table, int H, int W, int tiles_x, int hs,
+                                                            float value_scale, Thr thr, Scales scales, NprobOff off, int clear) {
+  __shared__ __attribute__((aligned(4))) uint16_t img[kFssSide][kFssPitch];
+  __shared__ uint32_t rs[kFssSide][kTile + 1];
+  __shared__ uint32_t hist[4 * kNprobBins];
+  const int f = blockIdx.y, tile = blockIdx.x, oy = (tile / tiles_x) * kTile, ox = (tile % tiles_x) * kTile;
+  const int side = kTile + 2 * hs;
+  stage_pair_bits<VEC, kFssPitch, false>(&img[0][0], pair.target(f), pair.forecast(f), H, W, oy - hs, ox - hs, side, side, value_scale, thr);
+  for (int i = threadIdx.x; i < clear; i += kBlock) hist[i] = 0u;   // clear = 4 * 2 * (max n^2 + 1): the bins any scale of this call uses
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int cx = threadIdx.x & 31, cy0 = (threadIdx.x >> 5) * 4;   // the column pass: centres (cy0 .. cy0 + 3, cx) of the tile
+  const bool col_in = ox + cx < W;
+  double* row_t = table + (int64_t)(f % pair.T) * thr.n * off.S;
+  for (int p = 0; p < scales.cnt; ++p) {
+    const int n = scales.n[p], c0 = hs - (n >> 1), per = n * n + 1;   // a threshold's bins: [o = 0: c = 0 .. n^2][o = 1: c = 0 .. n^2]
+    for (int h = 0; 4 * h < thr.n; ++h) {                            // the nibble: thresholds 4h .. 4h + 3
+      const int nk = min(4, thr.n - 4 * h);
+      if (lane < side) nprob_row_pass(rs, img[lane], lane, wave, 8 + 4 * h, c0, n);
+      __syncthreads();
+      uint32_t acc[2] = {0, 0}, zeros[4] = {0, 0, 0, 0};   // zeros: wave-uniform, the lanes of this wave in bin (o = 0, c = 0) per threshold
+      for (int u = 0; u < n - 1; ++u) nprob_rows(acc, rs, c0 + cy0 + u, cx, true);
+      for (int j = 0; j < 4; ++j) {                        // the same trips for every lane: the ballots below see whole waves
+        nprob_rows(acc, rs, c0 + cy0 + j + n - 1, cx, true);   // <= 2 * hs + 31 < side
+        const bool valid = col_in && oy + cy0 + j < H;
+        const uint32_t obs = img[hs + cy0 + j][hs + cx] >> (4 * h);   // the centre's target bits of this nibble
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+          if (kk < nk) {
+            const int bin = (int)((obs >> kk) & 1u) * per + (int)nprob_count(acc, kk);
+            zeros[kk] += (uint32_t)__popcll(__ballot(valid && bin == 0));
+            if (valid && bin != 0) atomicAdd(&hist[kk * 2 * per + bin], 1u);
+          }
+        nprob_rows(acc, rs, c0 + cy0 + j, cx, false);
+      }
+      if (lane == 0) {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+          if (kk < nk && zeros[kk]) atomicAdd(&hist[kk * 2 * per], zeros[kk]);
+      }
+      __syncthreads();
+      for (int i = threadIdx.x; i < nk * 2 * per; i += kBlock) {
+        const uint32_t v = hist[i];
+        if (v) {
+          const int kk = i / (2 * per), bin = i % (2 * per);
+          unsafeAtomicAdd(&row_t[(int64_t)(4 * h + kk) * off.S + off.at[p] + bin], (double)v);   // integers below 2^53: exact in any order
+          hist[i] = 0u;
+        }
+      }
+      __syncthreads();   // rs and hist are rewritten by the next nibble or scale
+    }
+  }
+}
+
+// the histogram pass's own limits: nullptr, or the one that refuses.  The scales are FSS's, so that one staging serves both.
+const char* nprob_why(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* scales_host, int64_t nscale) {
+  if (!scales_host) return "null pointer";
+  if (nscale < 1 || nscale > kFssMax) return "1..4 scales";
+  if (nthr < 1 || nthr > kMaxThr) return "1..8 thresholds";
+  if (const char* w = pair_frames_why(frames, T)) return w;
+  if (const char* w = pair_tiled_shape_why(H, W)) return w;
+  for (int64_t p = 0; p < nscale; ++p) {
+    const int64_t n = scales_host[p];
+    if (n < 1 || n > kFssWin || n % 2 == 0) return "a scale must be odd and in 1..33";
+    for (int64_t o = 0; o < p; ++o)
+      if (scales_host[o] == n) return "a scale is given twice";
+  }
+  return nullptr;
+}
+// S of a (t, k) row: the doubles of all scales; the scales have passed nprob_why
+inline int64_t nprob_row(const int64_t* scales_host, int64_t nscale) {
+  int64_t s = 0;
+  for (int64_t p = 0; p < nscale; ++p) s += 2 * (scales_host[p] * scales_host[p] + 1);
+  return s;
+}
+}  // namespace
+
+extern "C" int64_t adnm_valid_nprob_block_bytes(int64_t T, int64_t nthr, const int64_t* scales_host, int64_t nscale) {
+  if (T < 1 || T > 65535 || nprob_why(1, 1, 1, 1, nthr, scales_host, nscale)) return -1;
+  return (int64_t)sizeof(double) * T * nthr * nprob_row(scales_host, nscale);
+}
+
+extern "C" int64_t adnm_valid_nprob_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* scales_host, int64_t nscale) {
+  return nprob_why(frames, T, H, W, nthr, scales_host, nscale) ? -1 : 0;   // the partial histograms live in LDS
+}
+
+extern "C" int adnm_valid_nprob_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                                      const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* scales_host, int64_t nscale, void* ws,
+                                      int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream) {
+  const PairCall call = {"valid_nprob_accum", pred, pred_sample_stride, pred_frame_stride, target, table, ws, ws_bytes, H, W,
+                         /*flat*/ false, /*ws_optional*/ true, /*ws_aligned*/ false, /*ws_rc*/ ADNM_EINVAL};
+  if (int rc = pair_check(call, thresholds_host && scales_host, nprob_why(frames, T, H, W, nthr, scales_host, nscale),
+                          adnm_valid_nprob_accum_ws_bytes(frames, T, H, W, nthr, scales_host, nscale),
+                          "frames %lld T %lld %lld x %lld nthr %lld nscale %lld", (long long)frames, (long long)T, (long long)H, (long long)W,
+                          (long long)nthr, (long long)nscale))
+    return rc;
+  const Thr thr = thr_fill(thresholds_host, nthr);
+  Scales scales;
+  NprobOff off;
+  scales.cnt = (int)nscale;
+  off.S = (int)nprob_row(scales_host, nscale);   // <= 4 * 2180
+  int hs = 0, at = 0, clear = 0;
+  for (int p = 0; p < kFssMax; ++p) {
+    scales.n[p] = p < nscale ? (int)scales_host[p] : 1;
+    off.at[p] = at;
+    if (p < nscale) at += 2 * (scales.n[p] * scales.n[p] + 1);
+    hs = scales.n[p] / 2 > hs ? scales.n[p] / 2 : hs;
+    clear = 4 * 2 * (scales.n[p] * scales.n[p] + 1) > clear ? 4 * 2 * (scales.n[p] * scales.n[p] + 1) : clear;   // <= 4 * kNprobBins
+  }
+  const bool vec = pair_quads(W, pred_sample_stride, pred_frame_stride, pred, target);
+  if (vec) hs = (int)adnm_align(hs, 4);   // <= 16
+  const ScoredPair pair = {pred, pred_sample_stride, pred_frame_stride, target, (int)T, (int)(H * W)};
+  const int tiles_x = (int)adnm_cdiv(W, kTile), tiles = (int)tiles_of(H, W);
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ADNM_PROF("valid_nprob", st, 8.0 * frames * H * W);
+    const dim3 grid((unsigned)tiles, (unsigned)frames);
+    if (vec) nprob_hist_kernel<true><<<grid, kBlock, 0, st>>>(pair, (double*)table, (int)H, (int)W, tiles_x, hs, value_scale, thr, scales, off, clear);
+    else nprob_hist_kernel<false><<<grid, kBlock, 0, st>>>(pair, (double*)table, (int)H, (int)W, tiles_x, hs, value_scale, thr, scales, off, clear);
+  }
+  ADNM_CHECK_LAUNCH("valid_nprob_accum");
+  return ADNM_OK;
+}
+
+// ---- the probability field of ONE field at ONE scale: out[k][f][y][x] = float(c_f) / float(n^2) ----
+// The same tiles, halo and running sums on a one-byte image (bit k = q >= thr_k).  The counts of a nibble pass through LDS once more so
+// that a thread leaves with four consecutive columns of a row: one 16-byte store where the output allows it.  The quotient is one IEEE
+// division of two exactly represented integers (no reciprocal): the same bits as np.float32(c) / np.float32(n * n).
+namespace {
+constexpr int kProbPitch = kFssSide + 4;   // bytes per staged row: 17 dwords, so that the lanes of the row pass (one row each) hit distinct banks
+
+// the event bits of one field's rectangle -> img[r * kProbPitch + c], 0 outside the frame.  VEC: W, x0 and cols are multiples of 4 and
+// every row starts on 16 bytes.
+template <bool VEC>
+__device__ __forceinline__ void stage_field_bits(uint8_t* img, const float* __restrict__ src, int H, int W, int y0, int x0, int rows, int cols,
+                                                 float value_scale, const Thr& thr) {
+  auto bits = [&](float v) {
+    const float q = eval_trunc(eval_scaled(v, value_scale));
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < kMaxThr; ++k)
+      if (k < thr.n) m |= q >= thr.t[k] ? 1u << k : 0u;
+    return m;
+  };
+  if (VEC) {
+    const int q = cols >> 2;
+    for (int i = threadIdx.x; i < rows * q; i += kBlock) {
+      const int r = i / q, c = (i % q) * 4, gy = y0 + r, gx = x0 + c;
+      uint32_t m = 0;
+      if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+        const float4 a = *(const float4*)(src + (int64_t)gy * W + gx);
+        m = bits(a.x) | (bits(a.y) << 8) | (bits(a.z) << 16) | (bits(a.w) << 24);
+      }
+      *(uint32_t*)&img[r * kProbPitch + c] = m;   // c and kProbPitch are multiples of 4
+    }
+  } else {
+    for (int i = threadIdx.x; i < rows * cols; i += kBlock) {
+      const int r = i / cols, c = i % cols, gy = y0 + r, gx = x0 + c;
+      img[r * kProbPitch + c] = (uint8_t)((gy >= 0 && gy < H && gx >= 0 && gx < W) ? bits(src[(int64_t)gy * W + gx]) : 0u);
+    }
+  }
+}
+
+// grid (tiles, frames).  VIN: 16-byte loads (W % 4 == 0, src on 16 bytes); VOUT: 16-byte stores (W % 4 == 0, out on 16 bytes).
+template <bool VIN, bool VOUT>
+__global__ __launch_bounds__(kBlock) void nprob_field_kernel(const float* __restrict__ src, float* __restrict__ out, int frames, int H, int W, int tiles_x,
+                                                             int hs, float value_scale, Thr thr, int n) {
+  __shared__ __attribute__((aligned(4))) uint8_t img[kFssSide][kProbPitch];
+  __shared__ uint32_t rs[kFssSide][kTile + 1];
+  __shared__ __attribute__((aligned(8))) uint16_t cnt[4][kTile][kTile + 4];   // [threshold of the nibble][centre row][centre column]
+  const int f = blockIdx.y, tile = blockIdx.x, oy = (tile / tiles_x) * kTile, ox = (tile % tiles_x) * kTile;
+  const int side = kTile + 2 * hs, c0 = hs - (n >> 1);
+  const int64_t hw = (int64_t)H * W;
+  stage_field_bits<VIN>(&img[0][0], src + f * hw, H, W, oy - hs, ox - hs, side, side, value_scale, thr);
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int cx = threadIdx.x & 31, cy0 = (threadIdx.x >> 5) * 4;   // the column pass: centres (cy0 .. cy0 + 3, cx)
+  const int qy = threadIdx.x >> 3, qx = (threadIdx.x & 7) * 4;     // the store: centres (qy, qx .. qx + 3)
+  const float nn = (float)(n * n);
+  for (int h = 0; 4 * h < thr.n; ++h) {
+    const int nk = min(4, thr.n - 4 * h);
+    if (lane < side) nprob_row_pass(rs, img[lane], lane, wave, 4 * h, c0, n);
+    __syncthreads();
+    uint32_t acc[2] = {0, 0};
+    for (int u = 0; u < n - 1; ++u) nprob_rows(acc, rs, c0 + cy0 + u, cx, true);
+    for (int j = 0; j < 4; ++j) {
+      nprob_rows(acc, rs, c0 + cy0 + j + n - 1, cx, true);   // <= 2 * hs + 31 < side
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) cnt[kk][cy0 + j][cx] = (uint16_t)nprob_count(acc, kk);
+      nprob_rows(acc, rs, c0 + cy0 + j, cx, false);
+    }
+    __syncthreads();
+    const int gy = oy + qy, gx = ox + qx;
+    if (gy < H && gx < W) {
+      for (int kk = 0; kk < nk; ++kk) {
+        const uint16_t* c = &cnt[kk][qy][qx];
+        float* dst = out + (((int64_t)(4 * h + kk) * frames + f) * H + gy) * W + gx;
+        const float4 v = make_float4((float)c[0] / nn, (float)c[1] / nn, (float)c[2] / nn, (float)c[3] / nn);
+        if (VOUT) {
+          *(float4*)dst = v;   // W % 4 == 0: the four columns are inside
+        } else {
+          dst[0] = v.x;
+          if (gx + 1 < W) dst[1] = v.y;
+          if (gx + 2 < W) dst[2] = v.z;
+          if (gx + 3 < W) dst[3] = v.w;
+        }
+      }
+    }
+    __syncthreads();   // rs and cnt are rewritten by the next nibble
+  }
+}
+}  // namespace
+
+extern "C" int adnm_neighbour_prob(const float* field, float* out, const float* thresholds_host, int64_t nthr, float value_scale, int64_t scale,
+                                   int64_t frames, int64_t H, int64_t W, adnm_stream_t stream) {
+  ADNM_REQUIRE(field && out && thresholds_host, "neighbour_prob: null pointer");
+  ADNM_REQUIRE(((uintptr_t)field | (uintptr_t)out) % 4 == 0, "neighbour_prob: field and out must be 4-byte aligned");
+  ADNM_REQUIRE(nthr >= 1 && nthr <= kMaxThr, "neighbour_prob: 1..8 thresholds, got %lld", (long long)nthr);
+  ADNM_REQUIRE(scale >= 1 && scale <= kFssWin && scale % 2 == 1, "neighbour_prob: the scale must be odd and in 1..33, got %lld", (long long)scale);
+  ADNM_REQUIRE(frames >= 1 && frames <= 65535, "neighbour_prob: 1 <= frames <= 65535, got %lld", (long long)frames);
+  if (const char* w = pair_tiled_shape_why(H, W)) ADNM_REQUIRE(false, "neighbour_prob: %s (got %lld x %lld)", w, (long long)H, (long long)W);
+  const Thr thr = thr_fill(thresholds_host, nthr);
+  const bool vin = W % 4 == 0 && (uintptr_t)field % 16 == 0, vout = W % 4 == 0 && (uintptr_t)out % 16 == 0;
+  int hs = (int)scale / 2;
+  if (vin) hs = (int)adnm_align(hs, 4);   // <= 16
+  const int tiles_x = (int)adnm_cdiv(W, kTile);
+  const dim3 grid((unsigned)tiles_of(H, W), (unsigned)frames);
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ADNM_PROF("neighbour_prob", st, 4.0 * frames * H * W * (1 + nthr));
+#define ADNM_NPROB_FIELD(VIN, VOUT) \
+  nprob_field_kernel<VIN, VOUT><<<grid, kBlock, 0, st>>>(field, out, (int)frames, (int)H, (int)W, tiles_x, hs, value_scale, thr, (int)scale)
+    if (vin && vout) ADNM_NPROB_FIELD(true, true);
+    else if (vin) ADNM_NPROB_FIELD(true, false);
+    else if (vout) ADNM_NPROB_FIELD(false, true);
+    else ADNM_NPROB_FIELD(false, false);
+#undef ADNM_NPROB_FIELD
+  }
+  ADNM_CHECK_LAUNCH("neighbour_prob");
   return ADNM_OK;
 }

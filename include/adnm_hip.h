@@ -738,6 +738,35 @@ int adnm_valid_fss_accum(const float* pred, int64_t pred_sample_stride, int64_t 
                          const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* scales_host, int64_t nscale, void* ws,
                          int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
 
+/* Neighbourhood exceedance probability (Theis et al. 2005; Schwartz et al. 2010): the fraction of forecast pixels at or above a threshold
+ * in the n x n window around a pixel, read as the probability of the event at that pixel, and the one sufficient statistic that verifies
+ * it.  The reference has neither; the definitions are this project's and the yardstick is conv2d + np.bincount.
+ *   event, scale  adnm_valid_fss_accum's: q(v) >= thr_k on the quantised field; n odd, 1 <= n <= 33, at most four scales, none twice.
+ *   c_f(y, x)     FSS's window count of the FORECAST (zeros outside the frame: the denominator is always n^2); p = c_f / n^2.
+ *   o(y, x)       the TARGET's event bit at the pixel itself (no neighbourhood on the observation side).
+ *   statistic     N[t][k][scale][o][c] = the number of pixels of all frames f with f mod T = t that have o and c_f = c.
+ * table: adnm_valid_nprob_block_bytes(T, nthr, scales_host, nscale) = 8 * T * nthr * S bytes, S = SUM over the scales of 2 * (n^2 + 1),
+ *   8-byte aligned device memory, zeroed by the caller, all double, shape (T, nthr, S).  In a (t, k) row the scales stand in the order
+ *   given; each scale is [o = 0: c = 0 .. n^2][o = 1: c = 0 .. n^2].  Integers held in doubles, each below frames * H*W < 2^53.
+ * adnm_valid_nprob_accum ADDS a batch.  The arguments are adnm_valid_fss_accum's.  ONE launch, grid (tiles, frames), 32 x 32 tiles with
+ *   FSS's staging (both the 16-byte and the float-by-float path) and running sums; thresholds are taken four at a time into a u32 LDS
+ *   histogram (51.8 KB of static LDS with the image and the row counts), the lanes in bin (o = 0, c = 0) counted by ballot; after each
+ *   scale the non-zero bins are added to the table as no-return double atomics.  Every addend is an integer: exact and the same bits on
+ *   every run.  No workspace: adnm_valid_nprob_accum_ws_bytes is 0 for every accepted shape and ws may be NULL.
+ * Limits, refused before any launch (ADNM_EINVAL): adnm_valid_fss_accum's.  The *_bytes queries return -1.
+ * adnm_neighbour_prob is the product: field holds `frames` contiguous fp32 frames (4-byte aligned); out, fp32 (nthr, frames, H, W),
+ *   out[k][f][y][x] = (float)c_f / (float)(n^2), ONE correctly rounded IEEE division (np.float32(c) / np.float32(n * n), bit for bit), for
+ *   ONE scale and 1..8 thresholds.  Every element of out is written: 16 bytes per store where W % 4 == 0 and out is 16-byte aligned,
+ *   float by float otherwise; loads likewise by field's alignment.  Limits (ADNM_EINVAL): a null pointer; field / out not 4-byte
+ *   aligned; nthr outside 1..8; scale even or outside 1..33; frames outside 1..65535; H or W outside [1, 32768); H*W >= 2^24. */
+int64_t adnm_valid_nprob_block_bytes(int64_t T, int64_t nthr, const int64_t* scales_host, int64_t nscale);
+int64_t adnm_valid_nprob_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr, const int64_t* scales_host, int64_t nscale);
+int adnm_valid_nprob_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                           const float* thresholds_host, int64_t nthr, float value_scale, const int64_t* scales_host, int64_t nscale, void* ws,
+                           int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
+int adnm_neighbour_prob(const float* field, float* out, const float* thresholds_host, int64_t nthr, float value_scale, int64_t scale,
+                        int64_t frames, int64_t H, int64_t W, adnm_stream_t stream);
+
 /* The Lagrangian-persistence (advection) baseline: block-matched motion between the last two input frames (TREC, Rinehart & Garvey 1978)
  * and the last frame moved along it.  The reference has none; the definitions are this project's.  Integer arithmetic and
  * bit copies only: exact and bit-reproducible.
