@@ -3864,6 +3864,84 @@ def object_moments(field, thr, value_scale, min_area=1, intensity=None):
     return out
 
 
+# ======================================================================================= space-time tracks (csrc/tracks.hip)
+MAX_TRACK_VOXELS = 1 << 22
+TRACK_LIMITS = f"{OBJECTS_LIMITS}, volumes of T * H * W <= {MAX_TRACK_VOXELS} voxels"
+
+
+def tracks_spec(tracks):
+    """the Validator's `tracks` argument -> min_volume, or None for no track scores: None / False -> None, True -> 1, an int >= 1 -> itself,
+    dict(min_volume=) -> its value (tracks of fewer voxels are ignored).  ValueError on anything else."""
+    if tracks is None or tracks is False:
+        return None
+    if tracks is True:
+        return 1
+    if isinstance(tracks, dict) and set(tracks) <= {"min_volume"}:
+        tracks = tracks.get("min_volume", 1)
+    if not isinstance(tracks, bool) and isinstance(tracks, (int, np.integer)) and tracks >= 1:
+        return int(tracks)
+    raise ValueError(f"tracks: None / False, True, an int min_volume >= 1 or dict(min_volume=), got {tracks!r}")
+
+
+def track_cols(T):
+    """-> (C, offsets): the columns of a track table's row (include/adnm_hip.h: adnm_valid_tracks_accum), C = 7 + 4 T, and where each entry
+    starts: the seven sums, then births, deaths, deaths0 (deaths of the tracks born in frame 0) and the duration histogram, T columns each."""
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 1:
+        raise ValueError(f"track_cols: T is an int >= 1, got {T!r}")
+    T = int(T)
+    return 7 + 4 * T, {"count": 0, "volume": 1, "volume2": 2, "duration": 3, "matched": 4, "matched_volume": 5, "spanning": 6, "births": 7,
+                       "deaths": 7 + T, "deaths0": 7 + 2 * T, "duration_histogram": 7 + 3 * T}
+
+
+def _min_volume(op, min_volume):
+    if isinstance(min_volume, bool) or not isinstance(min_volume, (int, np.integer)) or min_volume < 1:
+        raise ValueError(f"{op}: min_volume is an int >= 1, got {min_volume!r}")
+    return int(min_volume)
+
+
+def track_stats(truth, pred, thresholds, value_scale, min_volume=1):
+    """truth / pred: contiguous fp32 GPU tensors (B, T, H, W) of one shape -> (B, 2, nthr, C) int64 on the device, C = track_cols(T)[0]: per
+    sample, field (0 = truth, 1 = pred) and threshold the row of include/adnm_hip.h: adnm_valid_tracks_accum over the 26-connected tracks of
+    the sample's event volume q >= thr.  Tracks of fewer than min_volume voxels are ignored.  Exact.  One call of adnm_valid_tracks_accum per
+    sample, each into its own zeroed slice; validate.track_entries reads the sum over the samples."""
+    _pair("track_stats", truth, pred, (4,), "(B, T, H, W)", contiguous=True)
+    thr = [float(t) for t in thresholds]
+    if not 1 <= len(thr) <= 8:
+        raise ValueError("track_stats: 1..8 thresholds")
+    min_volume = _min_volume("track_stats", min_volume)
+    B, T, H, W = truth.shape
+    nb = lib.query("adnm_valid_tracks_accum_ws_bytes", T, T, H, W, len(thr)) if B else -1
+    if nb < 0:
+        raise RuntimeError(f"track_stats: {B} samples of {T} x {H} x {W} are outside adnm_valid_tracks_accum's limits (B >= 1, T <= 65535, {TRACK_LIMITS})")
+    out = torch.zeros((B, 2, len(thr), track_cols(T)[0]), dtype=torch.float64, device=truth.device)
+    ws, host = _ws(nb, truth.device), (ctypes.c_float * len(thr))(*thr)
+    for b in range(B):
+        lib.call("adnm_valid_tracks_accum", pred[b].data_ptr(), T * H * W, H * W, truth[b].data_ptr(), out[b].data_ptr(), host, len(thr), float(value_scale),
+                 min_volume, ws.data_ptr(), int(nb), T, T, H, W, _stream())
+    return out.to(torch.int64)   # integers below 2^53 in doubles: exact
+
+
+def label_tracks(field, thr, value_scale, min_volume=1):
+    """field: a contiguous fp32 GPU tensor (..., T, H, W) -> int32 of the same shape: per (T, H, W) volume the canonical labels of the
+    26-connected tracks of the event mask q >= thr, 1 + the flat index t*H*W + y*W + x of a track's first voxel, 0 for the background and for
+    tracks of fewer than min_volume voxels (include/adnm_hip.h: adnm_label_tracks)."""
+    f = _frames("label_tracks", field, "the field")
+    if f.dim() < 3:
+        _unsupported("label_tracks", f"takes the field as an fp32 tensor (..., T, H, W), got {tuple(f.shape)}")
+    min_volume = _min_volume("label_tracks", min_volume)
+    T, H, W = f.shape[-3:]
+    frames = f.numel() // (H * W) if H * W else 0
+    nb = lib.query("adnm_label_tracks_ws_bytes", frames, T, H, W) if T else -1
+    if nb < 0:
+        raise RuntimeError(f"label_tracks: {frames} frames in volumes of {T} x {H} x {W} are outside adnm_label_tracks' limits (1 <= frames <= 65535, "
+                           f"{TRACK_LIMITS})")
+    out = torch.empty(f.shape, dtype=torch.int32, device=f.device)
+    ws = _ws(nb, f.device)
+    lib.call("adnm_label_tracks", f.data_ptr(), T * H * W, H * W, out.data_ptr(), float(thr), float(value_scale), min_volume, ws.data_ptr(), int(nb),
+             frames, T, H, W, _stream())
+    return out
+
+
 # ======================================================================================= the output side (csrc/dataio.hip: forecast_render)
 def edges_up_f32(edges):
     """double edges -> float32, each rounded UP to the smallest float >= it: the kernel compares an fp32 value with fp32 edges where

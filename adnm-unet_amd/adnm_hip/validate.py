@@ -14,7 +14,8 @@ include/adnm_hip.h, adnm_valid_accum).  done() reads that block — summed over 
 and aggregates it exactly as GpuEvaluator.done() does.
 
 Every option below adds tables of its own behind that block, in the same allocation.  block_parts is the ONE statement of which tables
-there are and where each lies: the allocation, the launches (one per table, in the table's order) and aggregate all read it.  The defaults
+there are and where each lies: the allocation, the launches (one per table, in the table's order) and aggregate all read it (through
+block_layout, which takes `tracks` as well; block_parts keeps the parameter list it had before the tracks arrived).  The defaults
 allocate and launch nothing new.
 
 Validator(..., pools=(4, 16, (16, 8)), persistence=True) adds neighbourhood scores and the persistence baseline:
@@ -57,6 +58,12 @@ Validator(..., nprob=(1, 5, 17, 33)) (or nprob=True for the fss scales) adds the
 forecast events in the n x n window) into a (T, nthr, S) table of integers; done() reports the Brier score and its decomposition, the ROC
 curve and its area and the reliability diagram of p = count / n^2 (nprob_entries).
 
+Validator(..., tracks=True) (or tracks=min_volume, or tracks=dict(min_volume=)) adds space-time rain-cell tracks:
+csrc/tracks.hip::valid_tracks_accum labels the 26-connected components of every sample's (T, H, W) event volume, per threshold and field, on the
+device and adds the number of tracks, their volumes and durations, the matched ones, births and deaths per frame index, the deaths of the tracks
+present at the first lead and a duration histogram into a (2, nthr, 7 + 4 T) table; done() reports lifetimes, the survival curve of the initial
+cells and the track POD / FAR / CSI (track_entries).
+
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
@@ -91,7 +98,7 @@ def baseline_pools(pools):
 
 
 class Part(NamedTuple):
-    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint / objects / sal / nprob, `field` the field it scores against the target
+    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint / objects / sal / nprob / tracks, `field` the field it scores against the target
     (pred: the forecast, last: the last input frame held, adv: that frame advected; None for main), `pools` the (size, stride) pairs of a
     pool part's pass, `offset` its place in the block in doubles"""
     name: str
@@ -106,12 +113,13 @@ class Part(NamedTuple):
         return math.prod(self.shape)
 
 
-def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, objects=None):
+def block_layout(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, tracks=None, objects=None):
     """-> (the parts of the ONE allocation in their order, its doubles).  The order of the block, and of the launches that fill it, is stated
     here and nowhere else.  pools: (size, stride) pairs; fss: scales; spectrum: (H, W) of the frames, or None; joint: the levels L, or None;
     objects: min_area, or None; sal: what ops.sal_spec returns, or None.  `sal` is passed BY NAME: it stands in front of `objects`, which
     stays the last parameter, and its position may move when a further table arrives.  nprob: the scales of the neighbourhood probability's
-    histogram, or None; passed BY NAME as well, for the same reason (its table is the last one whatever its place here)."""
+    histogram, or None; passed BY NAME as well, for the same reason.  tracks: min_volume, or None; BY NAME too: its table, (2, nthr, 7 + 4 T)
+    with no leading T axis, is the last one whatever its place here."""
     pools, fss, nprob = tuple(pools), tuple(fss), tuple(nprob or ())
     base = baseline_pools(pools)
     pooled, scaled = (T, len(base), 4 * nthr), (T, len(fss), 3 * nthr)
@@ -126,7 +134,8 @@ def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, s
             ("joint", "joint", "pred", (), (T, joint, joint), joint),
             ("objects", "objects", "pred", (), (T, 2, nthr, ops.OBJ_COLS), objects),
             ("sal", "sal", "pred", (), (T, nthr, ops.SAL_COLS), sal),
-            ("nprob", "nprob", "pred", (), (T, nthr, ops.nprob_layout(nprob)[1]), nprob))
+            ("nprob", "nprob", "pred", (), (T, nthr, ops.nprob_layout(nprob)[1]), nprob),
+            ("tracks", "tracks", "pred", (), (2, nthr, ops.track_cols(T)[0]), tracks))
     parts, at = [], 0
     for *head, shape, present in rows:
         if present:
@@ -135,9 +144,15 @@ def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, s
     return parts, at
 
 
+def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, objects=None):
+    """block_layout without the tables that came after the neighbourhood probability's: the parameter list callers and tests have pinned.
+    The Validator and aggregate go through block_layout, which states the rows."""
+    return block_layout(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, objects=objects)
+
+
 def _doubles(names, *options, **more):
-    """the doubles of the named parts of block_parts(*options, **more), 0 for a part that is not there"""
-    size = {p.name: p.size for p in block_parts(*options, **more)[0]}
+    """the doubles of the named parts of block_layout(*options, **more), 0 for a part that is not there"""
+    size = {p.name: p.size for p in block_layout(*options, **more)[0]}
     return tuple(size.get(n, 0) for n in names)
 
 
@@ -180,6 +195,11 @@ def sal_doubles(seq_len, nthr, sal=None):
 def nprob_doubles(seq_len, nthr, nprob=None):
     """-> doubles of the neighbourhood probability's table (T, nthr, S), S = ops.nprob_layout(scales)[1]; nprob: the scales (None / () for none)"""
     return _doubles(("nprob",), seq_len, nthr, nprob=ops.fss_scales(nprob))[0]
+
+
+def tracks_doubles(seq_len, nthr, tracks=None):
+    """-> doubles of the tracks table (2, nthr, 7 + 4 T); tracks: what ops.tracks_spec takes (None / False for none)"""
+    return _doubles(("tracks",), seq_len, nthr, tracks=ops.tracks_spec(tracks))[0]
 
 
 def _counts(hist):
@@ -408,6 +428,57 @@ def nprob_entries(rows, scales, thresholds, bins=10):
             for n, (a0, a1) in zip(scales, layout)}
 
 
+def track_entries(rows, samples, thresholds, T, min_volume=1):
+    """rows: (2, nthr, 7 + 4 T) integer sums (ops.track_stats' tensor summed over its samples, or the Validator's table; field 0 = target,
+    1 = forecast; columns: ops.track_cols) and `samples`, the number of samples behind them -> the entries of done()["tracks"]:
+      "min_volume"; then per threshold key
+        "target", "forecast": "count" N, "per_sample" N / samples, "volume" sum v, "mean_volume" sum v / N, "weighted_volume" sum v^2 / sum v
+            (the volume of the track a random event voxel lies in), "mean_duration" sum d / N, "duration_histogram" (T int64: tracks of d = k + 1
+            frames), "births", "deaths" (T int64: tracks by first / last frame), "alive" (T int64: alive[t] = births up to t minus deaths
+            before t), "initial" births[0], "survival" (T: the share of the initial tracks whose last frame is t or later; NaN without
+            initial tracks), "spanning" (first frame 0 and last frame T - 1), "matched" (tracks with a voxel that is an event of the other
+            field), "matched_volume";
+        "count_bias" N_f / N_o, "duration_bias" mean_duration_f / mean_duration_o, "survival_bias" survival_f / survival_o per frame index,
+            "track_POD" matched_o / N_o, "track_FAR" 1 - matched_f / N_f, "track_CSI" matched_o / (N_o + N_f - matched_f).
+    A division by zero gives NaN.  Every array is per lead time already: a track belongs to no single frame index."""
+    if torch.is_tensor(rows):
+        rows = rows.detach().cpu().numpy()
+    r = np.asarray(rows)
+    nthr, (C, at) = len(thresholds), ops.track_cols(T)
+    T = int(T)
+    if r.shape != (2, nthr, C):
+        raise ValueError(f"tracks: rows are (2, {nthr}, {C}) for {nthr} thresholds and T = {T}, got {r.shape}")
+    if r.dtype.kind == "f":
+        if not (np.isfinite(r).all() and (r == np.rint(r)).all()):
+            raise ValueError("tracks: the rows hold integer sums")
+    elif r.dtype.kind not in "iu":
+        raise ValueError(f"tracks: the rows hold integer sums, got {r.dtype}")
+    r = r.astype(np.int64)
+
+    def ratio(a, b):
+        """a / b in float64, NaN where b is 0"""
+        a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return _scalar(np.where(b == 0, np.nan, a / b))
+
+    def field(c):
+        n, v, v2, d, m, mv, span = (int(c[i]) for i in range(7))
+        births, deaths, deaths0, hist = (c[at[k]:at[k] + T].copy() for k in ("births", "deaths", "deaths0", "duration_histogram"))
+        alive = np.cumsum(births) - (np.cumsum(deaths) - deaths)
+        return {"count": n, "per_sample": ratio(n, samples), "volume": v, "mean_volume": ratio(v, n), "weighted_volume": ratio(v2, v),
+                "mean_duration": ratio(d, n), "duration_histogram": hist, "births": births, "deaths": deaths, "alive": alive,
+                "initial": int(births[0]), "survival": ratio(_tail_sums(deaths0, -1), np.full(T, births[0])), "spanning": span, "matched": m,
+                "matched_volume": mv}
+    res = {"min_volume": int(min_volume)}
+    for k, thr in enumerate(thresholds):
+        o, f = field(r[0, k]), field(r[1, k])
+        res[_thr_key(thr)] = {"target": o, "forecast": f, "count_bias": ratio(f["count"], o["count"]),
+                              "duration_bias": ratio(f["mean_duration"], o["mean_duration"]), "survival_bias": ratio(f["survival"], o["survival"]),
+                              "track_POD": ratio(o["matched"], o["count"]), "track_FAR": 1.0 - ratio(f["matched"], f["count"]),
+                              "track_CSI": ratio(o["matched"], o["count"] + f["count"] - f["matched"])}
+    return res
+
+
 def _spectrum_entries(sums, cells, wavelength):
     """(..., R, 3) sums P_o, P_f, C and the (..., R)-broadcastable number of coefficients behind each -> the entries of "spectrum"; the
     leading axes (none, or T) are kept"""
@@ -463,8 +534,8 @@ def _lead_scores(rows, thresholds):
 
 
 def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False, spectrum=None,
-              sal=None, nprob=None, objects=None, joint=None):
-    """host: the block (a float64 array laid out as block_parts states for these options; `spectrum` = (H, W), the frame size, `joint` = L,
+              sal=None, nprob=None, tracks=None, objects=None, joint=None):
+    """host: the block (a float64 array laid out as block_layout states for these options; `spectrum` = (H, W), the frame size, `joint` = L,
     the number of levels: include/adnm_hip.h) -> the dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's
     (Shanghai_metrics.py:218-290) as GpuEvaluator.done() states them, from per-frame-index sums; "pooled", "persistence", "advection" and
     "per_lead" apply the same formulas to the pooled tables, the baselines' tables and the single rows.  `fss`: "fss" {n: {thr: 2C / (A + F)}},
@@ -477,7 +548,8 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     ops.objects_spec takes): "objects" = object_entries of the table's sum over the horizon, and under "per_lead" object_entries of the table.
     `sal` (what ops.sal_spec takes; passed BY NAME, its position in front of `objects` is not part of the interface): "sal" = sal_entries of the
     table's sum over the horizon, and under "per_lead" sal_entries of the table.  `nprob` (the scales; BY NAME): "nprob" = nprob_entries of the
-    table's sum over the horizon, and under "per_lead" nprob_entries of the table."""
+    table's sum over the horizon, and under "per_lead" nprob_entries of the table.  `tracks` (what ops.tracks_spec takes; BY NAME): "tracks" =
+    track_entries of the table.  Its arrays are per lead time already, so per_lead=True adds nothing for tracks."""
     nthr, T = len(thresholds), seq_len
     pools, fss = tuple(pools), tuple(fss)
     spectrum = tuple(int(v) for v in spectrum) if spectrum else None
@@ -486,15 +558,15 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     joint = int(joint) if joint else None
     if joint is not None and not ops.MIN_JOINT_LEVELS <= joint <= ops.MAX_JOINT_LEVELS:
         raise ValueError(f"aggregate: joint is the number of levels, {ops.MIN_JOINT_LEVELS}..{ops.MAX_JOINT_LEVELS}, or None; got {joint}")
-    objects, sal, nprob = ops.objects_spec(objects), ops.sal_spec(sal), ops.fss_scales(nprob)
-    parts, total = block_parts(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, objects=objects)
+    objects, sal, nprob, tracks = ops.objects_spec(objects), ops.sal_spec(sal), ops.fss_scales(nprob), ops.tracks_spec(tracks)
+    parts, total = block_layout(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, tracks=tracks, objects=objects)
     blk = np.asarray(block, dtype=np.float64)
     if blk.shape != (total,):
         raise ValueError(f"aggregate: a block of {total} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
                          f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + (", advection" if advection else "")
                          + (f", spectrum of {spectrum[0]} x {spectrum[1]} frames" if spectrum else "") + (f", a joint histogram of {joint} levels" if joint else "")
                          + (", objects" if objects else "") + (", sal" if sal else "") + (f", nprob {nprob}" if nprob else "")
-                         + f"; got {blk.shape}")
+                         + (", tracks" if tracks else "") + f"; got {blk.shape}")
     tabs = {p.name: blk[p.offset:p.offset + p.size].reshape(p.shape) for p in parts}
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
     tab = tabs["main"][HEADER:].reshape(T, 4 * nthr + 3)
@@ -548,6 +620,8 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
             yield "sal", sal_entries(tabs["sal"] if lead else tabs["sal"].sum(axis=0), thresholds, sal)
         if nprob:
             yield "nprob", nprob_entries(tabs["nprob"] if lead else tabs["nprob"].sum(axis=0), nprob, thresholds)
+        if tracks and not lead:
+            yield "tracks", track_entries(tabs["tracks"], samples, thresholds, T, tracks)
     res.update(optional(False))
     if per_lead:
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -561,7 +635,7 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
 
 class Validator(ForwardClient):
     def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False,
-                 fss=None, advection=None, spectrum=False, objects=None, advection_flow=False, sal=None, nprob=None, joint=False):
+                 fss=None, advection=None, spectrum=False, objects=None, advection_flow=False, sal=None, nprob=None, tracks=None, joint=False):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -591,6 +665,7 @@ class Validator(ForwardClient):
         if nprob is True and not self.fss:
             raise ValueError("Validator: nprob=True takes the fss scales; give fss= as well, or the scales themselves")
         self.nprob = self.fss if nprob is True else ops.fss_scales(None if nprob is False else nprob)   # the scales, () for none; ValueError on a bad entry
+        self.tracks = ops.tracks_spec(tracks)   # min_volume, or None; ValueError on a bad entry
         self._parts, _ = self._table(None)   # the spectrum part comes with the block: its size follows the epoch's frames
         for part in self._parts:
             if len(part.pools) > ops.MAX_POOLS:   # a baseline's pass; pool_pairs has bounded the forecast's
@@ -604,9 +679,9 @@ class Validator(ForwardClient):
 
     # ---- device state
     def _table(self, frame):
-        """block_parts for this Validator's options; frame: (H, W) of the epoch, which sizes the spectrum part (None: without that part)"""
-        return block_parts(self.seq_len, len(self.thresholds), self.pools, self.persistence, self.fss, bool(self.advection),
-                           frame if self.spectrum else None, self._levels, sal=self.sal, nprob=self.nprob, objects=self.objects)
+        """block_layout for this Validator's options; frame: (H, W) of the epoch, which sizes the spectrum part (None: without that part)"""
+        return block_layout(self.seq_len, len(self.thresholds), self.pools, self.persistence, self.fss, bool(self.advection),
+                           frame if self.spectrum else None, self._levels, sal=self.sal, nprob=self.nprob, tracks=self.tracks, objects=self.objects)
 
     def _block_for(self, device):
         """ONE allocation, the parts of block_parts; done() reduces it with one all-reduce"""
@@ -668,6 +743,9 @@ class Validator(ForwardClient):
             elif part.kind == "nprob":   # (no workspace: the query in open() answered 0)
                 lib.call("adnm_valid_nprob_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, ops.fss_table(self.nprob),
                          len(self.nprob), None, 0, B * T, T, H, W, stream)
+            elif part.kind == "tracks":
+                lib.call("adnm_valid_tracks_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, self.tracks,
+                         ent["ws_tracks"].data_ptr(), ent["ws_tracks"].numel(), B * T, T, H, W, stream)
             else:   # objects
                 ws = ent["ws_objects"]
                 lib.call("adnm_valid_objects_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, self.objects,
@@ -693,7 +771,7 @@ class Validator(ForwardClient):
         ws_ssim = None
         if self.ssim and H > 10 and W > 10:   # 11 x 11 windows need a valid region; smaller frames: SSIM is None
             ws_ssim = torch.empty(max(int(lib.query("adnm_valid_ssim_accum_ws_bytes", B * T, T, H, W, nthr)), 16), dtype=torch.uint8, device=dev)
-        ws_pool = ws_fss = adv = motion = flow = ws_trec = ws_spectrum = ws_joint = ws_objects = ws_sal = None
+        ws_pool = ws_fss = adv = motion = flow = ws_trec = ws_spectrum = ws_joint = ws_objects = ws_sal = ws_tracks = None
         passes = [p.pools for p in self._parts if p.kind == "pool"]
         if passes:   # the passes follow one another on one stream: one workspace
             ws_pool = workspace("adnm_valid_pool_accum_ws_bytes", [(B * T, T, H, W, nthr, ops.pool_table(pools), len(pools)) for pools in passes],
@@ -735,8 +813,12 @@ class Validator(ForwardClient):
         if self.nprob and int(lib.query("adnm_valid_nprob_accum_ws_bytes", B * T, T, H, W, nthr, ops.fss_table(self.nprob), len(self.nprob))) != 0:
             raise RuntimeError(f"Validator: nprob on {B * T} frames of {H} x {W} is outside adnm_valid_nprob_accum's limits (frames <= 65535, H and W < 32768, "
                                "H*W < 2^24)")
+        if self.tracks:
+            ws_tracks = workspace("adnm_valid_tracks_accum_ws_bytes", [(B * T, T, H, W, nthr)],
+                                  f"tracks on {B * T} frames in volumes of {T} x {H} x {W} are outside adnm_valid_tracks_accum's limits (frames <= 65535, "
+                                  f"{ops.TRACK_LIMITS})")
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=ws, ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss,
-                   ws_spectrum=ws_spectrum, ws_joint=ws_joint, ws_objects=ws_objects, ws_sal=ws_sal, adv=adv, motion=motion, flow=flow, ws_trec=ws_trec,
+                   ws_spectrum=ws_spectrum, ws_joint=ws_joint, ws_objects=ws_objects, ws_sal=ws_sal, ws_tracks=ws_tracks, adv=adv, motion=motion, flow=flow, ws_trec=ws_trec,
                    loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
         self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
@@ -837,7 +919,10 @@ class Validator(ForwardClient):
         sal: plus "sal" {"min_area", "intensity", thr: {"A", "abs_A", "S", "abs_S", "L1", "L2", "L", "frames_A", "frames_L1", "frames_S",
         "missed_frames", "false_frames"}} (sal_entries of the table summed over the horizon) and "per_lead"/"sal", the same with a leading T axis.
         nprob: plus "nprob" {n: {thr: {"histogram", "base_rate", "brier", "reliability", "resolution", "uncertainty", "brier_skill", "roc",
-        "roc_area", "reliability_diagram"}}} (nprob_entries of the table summed over the horizon) and "per_lead"/"nprob", the same with a leading T axis."""
+        "roc_area", "reliability_diagram"}}} (nprob_entries of the table summed over the horizon) and "per_lead"/"nprob", the same with a leading T axis.
+        tracks: plus "tracks" {"min_volume", thr: {"target", "forecast", "count_bias", "duration_bias", "survival_bias", "track_POD", "track_FAR",
+        "track_CSI"}} (track_entries of the table).  Its births, deaths, alive and survival arrays are per lead time already, so per_lead=True
+        adds nothing for tracks."""
         if self._block is None or self._frame is None:
             raise RuntimeError("Validator.done: no batch since the last reset")
         blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
@@ -846,7 +931,7 @@ class Validator(ForwardClient):
         area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
         res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead,
                         fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None, joint=self._levels, objects=self.objects,
-                        sal=dict(min_area=self.sal[0], intensity=self.sal[1]) if self.sal else None, nprob=self.nprob)
+                        sal=dict(min_area=self.sal[0], intensity=self.sal[1]) if self.sal else None, nprob=self.nprob, tracks=self.tracks)
         if self.advection_flow:
             res["advection"]["scheme"] = "flow"
         if reset:

@@ -1,11 +1,12 @@
 // The scored pair: what every Validator score that compares a forecast with a target is handed, stated ONCE.
 //
 // An entry point of this contract (adnm_valid_pool_accum, adnm_valid_fss_accum, adnm_valid_nprob_accum: neighbour.hip; adnm_valid_spectrum_accum: spectrum.hip;
-// adnm_valid_joint_accum: joint.hip; adnm_valid_objects_accum: objects.hip; adnm_valid_sal_accum: sal.hip) takes
+// adnm_valid_joint_accum: joint.hip; adnm_valid_objects_accum: objects.hip; adnm_valid_sal_accum: sal.hip; adnm_valid_tracks_accum: tracks.hip) takes
 //   the forecast   `frames` frames addressed by (pred, pred_sample_stride, pred_frame_stride): frame f = b * T + t starts at
 //                  pred + b * sstride + t * fstride.  fstride = 0 holds one frame for all T lead times (the persistence baseline);
 //   the target     contiguous, frame f at target + f * hw;
-//   the table      doubles in the Validator's one allocation, ADDED to, row t = f mod T;
+//   the table      doubles in the Validator's one allocation, ADDED to, row t = f mod T (the ONE deviation: a track of tracks.hip spans frames and
+//                  belongs to no single frame index, so that table is (2, nthr, 7 + 4 T) with its per-frame entries as columns);
 //   a workspace    of at least the entry point's *_ws_bytes;
 // and, where it counts events, up to kMaxThr thresholds from a host array.  pair_check is the first thing each of them calls: a stride
 // or alignment mistake is refused there, on the host, before it can become an out-of-bounds read.  A new score writes its own limits

@@ -1015,6 +1015,53 @@ int adnm_object_moments(const float* src, int64_t sample_stride, int64_t frame_s
                         int64_t min_area, const uint16_t* intensity_host, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t H,
                         int64_t W, adnm_stream_t stream);
 
+/* Space-time rain-cell tracks by connected-component labelling of the (t, y, x) event volume: how long cells live, when
+ * they are born and die, and how many of the cells of the first lead time survive to each later one.  This is the space-time object of MODE
+ * Time Domain (MET).  The reference has no object score; the yardstick is scipy.ndimage.label with the full 3 x 3 x 3 structure on the CPU
+ * (tests/tracks_ref.py), integer for integer and voxel for voxel.  Field, quantisation and event are those of the object scores above.
+ *   track         a 26-connected component (|dt|, |dy|, |dx| <= 1) of the event voxels of ONE sample's (T, H, W) volume of ONE field.  Samples
+ *                 never connect; frames do not wrap.  A cell that moves at most 1 px per frame stays one track however thin it is.
+ *   label         1 + (t*H*W + y*W + x) of the track's first voxel, the smallest flat index inside the sample's volume; the background is 0.
+ *   per track     t0 the frame of the first voxel, t1 the last frame holding one of its voxels, d = t1 - t0 + 1, v its voxels; matched when
+ *                 any of its voxels is an event of the OTHER field at the same threshold.
+ *   min_volume    a track of fewer than min_volume (>= 1) voxels is ignored in every column and labelled 0.
+ * table: adnm_valid_tracks_block_bytes(T, nthr) = 8 * 2 * nthr * C bytes, C = 7 + 4 T, 8-byte aligned device memory, zeroed by the caller, all
+ *   double, shape (2, nthr, C): [field][k], field 0 = target, 1 = forecast, summed over every sample so far.  A track belongs to no single
+ *   frame index, so this table has NO leading T axis (the one deviation from the scored pair's "row t = f mod T").  Columns:
+ *     [0] tracks N   [1] SUM v   [2] SUM v^2   [3] SUM d   [4] matched tracks   [5] SUM v of the matched tracks   [6] spanning tracks (t0 = 0
+ *     and t1 = T - 1)   [7 + t] births: tracks with t0 = t   [7 + T + t] deaths: tracks with t1 = t   [7 + 2T + t] deaths of the initial
+ *     tracks: t1 = t among those with t0 = 0   [7 + 3T + d - 1] the duration histogram.
+ *   Hence SUM births = SUM deaths = SUM hist = N, SUM deaths0 = births[0], deaths0[T - 1] = spanning, SUM d = SUM (k + 1) hist[k].
+ *   Every addend is an integer, and the sums are exact while SUM v^2 < 2^53: a volume has at most 2^22 voxels, so one sample adds at most
+ *   2^44; at 20 x 128^2 a sample adds at most 2^36.7 and more than 80 000 all-event samples fit.
+ * adnm_valid_tracks_accum ADDS a batch; the arguments are adnm_valid_objects_accum's with min_volume in place of min_area.  A held frame
+ *   (pred_frame_stride = 0) is legal and gives only spanning tracks.  Per chunk of thresholds, four launches in stream order, no workgroup
+ *   waiting for another one: (1) a workgroup of 1024 lanes per (frame, threshold) labels the frame's 8-connected objects of both fields with
+ *   the device code of adnm_valid_objects_accum and writes, per voxel, the parent as an index into the sample's volume, at an object's first
+ *   pixel its area and matched flag, the frame index, and the event bits (a plane per frame, padded to whole ballots); (2) a workgroup per
+ *   (frame boundary, threshold, field) unites every event voxel with its event neighbours in the 3 x 3 window of the frame before, through
+ *   the same lock-free union on the global words with agent-scope atomics; (3) every object's first pixel finds its track's root and adds
+ *   its area, flag and frame to the root's words with integer atomics; (4) the roots of at least min_volume voxels add their columns to u64
+ *   LDS counters, whose non-zero entries go to the table as double atomics: integers below 2^53, the same bits on every run.
+ *   termination   a parent only decreases, so a find takes at most T*H*W steps; after a lost race the larger of a union's two roots is
+ *                 strictly smaller than before, so a union ends within T*H*W rounds and none is ever dropped.
+ *   ws            adnm_valid_tracks_accum_ws_bytes = c * 2 * frames * 4 * (3 H W + 2 ceil(H W / 64)) with c = the thresholds per chunk: all
+ *                 nthr where that stays within 256 MB, else as many as do, at least one.  Never NULL; what it held does not matter.
+ * adnm_label_tracks writes the int32 label volume (frames, H, W) of ONE field at ONE threshold with the same device code; every element is
+ *   written, 0 for the background and for dropped tracks.  Frame f = b*T + t starts at src + b*sample_stride + t*frame_stride.
+ *   adnm_label_tracks_ws_bytes = frames * 4 * (3 H W + 2 ceil(H W / 64)); never NULL.
+ * Limits, refused before any launch (ADNM_EINVAL): a null pointer; pred / target / src / labels not 4-byte or table / ws not 8-byte aligned;
+ *   nthr outside 1..8; min_volume < 1; T < 1 or not dividing frames; frames > 65535; H or W < 1; H * W > 65 536; T * H * W > 2^22; a frame
+ *   stride neither 0 nor >= H*W; a sample stride < 0; ws_bytes below the query.  The queries return -1. */
+int64_t adnm_valid_tracks_block_bytes(int64_t T, int64_t nthr);
+int64_t adnm_valid_tracks_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr);
+int adnm_valid_tracks_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                            const float* thresholds_host, int64_t nthr, float value_scale, int64_t min_volume, void* ws, int64_t ws_bytes,
+                            int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
+int64_t adnm_label_tracks_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W);
+int adnm_label_tracks(const float* src, int64_t sample_stride, int64_t frame_stride, void* labels_i32, float thr, float value_scale,
+                      int64_t min_volume, void* ws, int64_t ws_bytes, int64_t frames, int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
+
 /* The output side (pic_results.py:104-184 of the reference): a forecast as the bytes a consumer keeps, in ONE launch.
  * adnm_forecast_render: pred contiguous fp32 (B, T, H, W), 4-byte aligned.  fields: (B, T, H, W) uint8 or NULL.  strip: (B, H, Ws, 4) uint8
  *   (RGBA, 4-byte aligned) or NULL, Ws = n*W + (n-1)*gap, holding the n = ceil((T - frame_start) / frame_step) frames frame_start,
