@@ -3394,6 +3394,43 @@ def fss_sums(truth, pred, thresholds, value_scale, scales):
                        table_shape=(frames, len(ns), 3 * len(thr)), args=((ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale), tab, len(ns)))
 
 
+# ======================================================================================= intensity-scale block sums (csrc/neighbour.hip: valid_iscale_accum)
+MAX_ISCALE_SIDE = 1024
+
+
+def intensity_scale_levels(H, W):
+    """the frame size -> (P, L): the side of the zero-padded domain the intensity-scale skill score is taken on, the smallest power of two
+    >= max(H, W), and L = log2 P; the scales are 2^j px for j = 0 .. L.  ValueError outside adnm_valid_iscale_accum's limits, 1 <= H, W <= 1024."""
+    for v in (H, W):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"intensity_scale: H and W are integers, got {H!r} x {W!r}")
+    H, W = int(H), int(W)
+    if not (1 <= H <= MAX_ISCALE_SIDE and 1 <= W <= MAX_ISCALE_SIDE):
+        raise ValueError(f"intensity_scale: frames of 1..{MAX_ISCALE_SIDE} pixels a side (larger frames are out of scope), got {H} x {W}")
+    L = (max(H, W) - 1).bit_length()
+    return 1 << L, L
+
+
+def intensity_scale_sums(truth, pred, thresholds, value_scale):
+    """truth / pred: fp32 GPU tensors (..., H, W) of the same shape -> int64 (frames, L + 1, 3 * nthr) on the device, (P, L) =
+    intensity_scale_levels(H, W): per frame and level l A = sum o^2, F = sum f^2, C = sum o f per threshold, o and f the numbers of truth and
+    pred events in the 2^l x 2^l blocks that tile the P x P domain from its origin (zeros outside the frame), on the fields quantised as
+    adnm_eval_counts quantises them.  Exact.  The one-shot use of adnm_valid_iscale_accum (T = frames); validate.intensity_scale_entries reads it."""
+    _pair("intensity_scale_sums", truth, pred, None, "(..., H, W)")
+    thr = [float(t) for t in thresholds]
+    if not 1 <= len(thr) <= 8:
+        raise ValueError("intensity_scale_sums: 1..8 thresholds")
+    H, W = truth.shape[-2:]
+    _, L = intensity_scale_levels(H, W)
+    t, p = truth.contiguous(), pred.contiguous()
+    frames = t.numel() // (H * W)
+    out = _score_once("adnm_valid_iscale_accum", t, p, frames, dims=(H, W), query_tail=(len(thr),),
+                      limits=f"intensity_scale_sums: {frames} frames of {H} x {W} are outside adnm_valid_iscale_accum's limits (1 <= frames <= 65535, "
+                      f"H and W <= {MAX_ISCALE_SIDE})",
+                      table_shape=(frames, L + 1, 3 * len(thr)), args=((ctypes.c_float * len(thr))(*thr), len(thr), float(value_scale)))
+    return out.to(torch.int64)   # integers in doubles: exact
+
+
 # ======================================================================================= neighbourhood probability (csrc/neighbour.hip: valid_nprob_accum)
 def nprob_layout(scales):
     """scales (what fss_scales takes) -> (((at_o0, at_o1), ...) per scale, S): a (t, k) row of adnm_valid_nprob_accum's table holds S doubles,

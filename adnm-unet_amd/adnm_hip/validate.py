@@ -15,7 +15,7 @@ and aggregates it exactly as GpuEvaluator.done() does.
 
 Every option below adds tables of its own behind that block, in the same allocation.  block_parts is the ONE statement of which tables
 there are and where each lies: the allocation, the launches (one per table, in the table's order) and aggregate all read it (through
-block_layout, which takes `tracks` as well; block_parts keeps the parameter list it had before the tracks arrived).  The defaults
+block_tables, which states the rows; block_layout and block_parts keep the parameter lists they had before later tables arrived).  The defaults
 allocate and launch nothing new.
 
 Validator(..., pools=(4, 16, (16, 8)), persistence=True) adds neighbourhood scores and the persistence baseline:
@@ -64,6 +64,11 @@ device and adds the number of tracks, their volumes and durations, the matched o
 present at the first lead and a duration histogram into a (2, nthr, 7 + 4 T) table; done() reports lifetimes, the survival curve of the initial
 cells and the track POD / FAR / CSI (track_entries).
 
+Validator(..., intensity_scale=True) adds the intensity-scale skill score (DESIGN.md §4t): csrc/neighbour.hip::valid_iscale_accum adds, per frame
+index, threshold and level l = 0 .. L, the integer sums A, F, C of the squared event counts over the 2^l x 2^l blocks of the zero-padded
+P x P domain into a (T, L + 1, 3 nthr) table, for the forecast and for each baseline there is; done() reports the MSE, the skill and the
+energies of the binary error's Haar components of scale 1, 2, 4, ... P px (intensity_scale_entries).
+
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
@@ -98,7 +103,7 @@ def baseline_pools(pools):
 
 
 class Part(NamedTuple):
-    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint / objects / sal / nprob / tracks, `field` the field it scores against the target
+    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint / objects / sal / nprob / iscale / tracks, `field` the field it scores against the target
     (pred: the forecast, last: the last input frame held, adv: that frame advected; None for main), `pools` the (size, stride) pairs of a
     pool part's pass, `offset` its place in the block in doubles"""
     name: str
@@ -113,14 +118,19 @@ class Part(NamedTuple):
         return math.prod(self.shape)
 
 
-def block_layout(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, tracks=None, objects=None):
+def block_tables(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, tracks=None, objects=None,
+                 iscale=None):
     """-> (the parts of the ONE allocation in their order, its doubles).  The order of the block, and of the launches that fill it, is stated
-    here and nowhere else.  pools: (size, stride) pairs; fss: scales; spectrum: (H, W) of the frames, or None; joint: the levels L, or None;
+    here and nowhere else: block_layout and block_parts are its callers with the parameter lists they had, the Validator and aggregate go
+    through this one.  pools: (size, stride) pairs; fss: scales; spectrum: (H, W) of the frames, or None; joint: the levels L, or None;
     objects: min_area, or None; sal: what ops.sal_spec returns, or None.  `sal` is passed BY NAME: it stands in front of `objects`, which
     stays the last parameter, and its position may move when a further table arrives.  nprob: the scales of the neighbourhood probability's
     histogram, or None; passed BY NAME as well, for the same reason.  tracks: min_volume, or None; BY NAME too: its table, (2, nthr, 7 + 4 T)
-    with no leading T axis, is the last one whatever its place here."""
+    with no leading T axis, is the last one whatever its place here.  iscale: (H, W) of the frames, or None; BY NAME: the intensity-scale
+    tables (T, L + 1, 3 * nthr), L from ops.intensity_scale_levels (ValueError outside its limits), of the forecast and of each baseline
+    there is, directly in front of the tracks."""
     pools, fss, nprob = tuple(pools), tuple(fss), tuple(nprob or ())
+    levels = (T, ops.intensity_scale_levels(*iscale)[1] + 1, 3 * nthr) if iscale else ()
     base = baseline_pools(pools)
     pooled, scaled = (T, len(base), 4 * nthr), (T, len(fss), 3 * nthr)
     rows = (("main", "main", None, (), (HEADER + T * (4 * nthr + 3),), True),
@@ -135,6 +145,9 @@ def block_layout(T, nthr, pools=(), persistence=False, fss=(), advection=False, 
             ("objects", "objects", "pred", (), (T, 2, nthr, ops.OBJ_COLS), objects),
             ("sal", "sal", "pred", (), (T, nthr, ops.SAL_COLS), sal),
             ("nprob", "nprob", "pred", (), (T, nthr, ops.nprob_layout(nprob)[1]), nprob),
+            ("iscale", "iscale", "pred", (), levels, iscale),
+            ("persistence/iscale", "iscale", "last", (), levels, iscale and persistence),
+            ("advection/iscale", "iscale", "adv", (), levels, iscale and advection),
             ("tracks", "tracks", "pred", (), (2, nthr, ops.track_cols(T)[0]), tracks))
     parts, at = [], 0
     for *head, shape, present in rows:
@@ -144,15 +157,20 @@ def block_layout(T, nthr, pools=(), persistence=False, fss=(), advection=False, 
     return parts, at
 
 
+def block_layout(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, tracks=None, objects=None):
+    """block_tables without the tables that came after the tracks': the parameter list callers and tests have pinned."""
+    return block_tables(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, tracks=tracks, objects=objects)
+
+
 def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, objects=None):
-    """block_layout without the tables that came after the neighbourhood probability's: the parameter list callers and tests have pinned.
-    The Validator and aggregate go through block_layout, which states the rows."""
-    return block_layout(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, objects=objects)
+    """block_tables without the tables that came after the neighbourhood probability's: the parameter list callers and tests have pinned.
+    The Validator and aggregate go through block_tables, which states the rows."""
+    return block_tables(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, objects=objects)
 
 
 def _doubles(names, *options, **more):
-    """the doubles of the named parts of block_layout(*options, **more), 0 for a part that is not there"""
-    size = {p.name: p.size for p in block_layout(*options, **more)[0]}
+    """the doubles of the named parts of block_tables(*options, **more), 0 for a part that is not there"""
+    size = {p.name: p.size for p in block_tables(*options, **more)[0]}
     return tuple(size.get(n, 0) for n in names)
 
 
@@ -200,6 +218,12 @@ def nprob_doubles(seq_len, nthr, nprob=None):
 def tracks_doubles(seq_len, nthr, tracks=None):
     """-> doubles of the tracks table (2, nthr, 7 + 4 T); tracks: what ops.tracks_spec takes (None / False for none)"""
     return _doubles(("tracks",), seq_len, nthr, tracks=ops.tracks_spec(tracks))[0]
+
+
+def iscale_doubles(seq_len, nthr, frame=None, persistence=False, advection=False):
+    """-> (doubles of the forecast's intensity-scale table (T, L + 1, 3 * nthr), of the persistence baseline's, of the advection baseline's);
+    frame: (H, W), or None / False for none"""
+    return _doubles(("iscale", "persistence/iscale", "advection/iscale"), seq_len, nthr, persistence=persistence, advection=advection, iscale=frame or None)
 
 
 def _counts(hist):
@@ -479,6 +503,66 @@ def track_entries(rows, samples, thresholds, T, min_volume=1):
     return res
 
 
+def intensity_scale_entries(rows, frames, shape, thresholds):
+    """rows: (..., L + 1, 3 * nthr) integer sums A, F, C per level and threshold (ops.intensity_scale_sums' tensor summed over its frames, the
+    Validator's table or its sum over the horizon), `frames` the number n of frames behind every row (samples for a row of the table,
+    samples * T for the sum over the horizon) and shape = (H, W) of the frames -> the entries of done()["intensity_scale"], the leading axes
+    (none, or T) kept in front of every array.  (P, L) = ops.intensity_scale_levels(H, W), N = n P^2, D_l = A_l + F_l - 2 C_l and
+    E_l(X) = X_l / (4^l N), the mean square of the field of block means:
+      "scale_px" 2^j for j = 0 .. L (int64), "domain_px" P, "levels" L; then per threshold key
+        "mse" (L + 1): E_j(D) - E_(j+1)(D) for j < L and E_L(D) for the domain mean, the MSE of the Haar component of scale 2^j of the binary
+            error; formed as (4 D_j - D_(j+1)) / (4^(j+1) N) with the numerator in integers, so a component is never below 0;
+        "mse_total" D_0 / N = (FP + FN) / N (the components sum to it), "mse_share" mse / mse_total;
+        "base_rate" e = A_0 / N, "bias" B = F_0 / A_0, "mse_random" B e (1 - e) + e (1 - B e) (a random forecast of the same bias; 2 e (1 - e)
+            when unbiased: Casati 2004);
+        "skill" 1 - mse (L + 1) / mse_random (its mean over the scales is 1 - mse_total / mse_random);
+        "energy_target", "energy_forecast" (L + 1): the same split of A and of F (they sum to e and to B e);
+        "energy_rel_diff" (En_f - En_o) / (En_f + En_o).
+    A division by zero gives NaN."""
+    if torch.is_tensor(rows):
+        rows = rows.detach().cpu().numpy()
+    r = np.asarray(rows)
+    P, L = ops.intensity_scale_levels(*shape)
+    nthr = len(thresholds)
+    if r.ndim < 2 or r.shape[-2:] != (L + 1, 3 * nthr):
+        raise ValueError(f"intensity_scale: rows are (..., {L + 1}, {3 * nthr}) for {nthr} thresholds and frames of {shape[0]} x {shape[1]}, got {r.shape}")
+    if r.dtype.kind == "f":
+        if not (np.isfinite(r).all() and (r == np.rint(r)).all()):
+            raise ValueError("intensity_scale: the rows hold integer sums")
+    elif r.dtype.kind not in "iu":
+        raise ValueError(f"intensity_scale: the rows hold integer sums, got {r.dtype}")
+    r = r.astype(np.int64)
+    if (r < 0).any():
+        raise ValueError("intensity_scale: the rows hold sums >= 0")
+    N = np.asarray(frames, dtype=np.float64)[..., None] * float(P * P)      # (..., 1): broadcasts over the levels
+    if N.ndim > r.ndim - 1:
+        raise ValueError(f"intensity_scale: frames {np.shape(frames)} do not fit rows {r.shape}")
+    four = 4.0 ** np.arange(L + 1)
+
+    def ratio(a, b):
+        """a / b in float64, NaN where b is 0"""
+        a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(b == 0, np.nan, a / b)
+
+    def split(x):
+        """(..., L + 1) integer sums X_l -> (..., L + 1) E_j(X) - E_(j+1)(X), the last one E_L(X)"""
+        num = 4 * x
+        num[..., :-1] -= x[..., 1:]
+        return ratio(num, 4.0 * four * N)
+    res = {"scale_px": 2 ** np.arange(L + 1, dtype=np.int64), "domain_px": P, "levels": L}
+    for k, thr in enumerate(thresholds):
+        a, f, c = r[..., 3 * k], r[..., 3 * k + 1], r[..., 3 * k + 2]
+        d = a + f - 2 * c
+        mse, en_o, en_f = split(d), split(a), split(f)
+        total, base, bias = ratio(d[..., :1], N), ratio(a[..., :1], N), ratio(f[..., :1], a[..., :1])      # (..., 1)
+        rand = bias * base * (1.0 - base) + base * (1.0 - bias * base)
+        res[_thr_key(thr)] = {"mse": mse, "skill": 1.0 - ratio(mse * (L + 1), rand), "mse_share": ratio(mse, total), "mse_total": _scalar(total[..., 0]),
+                              "mse_random": _scalar(rand[..., 0]), "base_rate": _scalar(base[..., 0]), "bias": _scalar(bias[..., 0]),
+                              "energy_target": en_o, "energy_forecast": en_f, "energy_rel_diff": ratio(en_f - en_o, en_f + en_o)}
+    return res
+
+
 def _spectrum_entries(sums, cells, wavelength):
     """(..., R, 3) sums P_o, P_f, C and the (..., R)-broadcastable number of coefficients behind each -> the entries of "spectrum"; the
     leading axes (none, or T) are kept"""
@@ -534,7 +618,7 @@ def _lead_scores(rows, thresholds):
 
 
 def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False, spectrum=None,
-              sal=None, nprob=None, tracks=None, objects=None, joint=None):
+              sal=None, nprob=None, tracks=None, intensity_scale=None, objects=None, joint=None):
     """host: the block (a float64 array laid out as block_layout states for these options; `spectrum` = (H, W), the frame size, `joint` = L,
     the number of levels: include/adnm_hip.h) -> the dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's
     (Shanghai_metrics.py:218-290) as GpuEvaluator.done() states them, from per-frame-index sums; "pooled", "persistence", "advection" and
@@ -549,7 +633,9 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     `sal` (what ops.sal_spec takes; passed BY NAME, its position in front of `objects` is not part of the interface): "sal" = sal_entries of the
     table's sum over the horizon, and under "per_lead" sal_entries of the table.  `nprob` (the scales; BY NAME): "nprob" = nprob_entries of the
     table's sum over the horizon, and under "per_lead" nprob_entries of the table.  `tracks` (what ops.tracks_spec takes; BY NAME): "tracks" =
-    track_entries of the table.  Its arrays are per lead time already, so per_lead=True adds nothing for tracks."""
+    track_entries of the table.  Its arrays are per lead time already, so per_lead=True adds nothing for tracks.  `intensity_scale` ((H, W), the
+    frame size; BY NAME): "intensity_scale" = intensity_scale_entries of the table's sum over the horizon, the same under each baseline there
+    is, and under "per_lead" intensity_scale_entries of the tables."""
     nthr, T = len(thresholds), seq_len
     pools, fss = tuple(pools), tuple(fss)
     spectrum = tuple(int(v) for v in spectrum) if spectrum else None
@@ -559,14 +645,16 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     if joint is not None and not ops.MIN_JOINT_LEVELS <= joint <= ops.MAX_JOINT_LEVELS:
         raise ValueError(f"aggregate: joint is the number of levels, {ops.MIN_JOINT_LEVELS}..{ops.MAX_JOINT_LEVELS}, or None; got {joint}")
     objects, sal, nprob, tracks = ops.objects_spec(objects), ops.sal_spec(sal), ops.fss_scales(nprob), ops.tracks_spec(tracks)
-    parts, total = block_layout(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, tracks=tracks, objects=objects)
+    iscale = tuple(int(v) for v in intensity_scale) if intensity_scale else None
+    parts, total = block_tables(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, tracks=tracks, objects=objects,
+                                iscale=iscale)   # ValueError outside the intensity-scale limits
     blk = np.asarray(block, dtype=np.float64)
     if blk.shape != (total,):
         raise ValueError(f"aggregate: a block of {total} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
                          f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + (", advection" if advection else "")
                          + (f", spectrum of {spectrum[0]} x {spectrum[1]} frames" if spectrum else "") + (f", a joint histogram of {joint} levels" if joint else "")
                          + (", objects" if objects else "") + (", sal" if sal else "") + (f", nprob {nprob}" if nprob else "")
-                         + (", tracks" if tracks else "") + f"; got {blk.shape}")
+                         + (f", intensity_scale of {iscale[0]} x {iscale[1]} frames" if iscale else "") + (", tracks" if tracks else "") + f"; got {blk.shape}")
     tabs = {p.name: blk[p.offset:p.offset + p.size].reshape(p.shape) for p in parts}
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
     tab = tabs["main"][HEADER:].reshape(T, 4 * nthr + 3)
@@ -592,7 +680,13 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
         ent = dict(counted(rows[:, 0], lead), pooled={p: counted(rows[:, order.index(p)], lead) for p in pools})
         if fss:
             ent["fss"] = (_fss_lead if lead else _fss_scores)(tabs[name + "/fss"], fss, thresholds)
+        if iscale:
+            ent["intensity_scale"] = scales(tabs[name + "/iscale"], lead)
         return ent
+
+    def scales(itab, lead):
+        """(T, L + 1, 3 * nthr) intensity-scale sums of one field -> its entries over the horizon, or per frame index"""
+        return intensity_scale_entries(itab if lead else itab.sum(axis=0), samples if lead else samples * T, iscale, thresholds)
 
     def optional(lead):
         """the entries the options add, in the dictionary's order: over the horizon, or (lead) per frame index"""
@@ -620,6 +714,8 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
             yield "sal", sal_entries(tabs["sal"] if lead else tabs["sal"].sum(axis=0), thresholds, sal)
         if nprob:
             yield "nprob", nprob_entries(tabs["nprob"] if lead else tabs["nprob"].sum(axis=0), nprob, thresholds)
+        if iscale:
+            yield "intensity_scale", scales(tabs["iscale"], lead)
         if tracks and not lead:
             yield "tracks", track_entries(tabs["tracks"], samples, thresholds, T, tracks)
     res.update(optional(False))
@@ -635,7 +731,8 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
 
 class Validator(ForwardClient):
     def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False,
-                 fss=None, advection=None, spectrum=False, objects=None, advection_flow=False, sal=None, nprob=None, tracks=None, joint=False):
+                 fss=None, advection=None, spectrum=False, objects=None, advection_flow=False, sal=None, nprob=None, tracks=None, intensity_scale=False,
+                 joint=False):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -666,7 +763,8 @@ class Validator(ForwardClient):
             raise ValueError("Validator: nprob=True takes the fss scales; give fss= as well, or the scales themselves")
         self.nprob = self.fss if nprob is True else ops.fss_scales(None if nprob is False else nprob)   # the scales, () for none; ValueError on a bad entry
         self.tracks = ops.tracks_spec(tracks)   # min_volume, or None; ValueError on a bad entry
-        self._parts, _ = self._table(None)   # the spectrum part comes with the block: its size follows the epoch's frames
+        self.intensity_scale = bool(intensity_scale)
+        self._parts, _ = self._table(None)   # the spectrum and intensity-scale parts come with the block: their sizes follow the epoch's frames
         for part in self._parts:
             if len(part.pools) > ops.MAX_POOLS:   # a baseline's pass; pool_pairs has bounded the forecast's
                 raise ValueError(f"Validator: the {part.name.split('/')[0]} baseline is scored at (1, 1) and at every pool, which makes {len(self.pools) + 1} pools; "
@@ -679,9 +777,11 @@ class Validator(ForwardClient):
 
     # ---- device state
     def _table(self, frame):
-        """block_layout for this Validator's options; frame: (H, W) of the epoch, which sizes the spectrum part (None: without that part)"""
-        return block_layout(self.seq_len, len(self.thresholds), self.pools, self.persistence, self.fss, bool(self.advection),
-                           frame if self.spectrum else None, self._levels, sal=self.sal, nprob=self.nprob, tracks=self.tracks, objects=self.objects)
+        """block_tables for this Validator's options; frame: (H, W) of the epoch, which sizes the spectrum and the intensity-scale parts (None:
+        without those parts)"""
+        return block_tables(self.seq_len, len(self.thresholds), self.pools, self.persistence, self.fss, bool(self.advection),
+                            frame if self.spectrum else None, self._levels, sal=self.sal, nprob=self.nprob, tracks=self.tracks, objects=self.objects,
+                            iscale=frame if self.intensity_scale else None)
 
     def _block_for(self, device):
         """ONE allocation, the parts of block_parts; done() reduces it with one all-reduce"""
@@ -695,6 +795,9 @@ class Validator(ForwardClient):
             raise RuntimeError(f"Validator: one device per Validator (the block is on {self._block.device}, the batch on {device})")
         elif self.spectrum and self._spectrum_frame != self._frame:
             raise RuntimeError(f"Validator: spectrum=True keeps one frame size per Validator (the table in the block is for frames of "
+                               f"{self._spectrum_frame[0]} x {self._spectrum_frame[1]}, the batch has {self._frame[0]} x {self._frame[1]})")
+        elif self.intensity_scale and self._spectrum_frame != self._frame:
+            raise RuntimeError(f"Validator: intensity_scale=True keeps one frame size per Validator (the tables in the block are for frames of "
                                f"{self._spectrum_frame[0]} x {self._spectrum_frame[1]}, the batch has {self._frame[0]} x {self._frame[1]})")
         return self._block
 
@@ -743,6 +846,9 @@ class Validator(ForwardClient):
             elif part.kind == "nprob":   # (no workspace: the query in open() answered 0)
                 lib.call("adnm_valid_nprob_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, ops.fss_table(self.nprob),
                          len(self.nprob), None, 0, B * T, T, H, W, stream)
+            elif part.kind == "iscale":
+                lib.call("adnm_valid_iscale_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, ent["ws_iscale"].data_ptr(),
+                         ent["ws_iscale"].numel(), B * T, T, H, W, stream)
             elif part.kind == "tracks":
                 lib.call("adnm_valid_tracks_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, self.tracks,
                          ent["ws_tracks"].data_ptr(), ent["ws_tracks"].numel(), B * T, T, H, W, stream)
@@ -771,7 +877,7 @@ class Validator(ForwardClient):
         ws_ssim = None
         if self.ssim and H > 10 and W > 10:   # 11 x 11 windows need a valid region; smaller frames: SSIM is None
             ws_ssim = torch.empty(max(int(lib.query("adnm_valid_ssim_accum_ws_bytes", B * T, T, H, W, nthr)), 16), dtype=torch.uint8, device=dev)
-        ws_pool = ws_fss = adv = motion = flow = ws_trec = ws_spectrum = ws_joint = ws_objects = ws_sal = ws_tracks = None
+        ws_pool = ws_fss = adv = motion = flow = ws_trec = ws_spectrum = ws_joint = ws_objects = ws_sal = ws_tracks = ws_iscale = None
         passes = [p.pools for p in self._parts if p.kind == "pool"]
         if passes:   # the passes follow one another on one stream: one workspace
             ws_pool = workspace("adnm_valid_pool_accum_ws_bytes", [(B * T, T, H, W, nthr, ops.pool_table(pools), len(pools)) for pools in passes],
@@ -813,12 +919,16 @@ class Validator(ForwardClient):
         if self.nprob and int(lib.query("adnm_valid_nprob_accum_ws_bytes", B * T, T, H, W, nthr, ops.fss_table(self.nprob), len(self.nprob))) != 0:
             raise RuntimeError(f"Validator: nprob on {B * T} frames of {H} x {W} is outside adnm_valid_nprob_accum's limits (frames <= 65535, H and W < 32768, "
                                "H*W < 2^24)")
+        if self.intensity_scale:   # the passes follow one another on one stream: one workspace
+            ws_iscale = workspace("adnm_valid_iscale_accum_ws_bytes", [(B * T, T, H, W, nthr)],
+                                  f"intensity_scale on {B * T} frames of {H} x {W} is outside adnm_valid_iscale_accum's limits (frames <= 65535, "
+                                  f"H and W <= {ops.MAX_ISCALE_SIDE})")
         if self.tracks:
             ws_tracks = workspace("adnm_valid_tracks_accum_ws_bytes", [(B * T, T, H, W, nthr)],
                                   f"tracks on {B * T} frames in volumes of {T} x {H} x {W} are outside adnm_valid_tracks_accum's limits (frames <= 65535, "
                                   f"{ops.TRACK_LIMITS})")
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=ws, ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss,
-                   ws_spectrum=ws_spectrum, ws_joint=ws_joint, ws_objects=ws_objects, ws_sal=ws_sal, ws_tracks=ws_tracks, adv=adv, motion=motion, flow=flow, ws_trec=ws_trec,
+                   ws_spectrum=ws_spectrum, ws_joint=ws_joint, ws_objects=ws_objects, ws_sal=ws_sal, ws_tracks=ws_tracks, ws_iscale=ws_iscale, adv=adv, motion=motion, flow=flow, ws_trec=ws_trec,
                    loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
         self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
@@ -922,7 +1032,10 @@ class Validator(ForwardClient):
         "roc_area", "reliability_diagram"}}} (nprob_entries of the table summed over the horizon) and "per_lead"/"nprob", the same with a leading T axis.
         tracks: plus "tracks" {"min_volume", thr: {"target", "forecast", "count_bias", "duration_bias", "survival_bias", "track_POD", "track_FAR",
         "track_CSI"}} (track_entries of the table).  Its births, deaths, alive and survival arrays are per lead time already, so per_lead=True
-        adds nothing for tracks."""
+        adds nothing for tracks.
+        intensity_scale: plus "intensity_scale" {"scale_px", "domain_px", "levels", thr: {"mse", "skill", "mse_share", "mse_total", "mse_random",
+        "base_rate", "bias", "energy_target", "energy_forecast", "energy_rel_diff"}} (intensity_scale_entries of the table summed over the
+        horizon), the same under "persistence" and "advection" where those exist, and under "per_lead" with a leading T axis."""
         if self._block is None or self._frame is None:
             raise RuntimeError("Validator.done: no batch since the last reset")
         blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
@@ -931,7 +1044,8 @@ class Validator(ForwardClient):
         area = (H - 10) * (W - 10) if (self.ssim and H > 10 and W > 10) else None
         res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead,
                         fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None, joint=self._levels, objects=self.objects,
-                        sal=dict(min_area=self.sal[0], intensity=self.sal[1]) if self.sal else None, nprob=self.nprob, tracks=self.tracks)
+                        sal=dict(min_area=self.sal[0], intensity=self.sal[1]) if self.sal else None, nprob=self.nprob, tracks=self.tracks,
+                        intensity_scale=self._frame if self.intensity_scale else None)
         if self.advection_flow:
             res["advection"]["scheme"] = "flow"
         if reset:

@@ -5,7 +5,8 @@
 // leaves 3 * nthr uint32 per workgroup, part[frame][tile][pass][3 * nthr], and one fold adds them to the table in double, in a fixed
 // order.  What the two share is written once: the stager, the store of a pass's counts and the fold.  Behind them stand the neighbourhood
 // exceedance probability's histogram (adnm_valid_nprob_accum; §4r), which shares the FSS pass's staging and running sums and flushes an LDS
-// histogram instead of partials, and the probability field itself (adnm_neighbour_prob).
+// histogram instead of partials, and the probability field itself (adnm_neighbour_prob); and the intensity-scale skill score's dyadic
+// block sums (adnm_valid_iscale_accum; §4t), which stage the same bits with no halo and have a fold of their own.
 #include "scored_pair.h"
 
 namespace {
@@ -398,6 +399,230 @@ extern "C" int adnm_valid_fss_accum(const float* pred, int64_t pred_sample_strid
                                                                                             (int)nscale, (double*)table);
   }
   ADNM_CHECK_LAUNCH("valid_fss_fold");
+  return ADNM_OK;
+}
+
+// ---- intensity-scale skill score: sums of squared event counts over dyadic blocks ----
+// The frame sits at the origin of a P x P domain, P the smallest power of two >= max(H, W), zeros outside the frame (the padding FSS uses).
+// Block (l, i, j) is the 2^l x 2^l pixels at (i 2^l, j 2^l); o and f are its target and forecast events.  Per frame index, level
+// l = 0 .. L = log2 P and threshold the statistic is A_l = SUM o^2, F_l = SUM f^2, C_l = SUM o f over the blocks of the level
+// (include/adnm_hip.h: adnm_valid_iscale_accum): the Haar components of the binary error follow from it on the host.
+//   the tile   grid (tiles, frames), one 32 x 32 tile staged ONCE with no halo.  A lane owns one 2 x 2 cell, the lanes in Morton order over
+//              the tile's 16 x 16 cells, so that the 4 lanes that differ in bits 0-1 are a 4 x 4 block, the 16 that differ in bits 0-3 an
+//              8 x 8 block, a wave a 16 x 16 block.  Levels 0 and 1 are counts inside the lane; levels 2, 3 and 4 are two xor shuffles each
+//              on the packed pair (o, f <= 256: 16 bits each); level 5 is the four waves through LDS.  The leaders' squares of two levels
+//              share a dword (a wave's sum is <= 256, 1024, 4096, 16384 at levels 0 .. 3: no carry) and are added across the wave.
+//   the fold   one workgroup per (frame index, threshold): the tile partials of levels 0 .. min(L, 5) added over samples and tiles, and
+//              levels 6 .. L built per frame from the tiles' counts by a 4-to-1 pyramid in LDS, all in uint64; each (l, k) sum is added
+//              to the table once.
+// Integers throughout, no atomics, no workgroup waits for another, every loop bounded at launch.
+namespace {
+constexpr int kIsMaxSide = 1024;                  // P <= 1024: at most 32 x 32 tiles, L <= 10
+constexpr int kIsTileLevels = 6, kIsLevels = 11;  // levels a tile serves (0 .. 5), levels in all (0 .. 10)
+constexpr int kIsPitch = kTile + 4;               // uint16 per staged row: 72 bytes, a row start stays 8-byte aligned
+constexpr int kIsPyramid = 1024 + 256 + 64 + 16 + 4 + 1;
+
+// L of a frame: the smallest L with 2^L >= max(H, W)
+inline int iscale_levels(int64_t H, int64_t W) {
+  int L = 0;
+  while ((int64_t(1) << L) < (H > W ? H : W)) ++L;
+  return L;
+}
+// uint32 per (frame, tile): [level 0 .. nl - 1][3 * nthr] A, F, C of the tile's blocks, then [nthr][2] the tile's two counts
+__host__ __device__ inline int64_t iscale_tile_words(int nl, int64_t nthr) { return (3 * nl + 2) * nthr; }
+
+// the even bits of an 8-bit Morton code
+__device__ __forceinline__ uint32_t iscale_even_bits(uint32_t v) {
+  v &= 0x55u;
+  v = (v | (v >> 1)) & 0x33u;
+  return (v | (v >> 2)) & 0x0fu;
+}
+__device__ __forceinline__ uint64_t iscale_wave_sum64(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
+    v += ((uint64_t)hi << 32) | lo;
+  }
+  return v;
+}
+
+// grid (tiles, frames).  nl = min(L, 5) + 1: the levels written.
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void iscale_tile_kernel(ScoredPair pair, uint32_t* __restrict__ part, int H, int W, int tiles_x, int nl,
+                                                             float value_scale, Thr thr) {
+  __shared__ __attribute__((aligned(8))) uint16_t img[kTile][kIsPitch];
+  __shared__ uint32_t wred[kBlock / 64][kMaxThr][16];   // per wave and threshold: A, F, C of levels 0 .. 4, then the wave's counts (o | f << 16)
+  const int f = blockIdx.y, tile = blockIdx.x, oy = (tile / tiles_x) * kTile, ox = (tile % tiles_x) * kTile;
+  if (oy + kTile <= H && ox + kTile <= W)
+    stage_pair_bits<VEC, kIsPitch, true>(&img[0][0], pair.target(f), pair.forecast(f), H, W, oy, ox, kTile, kTile, value_scale, thr);
+  else
+    stage_pair_bits<VEC, kIsPitch, false>(&img[0][0], pair.target(f), pair.forecast(f), H, W, oy, ox, kTile, kTile, value_scale, thr);
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int cx = (int)iscale_even_bits(threadIdx.x), cy = (int)iscale_even_bits(threadIdx.x >> 1);   // the lane's cell of the 16 x 16
+  const uint32_t r0 = *(const uint32_t*)&img[2 * cy][2 * cx], r1 = *(const uint32_t*)&img[2 * cy + 1][2 * cx];   // two pixels each
+  const uint32_t b0 = r0 & (r0 >> 8), b1 = r1 & (r1 >> 8);   // bit k of a pixel: an event in both fields
+  const bool lead2 = (lane & 3) == 0, lead3 = (lane & 15) == 0;
+#pragma unroll
+  for (int k = 0; k < kMaxThr; ++k)
+    if (k < thr.n) {
+      auto cell = [](uint32_t a, uint32_t b, int sh) {   // the cell's pixels with bit sh set: 0 .. 4
+        const uint32_t s = ((a >> sh) & 0x00010001u) + ((b >> sh) & 0x00010001u);
+        return (s & 0xffffu) + (s >> 16);
+      };
+      const uint32_t o1 = cell(r0, r1, k), f1 = cell(r0, r1, 8 + k), c0 = cell(b0, b1, k);
+      uint32_t v = o1 | (f1 << 16);
+      v += (uint32_t)__shfl_xor((int)v, 1, 64);
+      v += (uint32_t)__shfl_xor((int)v, 2, 64);
+      const uint32_t o2 = v & 0xffffu, f2 = v >> 16;   // <= 16
+      v += (uint32_t)__shfl_xor((int)v, 4, 64);
+      v += (uint32_t)__shfl_xor((int)v, 8, 64);
+      const uint32_t o3 = v & 0xffffu, f3 = v >> 16;   // <= 64
+      v += (uint32_t)__shfl_xor((int)v, 16, 64);
+      v += (uint32_t)__shfl_xor((int)v, 32, 64);
+      const uint32_t o4 = v & 0xffffu, f4 = v >> 16;   // <= 256, the same in every lane
+      // levels 0 | 1 and levels 2 | 3 as 16-bit lanes; o^2 = o for a single pixel
+      uint32_t a01 = o1 | ((o1 * o1) << 16), f01 = f1 | ((f1 * f1) << 16), c01 = c0 | ((o1 * f1) << 16);
+      uint32_t a23 = (lead2 ? o2 * o2 : 0u) | ((lead3 ? o3 * o3 : 0u) << 16), f23 = (lead2 ? f2 * f2 : 0u) | ((lead3 ? f3 * f3 : 0u) << 16),
+               c23 = (lead2 ? o2 * f2 : 0u) | ((lead3 ? o3 * f3 : 0u) << 16);
+      a01 = fss_wave_sum(a01), f01 = fss_wave_sum(f01), c01 = fss_wave_sum(c01);
+      a23 = fss_wave_sum(a23), f23 = fss_wave_sum(f23), c23 = fss_wave_sum(c23);
+      if (lane == 0) {
+        uint32_t* w = wred[wave][k];
+        w[0] = a01 & 0xffffu, w[1] = f01 & 0xffffu, w[2] = c01 & 0xffffu;
+        w[3] = a01 >> 16, w[4] = f01 >> 16, w[5] = c01 >> 16;
+        w[6] = a23 & 0xffffu, w[7] = f23 & 0xffffu, w[8] = c23 & 0xffffu;
+        w[9] = a23 >> 16, w[10] = f23 >> 16, w[11] = c23 >> 16;
+        w[12] = o4 * o4, w[13] = f4 * f4, w[14] = o4 * f4;
+        w[15] = v;
+      }
+    }
+  __syncthreads();
+  const int nout = 3 * thr.n;
+  if ((int)threadIdx.x < nout) {
+    const int k = threadIdx.x / 3, c = threadIdx.x % 3;
+    uint32_t* out = part + ((int64_t)f * gridDim.x + tile) * iscale_tile_words(nl, thr.n);
+    for (int l = 0; l < kIsTileLevels - 1; ++l)
+      if (l < nl) out[l * nout + threadIdx.x] = (wred[0][k][3 * l + c] + wred[1][k][3 * l + c]) + (wred[2][k][3 * l + c] + wred[3][k][3 * l + c]);
+    const uint32_t both = (wred[0][k][15] + wred[1][k][15]) + (wred[2][k][15] + wred[3][k][15]);   // <= 1024 in each half
+    const uint32_t o5 = both & 0xffffu, f5 = both >> 16;
+    if (nl == kIsTileLevels) out[5 * nout + threadIdx.x] = c == 0 ? o5 * o5 : c == 1 ? f5 * f5 : o5 * f5;
+    if (c < 2) out[nl * nout + 2 * k + c] = c == 0 ? o5 : f5;
+  }
+}
+
+// grid (T, nthr).  table[t][l][3k .. 3k+2] += A_l, F_l, C_l of the batch's frames with frame index t
+__global__ __launch_bounds__(kFoldBlock) void iscale_fold_kernel(const uint32_t* __restrict__ part, int tiles_x, int tiles_y, int frames, int T, int nthr,
+                                                                 int L, double* __restrict__ table) {
+  __shared__ uint2 pyr[kIsPyramid];   // (o, f) of the blocks of levels 5, 6, ... of one frame, one level behind the other
+  __shared__ uint64_t red[kFoldBlock / 64][3 * kIsLevels];
+  const int t = blockIdx.x, k = blockIdx.y, B = frames / T, tiles = tiles_x * tiles_y;
+  const int nl = min(L, kIsTileLevels - 1) + 1, nout = 3 * nthr;
+  const int64_t words = iscale_tile_words(nl, nthr);
+  uint64_t acc[kIsLevels][3];
+#pragma unroll
+  for (int l = 0; l < kIsLevels; ++l) acc[l][0] = acc[l][1] = acc[l][2] = 0;
+  for (int i = threadIdx.x; i < B * tiles; i += kFoldBlock) {   // B * tiles <= 65535 * 1024
+    const int b = i / tiles, tile = i % tiles;
+    const uint32_t* q = part + (((int64_t)b * T + t) * tiles + tile) * words + 3 * k;
+#pragma unroll
+    for (int l = 0; l < kIsTileLevels; ++l)
+      if (l < nl) acc[l][0] += q[l * nout], acc[l][1] += q[l * nout + 1], acc[l][2] += q[l * nout + 2];
+  }
+  if (L >= kIsTileLevels) {
+    const int up = L - (kIsTileLevels - 1), PT = 1 << up;   // PT x PT tile places in the domain, tiles_y x tiles_x of them in the frame
+    for (int b = 0; b < B; ++b) {
+      const uint32_t* q = part + ((int64_t)b * T + t) * tiles * words + nl * nout + 2 * k;
+      for (int i = threadIdx.x; i < PT * PT; i += kFoldBlock) {
+        const int ty = i >> up, tx = i & (PT - 1);
+        uint2 v = make_uint2(0u, 0u);
+        if (ty < tiles_y && tx < tiles_x) {
+          const uint32_t* c = q + (int64_t)(ty * tiles_x + tx) * words;
+          v = make_uint2(c[0], c[1]);
+        }
+        pyr[i] = v;
+      }
+      __syncthreads();
+      int src = 0, side = PT;
+#pragma unroll
+      for (int j = 1; j <= kIsLevels - kIsTileLevels; ++j)
+        if (j <= up) {   // (the same for the whole workgroup)
+          const int dst = src + side * side, half = side >> 1;
+          for (int i = threadIdx.x; i < half * half; i += kFoldBlock) {
+            const uint2* p = &pyr[src + 2 * (i / half) * side + 2 * (i % half)];
+            const uint32_t o = (p[0].x + p[1].x) + (p[side].x + p[side + 1].x), fc = (p[0].y + p[1].y) + (p[side].y + p[side + 1].y);   // <= 2^20
+            pyr[dst + i] = make_uint2(o, fc);
+            acc[kIsTileLevels - 1 + j][0] += (uint64_t)o * o, acc[kIsTileLevels - 1 + j][1] += (uint64_t)fc * fc, acc[kIsTileLevels - 1 + j][2] += (uint64_t)o * fc;
+          }
+          __syncthreads();   // the level is there; and after the last one the next frame may rewrite level 5
+          src = dst, side = half;
+        }
+    }
+  }
+#pragma unroll
+  for (int l = 0; l < kIsLevels; ++l)
+    if (l <= L) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uint64_t s = iscale_wave_sum64(acc[l][c]);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][3 * l + c] = s;
+      }
+    }
+  __syncthreads();
+  if ((int)threadIdx.x < 3 * (L + 1)) {
+    const int l = threadIdx.x / 3, c = threadIdx.x % 3;
+    const uint64_t s = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    table[((int64_t)t * (L + 1) + l) * nout + 3 * k + c] += (double)s;
+  }
+}
+
+// the intensity-scale pass's own limits: nullptr, or the one that refuses
+const char* iscale_why(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr) {
+  if (nthr < 1 || nthr > kMaxThr) return "1..8 thresholds";
+  if (const char* w = pair_frames_why(frames, T)) return w;
+  if (H < 1 || W < 1 || H > kIsMaxSide || W > kIsMaxSide) return "H and W must be in [1, 1024]";
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int64_t adnm_valid_iscale_block_bytes(int64_t T, int64_t nthr, int64_t H, int64_t W) {
+  if (T < 1 || T > 65535 || iscale_why(1, 1, H, W, nthr)) return -1;
+  return (int64_t)sizeof(double) * T * (iscale_levels(H, W) + 1) * 3 * nthr;
+}
+
+extern "C" int64_t adnm_valid_iscale_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr) {
+  if (iscale_why(frames, T, H, W, nthr)) return -1;
+  const int L = iscale_levels(H, W), nl = (L < kIsTileLevels - 1 ? L : kIsTileLevels - 1) + 1;
+  return frames * tiles_of(H, W) * iscale_tile_words(nl, nthr) * (int64_t)sizeof(uint32_t);
+}
+
+extern "C" int adnm_valid_iscale_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                                       const float* thresholds_host, int64_t nthr, float value_scale, void* ws, int64_t ws_bytes, int64_t frames,
+                                       int64_t T, int64_t H, int64_t W, adnm_stream_t stream) {
+  const PairCall call = {"valid_iscale_accum", pred, pred_sample_stride, pred_frame_stride, target, table, ws, ws_bytes, H, W,
+                         /*flat*/ false, /*ws_optional*/ false, /*ws_aligned*/ true, /*ws_rc*/ ADNM_EWORKSPACE};
+  if (int rc = pair_check(call, thresholds_host != nullptr, iscale_why(frames, T, H, W, nthr), adnm_valid_iscale_accum_ws_bytes(frames, T, H, W, nthr),
+                          "frames %lld T %lld %lld x %lld nthr %lld", (long long)frames, (long long)T, (long long)H, (long long)W, (long long)nthr))
+    return rc;
+  const Thr thr = thr_fill(thresholds_host, nthr);
+  const bool vec = pair_quads(W, pred_sample_stride, pred_frame_stride, pred, target);
+  const ScoredPair pair = {pred, pred_sample_stride, pred_frame_stride, target, (int)T, (int)(H * W)};
+  const int tiles_x = (int)adnm_cdiv(W, kTile), tiles_y = (int)adnm_cdiv(H, kTile), tiles = tiles_x * tiles_y;
+  const int L = iscale_levels(H, W), nl = (L < kIsTileLevels - 1 ? L : kIsTileLevels - 1) + 1;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ADNM_PROF("valid_iscale", st, 8.0 * frames * H * W);
+    const dim3 grid((unsigned)tiles, (unsigned)frames);
+    if (vec) iscale_tile_kernel<true><<<grid, kBlock, 0, st>>>(pair, (uint32_t*)ws, (int)H, (int)W, tiles_x, nl, value_scale, thr);
+    else iscale_tile_kernel<false><<<grid, kBlock, 0, st>>>(pair, (uint32_t*)ws, (int)H, (int)W, tiles_x, nl, value_scale, thr);
+  }
+  ADNM_CHECK_LAUNCH("valid_iscale_accum");
+  {
+    ADNM_PROF("valid_iscale_fold", st, 4.0 * frames * tiles * iscale_tile_words(nl, nthr));
+    iscale_fold_kernel<<<dim3((unsigned)T, (unsigned)nthr), kFoldBlock, 0, st>>>((const uint32_t*)ws, tiles_x, tiles_y, (int)frames, (int)T, (int)nthr, L,
+                                                                                (double*)table);
+  }
+  ADNM_CHECK_LAUNCH("valid_iscale_fold");
   return ADNM_OK;
 }
 

@@ -1,6 +1,7 @@
 // The scored pair: what every Validator score that compares a forecast with a target is handed, stated ONCE.
 //
-// An entry point of this contract (adnm_valid_pool_accum, adnm_valid_fss_accum, adnm_valid_nprob_accum: neighbour.hip; adnm_valid_spectrum_accum: spectrum.hip;
+// An entry point of this contract (adnm_valid_pool_accum, adnm_valid_fss_accum, adnm_valid_iscale_accum, adnm_valid_nprob_accum: neighbour.hip;
+// adnm_valid_spectrum_accum: spectrum.hip;
 // adnm_valid_joint_accum: joint.hip; adnm_valid_objects_accum: objects.hip; adnm_valid_sal_accum: sal.hip; adnm_valid_tracks_accum: tracks.hip) takes
 //   the forecast   `frames` frames addressed by (pred, pred_sample_stride, pred_frame_stride): frame f = b * T + t starts at
 //                  pred + b * sstride + t * fstride.  fstride = 0 holds one frame for all T lead times (the persistence baseline);

@@ -767,6 +767,40 @@ int adnm_valid_nprob_accum(const float* pred, int64_t pred_sample_stride, int64_
 int adnm_neighbour_prob(const float* field, float* out, const float* thresholds_host, int64_t nthr, float value_scale, int64_t scale,
                         int64_t frames, int64_t H, int64_t W, adnm_stream_t stream);
 
+/* Intensity-scale skill score (Casati, Ross & Stephenson 2004; the energy form of Casati 2010, as MET's wavelet-stat and pysteps'
+ * intensity_scale report it): the binary error I_f - I_o of a threshold split into orthogonal 2-D Haar components of scale 1, 2, 4, ...
+ * pixels, from ONE integer statistic.  The reference has none; the definitions are this project's and the yardstick is
+ * reshape(P/s, s, P/s, s).sum((1, 3)) and, independently, an explicit orthonormal Haar matrix.
+ *   event         adnm_valid_fss_accum's: I_o = q(target) >= thr_k, I_f = q(forecast) >= thr_k on the quantised fields.
+ *   domain        1 <= H, W <= 1024.  P = the smallest power of two >= max(H, W), L = log2 P.  The frame sits at the origin of a P x P
+ *                 domain; pixels outside the frame are no event in either field (FSS's zero padding).
+ *   blocks        block (l, i, j), l = 0 .. L: rows i 2^l .. (i + 1) 2^l - 1, columns j 2^l .. (j + 1) 2^l - 1; o, f its numbers of target
+ *                 and forecast events.
+ *   sums          A_l = SUM o^2, F_l = SUM f^2, C_l = SUM o f over the blocks of level l.  l = 0: A = TP + FN, F = TP + FP, C = TP of the
+ *                 point-wise counts; l = L: the squared event counts of the whole frame.  With D_l = A_l + F_l - 2 C_l and N = P^2 per
+ *                 frame, the Haar component of scale 2^j of the error has MSE D_j / (4^j N) - D_(j+1) / (4^(j+1) N) (j < L) and
+ *                 D_L / (4^L N) (the domain mean): validate.intensity_scale_entries, the caller's arithmetic.
+ * table: adnm_valid_iscale_block_bytes(T, nthr, H, W) = 8 * T * (L + 1) * 3 * nthr bytes, 8-byte aligned, zeroed by the caller, all double,
+ *   shape (T, L + 1, 3*nthr): the levels stand where the FSS table has its scales, a row is the FSS row: [t][l][3k .. 3k+2] = A, F, C at
+ *   threshold k for frame index t (frame f of a batch belongs to row f mod T), summed over every sample so far.  No header.  Integers held
+ *   in doubles: a single addend is at most (H*W)^2 <= 2^40, so a row stays exact (< 2^53) for 2^13 frames per frame index at 1024 x 1024
+ *   and for 2^25 at 128 x 128.
+ * adnm_valid_iscale_accum ADDS a batch.  target, pred and the two strides: adnm_valid_pool_accum's meaning (persistence is (T_in*H*W, 0)).
+ *   thresholds_host (nthr floats) is read on the host at call time and passed by value: the call can be captured.  With T = frames on a
+ *   zeroed table it is the one-shot per-frame form.  Two launches: each 32 x 32 tile is read once, with no halo, as threshold bits, and
+ *   leaves uint32 partials of levels 0 .. min(L, 5) (a tile's A is at most 2^20) and its two counts per threshold in ws; one fold, a
+ *   workgroup per (frame index, threshold), adds the partials over samples and tiles and builds levels 6 .. L from the tile counts in
+ *   uint64.  No atomics, no floating-point sums, no workgroup waits for another: exact and bit-reproducible.  Aligned shapes (W, both
+ *   strides multiples of 4, both bases 16-byte aligned) are read 16 bytes per access, all others float by float: same result.
+ * Limits, refused before any launch (ADNM_EINVAL): a null pointer; pred / target not 4-byte, table or ws not 8-byte aligned; nthr outside
+ *   1..8; T < 1 or not dividing frames; frames > 65535; H or W outside [1, 1024]; pred_frame_stride neither 0 nor >= H*W;
+ *   pred_sample_stride < 0.  A short workspace is ADNM_EWORKSPACE.  The *_bytes queries return -1. */
+int64_t adnm_valid_iscale_block_bytes(int64_t T, int64_t nthr, int64_t H, int64_t W);
+int64_t adnm_valid_iscale_accum_ws_bytes(int64_t frames, int64_t T, int64_t H, int64_t W, int64_t nthr);
+int adnm_valid_iscale_accum(const float* pred, int64_t pred_sample_stride, int64_t pred_frame_stride, const float* target, void* table,
+                            const float* thresholds_host, int64_t nthr, float value_scale, void* ws, int64_t ws_bytes, int64_t frames,
+                            int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
+
 /* The Lagrangian-persistence (advection) baseline: block-matched motion between the last two input frames (TREC, Rinehart & Garvey 1978)
  * and the last frame moved along it.  The reference has none; the definitions are this project's.  Integer arithmetic and
  * bit copies only: exact and bit-reproducible.
