@@ -18,7 +18,7 @@ _CT = {
     "const char*": ctypes.c_char_p, "char*": ctypes.c_char_p, "void": None,
     "const uint8_t*": ctypes.c_void_p, "uint8_t*": ctypes.c_void_p,
     "float* const*": ctypes.c_void_p, "const float* const*": ctypes.c_void_p, "const int64_t*": ctypes.c_void_p, "const int*": ctypes.c_void_p,
-    "const int32_t*": ctypes.c_void_p, "const uint16_t*": ctypes.c_void_p,
+    "const int32_t*": ctypes.c_void_p, "const uint16_t*": ctypes.c_void_p, "int*": ctypes.c_void_p,
 }
 
 

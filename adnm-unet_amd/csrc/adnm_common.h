@@ -37,6 +37,8 @@ void adnm_launch_fold(const char* prof_name, const float* part, int rows, int n,
 // device memory (adnm_uncached_alloc) for the slabs alone — a slab store is then at the device-wide coherence point once it has
 // completed and the ticket needs no fences (ws only has to hold the counters).
 int64_t adnm_lgemm_ws_bytes(int64_t I, int64_t J, int64_t R, int nbs);
+// what a launch asked for `nbs` slices runs with after the kernel's own clamp: {slices, step tiles per slice, step tiles} (no device call)
+void adnm_lgemm_slices(int64_t I, int64_t J, int64_t R, int nbs, int out[3]);
 int adnm_lgemm_launch(bool b_oc, const float* a, int64_t lda, const void* b, int64_t ldb, int b_dtype, const float* b_scale, const float* bias, float* c,
                       int64_t ldc, void* ws, int64_t ws_bytes, void* slabs_uc, int64_t slabs_uc_bytes, int64_t I, int64_t J, int64_t R, int nbs, int prec,
                       float* q, const char* prof, double prof_bytes, hipStream_t st);   // (launched, or recorded by an open group, under `prof`)

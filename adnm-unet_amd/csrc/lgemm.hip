@@ -468,6 +468,10 @@ int64_t adnm_lgemm_ws_bytes(int64_t I, int64_t J, int64_t R, int nbs) {
   const LgPlan pl = make_plan(I, J, R, nbs);
   return pl.nbs > 1 ? adnm_ticket_bytes(pl.ntiles) + (int64_t)pl.ntiles * pl.nbs * kTile * kTile * (int64_t)sizeof(float) : 16;
 }
+void adnm_lgemm_slices(int64_t I, int64_t J, int64_t R, int nbs, int out[3]) {
+  const LgPlan pl = make_plan(I, J, R, nbs);
+  out[0] = pl.nbs, out[1] = pl.kt_per_slice, out[2] = pl.nkt;
+}
 
 int adnm_lgemm_launch(bool b_oc, const float* a, int64_t lda, const void* b, int64_t ldb, int b_dtype, const float* b_scale, const float* bias, float* c,
                       int64_t ldc, void* ws, int64_t ws_bytes, void* slabs_uc, int64_t slabs_uc_bytes, int64_t I, int64_t J, int64_t R, int nbs, int prec,

@@ -400,6 +400,7 @@ struct Plan {
   int tm, tn, kc;        // wave tile (16 tm) x (16 tn), 16 kc reduction steps per chunk
   int tiles_i, tiles_j, ntiles, nchunks, wpt, nbs, cpw;
   bool combine;          // nbs > 1 and the slabs are summed inside the launch (tickets) instead of by the fold kernel
+  int source;            // where (wpt, nbs) and the tile came from: 0 a row of the measured table, 1 the rules, 2 ADNM_SK_FORCE
 };
 
 void finish(Plan& pl, int64_t I, int64_t J, int64_t R) {
@@ -475,6 +476,7 @@ Plan plan_deferred(int64_t I, int64_t J, int64_t R, bool direct, bool bf16) {
   finish(pl, I, J, R);
   const bool force = forced().on;
   const Tuned* tu = force || use_table() == 0 ? nullptr : tuned(ADNM_SKGEMM_TN, I, J, R, bf16);
+  pl.source = force ? 2 : (tu ? 0 : 1);
   if (force || tu) {
     const int* v = force ? forced().v : tu->cfg;
     pl.wpt = v[4], pl.nbs = v[5];
@@ -512,6 +514,7 @@ Plan plan_critical(int op, int64_t I, int64_t J, int64_t R, bool can_split, bool
   pl.combine = false;
   const bool force = forced().on;
   const Tuned* tu = force || use_table() == 0 ? nullptr : tuned(op, I, J, R, bf16);
+  pl.source = force ? 2 : (tu ? 0 : 1);
   if (force || tu) {
     const int* v = force ? forced().v : tu->cfg;
     pl.kernel = v[0], pl.tm = v[1], pl.tn = v[2], pl.kc = v[3], pl.wpt = v[4], pl.nbs = v[5];
@@ -633,6 +636,30 @@ extern "C" int64_t adnm_skgemm_counter_bytes(int op, int64_t M, int64_t N, int64
     if (nbs > 1 && adnm_ticket_bytes(ntiles) > need) need = adnm_ticket_bytes(ntiles);
   }
   return need;
+}
+
+// The plan adnm_skgemm launches with, for tests and tools: the same make_plan, then what the LDS-tiled kernel's own clamp leaves of the
+// slices asked for.  out = {kernel, tm, tn, kc, wpt, nbs, cpw, nchunks, combine, source}; the LDS-tiled kernel reports its 64 x 64 tile
+// and 32-step tile in the same units (4, 4, 2), wpt 1 (its waves do not share a reduction), cpw / nchunks = step tiles per slice / in
+// all.  direct: the output takes no partials — what adnm_skgemm plans with for op TN when ldc != J, and never for NT / NN (their slabs
+// are combined in the launch and written through ldc).  Host only: no device call, no stream.
+extern "C" int adnm_skgemm_plan(int op, int64_t M, int64_t N, int64_t K, int bf16, int direct, int* out) {
+  ADNM_REQUIRE(out, "skgemm_plan: null pointer");
+  ADNM_REQUIRE(shape_ok(op, M, N, K), "skgemm_plan: unsupported op/shape op=%d M=%lld N=%lld K=%lld", op, (long long)M, (long long)N, (long long)K);
+  int64_t I, J, R;
+  dims(op, M, N, K, &I, &J, &R);
+  const Plan pl = make_plan(op, I, J, R, direct != 0, bf16 != 0);
+  ADNM_REQUIRE(pl.kernel >= 0, "skgemm_plan: ADNM_SK_FORCE names a configuration this op has no kernel for");
+  if (pl.kernel == KERNEL_LDS) {
+    int s[3];
+    adnm_lgemm_slices(I, J, R, pl.nbs, s);
+    const int v[10] = {KERNEL_LDS, 4, 4, 2, 1, s[0], s[1], s[2], s[0] > 1, pl.source};
+    memcpy(out, v, sizeof(v));
+    return ADNM_OK;
+  }
+  const int v[10] = {pl.kernel, pl.tm, pl.tn, pl.kc, pl.wpt, pl.nbs, pl.cpw, pl.nchunks, pl.combine, pl.source};
+  memcpy(out, v, sizeof(v));
+  return ADNM_OK;
 }
 
 extern "C" int adnm_skgemm(int op, const float* a, int64_t lda, const void* b, int64_t ldb, int b_dtype, const float* b_scale, const float* bias,

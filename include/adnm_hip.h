@@ -462,6 +462,16 @@ int adnm_skgemm(int op, const float* a, int64_t lda, const void* b, int64_t ldb,
                 int64_t ldc, float* dbias, void* ws, int64_t ws_bytes, void* slabs_uc, int64_t slabs_uc_bytes, int64_t M, int64_t N, int64_t K,
                 int prec, float* q, adnm_stream_t stream);
 int64_t adnm_skgemm_counter_bytes(int op, int64_t M, int64_t N, int64_t K);
+/* The plan adnm_skgemm launches with for this op, shape and precision (bf16 != 0: every narrow mode) — a read-only host query for tests
+ * and tools, answered by the planner the launch itself calls.  out[10] = {kernel (0 register-streaming, 1 LDS-tiled), tm, tn, kc (wave
+ * tile 16 tm x 16 tn, 16 kc reduction steps per chunk), wpt (waves sharing a tile), nbs (reduction slices over workgroups), cpw (chunks
+ * per wave), nchunks, combine (1: the slabs are summed inside the launch, 0: by the fold), source (0 a row of the measured table, 1 the
+ * rules, 2 a forced plan)}.  The LDS-tiled kernel reports {1, 4, 4, 2, 1, slices after its own clamp, step tiles per slice, step
+ * tiles, ...}.  Every chunk has an owner (nbs * wpt * cpw >= nchunks) and no slice is empty ((nbs - 1) * wpt * cpw < nchunks).
+ * direct != 0: the output takes no partials — adnm_skgemm plans so for op TN when ldc != K, never for NT / NN.  For op TN the answer
+ * depends, as the launch does, on whether the calling thread has a leaf queue (and a fold queue) bound.  ADNM_EINVAL for a shape
+ * adnm_skgemm_supported refuses. */
+int adnm_skgemm_plan(int op, int64_t M, int64_t N, int64_t K, int bf16, int direct, int* out);
 void* adnm_uncached_alloc(int64_t bytes);
 int adnm_uncached_free(void* ptr);
 
