@@ -111,19 +111,26 @@ class Forecast:
     """What a Forecaster call returns: .pred (fp32, the model's output in the model's own shape: (B, T, 1, H, W) from create_ADNMUNet's
     models, (B, T, H, W) from a model that emits that; for render() the tensor it was given), .fields (uint8 (B, T, H, W)),
     .strip (uint8 (B, H, Ws, 4)), and .prob (fp32 (K, B, T, H, W), the neighbourhood probability per threshold of a Forecaster with
-    probability=; None otherwise)."""
-    __slots__ = ("pred", "fields", "strip", "prob")
+    probability=; None otherwise).  With ensemble=: .members (fp32 (M, B, T, H, W), the member forecasts with their symmetries undone, member 0
+    the control), .ens_mean (fp32 (B, T, H, W)) and .ens_prob (fp32 (K, B, T, H, W), the share of members at or above each threshold; None
+    without thresholds); .pred, .fields, .strip and .prob are then the control's.  None otherwise."""
+    __slots__ = ("pred", "fields", "strip", "prob", "members", "ens_mean", "ens_prob")
 
-    def __init__(self, pred, fields, strip, prob=None):
+    def __init__(self, pred, fields, strip, prob=None, members=None, ens_mean=None, ens_prob=None):
         self.pred, self.fields, self.strip, self.prob = pred, fields, strip, prob
+        self.members, self.ens_mean, self.ens_prob = members, ens_mean, ens_prob
 
 
 class Forecaster(ForwardClient):
-    def __init__(self, model, palette, pixel_scale=90.0, size=None, in_frames=5, frame_start=0, frame_step=1, gap=10, probability=None):
+    def __init__(self, model, palette, pixel_scale=90.0, size=None, in_frames=5, frame_start=0, frame_step=1, gap=10, probability=None, ensemble=None):
         """pixel_scale: pic_results.py's PIXEL_SCALE; None or 0 bins the float itself (the LAPS form).  size: the model's input edge,
         needed for raw uint8 input only.  frame_start / frame_step: the frames of the strip (even_index_only=True is 1, 2).
         probability: dict(thresholds=(35, 40), scale=9) adds Forecast.prob, the fraction of the scale x scale window at or above each
-        threshold on the field quantised with pixel_scale: one adnm_neighbour_prob launch behind the render, in the graph."""
+        threshold on the field quantised with pixel_scale: one adnm_neighbour_prob launch behind the render, in the graph.
+        ensemble: dict(members=True | codes, thresholds=(35, 40)) forecasts a test-time-augmentation ensemble over the symmetries of the square
+        (the member recipe is the Validator's, ops.ensemble_spec): the forward runs at batch M * B on the transformed inputs,
+        adnm_d4_members undoes the symmetries, and one adnm_ensemble_product launch behind the render writes Forecast.ens_mean and, with
+        thresholds (on the field quantised with pixel_scale), Forecast.ens_prob.  render(res.ens_mean) colours the mean."""
         if not isinstance(palette, Palette):
             raise RuntimeError(f"Forecaster: palette must be a forecast.Palette, got {type(palette).__name__}")
         self.model, self.palette = model, palette
@@ -142,6 +149,17 @@ class Forecaster(ForwardClient):
             if len(scales) != 1 or not 1 <= len(thr) <= 8:
                 raise ValueError("Forecaster: probability takes one scale and 1..8 thresholds")
             self.probability = ((ctypes.c_float * len(thr))(*thr), len(thr), scales[0])
+        self.ensemble = None                # (the members argument, thresholds as the entry point reads them, K)
+        if ensemble is not None:
+            if not isinstance(ensemble, dict) or "members" not in ensemble or not set(ensemble) <= {"members", "thresholds"}:
+                raise ValueError(f"Forecaster: ensemble is dict(members=, thresholds=), got {ensemble!r}")
+            members = ops.ensemble_spec(ensemble["members"], None)   # ValueError on a bad entry
+            thr = [float(t) for t in ensemble.get("thresholds") or ()]
+            if members is None or len(thr) > 8:
+                raise ValueError("Forecaster: ensemble takes members (True or codes) and 0..8 thresholds")
+            if thr and not self.pixel_scale > 0.0:
+                raise ValueError("Forecaster: the ensemble's thresholds compare the field quantised with pixel_scale, which must be > 0 (not None or 0)")
+            self.ensemble = (members, (ctypes.c_float * max(len(thr), 1))(*thr), len(thr))
         self.out_frames = None              # T of the model's output, known after the first call
         self._fwd = GraphedForward(model, client=self, keep_quant=True)
         self._warm = set()                  # the devices the render kernel has run on
@@ -160,31 +178,70 @@ class Forecaster(ForwardClient):
             self._warm.add(x.device)
         raw = x.dtype == torch.uint8
         ent["xin"] = torch.empty((x.shape[0], x.shape[1], 1, self.size, self.size), dtype=torch.float32, device=x.device) if raw else None
+        ent["codes"] = ent["xmem"] = None
+        if self.ensemble:   # the members' inputs, made from the ingested frames; the forward direction once, eagerly
+            first = ent["xin"] if raw else ent["sx"]
+            H, W = first.shape[-2:]
+            codes = ops.ensemble_spec(self.ensemble[0], H == W)   # ValueError: a transposing code on frames that are not square
+            if first.numel() // (H * W) > 65535:
+                raise RuntimeError(f"Forecaster: ensemble= on {first.numel() // (H * W)} input frames is outside adnm_d4_members' limits (<= 65535)")
+            ent["codes"] = (ctypes.c_int * len(codes))(*codes)
+            ent["xmem"] = torch.zeros((len(codes) * first.shape[0],) + tuple(first.shape[1:]), dtype=torch.float32, device=x.device)
+            ops.d4_members_into(first, ent["xmem"], ent["codes"], len(codes), False)
 
     def model_input(self, ent, sx):
-        if ent["xin"] is None:
-            return sx
-        B, T, H0, W0 = sx.shape
-        lib.call("adnm_radar_ingest", sx.data_ptr(), ent["xin"].data_ptr(), B * T, H0, W0, self.size, 1.0 / 255.0, torch.cuda.current_stream().cuda_stream)
-        return ent["xin"]
+        """raw bytes: ingest first; ensemble: then the M transformed copies, member-major (sample m * B + b is member m of sample b)"""
+        first = sx
+        if ent["xin"] is not None:
+            B, T, H0, W0 = sx.shape
+            lib.call("adnm_radar_ingest", sx.data_ptr(), ent["xin"].data_ptr(), B * T, H0, W0, self.size, 1.0 / 255.0, torch.cuda.current_stream().cuda_stream)
+            first = ent["xin"]
+        if ent["xmem"] is None:
+            return first
+        ops.d4_members_into(first, ent["xmem"], ent["codes"], len(ent["codes"]), False)
+        return ent["xmem"]
 
     def check(self, ent, out):
         """the checks that may raise, and the buffers after() writes"""
         if out.dtype != torch.float32 or out.dim() not in (4, 5) or (out.dim() == 5 and out.shape[2] != 1):
             raise RuntimeError(f"Forecaster: the model's output must be fp32 (B, T, H, W) or (B, T, 1, H, W), got {out.dtype} {tuple(out.shape)}")
         B, T, H, W = out.shape[0], out.shape[1], out.shape[-2], out.shape[-1]
+        ent["members"] = ent["ens_mean"] = ent["ens_prob"] = None
+        if ent["codes"] is not None:   # the members' buffers, and the inverse direction and the product once, eagerly
+            M, K = len(ent["codes"]), self.ensemble[2]
+            if B % M or (H != W and any(c & 4 for c in ent["codes"])) or B * T > 65535 * M or H * W >= 1 << 24:
+                raise RuntimeError(f"Forecaster: ensemble= of {M} members does not fit the model's output {tuple(out.shape)} (batch M * B, square frames for a "
+                                   "transposing member, B * T <= 65535, H * W < 2^24)")
+            B //= M
+            ent["members"] = torch.zeros((M, B, T, H, W), dtype=torch.float32, device=out.device)
+            ent["ens_mean"] = torch.empty((B, T, H, W), dtype=torch.float32, device=out.device)
+            ent["ens_prob"] = torch.empty((K, B, T, H, W), dtype=torch.float32, device=out.device) if K else None
+            ops.d4_members_into(torch.zeros_like(ent["members"]), ent["members"], ent["codes"], M, True)
+            self._product(ent)
         if self.frame_start >= T:
             raise RuntimeError(f"Forecaster: frame_start {self.frame_start} outside the model's {T} output frames")
         ent["fields"] = torch.empty((B, T, H, W), dtype=torch.uint8, device=out.device)
         ent["strip"] = torch.empty((B, H, ops.strip_width(T, W, self.frame_start, self.frame_step, self.gap), 4), dtype=torch.uint8, device=out.device)
         ent["prob"] = torch.empty((self.probability[1], B, T, H, W), dtype=torch.float32, device=out.device) if self.probability else None
 
+    def _product(self, ent):
+        M, B, T, H, W = ent["members"].shape
+        ops.ensemble_product_into(ent["members"], B * T * H * W, T * H * W, H * W, ent["ens_mean"], ent["ens_prob"], self.ensemble[1], self.ensemble[2],
+                                  self.pixel_scale, M, B * T, T, H * W)
+
     def after(self, ent, sx, out):
         ent["keep"] = pred = (out.squeeze(2) if out.dim() == 5 else out).contiguous()   # (a copy made here belongs to the graph's pool and is kept with it)
+        if ent["members"] is not None:   # the symmetries undone; what follows renders member 0, the contiguous control forecast
+            mem = ent["members"]
+            ops.d4_members_into(pred, mem, ent["codes"], mem.shape[0], True)
+            pred = mem[0]
+            out = pred.view((mem.shape[1],) + tuple(out.shape[1:]))   # in the model's own shape
         ops.forecast_render_into(pred, ent["fields"], ent["strip"], self.palette._c, self.pixel_scale, self.frame_start, self.frame_step, self.gap)
         if self.probability:
             ops.neighbour_prob_into(pred, ent["prob"], *self.probability[:2], self.pixel_scale, self.probability[2])
-        ent["res"] = Forecast(out, ent["fields"], ent["strip"], ent["prob"])
+        if ent["members"] is not None:
+            self._product(ent)
+        ent["res"] = Forecast(out, ent["fields"], ent["strip"], ent["prob"], ent["members"], ent["ens_mean"], ent["ens_prob"])
         self.out_frames = out.shape[1]
 
     # ---- the public surface

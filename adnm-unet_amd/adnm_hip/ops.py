@@ -3491,6 +3491,164 @@ def neighbour_prob(field, thresholds, value_scale, scale):
     return out
 
 
+# ======================================================================================= ensembles (csrc/ensemble.hip)
+MAX_MEMBERS = 16
+D4_CODES = tuple(range(8))   # adnm_batch_fetch_aug's bits: 1 flip left-right, 2 flip up-down, 4 transpose
+ENSEMBLE_LIMITS = f"2 <= M <= {MAX_MEMBERS}, 1..8 thresholds, value_scale finite with 1 <= floor(value_scale) <= 255, frames <= 65535, H*W < 2^24"
+
+
+def ensemble_spec(arg, square):
+    """the `ensemble` / `members` argument of the Validator and the Forecaster -> the member codes (a tuple of ints) or None.  None / False:
+    None.  True: all eight symmetries of the square for square frames, the four without a transpose, (0, 1, 2, 3), otherwise.  A sequence of
+    codes: 2..16 distinct ints in 0..7 that begin with 0 (member 0 is the control, the untouched input); a transposing code (bit 2) needs
+    square frames.  dict(members=...) is read as its entry.  square None: the frames are not known yet and the transposing codes pass
+    (True is then not resolved: it comes back as True).  ValueError on anything else."""
+    if isinstance(arg, dict):
+        if set(arg) != {"members"}:
+            raise ValueError(f"ensemble: a dict is dict(members=), got {arg!r}")
+        arg = arg["members"]
+    if arg is None or arg is False:
+        return None
+    if arg is True:
+        return True if square is None else (D4_CODES if square else D4_CODES[:4])
+    if isinstance(arg, (str, bytes)) or not hasattr(arg, "__iter__"):
+        raise ValueError(f"ensemble: True or a sequence of member codes in 0..7, got {arg!r}")
+    codes = []
+    for c in arg:
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) <= 7:
+            raise ValueError(f"ensemble: a member code is an integer in 0..7, got {c!r}")
+        if int(c) in codes:
+            raise ValueError(f"ensemble: member code {int(c)} is given twice")
+        codes.append(int(c))
+    if not 2 <= len(codes) <= MAX_MEMBERS:
+        raise ValueError(f"ensemble: 2..{MAX_MEMBERS} members, got {len(codes)}")
+    if codes[0] != 0:
+        raise ValueError(f"ensemble: member 0 is the control, code 0; got {codes[0]}")
+    if square is False and any(c & 4 for c in codes):
+        raise ValueError(f"ensemble: a transposing member code (bit 2) needs square frames, got {tuple(codes)}")
+    return tuple(codes)
+
+
+def d4_members_into(src, dst, codes_c, M, inverse):
+    """the launch alone, on tensors the caller owns (src: fp32 contiguous (..., H, W), or (M, ..., H, W) with inverse; dst: fp32 contiguous
+    (M, ..., H, W)) and on the codes as a host int array: what a captured graph's body calls"""
+    H, W = dst.shape[-2:]
+    lib.call("adnm_d4_members", src.data_ptr(), dst.data_ptr(), codes_c, int(M), 1 if inverse else 0, dst.numel() // (int(M) * H * W), H, W, _stream())
+
+
+def d4_members(x, codes, inverse=False):
+    """x: fp32 GPU tensor (..., H, W); codes: M ints in 0..7 (bit 0 flip left-right, bit 1 flip up-down, bit 2 transpose, applied as
+    w.flip(-2), w.flip(-1), w.transpose(-1, -2)) -> (M, ..., H, W) with out[m] = g_m(x).  inverse=True: x is (M, ..., H, W) and
+    out[m] = g_m^-1(x[m]).  A copy of bit patterns.  A transposing code needs H == W.  adnm_d4_members."""
+    if not torch.is_tensor(x):
+        raise RuntimeError("d4_members: needs a GPU tensor")
+    _need_gpu(x)
+    codes = [int(c) for c in codes]
+    M = len(codes)
+    if x.dtype != torch.float32 or x.dim() < (3 if inverse else 2) or x.numel() == 0 or (inverse and x.shape[0] != M):
+        _unsupported("d4_members", f"takes a non-empty fp32 (..., H, W), or (M, ..., H, W) with inverse=True, got {x.dtype} {tuple(x.shape)} for {M} codes")
+    if not 1 <= M <= MAX_MEMBERS or any(not 0 <= c <= 7 for c in codes):
+        raise ValueError(f"d4_members: 1..{MAX_MEMBERS} codes in 0..7, got {codes}")
+    if x.shape[-1] != x.shape[-2] and any(c & 4 for c in codes):
+        raise ValueError(f"d4_members: a transposing code needs square frames, got {x.shape[-2]} x {x.shape[-1]}")
+    x = x.contiguous()
+    out = torch.empty(tuple(x.shape) if inverse else (M,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+    d4_members_into(x, out, (ctypes.c_int * M)(*codes), M, inverse)
+    return out
+
+
+def ensemble_cols(M, nthr):
+    """-> (C, {"rank": 7, "exceed": 7 + (M + 1)^2}): the doubles of a row of adnm_valid_ens_accum's table and where its two histograms
+    start.  Columns 0..6 are N, Z, S0, S1, S2, V, E; the rank bins are [b * (M + 1) + e]; threshold k's exceedance bins are
+    [exceed + (2 k + o) * (M + 1) + c] (include/adnm_hip.h).  The layout is stated here and nowhere else on the Python side."""
+    M, nthr = int(M), int(nthr)
+    if not 2 <= M <= MAX_MEMBERS or not 1 <= nthr <= 8:
+        raise ValueError(f"ensemble: 2..{MAX_MEMBERS} members and 1..8 thresholds, got {M} and {nthr}")
+    return 7 + (M + 1) ** 2 + 2 * nthr * (M + 1), {"rank": 7, "exceed": 7 + (M + 1) ** 2}
+
+
+def _member_strides(op, members, lead):
+    """members: fp32 GPU tensor (M, *lead, H, W) -> (the tensor to pass, member stride, frame stride) with the `lead` axes read as ONE axis of
+    frames: the strides as they are where a frame's pixels are contiguous and the lead axes share one stride (a broadcast member or frame
+    has stride 0), a contiguous copy otherwise"""
+    H, W = members.shape[-2:]
+    st, sh = members.stride(), members.shape
+    inner = st[-1] == 1 and st[-2] == W
+    fs = st[-3] if len(lead) else 0
+    flat = all(st[d] == st[d + 1] * sh[d + 1] for d in range(1, len(lead)))
+    if not (inner and flat) or (fs != 0 and fs < H * W) or st[0] < 0 or (st[0] != 0 and st[0] < (math.prod(lead) - 1) * fs + H * W):
+        members = members.contiguous()
+        return members, math.prod(lead) * H * W, H * W
+    return members, st[0], fs
+
+
+def _ens_args(op, members, thresholds, value_scale, need_thr):
+    if not torch.is_tensor(members):
+        raise RuntimeError(f"{op}: needs GPU tensors")
+    _need_gpu(members)
+    if members.dtype != torch.float32 or members.dim() < 3 or members.numel() == 0:
+        _unsupported(op, f"takes the members as a non-empty fp32 (M, ..., H, W), got {members.dtype} {tuple(members.shape)}")
+    thr = [float(t) for t in thresholds]
+    if not 2 <= members.shape[0] <= MAX_MEMBERS or not (1 if need_thr else 0) <= len(thr) <= 8:
+        raise ValueError(f"{op}: 2..{MAX_MEMBERS} members and {1 if need_thr else 0}..8 thresholds, got {members.shape[0]} and {len(thr)}")
+    return thr, (ctypes.c_float * max(len(thr), 1))(*thr)
+
+
+def ensemble_accum_into(members, member_stride, sample_stride, frame_stride, truth, table, thresholds_c, nthr, value_scale, M, frames, T, hw):
+    """the launch alone, on tensors the caller owns: `members` (a tensor, or an address) with its three strides in elements, truth contiguous
+    (frames, hw) fp32, table float64 (T, ensemble_cols(M, nthr)[0]), ADDED to.  What a captured graph's body calls."""
+    lib.call("adnm_valid_ens_accum", members.data_ptr() if torch.is_tensor(members) else int(members), int(member_stride), int(sample_stride), int(frame_stride),
+             truth.data_ptr(), table.data_ptr() if torch.is_tensor(table) else int(table), thresholds_c, int(nthr), float(value_scale), int(M), None, 0,
+             int(frames), int(T), int(hw), _stream())
+
+
+def ensemble_table(truth, members, thresholds, value_scale):
+    """truth: fp32 GPU tensor (..., H, W); members: fp32 (M, ..., H, W), 2 <= M <= 16, any stack of member forecasts (a broadcast view is
+    read as it is) -> int64 (frames, C) on the device, C and the columns from ensemble_cols(M, nthr): per frame N, Z, S0, S1, S2, V, E, the rank
+    bins and the exceedance bins of the levels q(v), with the DRY pixels (target and every member 0) in Z alone (include/adnm_hip.h states
+    the convention; validate.ensemble_entries reads the table).  Exact.  The one-shot use of adnm_valid_ens_accum (T = frames)."""
+    thr, thr_c = _ens_args("ensemble_table", members, thresholds, value_scale, True)
+    if not torch.is_tensor(truth) or truth.dtype != torch.float32 or truth.device != members.device or tuple(members.shape[1:]) != tuple(truth.shape) or truth.dim() < 2:
+        _unsupported("ensemble_table", f"takes fp32 truth (..., H, W) and members (M, ..., H, W) on one device, got {tuple(truth.shape) if torch.is_tensor(truth) else truth!r} "
+                                       f"and {tuple(members.shape)}")
+    M, (H, W) = members.shape[0], truth.shape[-2:]
+    t = truth.contiguous()
+    frames = t.numel() // (H * W)
+    if lib.query("adnm_valid_ens_accum_ws_bytes", frames, frames, H * W, len(thr), M, float(value_scale)) != 0:
+        raise RuntimeError(f"ensemble_table: {M} members of {frames} frames of {H} x {W} at value_scale {value_scale} are outside adnm_valid_ens_accum's limits "
+                           f"({ENSEMBLE_LIMITS})")
+    mem, ms, fs = _member_strides("ensemble_table", members, tuple(truth.shape[:-2]))
+    out = torch.zeros((frames, ensemble_cols(M, len(thr))[0]), dtype=torch.float64, device=t.device)
+    ensemble_accum_into(mem, ms, 0, fs, t, out, thr_c, len(thr), value_scale, M, frames, frames, H * W)
+    return out.to(torch.int64)   # integers in doubles: exact
+
+
+def ensemble_product_into(members, member_stride, sample_stride, frame_stride, mean, prob, thresholds_c, K, value_scale, M, frames, T, hw):
+    """the launch alone, on tensors the caller owns: mean fp32 (frames, hw), prob fp32 (K, frames, hw) or None with K = 0.  What a captured
+    graph's body calls."""
+    lib.call("adnm_ensemble_product", members.data_ptr() if torch.is_tensor(members) else int(members), int(member_stride), int(sample_stride), int(frame_stride),
+             mean.data_ptr(), None if prob is None else prob.data_ptr(), thresholds_c if K else None, int(K), float(value_scale) if K else 0.0, int(M), int(frames),
+             int(T), int(hw), _stream())
+
+
+def ensemble_product(members, thresholds=(), value_scale=None):
+    """members: fp32 GPU tensor (M, ..., H, W), 2 <= M <= 16 -> (mean, prob): mean fp32 (..., H, W) = ((x_0 + x_1) + ... + x_(M-1)) / float(M)
+    on the raw values, each operation rounded in fp32 in that order; prob fp32 (K, ..., H, W) = float(c) / float(M) with c the members whose
+    level q(v) is at or above the threshold, or None without thresholds (value_scale is then not needed).  adnm_ensemble_product."""
+    thr, thr_c = _ens_args("ensemble_product", members, thresholds, value_scale, False)
+    if thr and value_scale is None:
+        raise ValueError("ensemble_product: thresholds compare the quantised levels, which needs value_scale")
+    M, (H, W), lead = members.shape[0], members.shape[-2:], tuple(members.shape[1:-2])
+    frames = math.prod(lead)
+    if not 1 <= frames <= 65535 or H * W >= 1 << 24:
+        raise RuntimeError(f"ensemble_product: {frames} frames of {H} x {W} are outside adnm_ensemble_product's limits (frames <= 65535, H*W < 2^24)")
+    mem, ms, fs = _member_strides("ensemble_product", members, lead)
+    mean = torch.empty(lead + (H, W), dtype=torch.float32, device=mem.device)
+    prob = torch.empty((len(thr),) + lead + (H, W), dtype=torch.float32, device=mem.device) if thr else None
+    ensemble_product_into(mem, ms, 0, fs, mean, prob, thr_c, len(thr), value_scale, M, frames, frames, H * W)
+    return mean, prob
+
+
 # ======================================================================================= block-matched motion and advection (csrc/advect.hip)
 TREC_BLOCKS, MAX_TREC_RADIUS = (8, 16, 32), 8
 

@@ -15,7 +15,7 @@ and aggregates it exactly as GpuEvaluator.done() does.
 
 Every option below adds tables of its own behind that block, in the same allocation.  block_parts is the ONE statement of which tables
 there are and where each lies: the allocation, the launches (one per table, in the table's order) and aggregate all read it (through
-block_tables, which states the rows; block_layout and block_parts keep the parameter lists they had before later tables arrived).  The defaults
+block_rows, which states the rows; block_tables, block_layout and block_parts keep the parameter lists they had before later tables arrived).  The defaults
 allocate and launch nothing new.
 
 Validator(..., pools=(4, 16, (16, 8)), persistence=True) adds neighbourhood scores and the persistence baseline:
@@ -69,6 +69,13 @@ index, threshold and level l = 0 .. L, the integer sums A, F, C of the squared e
 P x P domain into a (T, L + 1, 3 nthr) table, for the forecast and for each baseline there is; done() reports the MSE, the skill and the
 energies of the binary error's Haar components of scale 1, 2, 4, ... P px (intensity_scale_entries).
 
+Validator(..., ensemble=True) (or ensemble=codes, or ensemble=dict(members=codes)) scores a test-time-augmentation ensemble over the symmetries
+of the square (DESIGN.md §4u): csrc/ensemble.hip::d4_members puts the M transformed copies of the input in front of the forward, which then runs at
+batch M * B, and undoes the symmetries on its output; valid_ens_accum adds the integer sums behind CRPS, spread and skill, the rank histogram and
+the ensemble exceedance probability's histogram into a (T, C) table; done() reports them (ensemble_entries).  Every other pass scores member 0,
+the control: the model on the untouched input, though at batch M * B, where the GEMM plans may differ from those at batch B, so it is NOT
+promised bit-equal to a plain Validator's forecast.
+
 The reference's loop iterates `for batch in val_dataloader` but evaluates `data`, the last TRAINING batch (train.py:159-160).  That is
 not reproduced: the Validator validates the batches it is given."""
 import ctypes
@@ -103,7 +110,7 @@ def baseline_pools(pools):
 
 
 class Part(NamedTuple):
-    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint / objects / sal / nprob / iscale / tracks, `field` the field it scores against the target
+    """one table of the Validator's block: `kind` is main / pool / fss / spectrum / joint / objects / sal / nprob / iscale / ensemble / tracks, `field` the field it scores against the target
     (pred: the forecast, last: the last input frame held, adv: that frame advected; None for main), `pools` the (size, stride) pairs of a
     pool part's pass, `offset` its place in the block in doubles"""
     name: str
@@ -118,11 +125,12 @@ class Part(NamedTuple):
         return math.prod(self.shape)
 
 
-def block_tables(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, tracks=None, objects=None,
-                 iscale=None):
+def block_rows(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, tracks=None, objects=None,
+               iscale=None, ensemble=None):
     """-> (the parts of the ONE allocation in their order, its doubles).  The order of the block, and of the launches that fill it, is stated
-    here and nowhere else: block_layout and block_parts are its callers with the parameter lists they had, the Validator and aggregate go
-    through this one.  pools: (size, stride) pairs; fss: scales; spectrum: (H, W) of the frames, or None; joint: the levels L, or None;
+    here and nowhere else: block_tables, block_layout and block_parts are its callers with the parameter lists they had, the Validator and
+    aggregate go through this one.  ensemble: the number of members M, or None; BY NAME: the ensemble's table (T, C), C from
+    ops.ensemble_cols(M, nthr), directly in front of the tracks.  pools: (size, stride) pairs; fss: scales; spectrum: (H, W) of the frames, or None; joint: the levels L, or None;
     objects: min_area, or None; sal: what ops.sal_spec returns, or None.  `sal` is passed BY NAME: it stands in front of `objects`, which
     stays the last parameter, and its position may move when a further table arrives.  nprob: the scales of the neighbourhood probability's
     histogram, or None; passed BY NAME as well, for the same reason.  tracks: min_volume, or None; BY NAME too: its table, (2, nthr, 7 + 4 T)
@@ -148,6 +156,7 @@ def block_tables(T, nthr, pools=(), persistence=False, fss=(), advection=False, 
             ("iscale", "iscale", "pred", (), levels, iscale),
             ("persistence/iscale", "iscale", "last", (), levels, iscale and persistence),
             ("advection/iscale", "iscale", "adv", (), levels, iscale and advection),
+            ("ensemble", "ensemble", "pred", (), (T, ops.ensemble_cols(ensemble, nthr)[0]) if ensemble else (), ensemble),
             ("tracks", "tracks", "pred", (), (2, nthr, ops.track_cols(T)[0]), tracks))
     parts, at = [], 0
     for *head, shape, present in rows:
@@ -157,6 +166,12 @@ def block_tables(T, nthr, pools=(), persistence=False, fss=(), advection=False, 
     return parts, at
 
 
+def block_tables(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, tracks=None, objects=None,
+                 iscale=None):
+    """block_rows without the table that came after the intensity-scale ones: the parameter list callers and tests have pinned."""
+    return block_rows(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, tracks=tracks, objects=objects, iscale=iscale)
+
+
 def block_layout(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, tracks=None, objects=None):
     """block_tables without the tables that came after the tracks': the parameter list callers and tests have pinned."""
     return block_tables(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, tracks=tracks, objects=objects)
@@ -164,13 +179,13 @@ def block_layout(T, nthr, pools=(), persistence=False, fss=(), advection=False, 
 
 def block_parts(T, nthr, pools=(), persistence=False, fss=(), advection=False, spectrum=None, joint=None, sal=None, nprob=None, objects=None):
     """block_tables without the tables that came after the neighbourhood probability's: the parameter list callers and tests have pinned.
-    The Validator and aggregate go through block_tables, which states the rows."""
+    The Validator and aggregate go through block_rows, which states the rows."""
     return block_tables(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, objects=objects)
 
 
 def _doubles(names, *options, **more):
-    """the doubles of the named parts of block_tables(*options, **more), 0 for a part that is not there"""
-    size = {p.name: p.size for p in block_tables(*options, **more)[0]}
+    """the doubles of the named parts of block_rows(*options, **more), 0 for a part that is not there"""
+    size = {p.name: p.size for p in block_rows(*options, **more)[0]}
     return tuple(size.get(n, 0) for n in names)
 
 
@@ -218,6 +233,11 @@ def nprob_doubles(seq_len, nthr, nprob=None):
 def tracks_doubles(seq_len, nthr, tracks=None):
     """-> doubles of the tracks table (2, nthr, 7 + 4 T); tracks: what ops.tracks_spec takes (None / False for none)"""
     return _doubles(("tracks",), seq_len, nthr, tracks=ops.tracks_spec(tracks))[0]
+
+
+def ensemble_doubles(seq_len, nthr, members=None):
+    """-> doubles of the ensemble's table (T, C), C = ops.ensemble_cols(M, nthr)[0]; members: M (None / 0 for none)"""
+    return _doubles(("ensemble",), seq_len, nthr, ensemble=members or None)[0]
 
 
 def iscale_doubles(seq_len, nthr, frame=None, persistence=False, advection=False):
@@ -392,6 +412,104 @@ def sal_entries(rows, thresholds, spec=(1, None)):
     return res
 
 
+def _ratio(a, b):
+    """a / b in float64, NaN where b is 0"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return _scalar(np.where(b == 0, np.nan, a / b))
+
+
+def _probability_entry(n0, n1, m, bins):
+    """n0, n1: (..., m + 1) counts of the pixels without / with the observed event per forecast count c = 0 .. m, the forecast being
+    p = c / m (m = n^2 window pixels for nprob_entries, m = M members for ensemble_entries) -> the verification of that discrete
+    probability forecast, as nprob_entries states it"""
+    ratio = _ratio
+    c = np.arange(m + 1)
+    p = c / float(m)
+    both = (n0 + n1).astype(np.float64)
+    total, events, quiet = both.sum(axis=-1), n1.sum(axis=-1), n0.sum(axis=-1)
+    base = np.asarray(ratio(events, total))
+    freq = np.asarray(ratio(n1, both))   # the observed frequency given the forecast value; NaN where the value never occurs
+    rel = np.where(both == 0, 0.0, both * (p - freq) ** 2).sum(axis=-1)
+    res = np.where(both == 0, 0.0, both * (freq - base[..., None]) ** 2).sum(axis=-1)
+    brier, unc = np.asarray(ratio((n0 * p ** 2 + n1 * (p - 1.0) ** 2).sum(axis=-1), total)), base * (1.0 - base)
+    zero = np.zeros(n0.shape[:-1] + (1,))
+    pod = np.concatenate([np.asarray(ratio(_tail_sums(n1, -1), events[..., None])), zero], axis=-1)
+    pofd = np.concatenate([np.asarray(ratio(_tail_sums(n0, -1), quiet[..., None])), zero], axis=-1)
+    area = ((pofd[..., :-1] - pofd[..., 1:]) * (pod[..., :-1] + pod[..., 1:]) / 2.0).sum(axis=-1)
+    member = (np.minimum(c * bins // m, bins - 1)[:, None] == np.arange(bins)).astype(np.float64)   # (m + 1, bins), one bin per value
+    count = both @ member
+    return {"histogram": np.stack([n0, n1], axis=-2), "base_rate": _scalar(base), "brier": _scalar(brier),
+            "reliability": ratio(rel, total), "resolution": ratio(res, total), "uncertainty": _scalar(unc),
+            "brier_skill": _scalar(1.0 - np.asarray(ratio(brier, unc))), "roc": {"pofd": pofd, "pod": pod}, "roc_area": _scalar(area),
+            "reliability_diagram": {"edges": np.linspace(0.0, 1.0, bins + 1), "count": count.astype(np.int64),
+                                    "forecast_mean": ratio((both * p) @ member, count), "observed_frequency": ratio(n1.astype(np.float64) @ member, count)}}
+
+
+def ensemble_entries(rows, M, thresholds, bins=10):
+    """rows: (..., C) integer sums laid out as ops.ensemble_cols(M, nthr) states (ops.ensemble_table's tensor summed over its frames, the
+    Validator's table or its sum over the horizon) -> the entries of done()["ensemble"], the leading axes (none, or T) kept in front of every
+    array.  Every level is in units of q, the quantised value floor(clip(v, 0, 1) * value_scale), NOT in the model's units.  With N pixels,
+    y the target's level and x_i the members':
+      "members" M, "pixels" N, "dry" Z (the pixels where the target and every member are 0);
+      "crps" S1 / (M N) - S2 / (M^2 N), the CRPS of the ensemble's empirical distribution; "crps_fair" with M (M - 1) in the second term
+        (Ferro's fair CRPS, NaN-free for M >= 2); "mae_control" S0 / N, the CRPS of the deterministic control (member 0) and so the skill's
+        zero; "crpss" 1 - crps / mae_control;
+      "spread" sqrt(V / (M (M - 1) N)), the root of the mean unbiased member variance; "rmse_mean" sqrt(E / (M^2 N)), the RMSE of the ensemble
+        mean; "spread_skill" sqrt((M + 1) / M) spread / rmse_mean (1 for a statistically consistent ensemble);
+      "rank_histogram" (M + 1) float64: the target's rank among the members, the ties of a pixel with b members below and e equal shared
+        equally among the ranks b .. b + e (the dry pixels are such ties: each adds 1 / (M + 1) to every rank); "rank_histogram_wet": the
+        same without the dry pixels;
+      per threshold key: the entry nprob_entries forms, from the counts of the pixels without / with the observed event per number c of
+        members at or above the threshold, the forecast being p = c / M: "histogram" (2, M + 1), "base_rate", "brier", "reliability",
+        "resolution", "uncertainty", "brier_skill", "roc", "roc_area", "reliability_diagram".
+    The table keeps the dry pixels in Z alone (include/adnm_hip.h); they are put back here: into rank bin (0, M), and per threshold into
+    (o = 0, c = 0), or for a threshold <= 0, where every pixel is an event, into (o = 1, c = M).  A division by zero gives NaN."""
+    if torch.is_tensor(rows):
+        rows = rows.detach().cpu().numpy()
+    r = np.asarray(rows)
+    M, nthr, bins = int(M), len(thresholds), int(bins)
+    C, at = ops.ensemble_cols(M, nthr)   # ValueError outside the limits
+    if r.ndim < 1 or r.shape[-1] != C:
+        raise ValueError(f"ensemble: rows are (..., {C}) for {M} members and {nthr} thresholds, got {r.shape}")
+    if bins < 1:
+        raise ValueError(f"ensemble: bins >= 1, got {bins}")
+    if r.dtype.kind == "f":
+        if not (np.isfinite(r).all() and (r == np.rint(r)).all()):
+            raise ValueError("ensemble: the rows hold integer sums")
+    elif r.dtype.kind not in "iu":
+        raise ValueError(f"ensemble: the rows hold integer sums, got {r.dtype}")
+    r = r.astype(np.int64)
+    if (r < 0).any():
+        raise ValueError("ensemble: the rows hold sums >= 0")
+    n, z, s0, s1, s2, v, e = (r[..., i].astype(np.float64) for i in range(7))
+    fm = float(M)
+    crps = np.asarray(_ratio(s1, fm * n)) - np.asarray(_ratio(s2, fm * fm * n))
+    fair = np.asarray(_ratio(s1, fm * n)) - np.asarray(_ratio(s2, fm * (fm - 1.0) * n))
+    mae = np.asarray(_ratio(s0, n))
+    spread, rmse = np.sqrt(np.asarray(_ratio(v, fm * (fm - 1.0) * n))), np.sqrt(np.asarray(_ratio(e, fm * fm * n)))
+    # ties: bin (b, e) gives 1 / (e + 1) to each of the ranks b .. b + e
+    bins_r = r[..., at["rank"]:at["rank"] + (M + 1) ** 2].reshape(r.shape[:-1] + (M + 1, M + 1)).astype(np.float64)
+    share = np.zeros((M + 1, M + 1, M + 1))
+    for b in range(M + 1):
+        for eq in range(M + 1 - b):
+            share[b, eq, b:b + eq + 1] = 1.0 / (eq + 1)
+    wet = np.einsum("...be,ber->...r", bins_r, share)
+    res = {"members": M, "pixels": _scalar(r[..., 0]), "dry": _scalar(r[..., 1]), "crps": _scalar(crps), "crps_fair": _scalar(fair), "mae_control": _scalar(mae),
+           "crpss": _scalar(1.0 - np.asarray(_ratio(crps, mae))), "spread": _scalar(spread), "rmse_mean": _scalar(rmse),
+           "spread_skill": _scalar(math.sqrt((fm + 1.0) / fm) * np.asarray(_ratio(spread, rmse))),
+           "rank_histogram": wet + z[..., None] / (fm + 1.0), "rank_histogram_wet": wet}
+    for k, thr in enumerate(thresholds):
+        a = at["exceed"] + 2 * k * (M + 1)
+        n0, n1 = r[..., a:a + M + 1].copy(), r[..., a + M + 1:a + 2 * (M + 1)].copy()
+        if float(thr) <= 0.0:
+            n1[..., M] += r[..., 1]
+        else:
+            n0[..., 0] += r[..., 1]
+        res[_thr_key(thr)] = _probability_entry(n0, n1, M, bins)
+    return res
+
+
 def nprob_entries(rows, scales, thresholds, bins=10):
     """rows: (..., nthr, S) integer counts laid out as ops.nprob_layout(scales) states (ops.neighbour_hist's tensor summed over its frames, the
     Validator's table or its sum over the horizon) -> the entries of done()["nprob"], {n: {thr: {...}}}, the leading axes (none, or T) kept
@@ -420,35 +538,7 @@ def nprob_entries(rows, scales, thresholds, bins=10):
         raise ValueError(f"nprob: the rows hold integer counts, got {r.dtype}")
     r = r.astype(np.int64)
 
-    def ratio(a, b):
-        """a / b in float64, NaN where b is 0"""
-        a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            return _scalar(np.where(b == 0, np.nan, a / b))
-
-    def entry(n0, n1, n):
-        """n0, n1: (..., n^2 + 1) counts of the pixels without / with the observed event per window count"""
-        c = np.arange(n * n + 1)
-        p = c / float(n * n)
-        both = (n0 + n1).astype(np.float64)
-        total, events, quiet = both.sum(axis=-1), n1.sum(axis=-1), n0.sum(axis=-1)
-        base = np.asarray(ratio(events, total))
-        freq = np.asarray(ratio(n1, both))   # the observed frequency given the forecast value; NaN where the value never occurs
-        rel = np.where(both == 0, 0.0, both * (p - freq) ** 2).sum(axis=-1)
-        res = np.where(both == 0, 0.0, both * (freq - base[..., None]) ** 2).sum(axis=-1)
-        brier, unc = np.asarray(ratio((n0 * p ** 2 + n1 * (p - 1.0) ** 2).sum(axis=-1), total)), base * (1.0 - base)
-        zero = np.zeros(n0.shape[:-1] + (1,))
-        pod = np.concatenate([np.asarray(ratio(_tail_sums(n1, -1), events[..., None])), zero], axis=-1)
-        pofd = np.concatenate([np.asarray(ratio(_tail_sums(n0, -1), quiet[..., None])), zero], axis=-1)
-        area = ((pofd[..., :-1] - pofd[..., 1:]) * (pod[..., :-1] + pod[..., 1:]) / 2.0).sum(axis=-1)
-        member = (np.minimum(c * bins // (n * n), bins - 1)[:, None] == np.arange(bins)).astype(np.float64)   # (n^2 + 1, bins), one bin per value
-        count = both @ member
-        return {"histogram": np.stack([n0, n1], axis=-2), "base_rate": _scalar(base), "brier": _scalar(brier),
-                "reliability": ratio(rel, total), "resolution": ratio(res, total), "uncertainty": _scalar(unc),
-                "brier_skill": _scalar(1.0 - np.asarray(ratio(brier, unc))), "roc": {"pofd": pofd, "pod": pod}, "roc_area": _scalar(area),
-                "reliability_diagram": {"edges": np.linspace(0.0, 1.0, bins + 1), "count": count.astype(np.int64),
-                                        "forecast_mean": ratio((both * p) @ member, count), "observed_frequency": ratio(n1.astype(np.float64) @ member, count)}}
-    return {n: {_thr_key(thr): entry(r[..., k, a0:a0 + n * n + 1], r[..., k, a1:a1 + n * n + 1], n) for k, thr in enumerate(thresholds)}
+    return {n: {_thr_key(thr): _probability_entry(r[..., k, a0:a0 + n * n + 1], r[..., k, a1:a1 + n * n + 1], n * n, bins) for k, thr in enumerate(thresholds)}
             for n, (a0, a1) in zip(scales, layout)}
 
 
@@ -618,7 +708,7 @@ def _lead_scores(rows, thresholds):
 
 
 def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=False, per_lead=False, fss=(), advection=False, spectrum=None,
-              sal=None, nprob=None, tracks=None, intensity_scale=None, objects=None, joint=None):
+              sal=None, nprob=None, tracks=None, intensity_scale=None, ensemble=None, objects=None, joint=None):
     """host: the block (a float64 array laid out as block_layout states for these options; `spectrum` = (H, W), the frame size, `joint` = L,
     the number of levels: include/adnm_hip.h) -> the dictionary of Validator.done().  The metrics are SimplifiedEvaluator.done's
     (Shanghai_metrics.py:218-290) as GpuEvaluator.done() states them, from per-frame-index sums; "pooled", "persistence", "advection" and
@@ -635,7 +725,8 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
     table's sum over the horizon, and under "per_lead" nprob_entries of the table.  `tracks` (what ops.tracks_spec takes; BY NAME): "tracks" =
     track_entries of the table.  Its arrays are per lead time already, so per_lead=True adds nothing for tracks.  `intensity_scale` ((H, W), the
     frame size; BY NAME): "intensity_scale" = intensity_scale_entries of the table's sum over the horizon, the same under each baseline there
-    is, and under "per_lead" intensity_scale_entries of the tables."""
+    is, and under "per_lead" intensity_scale_entries of the tables.  `ensemble` (the number of members M; BY NAME): "ensemble" =
+    ensemble_entries of the table's sum over the horizon, and under "per_lead" ensemble_entries of the table."""
     nthr, T = len(thresholds), seq_len
     pools, fss = tuple(pools), tuple(fss)
     spectrum = tuple(int(v) for v in spectrum) if spectrum else None
@@ -646,15 +737,16 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
         raise ValueError(f"aggregate: joint is the number of levels, {ops.MIN_JOINT_LEVELS}..{ops.MAX_JOINT_LEVELS}, or None; got {joint}")
     objects, sal, nprob, tracks = ops.objects_spec(objects), ops.sal_spec(sal), ops.fss_scales(nprob), ops.tracks_spec(tracks)
     iscale = tuple(int(v) for v in intensity_scale) if intensity_scale else None
-    parts, total = block_tables(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, tracks=tracks, objects=objects,
-                                iscale=iscale)   # ValueError outside the intensity-scale limits
+    ensemble = int(ensemble) if ensemble else None
+    parts, total = block_rows(T, nthr, pools, persistence, fss, advection, spectrum, joint, sal=sal, nprob=nprob, tracks=tracks, objects=objects,
+                              iscale=iscale, ensemble=ensemble)   # ValueError outside the intensity-scale limits
     blk = np.asarray(block, dtype=np.float64)
     if blk.shape != (total,):
         raise ValueError(f"aggregate: a block of {total} doubles is expected for {T} frames, {nthr} thresholds, pools {pools}, "
                          f"persistence {bool(persistence)}" + (f", fss {fss}" if fss else "") + (", advection" if advection else "")
                          + (f", spectrum of {spectrum[0]} x {spectrum[1]} frames" if spectrum else "") + (f", a joint histogram of {joint} levels" if joint else "")
                          + (", objects" if objects else "") + (", sal" if sal else "") + (f", nprob {nprob}" if nprob else "")
-                         + (f", intensity_scale of {iscale[0]} x {iscale[1]} frames" if iscale else "") + (", tracks" if tracks else "") + f"; got {blk.shape}")
+                         + (f", intensity_scale of {iscale[0]} x {iscale[1]} frames" if iscale else "") + (f", an ensemble of {ensemble}" if ensemble else "") + (", tracks" if tracks else "") + f"; got {blk.shape}")
     tabs = {p.name: blk[p.offset:p.offset + p.size].reshape(p.shape) for p in parts}
     loss_sum, batches, samples, nonfinite = (float(v) for v in blk[:HEADER])
     tab = tabs["main"][HEADER:].reshape(T, 4 * nthr + 3)
@@ -716,6 +808,8 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
             yield "nprob", nprob_entries(tabs["nprob"] if lead else tabs["nprob"].sum(axis=0), nprob, thresholds)
         if iscale:
             yield "intensity_scale", scales(tabs["iscale"], lead)
+        if ensemble:
+            yield "ensemble", ensemble_entries(tabs["ensemble"] if lead else tabs["ensemble"].sum(axis=0), ensemble, thresholds)
         if tracks and not lead:
             yield "tracks", track_entries(tabs["tracks"], samples, thresholds, T, tracks)
     res.update(optional(False))
@@ -732,7 +826,7 @@ def aggregate(block, thresholds, seq_len, hw, ssim_area, pools=(), persistence=F
 class Validator(ForwardClient):
     def __init__(self, model, loss_fn, seq_len, value_scale, thresholds=(20, 30, 35, 40), ssim=True, process_group=None, pools=None, persistence=False,
                  fss=None, advection=None, spectrum=False, objects=None, advection_flow=False, sal=None, nprob=None, tracks=None, intensity_scale=False,
-                 joint=False):
+                 ensemble=None, joint=False):
         from models.loss import enRainfallLoss
         if not isinstance(loss_fn, enRainfallLoss):   # RainfallLoss is a subclass
             raise RuntimeError(f"Validator: loss_fn must be an enRainfallLoss / RainfallLoss (the loss csrc/dataio.hip::valid_accum computes; "
@@ -764,6 +858,10 @@ class Validator(ForwardClient):
         self.nprob = self.fss if nprob is True else ops.fss_scales(None if nprob is False else nprob)   # the scales, () for none; ValueError on a bad entry
         self.tracks = ops.tracks_spec(tracks)   # min_volume, or None; ValueError on a bad entry
         self.intensity_scale = bool(intensity_scale)
+        self.ensemble = ops.ensemble_spec(ensemble, None)   # the member codes, True (resolved with the epoch's frames) or None; ValueError on a bad entry
+        if self.ensemble and not 1.0 <= float(np.float32(self.value_scale)) < 256.0:
+            raise ValueError(f"Validator: ensemble= keeps the members' levels as bytes, which needs value_scale finite with 1 <= floor(value_scale) <= 255, "
+                             f"got {self.value_scale}")
         self._parts, _ = self._table(None)   # the spectrum and intensity-scale parts come with the block: their sizes follow the epoch's frames
         for part in self._parts:
             if len(part.pools) > ops.MAX_POOLS:   # a baseline's pass; pool_pairs has bounded the forecast's
@@ -774,14 +872,22 @@ class Validator(ForwardClient):
         self._block = self._last = None    # the epoch's accumulator block and the last batch's fp32 loss: they outlive the graphs
         self._frame = None                  # (H, W) of the epoch
         self._spectrum_frame = None         # (H, W) the block's spectrum table was sized for
+        self._block_members = None          # M the block's ensemble table was sized for
 
     # ---- device state
     def _table(self, frame):
-        """block_tables for this Validator's options; frame: (H, W) of the epoch, which sizes the spectrum and the intensity-scale parts (None:
-        without those parts)"""
-        return block_tables(self.seq_len, len(self.thresholds), self.pools, self.persistence, self.fss, bool(self.advection),
-                            frame if self.spectrum else None, self._levels, sal=self.sal, nprob=self.nprob, tracks=self.tracks, objects=self.objects,
-                            iscale=frame if self.intensity_scale else None)
+        """block_rows for this Validator's options; frame: (H, W) of the epoch, which sizes the spectrum and the intensity-scale parts (None:
+        without those parts) and, with ensemble=True, says how many members there are (None: without that part)"""
+        codes = self._codes(frame)
+        return block_rows(self.seq_len, len(self.thresholds), self.pools, self.persistence, self.fss, bool(self.advection),
+                          frame if self.spectrum else None, self._levels, sal=self.sal, nprob=self.nprob, tracks=self.tracks, objects=self.objects,
+                          iscale=frame if self.intensity_scale else None, ensemble=len(codes) if codes else None)
+
+    def _codes(self, frame):
+        """the member codes for frames of (H, W): a tuple, or None (no ensemble, or ensemble=True before the frames are known).  ValueError for
+        a transposing code on frames that are not square."""
+        codes = ops.ensemble_spec(self.ensemble, None if frame is None else frame[0] == frame[1])
+        return None if codes is True else codes
 
     def _block_for(self, device):
         """ONE allocation, the parts of block_parts; done() reduces it with one all-reduce"""
@@ -791,6 +897,7 @@ class Validator(ForwardClient):
             self._block = torch.zeros(total, dtype=torch.float64, device=device)
             self._last = torch.zeros((), dtype=torch.float32, device=device)
             self._spectrum_frame = self._frame
+            self._block_members = len(self._codes(self._frame) or ())
         elif self._block.device != device:
             raise RuntimeError(f"Validator: one device per Validator (the block is on {self._block.device}, the batch on {device})")
         elif self.spectrum and self._spectrum_frame != self._frame:
@@ -799,6 +906,9 @@ class Validator(ForwardClient):
         elif self.intensity_scale and self._spectrum_frame != self._frame:
             raise RuntimeError(f"Validator: intensity_scale=True keeps one frame size per Validator (the tables in the block are for frames of "
                                f"{self._spectrum_frame[0]} x {self._spectrum_frame[1]}, the batch has {self._frame[0]} x {self._frame[1]})")
+        elif self.ensemble and self._block_members != len(self._codes(self._frame)):
+            raise RuntimeError(f"Validator: ensemble= keeps one number of members per Validator (the table in the block is for {self._block_members}, "
+                               f"frames of {self._frame[0]} x {self._frame[1]} give {len(self._codes(self._frame))})")
         return self._block
 
     def _launch(self, ent, sx, pred, block, loss_out):
@@ -849,6 +959,9 @@ class Validator(ForwardClient):
             elif part.kind == "iscale":
                 lib.call("adnm_valid_iscale_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, ent["ws_iscale"].data_ptr(),
                          ent["ws_iscale"].numel(), B * T, T, H, W, stream)
+            elif part.kind == "ensemble":   # the M members against the target: `pred` is member 0 of the same buffer (no workspace: the query answered 0)
+                mem = ent["members"]
+                ops.ensemble_accum_into(mem, B * T * H * W, T * H * W, H * W, ent["tgt"], table, self._thr, nthr, self.value_scale, mem.shape[0], B * T, T, H * W)
             elif part.kind == "tracks":
                 lib.call("adnm_valid_tracks_accum", *src, ent["tgt"].data_ptr(), table, self._thr, nthr, self.value_scale, self.tracks,
                          ent["ws_tracks"].data_ptr(), ent["ws_tracks"].numel(), B * T, T, H, W, stream)
@@ -927,19 +1040,50 @@ class Validator(ForwardClient):
             ws_tracks = workspace("adnm_valid_tracks_accum_ws_bytes", [(B * T, T, H, W, nthr)],
                                   f"tracks on {B * T} frames in volumes of {T} x {H} x {W} are outside adnm_valid_tracks_accum's limits (frames <= 65535, "
                                   f"{ops.TRACK_LIMITS})")
+        codes = self._codes(self._frame)
+        if codes:
+            M = len(codes)
+            if x.dtype != torch.float32 or x.dim() < 3 or tuple(x.shape[-2:]) != (H, W) or not x.is_contiguous():
+                raise RuntimeError(f"Validator: ensemble= transforms the model's input, which must be contiguous fp32 (B, ..., H, W) with the target's "
+                                   f"{H} x {W} frames, got {x.dtype} {tuple(x.shape)}")
+            if int(lib.query("adnm_valid_ens_accum_ws_bytes", B * T, T, H * W, nthr, M, self.value_scale)) != 0 or x.numel() // (H * W) > 65535:
+                raise RuntimeError(f"Validator: an ensemble of {M} on {B * T} frames of {H} x {W} is outside adnm_valid_ens_accum's or adnm_d4_members' limits "
+                                   f"({ops.ENSEMBLE_LIMITS}; input planes <= 65535)")
+            ent.update(codes=(ctypes.c_int * M)(*codes), xin=torch.zeros((M * B,) + tuple(x.shape[1:]), dtype=torch.float32, device=dev),
+                       members=torch.zeros((M,) + shape, dtype=torch.float32, device=dev))
+            # the two directions once, eagerly, on the buffers and so on the access paths the graph will use
+            ops.d4_members_into(ent["sx"], ent["xin"], ent["codes"], M, False)
+            ops.d4_members_into(torch.zeros_like(ent["members"]), ent["members"], ent["codes"], M, True)
+        else:
+            ent.update(codes=None, xin=None, members=None)
         ent.update(shape=shape, tgt=torch.zeros(shape, dtype=torch.float32, device=dev), ws=ws, ws_ssim=ws_ssim, ws_pool=ws_pool, ws_fss=ws_fss,
                    ws_spectrum=ws_spectrum, ws_joint=ws_joint, ws_objects=ws_objects, ws_sal=ws_sal, ws_tracks=ws_tracks, ws_iscale=ws_iscale, adv=adv, motion=motion, flow=flow, ws_trec=ws_trec,
                    loss=(float(self.loss_fn.omega_t), float(self.loss_fn.alpha), float(self.loss_fn.gamma)))
         scratch = torch.zeros_like(self._block_for(dev))
         self._launch(ent, ent["sx"], ent["tgt"], scratch, torch.zeros((), dtype=torch.float32, device=dev))
 
+    def model_input(self, ent, sx):
+        """ensemble: the M transformed copies of the static input, member-major: sample m * B + b of the forward is member m of sample b"""
+        if ent["xin"] is None:
+            return sx
+        ops.d4_members_into(sx, ent["xin"], ent["codes"], ent["members"].shape[0], False)
+        return ent["xin"]
+
     def check(self, ent, out):
         B, T, H, W = ent["shape"]
+        if ent["members"] is not None:
+            B *= ent["members"].shape[0]
         if out.dtype != torch.float32 or out.numel() != B * T * H * W or tuple(out.shape[:2]) != (B, T):
-            raise RuntimeError(f"Validator: the model's output {tuple(out.shape)} {out.dtype} does not match the target's (B, T, H, W) = {ent['shape']} fp32")
+            raise RuntimeError(f"Validator: the model's output {tuple(out.shape)} {out.dtype} does not match the target's (B, T, H, W) = {(B, T, H, W)} fp32")
 
     def after(self, ent, sx, out):
-        ent["pred"] = out.contiguous()   # (the model emits it contiguous; a copy made here belongs to the graph's pool and is kept with it)
+        if ent["members"] is None:
+            ent["pred"] = ent["control"] = out.contiguous()   # (the model emits it contiguous; a copy made here belongs to the graph's pool and is kept with it)
+        else:   # the symmetries undone; every pass but the ensemble's scores member 0, the contiguous control forecast
+            mem = ent["members"]
+            ops.d4_members_into(out.contiguous(), mem, ent["codes"], mem.shape[0], True)
+            ent["pred"] = mem[0]
+            ent["control"] = mem[0].view((mem.shape[1],) + tuple(out.shape[1:]))   # in the model's own shape
         self._launch(ent, sx, ent["pred"], self._block, self._last)
 
     # ---- the public surface
@@ -960,7 +1104,11 @@ class Validator(ForwardClient):
         if ent["shape"] != shape:
             raise RuntimeError(f"Validator: input {tuple(x.shape)} came with a target of {ent['shape']} before, now {shape}")
         ent["tgt"].view(tgt.shape).copy_(tgt, non_blocking=True)
-        return self._fwd.replay(ent, x)["out"]
+        return self._result(self._fwd.replay(ent, x))
+
+    def _result(self, ent):
+        """what a step returns: the model's output, or with ensemble= the control forecast (member 0) in the model's output shape"""
+        return ent["out"] if ent["members"] is None else ent["control"]
 
     def _begin(self, shape, device):
         """a batch of (B, T, H, W) targets enters the epoch: its frames are the epoch's, the block is on its device"""
@@ -984,7 +1132,15 @@ class Validator(ForwardClient):
             raise RuntimeError(f"Validator: input {feed.x_shape} came with a target of {ent['shape']} before, the feed gives {(B, T, H, W)}")
         self._begin((B, T, H, W), feed.device)
         feed.fetch_into(ent["sx"], ent["tgt"])
-        return self._fwd.replay(ent, ent["sx"])["out"]
+        return self._result(self._fwd.replay(ent, ent["sx"]))
+
+    def members(self, x):
+        """ensemble: the member forecasts of the last batch of x's shape, symmetries undone: the graph's static fp32 (M, B, T, H, W) tensor,
+        member 0 the control, valid until the next step of that shape (ops.ensemble_product forms the mean and the exceedance probabilities)"""
+        ent = self._fwd._graphs.get((tuple(x.shape), x.dtype, x.device))
+        if not self.ensemble or ent is None or ent.get("members") is None:
+            raise RuntimeError("Validator.members: needs ensemble= and a step() on an input of this shape, dtype and device first")
+        return ent["members"]
 
     def advected(self, x):
         """the advected forecast of the last batch of x's shape: the graph's static fp32 (B, T, H, W) tensor, valid until the next step
@@ -1035,7 +1191,10 @@ class Validator(ForwardClient):
         adds nothing for tracks.
         intensity_scale: plus "intensity_scale" {"scale_px", "domain_px", "levels", thr: {"mse", "skill", "mse_share", "mse_total", "mse_random",
         "base_rate", "bias", "energy_target", "energy_forecast", "energy_rel_diff"}} (intensity_scale_entries of the table summed over the
-        horizon), the same under "persistence" and "advection" where those exist, and under "per_lead" with a leading T axis."""
+        horizon), the same under "persistence" and "advection" where those exist, and under "per_lead" with a leading T axis.
+        ensemble: plus "ensemble" {"members", "pixels", "dry", "crps", "crps_fair", "mae_control", "crpss", "spread", "rmse_mean", "spread_skill",
+        "rank_histogram", "rank_histogram_wet", thr: {what nprob reports, for p = c / M}} (ensemble_entries of the table summed over the horizon; levels
+        in units of the quantised value) and "per_lead"/"ensemble", the same with a leading T axis.  Every other entry is the control's."""
         if self._block is None or self._frame is None:
             raise RuntimeError("Validator.done: no batch since the last reset")
         blk = reduce_block(self._block.clone(), self.process_group) if self.process_group is not None else self._block
@@ -1045,7 +1204,7 @@ class Validator(ForwardClient):
         res = aggregate(host, self.thresholds, self.seq_len, H * W, area, pools=self.pools, persistence=self.persistence, per_lead=per_lead,
                         fss=self.fss, advection=bool(self.advection), spectrum=self._frame if self.spectrum else None, joint=self._levels, objects=self.objects,
                         sal=dict(min_area=self.sal[0], intensity=self.sal[1]) if self.sal else None, nprob=self.nprob, tracks=self.tracks,
-                        intensity_scale=self._frame if self.intensity_scale else None)
+                        intensity_scale=self._frame if self.intensity_scale else None, ensemble=self._block_members or None)
         if self.advection_flow:
             res["advection"]["scheme"] = "flow"
         if reset:

@@ -811,6 +811,62 @@ int adnm_valid_iscale_accum(const float* pred, int64_t pred_sample_stride, int64
                             const float* thresholds_host, int64_t nthr, float value_scale, void* ws, int64_t ws_bytes, int64_t frames,
                             int64_t T, int64_t H, int64_t W, adnm_stream_t stream);
 
+/* Ensembles of M member forecasts (csrc/ensemble.hip): the members of a test-time-augmentation ensemble over the eight
+ * symmetries of the square, the ONE integer statistic that verifies an ensemble, and the ensemble's products.  The reference has none; the
+ * definitions are this project's and the yardstick is numpy (tests/ensemble_ref.py).  The score and the product take ANY stack of members.
+ * These are not entry points of the scored-pair contract (they have M forecasts); they use its thresholds and its quantisation
+ *   q(v) = floorf(fminf(fmaxf(v, 0), 1) * value_scale): NaN, -Inf and negatives give 0, +Inf and values >= 1 give Q = floor(value_scale).
+ * adnm_d4_members: codes_host holds M ints in 0..7 with adnm_batch_fetch_aug's bits (bit 0 flip left-right, bit 1 flip up-down, bit 2
+ *   transpose; g(w) = w.flip(-2), w.flip(-1), w.transpose(-1, -2) in that order), read on the host at call time.  `planes` = B * F planes of
+ *   H x W fp32, contiguous.  inverse = 0: src is (planes, H, W), dst is (M, planes, H, W) and dst[m][p] = g_m(src[p]).  inverse = 1: src is
+ *   (M, planes, H, W) too and dst[m][p] = g_m^-1(src[m][p]): transpose first, then the flips; the two quarter turns (codes 5 and 6) are each
+ *   other's inverse, every other element is its own.  A copy of bit patterns: NaN payloads and -0.0 survive.  ONE launch, grid
+ *   (32 x 32 tiles, planes, M), no workspace, every element of dst written.  Members without the transpose bit move 16 bytes per access
+ *   when W % 4 == 0 and src and dst are 16-byte aligned (a mirrored row swaps the components of each piece), float by float otherwise;
+ *   transposing members go float by float through a 32 x 33 LDS tile, coalesced on both sides.  The result is the same on every path.
+ *   Refused (ADNM_EINVAL): a null pointer or one not 4-byte aligned; M outside 1..16; a code outside 0..7; the transpose bit with H != W;
+ *   planes outside 1..65535; H or W outside [1, 32768); H*W >= 2^24.
+ * adnm_valid_ens_accum ADDS a batch to table.  Frame f = b*T + t of member m starts at members + m*member_stride + b*sample_stride +
+ *   t*frame_stride (in elements; a frame's hw pixels contiguous); target: contiguous (frames, hw).  y = q(target), x_i = q(member i); all
+ *   further arithmetic is integer.  table: adnm_valid_ens_block_bytes(T, nthr, M) = 8 * T * C bytes, C = 7 + (M+1)^2 + 2*nthr*(M+1), 8-byte
+ *   aligned, zeroed by the caller, all double, row t = f mod T:
+ *     [0] N pixels   [1] Z: the DRY pixels, y = 0 and every x_i = 0   [2] S0 = SUM |x_0 - y| (member 0 is the control)
+ *     [3] S1 = SUM_px SUM_i |x_i - y|   [4] S2 = SUM_px SUM_{i<j} |x_i - x_j|   [5] V = SUM_px (M SUM x_i^2 - (SUM x_i)^2)
+ *     [6] E = SUM_px (SUM x_i - M y)^2
+ *     [7 + b*(M+1) + e] rank bins R, b = #{x_i < y}, e = #{x_i = y}, over the pixels NOT counted in Z
+ *     then per threshold k  X[k][o][c], o = (y >= thr_k), c = #{x_i >= thr_k}, laid out [o = 0: c = 0..M][o = 1: c = 0..M] as
+ *       adnm_valid_nprob_accum's runs are, over the pixels NOT counted in Z.
+ *   THE CONVENTION: a dry pixel is counted in Z alone.  Whoever reads the table adds Z to R[(0, M)] and, for a threshold > 0, to X[k][0][0]
+ *   (for a threshold <= 0 every pixel is an event: to X[k][1][M]); validate.ensemble_entries does.  That is what lets the dry pixels, nearly
+ *   all pixels of a radar field, leave the kernel through one ballot and popcount per wave.
+ *   ONE launch, grid (items of 4096 pixels, frames), no workspace (adnm_valid_ens_accum_ws_bytes is 0 for every accepted shape, ws may be
+ *   NULL).  Every float is read once, 16 bytes per access when hw and the three strides are multiples of 4 and both bases 16-byte aligned,
+ *   float by float otherwise: same result.  Wet pixels keep their M levels as packed bytes, issue LDS atomics for their rank bin and their
+ *   nthr exceedance bins only; the seven sums are reduced over the wave by shuffles and over the workgroup in uint64; non-zero entries
+ *   reach the table as double atomics of integers: exact and the same bits on every run.  No workgroup waits for another.
+ *   A pixel adds at most (M Q)^2 <= 4080^2 < 2^24 to E, the largest column.  Every sum stays below 2^53, and so exact, for 33024 frames per
+ *   frame index at 128 x 128 and M = 16, Q = 255 (more than 10^6 at M = 8, Q = 90), and for 32 frames per frame index at hw = 2^24 - 1.
+ *   Limits, refused before any launch (ADNM_EINVAL): a null pointer; members / target not 4-byte or table not 8-byte aligned; M outside
+ *   2..16; nthr outside 1..8; value_scale not finite or floor(value_scale) outside 1..255; T < 1 or not dividing frames; frames > 65535;
+ *   hw outside [1, 2^24); a stride that is neither 0 (held) nor at least the extent below it (frame_stride >= hw, sample_stride >=
+ *   (T-1)*frame_stride + hw, member_stride >= (frames/T - 1)*sample_stride + that).  The *_bytes queries are pure host code and return -1.
+ * adnm_ensemble_product: members as above.  mean, fp32 (frames, hw): ((x_0 + x_1) + ... + x_(M-1)) / float(M) on the RAW values, every add
+ *   and the one division rounded on their own in fp32 (no FMA, no reassociation: a np.float32 loop gives the same bits).  prob, fp32
+ *   (K, frames, hw): float(c) / float(M), c = #{q(x_i) >= thr_k}, one IEEE division (adnm_neighbour_prob's rule).  K = 0..8; K = 0 writes
+ *   the mean only, prob and thresholds_host may be NULL and value_scale is not looked at.  Every element is written; 16 bytes per access
+ *   when hw and the strides are multiples of 4 and members, mean and prob are 16-byte aligned, float by float otherwise.  Limits
+ *   (ADNM_EINVAL): adnm_valid_ens_accum's on M, frames, T, hw, the strides and the pointers. */
+int adnm_d4_members(const float* src, float* dst, const int* codes_host, int64_t M, int inverse, int64_t planes, int64_t H, int64_t W,
+                    adnm_stream_t stream);
+int64_t adnm_valid_ens_block_bytes(int64_t T, int64_t nthr, int64_t M);
+int64_t adnm_valid_ens_accum_ws_bytes(int64_t frames, int64_t T, int64_t hw, int64_t nthr, int64_t M, float value_scale);
+int adnm_valid_ens_accum(const float* members, int64_t member_stride, int64_t sample_stride, int64_t frame_stride, const float* target,
+                         void* table, const float* thresholds_host, int64_t nthr, float value_scale, int64_t M, void* ws, int64_t ws_bytes,
+                         int64_t frames, int64_t T, int64_t hw, adnm_stream_t stream);
+int adnm_ensemble_product(const float* members, int64_t member_stride, int64_t sample_stride, int64_t frame_stride, float* mean, float* prob,
+                          const float* thresholds_host, int64_t K, float value_scale, int64_t M, int64_t frames, int64_t T, int64_t hw,
+                          adnm_stream_t stream);
+
 /* The Lagrangian-persistence (advection) baseline: block-matched motion between the last two input frames (TREC, Rinehart & Garvey 1978)
  * and the last frame moved along it.  The reference has none; the definitions are this project's.  Integer arithmetic and
  * bit copies only: exact and bit-reproducible.
